@@ -71,7 +71,10 @@ def _run_levels_concurrently(fns):
     the temporal encoder of a stage, applied to each temporal level on its own (WC/msdeformattn.py:258-264: a Python loop over independent levels
     of 16 and 64 row tiles at BASELINE config 3, on a 256-CU chip), and (round 6) for the 1x1 convolution + GroupNorm projections of the levels
     (WC/msdeformattn.py:404-435: three independent GEMM -> statistics -> normalise chains of 30 - 40 us each).  Returns the results in order."""
-    if len(fns) < 2:
+    # Inside a graph capture the chains run one after another on the capturing stream: a capture forked onto side streams becomes a graph with
+    # parallel branches, and replaying the whole within-clip module from such a graph crashed the host process inside the graph launch.  The chains
+    # are independent, so the order changes no bits; the replay only loses their overlap.
+    if len(fns) < 2 or torch.cuda.is_current_stream_capturing():
         return [f() for f in fns]
     cur = torch.cuda.current_stream()
     key = str(cur.device)

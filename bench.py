@@ -57,6 +57,50 @@ def layer_bytes(B, T, H, W, C, F, e=4):
     return 3 * B * T * H * W * C * e + P * 2
 
 
+DUMP_LIMIT_BYTES = 64_000_000      # --dump-outputs: at most 64 MB of .npy files in all
+
+
+def _named_tensors(obj, name, out):
+    """dotted name -> tensor for every tensor in a nested output (dicts, lists, tuples); leaves that are not tensors (None, numbers,
+    strings) are skipped"""
+    import torch
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            _named_tensors(v, f"{name}.{k}" if name else str(k), out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _named_tensors(v, f"{name}.{i}" if name else str(i), out)
+    elif isinstance(obj, torch.Tensor):
+        out[name] = obj
+    return out
+
+
+def dump_outputs(directory, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `outputs` (a dict, possibly nested) as directory/<dotted name>.npy; float64 stays float64,
+    every other type is written as float32.  The arrays share `limit` (smallest first, each up to an equal share of what is left);
+    one that does not fit its share is written as a fixed sample: its flattened elements at sorted indices drawn by a generator
+    seeded 0, a 1-D array -- the same indices in every run and every build of the same shape."""
+    import numpy as np
+    import torch
+    tensors = _named_tensors(outputs, "", {})
+    os.makedirs(directory, exist_ok=True)
+    left, n_left = limit - 256 * len(tensors), len(tensors)          # (256 B: room for each .npy header)
+    for name, t in sorted(tensors.items(), key=lambda kv: (kv[1].numel(), kv[0])):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        share = left // n_left // (8 if dt == torch.float64 else 4)
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = flat[idx.to(flat.device)].to(dt).cpu().numpy()
+        else:
+            a = t.detach().to(dt).cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+        n_left -= 1
+        print(f"[dump] {name}: {tuple(t.shape)} {t.dtype} -> {a.dtype}" + (f", {a.size} sampled elements" if a.size != t.numel() else ""),
+              file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -87,7 +131,13 @@ def main():
     ap.add_argument("--workload", default="layer", choices=["layer", "cc"],
                     help="layer: the headline metric (default); cc: BASELINE config 4, the cross-clip tracking module alone "
                          "(one JSON line: us per forward, frames/s, HBM GB/s against 8 TB/s; single GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed seeded sample of a larger output; rank 0).  The inputs are seeded: the same "
+                         "arguments give the same inputs in every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import __graft_entry__ as ge
     if "RANK" not in os.environ and args.gpus > 1:
@@ -219,8 +269,9 @@ def main():
             pos = pos.clone()
         return layer, w, src, pos
 
-    def measure_cc(n_cc=30, graph=False, aux=True):
-        """BASELINE config 4: CrossClipTrackingModule.forward over 4 clips x 4 frames, [C=256, H=W=64] features, 4 layers."""
+    def measure_cc(n_cc=30, graph=False, aux=True, dump_dir=None):
+        """BASELINE config 4: CrossClipTrackingModule.forward over 4 clips x 4 frames, [C=256, H=W=64] features, 4 layers.
+        `dump_dir`: write the last timed forward's outputs there (dump_outputs)."""
         Q, Tc, V, Hc, Wc, layers_cc, ncls = 128, 4, 4, 64, 64, 4, 124
         cc = ax.CrossClipTrackingModule(num_layers=layers_cc, num_classes=ncls, attn_drop=0.0, aspp_drop=0.0, kernel_sizes=[3, 3, 3],
                                         atrous_rates=[1, 2, 3], norm_fn="ln", num_clip_frames=V, mfma_dtype=args.dtype).eval()
@@ -242,10 +293,12 @@ def main():
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
         for _ in range(n_cc):
-            run()
+            res = run()
         ev1.record()
         torch.cuda.synchronize(dev)
         us = ev0.elapsed_time(ev1) / n_cc * 1e3
+        if dump_dir:
+            dump_outputs(dump_dir, res)
         out_bytes = layers_cc * (Q * Tc * V * Hc * Wc * 4 + 128 * Tc * V * Hc * Wc * 4)     # masks written + features read, per layer
         return {"us_per_forward": round(us, 1), "unit": "us", "layers": layers_cc, "frames_per_s": round(Tc * V / (us * 1e-6), 1),
                 "shape": {"clip_query": [1, Q, Tc, 256], "panoptic_features": [1, 128, Tc * V, Hc, Wc]},
@@ -258,9 +311,9 @@ def main():
     if args.workload == "cc":
         if world != 1:
             raise SystemExit("--workload cc is a single-GPU measurement (replicas only across GPUs)")
-        r = measure_cc(max(args.steps, 10), graph=args.graph)
+        r = measure_cc(args.steps, graph=args.graph, dump_dir=args.dump_outputs)
         line = {"metric": "cross-clip tracking module fwd at BASELINE config 4 (4 clips x T=4, [C=256,H=W=64], 4 layers)",
-                "value": r["frames_per_s"], "unit": "frames/s", "n_gpus": 1, "steps": max(args.steps, 10), "warmup": 5,
+                "value": r["frames_per_s"], "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": 5,
                 "ms_per_step": round(r["us_per_forward"] / 1e3, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                 "dtype": args.dtype, "data": "synthetic", "config": {"workload": r["what"], "launch": r["launch"]},
                 "roofline": {"bound": "hbm", "achieved": r["hbm_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": r["hbm_frac"], "traffic": None,
@@ -304,6 +357,8 @@ def main():
         torch.cuda.synchronize(dev)
     elapsed, out = timed(step, args.steps, args.warmup)
     main_event_ms = timed.last_event_ms          # device time of exactly those K steps (this rank's stream)
+    if args.dump_outputs and rank == 0:          # before anything else launches: the last timed step's output map (and the gathered maps)
+        dump_outputs(args.dump_outputs, dict(out=out, **({"gathered": gathered} if args.gather and gathered is not None else {})))
     assert torch.isfinite(out).all()
     frames = world * B * T * args.steps
     value = frames / elapsed

@@ -318,10 +318,15 @@ def test_train_amp_context_releases_its_lock_when_the_option_call_fails(monkeypa
         raise RuntimeError("option call failed")
     prev = _lib.current_amp()
     monkeypatch.setattr(_lib, "check", boom)
-    with pytest.raises(RuntimeError):
-        with _lib.train_amp(1 if prev != 1 else 2):
-            pass
-    monkeypatch.undo()
+    try:
+        with pytest.raises(RuntimeError):
+            with _lib.train_amp(1 if prev != 1 else 2):
+                pass
+    finally:
+        monkeypatch.undo()
+        # the failure is simulated AFTER the library accepted the option: put the library's own setting back, or every later
+        # training-tier call in this process (the GPU tests of the same session) would run its GEMMs on 16-bit products
+        _lib.check(_lib.lib().axvs_set_option(b"train_amp", prev), "axvs_set_option")
     assert _lib.current_amp() == prev
     assert _lib._AMP_LOCK.acquire(blocking=False)       # free again (an RLock held by this thread would also succeed: check the count)
     _lib._AMP_LOCK.release()

@@ -912,6 +912,38 @@ def test_decoder_in_place_levels_equal_the_split_and_cat_path(name):
         assert torch.equal(out_a[k], out_b[k]), k
 
 
+@pytest.mark.parametrize("name", ["g8_pixel_decoder_T2_S2", "g8_pixel_decoder_full_T4_S2"])
+def test_within_clip_module_graph_replay_equals_the_eager_forward(name):
+    """The whole WithinClipTrackingModule.forward_features (side streams for the levels, deformable layers, in-place temporal levels,
+    projections) captured by GraphedForward: a replay gives the eager forward's bits, on the captured inputs and on new ones."""
+    import axial_vs_amd as ax
+    z, m = load(name)
+    w = weights(z, m)
+    if m.get("full_size"):
+        mod = _full_size_decoder(m, w)
+    else:
+        from test_cabi_cpu import _decoder_from_meta
+        mod = _decoder_from_meta(m).eval()
+        mod.within_clip_tracking_module.load_state_dict(w, strict=True)
+        mod = mod.cuda()
+    keys = list(m["chans"])
+    g = torch.Generator().manual_seed(m["seed"] + 1)
+    feats = [{k: torch.randn(m["B"] * m["T"], m["chans"][k], *m["sizes"][k], generator=g).cuda() for k in keys} for _ in range(2)]
+
+    class Fwd(torch.nn.Module):
+        def forward(self, *ts):
+            out, _, _ = mod.forward_features(dict(zip(keys, ts)))
+            return tuple(out[k] for k in keys)
+    with torch.no_grad():
+        gf = ax.GraphedForward(Fwd(), *[feats[0][k] for k in keys])
+        for inputs in feats:
+            eager = [t_.clone() for t_ in Fwd()(*[inputs[k] for k in keys])]
+            replay = gf(*[inputs[k] for k in keys])
+            torch.cuda.synchronize()
+            for k, a, b in zip(keys, replay, eager):
+                assert torch.equal(a, b), k
+
+
 def _full_size_decoder(m, w):
     from test_cabi_cpu import _decoder_from_meta
     mod = _decoder_from_meta(dict(m, d_ffn=m["d_ffn"]), cross_clip_training=True).eval()
