@@ -124,6 +124,12 @@ SIGNATURES = {
                                    [C.c_float, C.c_float, C.c_uint, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
     "axvs_axial_layer_train_bwd": (C.c_int, [_fp, _fp, _fp, C.POINTER(AxvsAxialLayerParams), C.POINTER(AxvsAxialLayerParams), _fp, _fp] +
                                    [C.c_int] * 7 + [C.c_float, C.c_float, C.c_uint, C.c_int, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
+    "axvs_traj_layer_train_saved_bytes": (C.c_size_t, [C.c_int] * 6),
+    "axvs_traj_layer_train_scratch_bytes": (C.c_size_t, [C.c_int] * 7),
+    "axvs_traj_layer_train_fwd": (C.c_int, [_fp, _fp, _fp, C.POINTER(AxvsTrajLayerParams)] + [C.c_int] * 6 +
+                                  [C.c_float, C.c_float, C.c_uint, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
+    "axvs_traj_layer_train_bwd": (C.c_int, [_fp, _fp, _fp, C.POINTER(AxvsTrajLayerParams), C.POINTER(AxvsTrajLayerParams), _fp, _fp] +
+                                  [C.c_int] * 6 + [C.c_float, C.c_float, C.c_uint, C.c_int, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
     "axvs_cc_module_train_saved_bytes": (C.c_size_t, [C.POINTER(AxvsCCTrainCfg)]),
     "axvs_cc_module_train_scratch_bytes": (C.c_size_t, [C.POINTER(AxvsCCTrainCfg), C.c_int]),
     "axvs_cc_module_train_bn_stats_floats": (C.c_size_t, [C.POINTER(AxvsCCTrainCfg)]),

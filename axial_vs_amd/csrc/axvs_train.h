@@ -591,6 +591,232 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float
   }
 }
 
+// ---- long frames (the full T*H*W layer: a frame is all H*W keys -- 4096 at 64 x 64): the same two query-side kernels with a
+//      frame's keys staged kSpChunk at a time.  The forward's running max / sum per 16-key tile is the one of
+//      tr_spatial_fwd_mfma_kernel (same tile order: the same statistics (max, 1 / sum) into `stats`, the same x layout), so the
+//      key-side backward (tr_spatial_bwd_kv_mfma_kernel, which stages QUERIES in chunks and never holds a whole frame) serves
+//      both.  A wave owns kSpQT query tiles at a time, so each K / V fragment read from LDS feeds kSpQT tiles.  LDS: K and V
+//      chunks [kSpChunk][kTrLd] = 72 KiB (two workgroups per CU).  Dropout element indices are 64-bit (2.1e9 at 64 x 64 x 4).
+constexpr int kSpChunk = 256;   // keys of a frame per LDS stage (a multiple of 16)
+constexpr int kSpQT = 2;        // 16-query tiles per wave
+__host__ __device__ inline size_t spatial_chunk_lds() { return (size_t)2 * kSpChunk * kTrLd * sizeof(float); }
+
+// keys c0 .. c0 + ceil16(Lc) of frame f of (sequence s, head h) -> LDS [.][kTrLd], rows past the frame zero
+__device__ __forceinline__ void stage_chunk36(float* dst, const float* src, const RowMap& rm, int s, int f, int c0, int h, int C, int tid) {
+  const int Lc = min(kSpChunk, rm.L - c0), Lp = (Lc + 15) & ~15;
+  for (int i = tid; i < Lp * 8; i += 256) {
+    const int n = i >> 3, c4 = i & 7;
+    float4 v = {0.f, 0.f, 0.f, 0.f};
+    if (n < Lc) v = *reinterpret_cast<const float4*>(src + nat_row(rm, s * rm.N + f * rm.L + c0 + n) * C + h * 32 + c4 * 4);
+    *reinterpret_cast<float4*>(dst + n * kTrLd + c4 * 4) = v;
+  }
+}
+
+// grid: x = (sequence, head), y = blocks of 4 * kSpQT query tiles, z = frames (as tr_spatial_fwd_mfma_kernel)
+__global__ __launch_bounds__(256) void tr_spatial_fwd_chunk_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                    const float* __restrict__ v, float* __restrict__ x,
+                                                                    float* __restrict__ stats, RowMap rm, int T, int C, int heads, float scale,
+                                                                    Drop dr) {
+  extern __shared__ float smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+  const int s = blockIdx.x / heads, h = blockIdx.x - s * heads, N = rm.N, L = rm.L;
+  const int nqt = (N + 15) >> 4, nqb = (nqt + 4 * kSpQT - 1) / (4 * kSpQT);
+  float* ks = smem;
+  float* vs = smem + kSpChunk * kTrLd;
+  const int fper = (T + (int)gridDim.z - 1) / (int)gridDim.z, f0 = (int)blockIdx.z * fper, f1 = min(T, f0 + fper);
+  for (int f = f0; f < f1; ++f)
+    for (int qb = (int)blockIdx.y; qb < nqb; qb += (int)gridDim.y) {
+      float qr[kSpQT][8], m[kSpQT], sum[kSpQT];
+      f32x4 acc[kSpQT][2];
+      unsigned long long base[kSpQT];
+#pragma unroll
+      for (int u = 0; u < kSpQT; ++u) {
+        const int qc = min((qb * 4 * kSpQT + u * 4 + wave) * 16 + j, N - 1);
+        const float* qp = q + nat_row(rm, s * N + qc) * C + h * 32 + 8 * g;
+        const float4 a = *reinterpret_cast<const float4*>(qp), b = *reinterpret_cast<const float4*>(qp + 4);
+        qr[u][0] = a.x * scale; qr[u][1] = a.y * scale; qr[u][2] = a.z * scale; qr[u][3] = a.w * scale;
+        qr[u][4] = b.x * scale; qr[u][5] = b.y * scale; qr[u][6] = b.z * scale; qr[u][7] = b.w * scale;
+        m[u] = -INFINITY;
+        sum[u] = 0.f;
+        acc[u][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc[u][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        base[u] = ((((unsigned long long)s * heads + h) * N + qc) * T + f) * L;
+      }
+      for (int c0 = 0; c0 < L; c0 += kSpChunk) {
+        __syncthreads();
+        stage_chunk36(ks, k, rm, s, f, c0, h, C, tid);
+        stage_chunk36(vs, v, rm, s, f, c0, h, C, tid);
+        __syncthreads();
+        const int nkt = (min(kSpChunk, L - c0) + 15) >> 4;
+        for (int kt = 0; kt < nkt; ++kt) {
+          const float* kp = ks + (kt * 16 + j) * kTrLd + 8 * g;
+          const float4 ka = *reinterpret_cast<const float4*>(kp), kb = *reinterpret_cast<const float4*>(kp + 4);
+          const float kr[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+          const int nl = kt * 16 + 4 * g, n0 = c0 + nl;          // my 4 keys: n0 .. n0 + 3 of the frame (nl .. within the chunk)
+          float vr[4][2];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            vr[r][0] = vs[(nl + r) * kTrLd + j];
+            vr[r][1] = vs[(nl + r) * kTrLd + j + 16];
+          }
+#pragma unroll
+          for (int u = 0; u < kSpQT; ++u) {
+            if ((qb * 4 * kSpQT + u * 4 + wave) >= nqt) continue;      // (uniform per wave)
+            f32x4 sc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < 8; ++t) sc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[t], qr[u][t], sc, 0, 0, 0);
+            float tmax = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              if (n0 + r >= L) sc[r] = -INFINITY;
+              tmax = fmaxf(tmax, sc[r]);
+            }
+            const float mn = fmaxf(m[u], xor_max16_32(tmax));
+            const float alpha = __expf(m[u] - mn);
+            float p[4], ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              p[r] = __expf(sc[r] - mn);
+              ps += p[r];
+              if (n0 + r < L) p[r] *= drop_keep(dr, base[u] + n0 + r);
+            }
+            sum[u] = sum[u] * alpha + xor_sum16_32(ps);
+            m[u] = mn;
+            acc[u][0] *= alpha;
+            acc[u][1] *= alpha;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[r][0], p[r], acc[u][0], 0, 0, 0);
+              acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[r][1], p[r], acc[u][1], 0, 0, 0);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kSpQT; ++u) {
+        const int qn = (qb * 4 * kSpQT + u * 4 + wave) * 16 + j;
+        if (qn < N) {
+          const long long mq = nat_row(rm, s * N + qn);
+          const float inv = 1.f / sum[u];
+          float* xo = x + (mq * T + f) * C + h * 32 + 4 * g;
+          *reinterpret_cast<float4*>(xo) = float4{acc[u][0][0] * inv, acc[u][0][1] * inv, acc[u][0][2] * inv, acc[u][0][3] * inv};
+          *reinterpret_cast<float4*>(xo + 16) = float4{acc[u][1][0] * inv, acc[u][1][1] * inv, acc[u][1][2] * inv, acc[u][1][3] * inv};
+          if (g == 0) {
+            float* st = stats + ((((size_t)s * heads + h) * N + qn) * T + f) * 3;
+            st[0] = m[u];
+            st[1] = inv;
+          }
+        }
+      }
+    }
+}
+
+// backward, query side (tr_spatial_bwd_q_mfma_kernel with chunked keys): per (query, frame) D = dx . x, then per 16-key tile
+// S^T = K Q^T, dP^T = V dX^T, dS = P (keep dP - D) with P from the forward's (max, 1 / sum), dq^T += K^T dS^T.  dq stays in
+// registers over all frames and chunks (one store); D goes to stats[.., 2] for the key side.  grid: x = (sequence, head),
+// y = blocks of 4 * kSpQT query tiles.
+__global__ __launch_bounds__(256) void tr_spatial_bwd_q_chunk_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                      const float* __restrict__ v, const float* __restrict__ x,
+                                                                      const float* __restrict__ dx, float* __restrict__ dq,
+                                                                      float* __restrict__ stats, RowMap rm, int T, int C, int heads, float scale,
+                                                                      Drop dr) {
+  extern __shared__ float smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+  const int s = blockIdx.x / heads, h = blockIdx.x - s * heads, N = rm.N, L = rm.L;
+  const int nqt = (N + 15) >> 4, nqb = (nqt + 4 * kSpQT - 1) / (4 * kSpQT);
+  float* ks = smem;
+  float* vs = smem + kSpChunk * kTrLd;
+  for (int qb = (int)blockIdx.y; qb < nqb; qb += (int)gridDim.y) {
+    float qr[kSpQT][8];
+    long long mq[kSpQT];
+    int qc[kSpQT];
+    f32x4 acc[kSpQT][2];
+#pragma unroll
+    for (int u = 0; u < kSpQT; ++u) {
+      qc[u] = min((qb * 4 * kSpQT + u * 4 + wave) * 16 + j, N - 1);
+      mq[u] = nat_row(rm, s * N + qc[u]);
+      const float* qp = q + mq[u] * C + h * 32 + 8 * g;
+      const float4 a = *reinterpret_cast<const float4*>(qp), b = *reinterpret_cast<const float4*>(qp + 4);
+      qr[u][0] = a.x * scale; qr[u][1] = a.y * scale; qr[u][2] = a.z * scale; qr[u][3] = a.w * scale;
+      qr[u][4] = b.x * scale; qr[u][5] = b.y * scale; qr[u][6] = b.z * scale; qr[u][7] = b.w * scale;
+      acc[u][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+      acc[u][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int f = 0; f < T; ++f) {
+      float dxr[kSpQT][8], dsum[kSpQT], m[kSpQT], inv[kSpQT];
+      unsigned long long base[kSpQT];
+#pragma unroll
+      for (int u = 0; u < kSpQT; ++u) {
+        const float* gp = dx + (mq[u] * T + f) * C + h * 32 + 8 * g;
+        const float* xp = x + (mq[u] * T + f) * C + h * 32 + 8 * g;
+        const float4 c = *reinterpret_cast<const float4*>(gp), d = *reinterpret_cast<const float4*>(gp + 4);
+        const float4 e = *reinterpret_cast<const float4*>(xp), e2 = *reinterpret_cast<const float4*>(xp + 4);
+        dxr[u][0] = c.x; dxr[u][1] = c.y; dxr[u][2] = c.z; dxr[u][3] = c.w; dxr[u][4] = d.x; dxr[u][5] = d.y; dxr[u][6] = d.z; dxr[u][7] = d.w;
+        dsum[u] = xor_sum16_32(c.x * e.x + c.y * e.y + c.z * e.z + c.w * e.w + d.x * e2.x + d.y * e2.y + d.z * e2.z + d.w * e2.w);
+        const float* st = stats + ((((size_t)s * heads + h) * N + qc[u]) * T + f) * 3;
+        m[u] = st[0];
+        inv[u] = st[1];
+        base[u] = ((((unsigned long long)s * heads + h) * N + qc[u]) * T + f) * L;
+      }
+      for (int c0 = 0; c0 < L; c0 += kSpChunk) {
+        __syncthreads();
+        stage_chunk36(ks, k, rm, s, f, c0, h, C, tid);
+        stage_chunk36(vs, v, rm, s, f, c0, h, C, tid);
+        __syncthreads();
+        const int nkt = (min(kSpChunk, L - c0) + 15) >> 4;
+        for (int kt = 0; kt < nkt; ++kt) {
+          const float* kp = ks + (kt * 16 + j) * kTrLd + 8 * g;
+          const float* vp = vs + (kt * 16 + j) * kTrLd + 8 * g;
+          const float4 ka = *reinterpret_cast<const float4*>(kp), kb = *reinterpret_cast<const float4*>(kp + 4);
+          const float4 va = *reinterpret_cast<const float4*>(vp), vb = *reinterpret_cast<const float4*>(vp + 4);
+          const float kr[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+          const float vr[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
+          const int nl = kt * 16 + 4 * g, n0 = c0 + nl;
+          float kt_[4][2];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            kt_[r][0] = ks[(nl + r) * kTrLd + j];
+            kt_[r][1] = ks[(nl + r) * kTrLd + j + 16];
+          }
+#pragma unroll
+          for (int u = 0; u < kSpQT; ++u) {
+            if ((qb * 4 * kSpQT + u * 4 + wave) >= nqt) continue;      // (uniform per wave)
+            f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+              sc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[t], qr[u][t], sc, 0, 0, 0);
+              dp = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[t], dxr[u][t], dp, 0, 0, 0);
+            }
+            float ds[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const bool valid = n0 + r < L;
+              const float P = valid ? __expf(sc[r] - m[u]) * inv[u] : 0.f;
+              const float kp_ = valid ? drop_keep(dr, base[u] + n0 + r) : 0.f;
+              ds[r] = P * (kp_ * dp[r] - dsum[u]);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(kt_[r][0], ds[r], acc[u][0], 0, 0, 0);
+              acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(kt_[r][1], ds[r], acc[u][1], 0, 0, 0);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kSpQT; ++u)
+        if (g == 0 && (qb * 4 * kSpQT + u * 4 + wave) * 16 + j < N) stats[((((size_t)s * heads + h) * N + qc[u]) * T + f) * 3 + 2] = dsum[u];
+    }
+#pragma unroll
+    for (int u = 0; u < kSpQT; ++u) {
+      if ((qb * 4 * kSpQT + u * 4 + wave) * 16 + j >= N) continue;
+      float* o = dq + mq[u] * C + h * 32 + 4 * g;
+      *reinterpret_cast<float4*>(o) = float4{acc[u][0][0] * scale, acc[u][0][1] * scale, acc[u][0][2] * scale, acc[u][0][3] * scale};
+      *reinterpret_cast<float4*>(o + 16) = float4{acc[u][1][0] * scale, acc[u][1][1] * scale, acc[u][1][2] * scale, acc[u][1][3] * scale};
+    }
+  }
+}
+
 // ---- spatial half, backward, part 1 (one thread per query): the softmax statistics (max, 1/sum, D = sum_n P dP) of every
 //      (query, frame) and dq.  dP_n = keep_n (dx_f . v_n),  dS_n = P_n (dP_n - D),  dq = scale sum_{f,n} dS_n k_n.
 //      stats: [(s heads + h), N, T, 3].

@@ -144,7 +144,7 @@ struct Dims {
   long long M, HW;
 };
 
-int make_dims(Dims& d, int B, int T, int H, int W, int C, int heads, int F) {
+int make_dims_any(Dims& d, int B, int T, int H, int W, int C, int heads, int F) {
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0 || F <= 0) return fail(AXVS_ERR_ARG, "non-positive dimension");
   if (C % heads) return fail(AXVS_ERR_ARG, "C=%d must be a multiple of heads=%d", C, heads);
   const int D = C / heads;
@@ -153,9 +153,32 @@ int make_dims(Dims& d, int B, int T, int H, int W, int C, int heads, int F) {
   if (T > 16) return fail(AXVS_ERR_ARG, "training tier: T=%d > 16 frames per clip not built", T);
   const long long M = (long long)B * T * H * W;
   if (M * (long long)(T > 1 ? T : 1) > INT32_MAX) return fail(AXVS_ERR_ARG, "training tier: B*T*H*W*T exceeds 2^31 rows");
-  if ((size_t)2 * (H > W ? H : W) * D * sizeof(float) > 160 * 1024) return fail(AXVS_ERR_ARG, "training tier: axis length too long for LDS");
   d = Dims{B, T, H, W, C, heads, F, D, M, (long long)H * W};
   return AXVS_OK;
+}
+
+// the axial layer: frames are axis lengths (H or W keys)
+int make_dims(Dims& d, int B, int T, int H, int W, int C, int heads, int F) {
+  if (int rc = make_dims_any(d, B, T, H, W, C, heads, F)) return rc;
+  if ((size_t)2 * (H > W ? H : W) * d.D * sizeof(float) > 160 * 1024) return fail(AXVS_ERR_ARG, "training tier: axis length too long for LDS");
+  return AXVS_OK;
+}
+
+// Frame length the spatial half's kernels take: the fp32 MFMA kernels (head_dim 32) any (keys chunked through LDS beyond ~550);
+// the VALU kernels (head_dim 8 / 16 / 64, or option train_valu) hold a whole frame's K and V in LDS.
+int check_frame(int D, long long L) {
+  if (D == 32 && !g_train_valu) return AXVS_OK;
+  const long long maxL = 160 * 1024 / (2 * D * (long long)sizeof(float));
+  if (L > maxL)
+    return fail(AXVS_ERR_ARG, "training tier: head_dim=%d with frames of %lld keys: the VALU attention kernel holds a frame in LDS, at most %lld keys "
+                "(frames of any length need head_dim 32)", D, L, maxL);
+  return AXVS_OK;
+}
+
+// the full T*H*W layer: one frame is all HW tokens of an image
+int make_traj_dims(Dims& d, int B, int T, int HW, int C, int heads, int F) {
+  if (int rc = make_dims_any(d, B, T, 1, HW, C, heads, F)) return rc;
+  return check_frame(d.D, HW);
 }
 
 struct PassSaved {
@@ -182,11 +205,12 @@ PassSaved carve_pass(Bump& b, const Dims& d) {
   return p;
 }
 
-Saved carve_saved(Bump& b, const Dims& d) {
+// npass: 2 (axial layer: height and width pass, buf1 between them) or 1 (full layer: its pass writes buf2)
+Saved carve_saved(Bump& b, const Dims& d, int npass = 2) {
   Saved s{};
   const size_t MC = (size_t)d.M * d.C;
-  for (int i = 0; i < 2; ++i) s.p[i] = carve_pass(b, d);
-  s.buf1 = b.f(MC);
+  for (int i = 0; i < npass; ++i) s.p[i] = carve_pass(b, d);
+  if (npass == 2) s.buf1 = b.f(MC);
   s.buf2 = b.f(MC);
   s.mean1 = b.f(d.M);
   s.rstd1 = b.f(d.M);
@@ -316,6 +340,10 @@ bool mfma_spatial(const Dims& d, const RowMap& rm) {
   const size_t lds_q = (size_t)2 * ((rm.L + 15) / 16 * 16) * kTrLd * sizeof(float);
   return d.D == 32 && !g_train_valu && lds_q <= 160 * 1024;
 }
+// head_dim 32, frames too long for LDS: the chunked-key query-side kernels (the key side is tr_spatial_bwd_kv_mfma_kernel either way)
+bool chunk_spatial(const Dims& d, const RowMap& rm) { return d.D == 32 && !g_train_valu && !mfma_spatial(d, rm); }
+// grid of the chunked kernels: y counts blocks of 4 * kSpQT query tiles
+inline int chunk_tiles(const RowMap& rm) { return (((rm.N + 15) / 16 + 4 * kSpQT - 1) / (4 * kSpQT)) * 4; }
 
 // Launch grid of the fp32 MFMA spatial-attention kernels: x = (sequence, head); the 16-row tiles each wave walks (y) and the frames (z)
 // are spread over more workgroups until there are about g_spatial_wgs of them -- every (tile, frame) is computed by exactly one
@@ -356,12 +384,18 @@ int pass_fwd(const Ctx& c, const float* xin, const float* pos, float* xout, cons
     if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_mfma_kernel), lds_mfma)) != AXVS_OK) return rc;
     hipLaunchKernelGGL(tr_spatial_fwd_mfma_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, d.T), dim3(256), lds_mfma, c.st, (const float*)s.q, (const float*)s.k,
                        (const float*)s.v, s.x, s.st, rm, d.T, C, d.heads, c.scale, attn_drop);
-  } else
+  } else if (chunk_spatial(d, rm)) {                                    // head_dim 32, long frames: keys chunked through LDS
+    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_chunk_kernel), spatial_chunk_lds())) != AXVS_OK) return rc;
+    hipLaunchKernelGGL(tr_spatial_fwd_chunk_kernel, spatial_grid(S * d.heads, chunk_tiles(rm), d.T), dim3(256), spatial_chunk_lds(), c.st, (const float*)s.q,
+                       (const float*)s.k, (const float*)s.v, s.x, s.st, rm, d.T, C, d.heads, c.scale, attn_drop);
+  } else {
+  if ((rc = check_frame(d.D, rm.L)) != AXVS_OK) return rc;
   AXVS_D_SWITCH(d.D, {
     if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_kernel<kD>), lds)) != AXVS_OK) return rc;
     hipLaunchKernelGGL(tr_spatial_fwd_kernel<kD>, dim3(S * d.heads), dim3(256), lds, c.st, (const float*)s.q, (const float*)s.k,
                        (const float*)s.v, s.x, rm, d.T, C, d.heads, c.scale, attn_drop);
   })
+  }
   hipLaunchKernelGGL(tr_diag_gather_kernel, dim3(blocks((size_t)M * C / 4)), dim3(256), 0, c.st, (const float*)s.x, s.xd, M, d.T, d.HW, C);
   const GemmEpi epq{w.proj_q_b, c.scale, 0, none, 0.f}, epkv{w.proj_kv_b, 1.f, 0, none, 0.f};
   if ((rc = c.g.fwd(s.xd, w.proj_q_w, s.q2, M, C, C, 0.f, &epq, ex)) != AXVS_OK) return rc;
@@ -412,14 +446,21 @@ int pass_bwd(const Ctx& c, const float* d_out, const float* xin, const float* po
   const size_t lds_q = (size_t)2 * ((rm.L + 15) / 16 * 16) * kTrLd * sizeof(float);
   const int kv_chunk = spatial_kv_chunk(rm);
   const size_t lds_kv = (size_t)kv_chunk * (2 * kTrLd + 4) * sizeof(float);
-  if (mfma_spatial(d, rm)) {       // the forward was the MFMA kernel too: (max, 1 / sum) are in s.st
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_mfma_kernel), lds_q)) != AXVS_OK) return rc;
+  if (mfma_spatial(d, rm) || chunk_spatial(d, rm)) {       // the forward was an MFMA kernel too: (max, 1 / sum) are in s.st
+    if (chunk_spatial(d, rm)) {
+      if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_chunk_kernel), spatial_chunk_lds())) != AXVS_OK) return rc;
+      hipLaunchKernelGGL(tr_spatial_bwd_q_chunk_kernel, spatial_grid(S * d.heads, chunk_tiles(rm), 1), dim3(256), spatial_chunk_lds(), c.st, (const float*)s.q,
+                         (const float*)s.k, (const float*)s.v, (const float*)s.x, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
+    } else {
+      if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_mfma_kernel), lds_q)) != AXVS_OK) return rc;
+      hipLaunchKernelGGL(tr_spatial_bwd_q_mfma_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, 1), dim3(256), lds_q, c.st, (const float*)s.q, (const float*)s.k,
+                         (const float*)s.v, (const float*)s.x, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
+    }
     if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_kv_mfma_kernel), lds_kv)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_bwd_q_mfma_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, 1), dim3(256), lds_q, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, (const float*)s.x, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
     hipLaunchKernelGGL(tr_spatial_bwd_kv_mfma_kernel, spatial_grid(S * d.heads, (rm.L + 15) / 16, T), dim3(256), lds_kv, c.st, (const float*)s.q, (const float*)s.k,
                        (const float*)s.v, (const float*)sc.dx, (const float*)s.st, sc.dk, sc.dv, rm, T, C, d.heads, c.scale, attn_drop, kv_chunk);
-  } else
+  } else {
+  if ((rc = check_frame(d.D, rm.L)) != AXVS_OK) return rc;
   AXVS_D_SWITCH(d.D, {
     if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_kernel<kD>), lds)) != AXVS_OK) return rc;
     hipLaunchKernelGGL(tr_spatial_bwd_q_kernel<kD>, dim3(S * d.heads), dim3(256), lds, c.st, (const float*)s.q, (const float*)s.k,
@@ -427,6 +468,7 @@ int pass_bwd(const Ctx& c, const float* d_out, const float* xin, const float* po
     hipLaunchKernelGGL(tr_spatial_bwd_kv_kernel<kD>, dim3(S * d.heads), dim3(256), lds2, c.st, (const float*)s.q, (const float*)s.k,
                        (const float*)s.v, (const float*)sc.dx, (const float*)s.st, sc.dk, sc.dv, rm, T, C, d.heads, c.scale, attn_drop, QC);
   })
+  }
   // q / k / v projections
   const float* const xa = pos ? sc.a : xin;
   if (pos) c.add(xin, pos, sc.a, MC);
@@ -447,18 +489,35 @@ int pass_bwd(const Ctx& c, const float* d_out, const float* xin, const float* po
   return AXVS_OK;
 }
 
-int check_ptrs(const AxvsAxialLayerParams* p) {
+// every field of a parameter / gradient struct (pointers only) is non-null
+template <class P>
+int check_ptrs(const P* p, const char* what = "AxvsAxialLayerParams") {
   const float* const* f = reinterpret_cast<const float* const*>(p);
-  for (size_t i = 0; i < sizeof(AxvsAxialLayerParams) / sizeof(float*); ++i)
-    if (!f[i]) return fail(AXVS_ERR_ARG, "null parameter pointer (field %zu of AxvsAxialLayerParams)", i);
+  for (size_t i = 0; i < sizeof(P) / sizeof(float*); ++i)
+    if (!f[i]) return fail(AXVS_ERR_ARG, "null parameter pointer (field %zu of %s)", i, what);
   return AXVS_OK;
 }
+
+// norm1 -> FFN -> norm2 behind the attention (WC/temporal_attention.py:181-185): the same in both layers, whose parameter / gradient
+// structs end in these eight fields
+struct TailParams {
+  const float *norm1_w, *norm1_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b, *norm2_w, *norm2_b;
+};
+struct TailGrads {
+  float *norm1_w, *norm1_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b, *norm2_w, *norm2_b;
+};
+template <class P>
+TailParams tail_params(const P& p) { return TailParams{p.norm1_w, p.norm1_b, p.linear1_w, p.linear1_b, p.linear2_w, p.linear2_b, p.norm2_w, p.norm2_b}; }
+template <class G>
+TailGrads tail_grads(const G& g) { return TailGrads{g.norm1_w, g.norm1_b, g.linear1_w, g.linear1_b, g.linear2_w, g.linear2_b, g.norm2_w, g.norm2_b}; }
 
 int status() {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(AXVS_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
   return AXVS_OK;
 }
+
+int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, float p_drop, unsigned seed);
 
 int forward(const Ctx& c, const float* src, const float* pos, float* out, const AxvsAxialLayerParams& p, const Saved& s, float p_drop,
             float p_attn, unsigned seed) {
@@ -474,7 +533,15 @@ int forward(const Ctx& c, const float* src, const float* pos, float* out, const 
   const RowMap rmw{d.T * d.W, d.W, d.H, sB, sT, 1, d.W};
   if ((rc = pass_fwd(c, s.buf1, pos, s.buf2, p.width_attn, s.p[1], rmw, d.B * d.H, make_drop(p_drop, seed, 3), make_drop(p_attn, seed, 4))) != AXVS_OK)
     return rc;
-  // norm1 -> FFN -> norm2                               :181-185, :217-218
+  return tail_fwd(c, tail_params(p), s, out, p_drop, seed);
+}
+
+// norm1 -> FFN -> norm2 on s.buf2 (dropout sites 5, 6)    WC/temporal_attention.py:181-185, :217-218 (:150-155 in the full layer)
+int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, float p_drop, unsigned seed) {
+  const Dims& d = c.d;
+  const long long M = d.M;
+  const int C = d.C;
+  int rc;
   hipLaunchKernelGGL(tr_ln_fwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, (const float*)s.buf2, p.norm1_w, p.norm1_b, s.z, s.mean1, s.rstd1, M, C, 1e-5f);
   {   // linear1 + bias + ReLU + dropout2 in one launch
     const GemmEpi e1{p.linear1_b, 1.f, 1, make_drop(p_drop, seed, 5), 0.f};
@@ -486,6 +553,56 @@ int forward(const Ctx& c, const float* src, const float* pos, float* out, const 
                      s.u, id, M, C, make_drop(p_drop, seed, 6));
   hipLaunchKernelGGL(tr_ln_fwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, (const float*)s.u, p.norm2_w, p.norm2_b, out, s.mean2, s.rstd2, M, C, 1e-5f);
   return status();
+}
+
+// the full layer (WC/temporal_attention.py:133-155): one pass over all T*HW tokens of a clip (one sequence per clip, frames of HW keys;
+// natural row order [(B T), HW] is the sequence order), dropout sites 1 (attention map) and 2 (pass output), then the same tail
+inline RowMap traj_rowmap(const Dims& d) { return RowMap{d.T * (int)d.HW, (int)d.HW, 1, (long long)d.T * d.HW, d.HW, 1, 0}; }
+
+int traj_forward(const Ctx& c, const float* src, const float* pos, float* out, const AxvsTrajLayerParams& p, const Saved& s, float p_drop,
+                 float p_attn, unsigned seed) {
+  int rc;
+  if ((rc = pass_fwd(c, src, pos, s.buf2, p.temporal_attn, s.p[0], traj_rowmap(c.d), c.d.B, make_drop(p_drop, seed, 1), make_drop(p_attn, seed, 2))) != AXVS_OK)
+    return rc;
+  return tail_fwd(c, tail_params(p), s, out, p_drop, seed);
+}
+
+// backward of the tail: d_out -> sc.g1 = gradient of s.buf2 (sc.g0 is overwritten)
+int tail_bwd(const Ctx& c, const float* d_out, const TailParams& p, const TailGrads& g, const Saved& s, float p_dropout, unsigned seed) {
+  const Dims& d = c.d;
+  const Scratch& sc = c.sc;
+  const long long M = d.M;
+  const int C = d.C;
+  const size_t MC = (size_t)M * C, MF = (size_t)M * d.F;
+  int rc;
+  // norm2                                                                       WC/temporal_attention.py:184
+  c.colsum(d_out, M, C, g.norm2_b, s.u, s.mean2, s.rstd2, g.norm2_w);
+  hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, d_out, (const float*)s.u, p.norm2_w, (const float*)s.mean2,
+                     (const float*)s.rstd2, sc.g0, M, C);                                 // g0 = d u
+  // FFN: u = z + dropout3(linear2(r)), r = dropout2(relu(linear1(z)))             :181-183
+  const RowMap id{(int)M, (int)M, 1, M, M, 1, 0};
+  hipLaunchKernelGGL(tr_drop_bwd_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, (const float*)sc.g0, sc.t0, id, M, C, make_drop(p_dropout, seed, 6));
+  if ((rc = c.wgrad(sc.t0, s.r, g.linear2_w, M, C, d.F, g.linear2_b)) != AXVS_OK) return rc;
+  if ((rc = c.dgrad(sc.t0, p.linear2_w, sc.dr, M, C, d.F, 0.f)) != AXVS_OK) return rc;
+  hipLaunchKernelGGL(tr_relu_drop_bwd_kernel, dim3(blocks(MF / 4)), dim3(256), 0, c.st, sc.dr, (const float*)s.r, MF / 4, make_drop(p_dropout, seed, 5).scale);
+  if ((rc = c.wgrad(sc.dr, s.z, g.linear1_w, M, d.F, C, g.linear1_b)) != AXVS_OK) return rc;
+  if ((rc = c.dgrad(sc.dr, p.linear1_w, sc.g0, M, d.F, C, 1.f)) != AXVS_OK) return rc;   // g0 = d z = d u + d r W1
+  // norm1                                                                       :217
+  c.colsum(sc.g0, M, C, g.norm1_b, s.buf2, s.mean1, s.rstd1, g.norm1_w);
+  hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, (const float*)sc.g0, (const float*)s.buf2, p.norm1_w,
+                     (const float*)s.mean1, (const float*)s.rstd1, sc.g1, M, C);          // g1 = d buf2
+  return AXVS_OK;
+}
+
+// the shared prologue of the four entry points of each layer: checks, buffers, stream
+int train_setup(Ctx& c, Saved& s, int npass, bool backward, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  Bump sb(saved), cb(scratch);
+  s = carve_saved(sb, c.d, npass);
+  c.sc = carve_scratch(cb, c.d, backward);
+  if (sb.off > saved_bytes || cb.off > scratch_bytes) return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
+  c.st = static_cast<hipStream_t>(stream);
+  c.scale = 1.f / sqrtf((float)c.d.D);
+  return c.g.init(c.st);
 }
 
 #include "axvs_cc_train_host.h"
@@ -562,15 +679,10 @@ int axvs_axial_layer_train_fwd(const float* src, const float* pos, float* out, c
   if (!src || !pos || !out || !params || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
   if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
   Ctx c{};
+  Saved s;
   int rc;
   if ((rc = make_dims(c.d, B, T, H, W, C, heads, d_ffn)) != AXVS_OK || (rc = check_ptrs(params)) != AXVS_OK) return rc;
-  Bump sb(saved), cb(scratch);
-  const Saved s = carve_saved(sb, c.d);
-  c.sc = carve_scratch(cb, c.d, false);
-  if (sb.off > saved_bytes || cb.off > scratch_bytes) return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
-  c.st = static_cast<hipStream_t>(stream);
-  c.scale = 1.f / sqrtf((float)c.d.D);
-  if ((rc = c.g.init(c.st)) != AXVS_OK) return rc;
+  if ((rc = train_setup(c, s, 2, false, saved, saved_bytes, scratch, scratch_bytes, stream)) != AXVS_OK) return rc;
   return forward(c, src, pos, out, *params, s, p_dropout, p_attn_drop, seed);
 }
 
@@ -581,42 +693,21 @@ int axvs_axial_layer_train_bwd(const float* d_out, const float* src, const float
   if (!d_out || !src || !pos || !params || !grads || !d_src || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
   if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
   Ctx c{};
+  Saved s;
   int rc;
   if ((rc = make_dims(c.d, B, T, H, W, C, heads, d_ffn)) != AXVS_OK || (rc = check_ptrs(params)) != AXVS_OK ||
       (rc = check_ptrs(reinterpret_cast<const AxvsAxialLayerParams*>(grads))) != AXVS_OK)
     return rc;
-  Bump sb(saved), cb(scratch);
-  const Saved s = carve_saved(sb, c.d);
-  c.sc = carve_scratch(cb, c.d, true);
-  if (sb.off > saved_bytes || cb.off > scratch_bytes) return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
-  c.st = static_cast<hipStream_t>(stream);
-  c.scale = 1.f / sqrtf((float)c.d.D);
-  if ((rc = c.g.init(c.st)) != AXVS_OK) return rc;
+  if ((rc = train_setup(c, s, 2, true, saved, saved_bytes, scratch, scratch_bytes, stream)) != AXVS_OK) return rc;
   const Dims& d = c.d;
   const AxvsAxialLayerParams& p = *params;
   const AxvsAxialLayerGrads& g = *grads;
   const Scratch& sc = c.sc;
-  const long long M = d.M, sB = (long long)d.T * d.H * d.W, sT = (long long)d.H * d.W;
-  const size_t MC = (size_t)M * C, MF = (size_t)M * d.F;
+  const long long sB = (long long)d.T * d.H * d.W, sT = (long long)d.H * d.W;
   if (recompute) {   // rebuild the activations from (src, pos, seed) instead of having kept them since the forward pass
     if ((rc = forward(c, src, pos, sc.g0, p, s, p_dropout, p_attn_drop, seed)) != AXVS_OK) return rc;
   }
-  // norm2                                                                       WC/temporal_attention.py:184
-  c.colsum(d_out, M, C, g.norm2_b, s.u, s.mean2, s.rstd2, g.norm2_w);
-  hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, d_out, (const float*)s.u, p.norm2_w, (const float*)s.mean2,
-                     (const float*)s.rstd2, sc.g0, M, C);                                 // g0 = d u
-  // FFN: u = z + dropout3(linear2(r)), r = dropout2(relu(linear1(z)))             :181-183
-  const RowMap id{(int)M, (int)M, 1, M, M, 1, 0};
-  hipLaunchKernelGGL(tr_drop_bwd_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, (const float*)sc.g0, sc.t0, id, M, C, make_drop(p_dropout, seed, 6));
-  if ((rc = c.wgrad(sc.t0, s.r, g.linear2_w, M, C, d.F, g.linear2_b)) != AXVS_OK) return rc;
-  if ((rc = c.dgrad(sc.t0, p.linear2_w, sc.dr, M, C, d.F, 0.f)) != AXVS_OK) return rc;
-  hipLaunchKernelGGL(tr_relu_drop_bwd_kernel, dim3(blocks(MF / 4)), dim3(256), 0, c.st, sc.dr, (const float*)s.r, MF / 4, make_drop(p_dropout, seed, 5).scale);
-  if ((rc = c.wgrad(sc.dr, s.z, g.linear1_w, M, d.F, C, g.linear1_b)) != AXVS_OK) return rc;
-  if ((rc = c.dgrad(sc.dr, p.linear1_w, sc.g0, M, d.F, C, 1.f)) != AXVS_OK) return rc;   // g0 = d z = d u + d r W1
-  // norm1                                                                       :217
-  c.colsum(sc.g0, M, C, g.norm1_b, s.buf2, s.mean1, s.rstd1, g.norm1_w);
-  hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, (const float*)sc.g0, (const float*)s.buf2, p.norm1_w,
-                     (const float*)s.mean1, (const float*)s.rstd1, sc.g1, M, C);          // g1 = d buf2
+  if ((rc = tail_bwd(c, d_out, tail_params(p), tail_grads(g), s, p_dropout, seed)) != AXVS_OK) return rc;     // sc.g1 = d buf2
   // width pass, then height pass
   const RowMap rmw{d.T * d.W, d.W, d.H, sB, sT, 1, d.W};
   if ((rc = pass_bwd(c, sc.g1, s.buf1, pos, p.width_attn, g.width_attn, s.p[1], rmw, d.B * d.H, make_drop(p_dropout, seed, 3),
@@ -625,6 +716,58 @@ int axvs_axial_layer_train_bwd(const float* d_out, const float* src, const float
   const RowMap rmh{d.T * d.H, d.H, d.W, sB, sT, d.W, 1};
   if ((rc = pass_bwd(c, sc.g0, src, pos, p.height_attn, g.height_attn, s.p[0], rmh, d.B * d.W, make_drop(p_dropout, seed, 1),
                      make_drop(p_attn_drop, seed, 2), d_src, d_pos, false)) != AXVS_OK)
+    return rc;
+  return status();
+}
+
+// ---- the full T*H*W layer (TemporalTrajectoryAttentionLayer), training tier: the axial layer's pass and tail code -----------------------
+size_t axvs_traj_layer_train_saved_bytes(int B, int T, int HW, int C, int heads, int d_ffn) {
+  Dims d;
+  if (make_traj_dims(d, B, T, HW, C, heads, d_ffn) != AXVS_OK) return 0;
+  Bump b(nullptr);
+  carve_saved(b, d, 1);
+  return b.off;
+}
+
+size_t axvs_traj_layer_train_scratch_bytes(int B, int T, int HW, int C, int heads, int d_ffn, int backward) {
+  Dims d;
+  if (make_traj_dims(d, B, T, HW, C, heads, d_ffn) != AXVS_OK) return 0;
+  Bump b(nullptr);
+  carve_scratch(b, d, backward != 0);
+  return b.off;
+}
+
+int axvs_traj_layer_train_fwd(const float* src, const float* pos, float* out, const AxvsTrajLayerParams* params, int B, int T, int HW, int C,
+                              int heads, int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, void* saved, size_t saved_bytes, void* scratch,
+                              size_t scratch_bytes, void* stream) {
+  if (!src || !pos || !out || !params || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
+  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  Ctx c{};
+  Saved s;
+  int rc;
+  if ((rc = make_traj_dims(c.d, B, T, HW, C, heads, d_ffn)) != AXVS_OK || (rc = check_ptrs(params, "AxvsTrajLayerParams")) != AXVS_OK) return rc;
+  if ((rc = train_setup(c, s, 1, false, saved, saved_bytes, scratch, scratch_bytes, stream)) != AXVS_OK) return rc;
+  return traj_forward(c, src, pos, out, *params, s, p_dropout, p_attn_drop, seed);
+}
+
+int axvs_traj_layer_train_bwd(const float* d_out, const float* src, const float* pos, const AxvsTrajLayerParams* params, const AxvsTrajLayerGrads* grads,
+                              float* d_src, float* d_pos, int B, int T, int HW, int C, int heads, int d_ffn, float p_dropout, float p_attn_drop,
+                              unsigned seed, int recompute, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!d_out || !src || !pos || !params || !grads || !d_src || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
+  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  Ctx c{};
+  Saved s;
+  int rc;
+  if ((rc = make_traj_dims(c.d, B, T, HW, C, heads, d_ffn)) != AXVS_OK || (rc = check_ptrs(params, "AxvsTrajLayerParams")) != AXVS_OK ||
+      (rc = check_ptrs(grads, "AxvsTrajLayerGrads")) != AXVS_OK)
+    return rc;
+  if ((rc = train_setup(c, s, 1, true, saved, saved_bytes, scratch, scratch_bytes, stream)) != AXVS_OK) return rc;
+  if (recompute) {
+    if ((rc = traj_forward(c, src, pos, c.sc.g0, *params, s, p_dropout, p_attn_drop, seed)) != AXVS_OK) return rc;
+  }
+  if ((rc = tail_bwd(c, d_out, tail_params(*params), tail_grads(*grads), s, p_dropout, seed)) != AXVS_OK) return rc;     // sc.g1 = d buf2
+  if ((rc = pass_bwd(c, c.sc.g1, src, pos, params->temporal_attn, grads->temporal_attn, s.p[0], traj_rowmap(c.d), B, make_drop(p_dropout, seed, 1),
+                     make_drop(p_attn_drop, seed, 2), d_src, d_pos, true)) != AXVS_OK)
     return rc;
   return status();
 }

@@ -8,8 +8,9 @@ Same constructor arguments, attribute / parameter names (state-dict keys) and ca
 so checkpoints load with ``strict=True`` and the callers (WC/msdeformattn.py:262, TL:623-627) are unchanged.
 ``forward`` hands raw device pointers to libaxvs.so; PyTorch only owns the memory and the stream.
 
-Forward-only: modules must be in ``eval()`` mode (the training path with dropout / autograd is out of scope,
-SURVEY.md section 8f).  There is no CPU fallback -- tensors must live on the GPU.
+Forward-only, except TemporalAxialTrajectoryAttentionLayer and TemporalTrajectoryAttentionLayer (and the TemporalEncoder built
+from either): those run their training tier in ``train()`` mode (axial_vs_amd/training.py); every other module must be in
+``eval()`` mode.  There is no CPU fallback -- tensors must live on the GPU.
 """
 from __future__ import annotations
 
@@ -128,7 +129,7 @@ def _dev_f32(t: Tensor, what: str) -> Tensor:
 def _require_eval(m: nn.Module) -> None:
     if m.training:
         raise NotImplementedError("axial_vs_amd: this module has a forward-only HIP path -- call .eval() (the training tier covers "
-                                  "TemporalAxialTrajectoryAttentionLayer / TemporalEncoder('axial-trajectory'), axial_vs_amd/training.py)")
+                                  "TemporalAxialTrajectoryAttentionLayer / TemporalTrajectoryAttentionLayer / TemporalEncoder, axial_vs_amd/training.py)")
 
 
 def _ptr(t: Optional[Tensor]) -> Optional[int]:
@@ -724,7 +725,11 @@ class TemporalAxialTrajectoryAttentionLayer(nn.Module):
 class TemporalTrajectoryAttentionLayer(nn.Module):
     """Full T*H*W trajectory attention (WC/temporal_attention.py:103-155, `temporal_attn_type="trajectory"`): ONE
     TrajectoryAttention over all tokens of a clip, then norm1 -> FFN -> norm2.  Unused by every shipped config (all select
-    'axial-trajectory'); same parameter names; returns (src', None, None) like the reference."""
+    'axial-trajectory'); same parameter names; returns (src', None, None) like the reference.
+
+    ``train()`` mode: the fp32 training tier (`axial_vs_amd.training.traj_layer_train`; frames of any length at head_dim 32).
+    ``eval()`` mode: the 16-bit inference tier, or -- mfma_dtype='f32', or head_dim 64 -- the training tier's forward with dropout
+    off (fp32 throughout; head_dim 64 holds a frame in LDS: at most 320 keys)."""
 
     def __init__(self, d_model=256, d_ffn=1024, dropout=0.0, attn_drop=0.0, activation="relu", n_heads=8,
                  mfma_dtype: Optional[str] = None):
@@ -740,10 +745,16 @@ class TemporalTrajectoryAttentionLayer(nn.Module):
         self.norm2 = nn.LayerNorm(d_model)
         self.n_heads = n_heads
         self.mfma_dtype = mfma_dtype
+        # train() mode, as on TemporalAxialTrajectoryAttentionLayer: True = backward rebuilds the activations from (src, pos, seed);
+        # fixed dropout seed (tests) or None = drawn from torch's CPU generator
+        self.recompute = False
+        self.dropout_seed: Optional[int] = None
         self._packed: Optional[Tensor] = None
         self._packed_key = None
 
     def _dtype(self) -> str:
+        if self.mfma_dtype == "f32" or self.linear1.in_features // self.n_heads > 32:
+            return "f32"          # the training tier's forward (head_dim 64: the 16-bit kernels stop at 32)
         return self.mfma_dtype or default_operand_dtype()
 
     def _pack(self) -> Tensor:
@@ -775,7 +786,16 @@ class TemporalTrajectoryAttentionLayer(nn.Module):
         :param src: tensor of shape [B*T, H*W, C]
         :param pos: tensor of shape [B, T, H, W, C]
         """
-        _require_eval(self)
+        if self.training:
+            if not src.is_cuda:        # (before the library is touched)
+                raise NotImplementedError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
+            from .training import traj_layer_train
+            return traj_layer_train(self, src, pos, recompute=self.recompute), None, None
+        if self._dtype() == "f32":
+            # fp32 tier: the training tier's forward with dropout off, as TemporalAxialTrajectoryAttentionLayer does
+            from .training import traj_layer_train
+            with torch.no_grad(), torch.autocast(device_type="cuda", enabled=False):
+                return traj_layer_train(self, src, pos, dropout=False), None, None
         B, T, H, W = pos.shape[:4]
         s, p = _dev_f32(src, "src"), _dev_f32(pos, "pos")
         C_ = s.shape[-1]

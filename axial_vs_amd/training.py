@@ -1,4 +1,6 @@
-"""Training path of TemporalAxialTrajectoryAttentionLayer: autograd over libaxvs.so's training tier.
+"""Training path of TemporalAxialTrajectoryAttentionLayer and of the full T*H*W TemporalTrajectoryAttentionLayer:
+autograd over libaxvs.so's training tier (``axvs_traj_layer_train_fwd`` / ``_bwd`` for the full layer: the same pass and tail code, one
+pass over all T*H*W tokens of a clip; frames longer than LDS holds run on chunked-key attention kernels).
 
 Reference: the layer in ``train()`` mode under autograd, WC/temporal_attention.py:187-220 (and TrajectoryAttention :35-76), as the
 shipped configs train it (``ATTN_DROP: 0.1``, AMP -- VK/configs/VIPSeg/.../maxtron_wc_convnext_large.yaml).  The forward and the
@@ -45,6 +47,18 @@ def layer_parameters(layer) -> List[Tensor]:
     return ps
 
 
+def traj_layer_parameters(layer) -> List[Tensor]:
+    """A TemporalTrajectoryAttentionLayer's parameters in AxvsTrajLayerParams field order (include/axvs.h)."""
+    ps: List[Tensor] = []
+    for n in _TRAJ:
+        m = getattr(layer.temporal_attn, n)
+        ps += [m.weight, m.bias]
+    for n in _TAIL:
+        m = getattr(layer, n)
+        ps += [m.weight, m.bias]
+    return ps
+
+
 def _struct(ptrs: List[int]) -> _lib.AxvsAxialLayerParams:
     s = _lib.AxvsAxialLayerParams()
     s.height_attn = _lib.AxvsTrajParams(*ptrs[0:12])
@@ -54,6 +68,19 @@ def _struct(ptrs: List[int]) -> _lib.AxvsAxialLayerParams:
     return s
 
 
+def _traj_struct(ptrs: List[int]) -> _lib.AxvsTrajLayerParams:
+    s = _lib.AxvsTrajLayerParams()
+    s.temporal_attn = _lib.AxvsTrajParams(*ptrs[0:12])
+    for name, p in zip(("norm1_w", "norm1_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b", "norm2_w", "norm2_b"), ptrs[12:20]):
+        setattr(s, name, p)
+    return s
+
+
+# the two layers' entry points: (library symbol prefix, parameter struct builder); `dims` is the size argument list of each
+_AXIAL = ("axvs_axial_layer_train", _struct)
+_FULL = ("axvs_traj_layer_train", _traj_struct)
+
+
 def _f32c(t: Tensor) -> Tensor:
     t = t.detach()
     if t.dtype != torch.float32:
@@ -61,24 +88,26 @@ def _f32c(t: Tensor) -> Tensor:
     return t.contiguous()
 
 
-class _AxialLayerTrain(torch.autograd.Function):
+class _LayerTrain(torch.autograd.Function):
+    """forward / backward of one layer through the library's training tier (`kind`: _AXIAL or _FULL)."""
+
     @staticmethod
-    def forward(ctx, src, pos, dims, p_dropout, p_attn_drop, seed, recompute, *params):
+    def forward(ctx, src, pos, kind, dims, p_dropout, p_attn_drop, seed, recompute, *params):
         from .modules import _stream, _workspace
-        B, T, H, W, C_, heads, F = dims
+        name, make = kind
         if not src.is_cuda:
             raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
         s, p = _f32c(src), _f32c(pos)
         ws = [_f32c(w) for w in params]
         L = _lib.lib()
         dev = s.device
-        nsaved = L.axvs_axial_layer_train_saved_bytes(B, T, H, W, C_, heads, F)
+        nsaved = getattr(L, name + "_saved_bytes")(*dims)
         if nsaved == 0:
-            raise RuntimeError("axvs_axial_layer_train_saved_bytes: " + L.axvs_last_error().decode())
+            raise RuntimeError(name + "_saved_bytes: " + L.axvs_last_error().decode())
         with torch.cuda.device(dev):
             out = torch.empty_like(s)
             # with recompute the forward's activations are scratch too: they live in the shared workspace, after the scratch part
-            nscr = L.axvs_axial_layer_train_scratch_bytes(B, T, H, W, C_, heads, F, 0)
+            nscr = getattr(L, name + "_scratch_bytes")(*dims, 0)
             if recompute:
                 buf = _workspace(dev, nscr + nsaved)
                 scratch_ptr, saved_ptr, saved = buf.data_ptr(), buf.data_ptr() + nscr, None
@@ -86,13 +115,13 @@ class _AxialLayerTrain(torch.autograd.Function):
                 saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
                 buf = _workspace(dev, nscr)
                 scratch_ptr, saved_ptr = buf.data_ptr(), saved.data_ptr()
-            st = _struct([w.data_ptr() for w in ws])
-            _lib.check(L.axvs_axial_layer_train_fwd(s.data_ptr(), p.data_ptr(), out.data_ptr(), C.byref(st), B, T, H, W, C_, heads, F,
-                                                    float(p_dropout), float(p_attn_drop), int(seed), saved_ptr, nsaved, scratch_ptr, nscr,
-                                                    _stream(dev)), "axvs_axial_layer_train_fwd")
+            st = make([w.data_ptr() for w in ws])
+            _lib.check(getattr(L, name + "_fwd")(s.data_ptr(), p.data_ptr(), out.data_ptr(), C.byref(st), *dims, float(p_dropout),
+                                                 float(p_attn_drop), int(seed), saved_ptr, nsaved, scratch_ptr, nscr, _stream(dev)),
+                       name + "_fwd")
         ctx.save_for_backward(s, p, *ws)
         ctx.amp = _lib.current_amp()
-        ctx.cfg = (dims, float(p_dropout), float(p_attn_drop), int(seed), bool(recompute))
+        ctx.cfg = (kind, dims, float(p_dropout), float(p_attn_drop), int(seed), bool(recompute))
         ctx.saved_buf = saved
         ctx.in_dtypes = (src.dtype, pos.dtype, [w.dtype for w in params])
         ctx.shapes = (src.shape, pos.shape)
@@ -103,8 +132,8 @@ class _AxialLayerTrain(torch.autograd.Function):
     def backward(ctx, d_out):
         from .modules import _stream, _workspace
         s, p, *ws = ctx.saved_tensors
-        dims, p_dropout, p_attn_drop, seed, recompute = ctx.cfg
-        B, T, H, W, C_, heads, F = dims
+        kind, dims, p_dropout, p_attn_drop, seed, recompute = ctx.cfg
+        name, make = kind
         L = _lib.lib()
         dev = s.device
         with torch.cuda.device(dev):
@@ -118,49 +147,71 @@ class _AxialLayerTrain(torch.autograd.Function):
             for w, n in zip(ws, sizes):
                 grads.append(flat[off:off + n].view(w.shape))
                 off += n
-            nsaved = L.axvs_axial_layer_train_saved_bytes(B, T, H, W, C_, heads, F)
-            nscr = L.axvs_axial_layer_train_scratch_bytes(B, T, H, W, C_, heads, F, 1)
+            nsaved = getattr(L, name + "_saved_bytes")(*dims)
+            nscr = getattr(L, name + "_scratch_bytes")(*dims, 1)
             if recompute:
                 buf = _workspace(dev, nscr + nsaved)
                 scratch_ptr, saved_ptr = buf.data_ptr(), buf.data_ptr() + nscr
             else:
                 buf = _workspace(dev, nscr)
                 scratch_ptr, saved_ptr = buf.data_ptr(), ctx.saved_buf.data_ptr()
-            st = _struct([w.data_ptr() for w in ws])
-            gs = _struct([t.data_ptr() for t in grads])
+            st = make([w.data_ptr() for w in ws])
+            gs = make([t.data_ptr() for t in grads])       # (the gradient structs have the parameter structs' layout)
             with _lib.train_amp(ctx.amp):
-                _lib.check(L.axvs_axial_layer_train_bwd(g.data_ptr(), s.data_ptr(), p.data_ptr(), C.byref(st), C.byref(gs), d_src.data_ptr(),
-                                                        d_pos.data_ptr() if want_pos else None, B, T, H, W, C_, heads, F, p_dropout, p_attn_drop,
-                                                        seed, int(recompute), saved_ptr, nsaved, scratch_ptr, nscr, _stream(dev)),
-                           "axvs_axial_layer_train_bwd")
+                _lib.check(getattr(L, name + "_bwd")(g.data_ptr(), s.data_ptr(), p.data_ptr(), C.byref(st), C.byref(gs), d_src.data_ptr(),
+                                                     d_pos.data_ptr() if want_pos else None, *dims, p_dropout, p_attn_drop, seed,
+                                                     int(recompute), saved_ptr, nsaved, scratch_ptr, nscr, _stream(dev)),
+                           name + "_bwd")
         # (the saved activations stay with ctx until autograd releases it: a second backward through the same graph --
         #  retain_graph=True, shared subgraphs -- finds them again)
         sd, pd, wd = ctx.in_dtypes
         out_grads = [gr.to(dt) for gr, dt in zip(grads, wd)]
-        return (d_src.view(ctx.shapes[0]).to(sd), d_pos.view(ctx.shapes[1]).to(pd) if want_pos else None, None, None, None, None, None,
+        return (d_src.view(ctx.shapes[0]).to(sd), d_pos.view(ctx.shapes[1]).to(pd) if want_pos else None, None, None, None, None, None, None,
                 *out_grads)
 
 
-def axial_layer_train(layer, src: Tensor, pos: Tensor, dropout: bool = True, recompute: bool = True) -> Tensor:
-    """Differentiable forward of a TemporalAxialTrajectoryAttentionLayer through the training tier.
-    src [(B T),(H W),C], pos [B,T,H,W,C] -> out like src (fp32).  dropout=False: probabilities forced to 0 (gradients in eval mode)."""
+def _check_tail(layer) -> None:
     if layer.activation != "relu":
         raise NotImplementedError("axial_vs_amd: only activation='relu' (every shipped config) has a HIP path")
     if abs(layer.norm1.eps - 1e-5) > 0 or abs(layer.norm2.eps - 1e-5) > 0:
         raise NotImplementedError("axial_vs_amd: LayerNorm eps must be 1e-5")
-    B, T, H, W = pos.shape[:4]
-    C_ = src.shape[-1]
-    if src.numel() != B * T * H * W * C_ or pos.shape[-1] != C_:
-        raise RuntimeError(f"src {tuple(src.shape)} does not match pos {tuple(pos.shape)}")
+
+
+def _apply(layer, src: Tensor, pos: Tensor, kind, dims, dropout: bool, recompute: bool, params: List[Tensor]) -> Tensor:
     p_drop = float(layer.dropout2.p) if dropout else 0.0        # = the attention maps' dropout (reference :164-165) = dropout2 = dropout3
     p_attn = float(layer.dropout1.p) if dropout else 0.0
     seed = getattr(layer, "dropout_seed", None)
     if seed is None:
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p_drop > 0 or p_attn > 0) else 0
-    dims = (int(B), int(T), int(H), int(W), int(C_), int(layer.n_heads), int(layer.linear1.out_features))
-    args = (src, pos, dims, p_drop, p_attn, int(seed), bool(recompute), *layer_parameters(layer))
+    args = (src, pos, kind, dims, p_drop, p_attn, int(seed), bool(recompute), *params)
     if torch.is_autocast_enabled():
         amp = _lib.autocast_mode(layer)       # (read before autocast is switched off for the call)
         with torch.autocast(device_type="cuda", enabled=False), _lib.train_amp(amp):
-            return _AxialLayerTrain.apply(*args)
-    return _AxialLayerTrain.apply(*args)
+            return _LayerTrain.apply(*args)
+    return _LayerTrain.apply(*args)
+
+
+def axial_layer_train(layer, src: Tensor, pos: Tensor, dropout: bool = True, recompute: bool = True) -> Tensor:
+    """Differentiable forward of a TemporalAxialTrajectoryAttentionLayer through the training tier.
+    src [(B T),(H W),C], pos [B,T,H,W,C] -> out like src (fp32).  dropout=False: probabilities forced to 0 (gradients in eval mode)."""
+    _check_tail(layer)
+    B, T, H, W = pos.shape[:4]
+    C_ = src.shape[-1]
+    if src.numel() != B * T * H * W * C_ or pos.shape[-1] != C_:
+        raise RuntimeError(f"src {tuple(src.shape)} does not match pos {tuple(pos.shape)}")
+    dims = (int(B), int(T), int(H), int(W), int(C_), int(layer.n_heads), int(layer.linear1.out_features))
+    return _apply(layer, src, pos, _AXIAL, dims, dropout, recompute, layer_parameters(layer))
+
+
+def traj_layer_train(layer, src: Tensor, pos: Tensor, dropout: bool = True, recompute: bool = True) -> Tensor:
+    """Differentiable forward of a TemporalTrajectoryAttentionLayer (the full T*H*W layer, WC/temporal_attention.py:103-155) through
+    the training tier: one trajectory attention over all T*H*W tokens of a clip, frames of H*W keys.  src [(B T),(H W),C],
+    pos [B,T,H,W,C] -> out like src (fp32).  dropout=False: probabilities forced to 0.  Activations kept: (9 + 3 T) C + d_ffn
+    floats per token -- no T*H*W x H*W attention map, which the reference's autograd holds twice."""
+    _check_tail(layer)
+    B, T, H, W = pos.shape[:4]
+    C_ = src.shape[-1]
+    if src.numel() != B * T * H * W * C_ or pos.shape[-1] != C_:
+        raise RuntimeError(f"src {tuple(src.shape)} does not match pos {tuple(pos.shape)}")
+    dims = (int(B), int(T), int(H * W), int(C_), int(layer.n_heads), int(layer.linear1.out_features))
+    return _apply(layer, src, pos, _FULL, dims, dropout, recompute, traj_layer_parameters(layer))

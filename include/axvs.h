@@ -460,6 +460,31 @@ int axvs_axial_layer_train_bwd(const float* d_out, const float* src, const float
                                int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, int recompute, void* saved, size_t saved_bytes,
                                void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- the same tier for TemporalTrajectoryAttentionLayer (the full T*H*W layer, temporal_attn_type = "trajectory"):
+ *      WC/temporal_attention.py:103-155 in train() mode under autograd -- ONE TrajectoryAttention over all T*HW tokens of a clip
+ *      (q = k = src + pos, v = src, frames of HW keys), residual, norm1, FFN, norm2.  Arguments as for the axial layer with HW in
+ *      place of H, W.  Dropout sites (element index = the element's offset in the reference's tensor at that site):
+ *        1  the attention map [(B heads), T HW, T, HW]    (`dropout`, the attention's attn_drop: :109, :55)
+ *        2  the attention output [B, T HW, C]              (dropout1 = `attn_drop`: :110, :145)
+ *        5  the FFN hidden [M, F], 6  the FFN output [M, C] (dropout2 / dropout3 = `dropout`: :124-128)
+ *      The attention map's indices pass 2^31 at [1,4,256,64,64]: they are formed in 64 bits.  head_dim 32 takes frames of any
+ *      length (keys chunked through LDS, online softmax); head_dim 8 / 16 / 64 hold a frame in LDS: HW <= 2560 / 1280 / 320
+ *      (the size functions return 0, axvs_last_error() names the bound).  T <= 16, B*T*HW*T < 2^31. */
+typedef struct AxvsTrajLayerGrads {   /* same field order as AxvsTrajLayerParams; every buffer is WRITTEN (not accumulated) */
+  AxvsTrajGrads temporal_attn;
+  float *norm1_w, *norm1_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b, *norm2_w, *norm2_b;
+} AxvsTrajLayerGrads;
+size_t axvs_traj_layer_train_saved_bytes(int B, int T, int HW, int C, int heads, int d_ffn);
+size_t axvs_traj_layer_train_scratch_bytes(int B, int T, int HW, int C, int heads, int d_ffn, int backward);
+/* src fp32 [(B T), HW, C]; pos fp32 [B,T,H,W,C] (= [B, T HW, C]); out like src */
+int axvs_traj_layer_train_fwd(const float* src, const float* pos, float* out, const AxvsTrajLayerParams* params, int B, int T, int HW, int C,
+                              int heads, int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, void* saved, size_t saved_bytes,
+                              void* scratch, size_t scratch_bytes, void* stream);
+int axvs_traj_layer_train_bwd(const float* d_out, const float* src, const float* pos, const AxvsTrajLayerParams* params,
+                              const AxvsTrajLayerGrads* grads, float* d_src, float* d_pos, int B, int T, int HW, int C, int heads, int d_ffn,
+                              float p_dropout, float p_attn_drop, unsigned seed, int recompute, void* saved, size_t saved_bytes, void* scratch,
+                              size_t scratch_bytes, void* stream);
+
 /* =====================================================================================================
  * Training tier of the cross-clip tracking module: CrossClipTrackingModule.forward in train() mode,
  * CC/maxtron_cross_clip_tracking_module.py:275-322 under autograd -- the module the reference trains on its own with the
