@@ -187,6 +187,13 @@ SIGNATURES = {
     "axvs_msda_layer_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, _fp, C.POINTER(C.c_int), _fp, _fp] + [C.c_int] * 8 + [_fp, C.c_size_t, _fp]),
     "axvs_msda_core_fwd": (C.c_int, [_fp, C.POINTER(C.c_int), _fp, _fp, _fp] + [C.c_int] * 7 + [_fp]),
     "axvs_msda_core_bwd": (C.c_int, [_fp, C.POINTER(C.c_int), _fp, _fp, _fp, _fp, _fp, _fp] + [C.c_int] * 7 + [_fp]),
+    "axvs_msda_layer_train_saved_bytes": (C.c_size_t, [C.c_int] * 7),
+    "axvs_msda_layer_train_scratch_bytes": (C.c_size_t, [C.c_int] * 8),
+    "axvs_msda_layer_train_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, _fp, C.POINTER(C.c_int), _fp, C.POINTER(AxvsMsdaLayerParams)] + [C.c_int] * 7 +
+                                  [C.c_float, C.c_float, C.c_uint, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
+    "axvs_msda_layer_train_bwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, _fp, C.POINTER(C.c_int), C.POINTER(AxvsMsdaLayerParams),
+                                            C.POINTER(AxvsMsdaLayerParams), _fp, _fp] + [C.c_int] * 7 +
+                                  [C.c_float, C.c_float, C.c_uint, C.c_int, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
     "axvs_cc_module_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "axvs_cc_module_fwd": (C.c_int, [_fp] * 5 + [C.POINTER(_fp), _fp] + [C.c_int] * 8 + [C.POINTER(C.c_int), C.c_int, _fp, C.c_size_t, _fp]),
     "axvs_tl_cc_module_workspace_bytes": (C.c_size_t, [C.c_int] * 5),

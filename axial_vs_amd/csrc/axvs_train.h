@@ -1312,5 +1312,108 @@ __global__ __launch_bounds__(256) void tr_scale_kernel(float* __restrict__ y, si
   reinterpret_cast<float4*>(y)[i] = v;
 }
 
+// ---- the deformable encoder layer (MSDeformAttnTransformerEncoderLayer, WC/msdeformattn.py:177-216): the sampling head of its
+//      attention (OPS/modules/ms_deform_attn.py:98-117) around the fp32 core op of the inference library ------------------------------
+constexpr int kMdMaxLevels = 8;   // = the core op's level bound
+constexpr int kMdMaxLP = 32;      // n_levels * n_points: one thread holds a (row, head)'s logits in registers
+
+struct MdLevels {
+  float w[kMdMaxLevels], h[kMdMaxLevels];   // W_l, H_l (the offsets of 2-dim reference points are in pixels of their level)
+  int L, P;
+};
+
+// rows flagged in `mask` (one byte per row, non-zero = padded key) are zeroed: value_proj(src).masked_fill (:99-100) and its gradient
+__global__ __launch_bounds__(256) void md_zero_rows_kernel(float* __restrict__ x, const unsigned char* __restrict__ mask, long long M, int C) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int n4 = C / 4;
+  if (i >= (size_t)M * n4) return;
+  if (mask[i / n4]) reinterpret_cast<float4*>(x)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// sampling head, forward: one thread per (query row r, head m).  offlog [rows][heads L P 2 | heads L P]: the fused GEMM of the
+// sampling_offsets and attention_weights Linears.  aw [rows][heads][L P] = softmax of the row's L P logits (:103-104);
+// loc [rows][heads][L][P][2] = ref + off / (W_l, H_l) (2-dim points, :107-109) or ref[:2] + off / P * ref[2:] * 0.5 (boxes, :110-113)
+__global__ __launch_bounds__(256) void md_head_fwd_kernel(const float* __restrict__ offlog, const float* __restrict__ ref, int ref_dim,
+                                                         float* __restrict__ loc, float* __restrict__ aw, long long rows, int heads, MdLevels lv) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * heads) return;
+  const long long r = i / heads;
+  const int m = (int)(i - r * heads);
+  const int L = lv.L, P = lv.P, LP = L * P;
+  const long long NO = (long long)heads * LP * 3;
+  const float* const lg = offlog + r * NO + (long long)heads * LP * 2 + (long long)m * LP;
+  float e[kMdMaxLP];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < kMdMaxLP; ++j)
+    if (j < LP) {
+      e[j] = lg[j];
+      mx = fmaxf(mx, e[j]);
+    }
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < kMdMaxLP; ++j)
+    if (j < LP) {
+      e[j] = expf(e[j] - mx);
+      sum += e[j];
+    }
+  const float inv = 1.f / sum;
+  float* const a = aw + i * LP;
+#pragma unroll
+  for (int j = 0; j < kMdMaxLP; ++j)
+    if (j < LP) a[j] = e[j] * inv;
+  const float* const of = offlog + r * NO + (long long)m * LP * 2;
+  const float* const rp = ref + r * L * ref_dim;
+  float* const lo = loc + i * LP * 2;
+  for (int l = 0; l < L; ++l) {
+    const float rx = rp[l * ref_dim], ry = rp[l * ref_dim + 1];
+    for (int p = 0; p < P; ++p) {
+      const int j = l * P + p;
+      const float ox = of[2 * j], oy = of[2 * j + 1];
+      if (ref_dim == 2) {
+        lo[2 * j] = rx + ox / lv.w[l];
+        lo[2 * j + 1] = ry + oy / lv.h[l];
+      } else {
+        lo[2 * j] = rx + ox / (float)P * rp[l * 4 + 2] * 0.5f;
+        lo[2 * j + 1] = ry + oy / (float)P * rp[l * 4 + 3] * 0.5f;
+      }
+    }
+  }
+}
+
+// sampling head, backward: from the core op's gradients of the locations and weights to d_offlog (offlog's layout).
+// d_logits = w (g - sum w g) over the row's L P weights; d_off = grad_loc times the factor each offset entered its location with.
+// The reference points are constants (every caller builds them from the shapes): no gradient.
+__global__ __launch_bounds__(256) void md_head_bwd_kernel(const float* __restrict__ gloc, const float* __restrict__ gaw, const float* __restrict__ aw,
+                                                         const float* __restrict__ ref, int ref_dim, float* __restrict__ d_offlog, long long rows,
+                                                         int heads, MdLevels lv) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * heads) return;
+  const long long r = i / heads;
+  const int m = (int)(i - r * heads);
+  const int L = lv.L, P = lv.P, LP = L * P;
+  const long long NO = (long long)heads * LP * 3;
+  const float* const a = aw + i * LP;
+  const float* const g = gaw + i * LP;
+  float dot = 0.f;
+  for (int j = 0; j < LP; ++j) dot += a[j] * g[j];
+  float* const dl = d_offlog + r * NO + (long long)heads * LP * 2 + (long long)m * LP;
+  for (int j = 0; j < LP; ++j) dl[j] = a[j] * (g[j] - dot);
+  const float* const gl = gloc + i * LP * 2;
+  const float* const rp = ref + r * L * ref_dim;
+  float* const dof = d_offlog + r * NO + (long long)m * LP * 2;
+  for (int l = 0; l < L; ++l)
+    for (int p = 0; p < P; ++p) {
+      const int j = l * P + p;
+      if (ref_dim == 2) {
+        dof[2 * j] = gl[2 * j] / lv.w[l];
+        dof[2 * j + 1] = gl[2 * j + 1] / lv.h[l];
+      } else {
+        dof[2 * j] = gl[2 * j] / (float)P * rp[l * 4 + 2] * 0.5f;
+        dof[2 * j + 1] = gl[2 * j + 1] / (float)P * rp[l * 4 + 3] * 0.5f;
+      }
+    }
+}
+
 }  // namespace tr
 }  // namespace axvs

@@ -517,7 +517,8 @@ int status() {
   return AXVS_OK;
 }
 
-int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, float p_drop, unsigned seed);
+// site_h / site_o: dropout sites of the FFN hidden and output (5, 6 in the trajectory layers)
+int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, float p_drop, unsigned seed, unsigned site_h = 5, unsigned site_o = 6);
 
 int forward(const Ctx& c, const float* src, const float* pos, float* out, const AxvsAxialLayerParams& p, const Saved& s, float p_drop,
             float p_attn, unsigned seed) {
@@ -536,21 +537,21 @@ int forward(const Ctx& c, const float* src, const float* pos, float* out, const 
   return tail_fwd(c, tail_params(p), s, out, p_drop, seed);
 }
 
-// norm1 -> FFN -> norm2 on s.buf2 (dropout sites 5, 6)    WC/temporal_attention.py:181-185, :217-218 (:150-155 in the full layer)
-int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, float p_drop, unsigned seed) {
+// norm1 -> FFN -> norm2 on s.buf2 (dropout sites site_h, site_o)    WC/temporal_attention.py:181-185, :217-218 (:150-155 in the full layer)
+int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, float p_drop, unsigned seed, unsigned site_h, unsigned site_o) {
   const Dims& d = c.d;
   const long long M = d.M;
   const int C = d.C;
   int rc;
   hipLaunchKernelGGL(tr_ln_fwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, (const float*)s.buf2, p.norm1_w, p.norm1_b, s.z, s.mean1, s.rstd1, M, C, 1e-5f);
   {   // linear1 + bias + ReLU + dropout2 in one launch
-    const GemmEpi e1{p.linear1_b, 1.f, 1, make_drop(p_drop, seed, 5), 0.f};
+    const GemmEpi e1{p.linear1_b, 1.f, 1, make_drop(p_drop, seed, site_h), 0.f};
     if ((rc = c.g.fwd(s.z, p.linear1_w, s.r, M, d.F, C, 0.f, &e1, g_train_exact != 0)) != AXVS_OK) return rc;
   }
   if ((rc = c.g.fwd(s.r, p.linear2_w, c.sc.t0, M, C, d.F, 0.f, nullptr, g_train_exact != 0)) != AXVS_OK) return rc;
   const RowMap id{(int)(M > INT32_MAX ? INT32_MAX : M), (int)(M > INT32_MAX ? INT32_MAX : M), 1, M, M, 1, 0};
   hipLaunchKernelGGL(tr_bias_drop_res_kernel, dim3(blocks((size_t)M * C / 4)), dim3(256), 0, c.st, (const float*)c.sc.t0, p.linear2_b, (const float*)s.z,
-                     s.u, id, M, C, make_drop(p_drop, seed, 6));
+                     s.u, id, M, C, make_drop(p_drop, seed, site_o));
   hipLaunchKernelGGL(tr_ln_fwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, (const float*)s.u, p.norm2_w, p.norm2_b, out, s.mean2, s.rstd2, M, C, 1e-5f);
   return status();
 }
@@ -568,7 +569,8 @@ int traj_forward(const Ctx& c, const float* src, const float* pos, float* out, c
 }
 
 // backward of the tail: d_out -> sc.g1 = gradient of s.buf2 (sc.g0 is overwritten)
-int tail_bwd(const Ctx& c, const float* d_out, const TailParams& p, const TailGrads& g, const Saved& s, float p_dropout, unsigned seed) {
+int tail_bwd(const Ctx& c, const float* d_out, const TailParams& p, const TailGrads& g, const Saved& s, float p_dropout, unsigned seed,
+             unsigned site_h = 5, unsigned site_o = 6) {
   const Dims& d = c.d;
   const Scratch& sc = c.sc;
   const long long M = d.M;
@@ -581,10 +583,10 @@ int tail_bwd(const Ctx& c, const float* d_out, const TailParams& p, const TailGr
                      (const float*)s.rstd2, sc.g0, M, C);                                 // g0 = d u
   // FFN: u = z + dropout3(linear2(r)), r = dropout2(relu(linear1(z)))             :181-183
   const RowMap id{(int)M, (int)M, 1, M, M, 1, 0};
-  hipLaunchKernelGGL(tr_drop_bwd_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, (const float*)sc.g0, sc.t0, id, M, C, make_drop(p_dropout, seed, 6));
+  hipLaunchKernelGGL(tr_drop_bwd_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, (const float*)sc.g0, sc.t0, id, M, C, make_drop(p_dropout, seed, site_o));
   if ((rc = c.wgrad(sc.t0, s.r, g.linear2_w, M, C, d.F, g.linear2_b)) != AXVS_OK) return rc;
   if ((rc = c.dgrad(sc.t0, p.linear2_w, sc.dr, M, C, d.F, 0.f)) != AXVS_OK) return rc;
-  hipLaunchKernelGGL(tr_relu_drop_bwd_kernel, dim3(blocks(MF / 4)), dim3(256), 0, c.st, sc.dr, (const float*)s.r, MF / 4, make_drop(p_dropout, seed, 5).scale);
+  hipLaunchKernelGGL(tr_relu_drop_bwd_kernel, dim3(blocks(MF / 4)), dim3(256), 0, c.st, sc.dr, (const float*)s.r, MF / 4, make_drop(p_dropout, seed, site_h).scale);
   if ((rc = c.wgrad(sc.dr, s.z, g.linear1_w, M, d.F, C, g.linear1_b)) != AXVS_OK) return rc;
   if ((rc = c.dgrad(sc.dr, p.linear1_w, sc.g0, M, d.F, C, 1.f)) != AXVS_OK) return rc;   // g0 = d z = d u + d r W1
   // norm1                                                                       :217
@@ -642,6 +644,187 @@ int convgn_check(int N, int HW, int Cin, int Cout, int G, int in_layout, int out
   if (in_layout == 1 && (in_ld % 4 || in_bs % 4 || in_ld < Cin)) return fail(AXVS_ERR_ARG, "token rows: strides must be multiples of 4 floats");
   if (out_layout == 1 && (out_ld % 4 || out_bs % 4 || out_ld < Cout)) return fail(AXVS_ERR_ARG, "token rows: strides must be multiples of 4 floats");
   return AXVS_OK;
+}
+
+// ---- MSDeformAttnTransformerEncoderLayer in train() mode (WC/msdeformattn.py:177-216 under autograd) ----------------------------------
+// value_proj (padded keys zeroed), the sampling_offsets | attention_weights GEMM on src + pos, the sampling head (md_head_*_kernel),
+// the fp32 core op of the library (axvs_msda_core_fwd / _bwd), output_proj, dropout1 + residual, then the trajectory layers' tail.
+// Dropout sites 7 (dropout1, [N, S, C]), 8 (dropout2, [N, S, d_ffn]), 9 (dropout3, [N, S, C]).
+constexpr unsigned kMdSite1 = 7, kMdSite2 = 8, kMdSite3 = 9;
+
+struct MdShape {
+  Dims d;                          // B = N, T = 1, H = 1, W = S: M = N S token rows
+  int N, S, L, P, LP, NO;          // NO = heads L P 3: width of the offsets | logits rows
+  int ref_dim;
+  int shapes[2 * kMdMaxLevels];    // (H_l, W_l)
+  MdLevels lv;
+};
+
+int make_md_shape(MdShape& m, int N, int S, int C, int heads, int L, int P, int F) {
+  if (N <= 0 || S <= 0 || L <= 0 || P <= 0) return fail(AXVS_ERR_ARG, "non-positive dimension");
+  if (L > kMdMaxLevels) return fail(AXVS_ERR_ARG, "deformable layer training tier: n_levels=%d > %d", L, kMdMaxLevels);
+  if (L * P > kMdMaxLP) return fail(AXVS_ERR_ARG, "deformable layer training tier: n_levels * n_points = %d > %d", L * P, kMdMaxLP);
+  if ((long long)heads * L * P % 8) return fail(AXVS_ERR_ARG, "deformable layer training tier: n_heads * n_levels * n_points = %d must be a multiple of 8", heads * L * P);
+  if (int rc = make_dims_any(m.d, N, 1, 1, S, C, heads, F)) return rc;
+  m.N = N; m.S = S; m.L = L; m.P = P; m.LP = L * P; m.NO = heads * L * P * 3;
+  m.lv.L = L;
+  m.lv.P = P;
+  return AXVS_OK;
+}
+
+// the run-time arguments the size functions do not see: reference-point form and spatial shapes (HOST ints)
+int md_levels(MdShape& m, int ref_dim, const int* spatial_shapes) {
+  if (ref_dim != 2 && ref_dim != 4) return fail(AXVS_ERR_ARG, "Last dim of reference_points must be 2 or 4, got %d", ref_dim);
+  m.ref_dim = ref_dim;
+  long long total = 0;
+  for (int l = 0; l < m.L; ++l) {
+    const int H = spatial_shapes[2 * l], W = spatial_shapes[2 * l + 1];
+    if (H <= 0 || W <= 0) return fail(AXVS_ERR_ARG, "empty level %d", l);
+    m.shapes[2 * l] = H;
+    m.shapes[2 * l + 1] = W;
+    m.lv.h[l] = (float)H;
+    m.lv.w[l] = (float)W;
+    total += (long long)H * W;
+  }
+  if (total != m.S) return fail(AXVS_ERR_ARG, "spatial shapes cover %lld tokens, src has %d", total, m.S);
+  return AXVS_OK;
+}
+
+struct MdSaved {
+  Saved t;                         // buf2 = src + dropout1(attention), then the tail's activations
+  float *value, *loc, *aw, *samp;  // value_proj(src) masked [M][C], locations, softmaxed weights, sampled rows [M][C]
+};
+struct MdScratch {
+  float *wcat, *bcat, *offlog;                  // [sampling_offsets; attention_weights] weight / bias, offsets | logits [M][NO]
+  float *dval, *dsamp, *gloc, *gaw, *doff;      // backward
+};
+
+MdSaved carve_md_saved(Bump& b, const MdShape& m) {
+  MdSaved s{};
+  const size_t MC = (size_t)m.d.M * m.d.C, MH = (size_t)m.d.M * m.d.heads * m.LP;
+  s.t = carve_saved(b, m.d, 0);
+  s.value = b.f(MC);
+  s.loc = b.f(MH * 2);
+  s.aw = b.f(MH);
+  s.samp = b.f(MC);
+  return s;
+}
+
+// the Scratch fields the shared code uses here: a, t0 (forward); g0, g1, dr, part_a / part_b, wpart, wt (backward)
+void carve_md_scratch(Bump& b, const MdShape& m, bool backward, Scratch& sc, MdScratch& x) {
+  const Dims& d = m.d;
+  const size_t MC = (size_t)d.M * d.C, MH = (size_t)d.M * d.heads * m.LP;
+  sc = Scratch{};
+  x = MdScratch{};
+  sc.a = b.f(MC);
+  sc.t0 = b.f(MC);
+  x.wcat = b.f((size_t)m.NO * d.C);
+  x.bcat = b.f(m.NO);
+  x.offlog = b.f((size_t)d.M * m.NO);
+  if (!backward) return;
+  sc.g0 = b.f(MC);
+  sc.g1 = b.f(MC);
+  sc.dr = b.f((size_t)d.M * d.F);
+  size_t wide = (size_t)(d.F > m.NO ? d.F : m.NO);
+  if (wide < (size_t)d.C) wide = d.C;
+  sc.part_a = b.f(kColsumBlocks * wide);
+  sc.part_b = b.f(kColsumBlocks * wide);
+  const size_t wmax = (size_t)d.C * wide;       // largest weight: linear1 / linear2 [F, C] or the fused [NO, C]
+  sc.wpart = b.f((Gemm::kSplit + 1) * wmax);
+  sc.wt = b.f(wmax);
+  x.dval = b.f(MC);
+  x.dsamp = b.f(MC);
+  x.gloc = b.f(MH * 2);
+  x.gaw = b.f(MH);
+  x.doff = b.f((size_t)d.M * m.NO);
+}
+
+int md_setup(Ctx& c, const MdShape& m, MdSaved& s, MdScratch& x, bool backward, void* saved, size_t saved_bytes, void* scratch,
+             size_t scratch_bytes, void* stream) {
+  Bump sb(saved), cb(scratch);
+  c.d = m.d;
+  s = carve_md_saved(sb, m);
+  carve_md_scratch(cb, m, backward, c.sc, x);
+  if (sb.off > saved_bytes || cb.off > scratch_bytes) return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
+  c.st = static_cast<hipStream_t>(stream);
+  c.scale = 1.f;
+  return c.g.init(c.st);
+}
+
+// [sampling_offsets; attention_weights] weight and bias, so that the query path is one GEMM (and one input-gradient GEMM)
+int md_concat_weights(const Ctx& c, const MdShape& m, const AxvsMsdaParams& a, const MdScratch& x) {
+  const size_t no = (size_t)m.d.heads * m.LP * 2, nl = (size_t)m.d.heads * m.LP, C = m.d.C;
+  if (hipMemcpyAsync(x.wcat, a.sampling_offsets_w, no * C * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess ||
+      hipMemcpyAsync(x.wcat + no * C, a.attention_weights_w, nl * C * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess ||
+      hipMemcpyAsync(x.bcat, a.sampling_offsets_b, no * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess ||
+      hipMemcpyAsync(x.bcat + no, a.attention_weights_b, nl * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
+    return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
+  return AXVS_OK;
+}
+
+inline RowMap md_rowmap(long long M) { return RowMap{(int)M, (int)M, 1, M, M, 1, 0}; }
+
+int md_forward(const Ctx& c, const MdShape& m, const MdScratch& x, const float* src, const float* pos, const float* ref,
+               const unsigned char* mask, float* out, const AxvsMsdaLayerParams& p, const MdSaved& s, float p_drop, float p_attn, unsigned seed) {
+  const Dims& d = c.d;
+  const long long M = d.M;
+  const int C = d.C;
+  const AxvsMsdaParams& a = p.self_attn;
+  const bool ex = g_train_exact != 0;
+  const Drop none = make_drop(0.f, 0, 0);
+  int rc;
+  // value = value_proj(src), rows of padded keys zeroed                       OPS/modules/ms_deform_attn.py:98-100
+  const GemmEpi ev{a.value_proj_b, 1.f, 0, none, 0.f};
+  if ((rc = c.g.fwd(src, a.value_proj_w, s.value, M, C, C, 0.f, &ev, ex)) != AXVS_OK) return rc;
+  if (mask) hipLaunchKernelGGL(md_zero_rows_kernel, dim3(blocks((size_t)M * C / 4)), dim3(256), 0, c.st, s.value, mask, M, C);
+  // offsets | logits = [sampling_offsets; attention_weights](src + pos): the sum is formed in the GEMM's loader    :101-104
+  if ((rc = md_concat_weights(c, m, a, x)) != AXVS_OK) return rc;
+  const GemmEpi eo{x.bcat, 1.f, 0, none, 0.f};
+  if ((rc = c.g.fwd(src, x.wcat, x.offlog, M, m.NO, C, 0.f, &eo, ex, pos)) != AXVS_OK) return rc;
+  hipLaunchKernelGGL(md_head_fwd_kernel, dim3(blocks((size_t)M * d.heads)), dim3(256), 0, c.st, (const float*)x.offlog, ref, m.ref_dim, s.loc, s.aw,
+                     M, d.heads, m.lv);
+  if ((rc = axvs_msda_core_fwd(s.value, m.shapes, s.loc, s.aw, s.samp, m.N, m.S, d.heads, d.D, m.S, m.L, m.P, c.st)) != AXVS_OK) return rc;
+  // buf2 = src + dropout1(output_proj(sampled))                                 WC/msdeformattn.py:210-211
+  if ((rc = c.g.fwd(s.samp, a.output_proj_w, c.sc.t0, M, C, C, 0.f, nullptr, ex)) != AXVS_OK) return rc;
+  hipLaunchKernelGGL(tr_bias_drop_res_kernel, dim3(blocks((size_t)M * C / 4)), dim3(256), 0, c.st, (const float*)c.sc.t0, a.output_proj_b, src, s.t.buf2,
+                     md_rowmap(M), M, C, make_drop(p_attn, seed, kMdSite1));
+  return tail_fwd(c, tail_params(p), s.t, out, p_drop, seed, kMdSite2, kMdSite3);                          // :211-215
+}
+
+int md_backward(const Ctx& c, const MdShape& m, const MdScratch& x, const float* d_out, const float* src, const float* pos, const float* ref,
+                const unsigned char* mask, const AxvsMsdaLayerParams& p, const AxvsMsdaLayerGrads& g, float* d_src, float* d_pos, const MdSaved& s,
+                float p_drop, float p_attn, unsigned seed) {
+  const Dims& d = c.d;
+  const Scratch& sc = c.sc;
+  const long long M = d.M;
+  const int C = d.C, HLP = d.heads * m.LP;
+  const size_t MC = (size_t)M * C;
+  const AxvsMsdaParams& a = p.self_attn;
+  int rc;
+  if ((rc = tail_bwd(c, d_out, tail_params(p), tail_grads(g), s.t, p_drop, seed, kMdSite2, kMdSite3)) != AXVS_OK) return rc;   // sc.g1 = d buf2
+  // output_proj and dropout1
+  hipLaunchKernelGGL(tr_drop_bwd_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, (const float*)sc.g1, sc.t0, md_rowmap(M), M, C, make_drop(p_attn, seed, kMdSite1));
+  if ((rc = c.wgrad(sc.t0, s.samp, g.self_attn.output_proj_w, M, C, C, g.self_attn.output_proj_b)) != AXVS_OK) return rc;
+  if ((rc = c.dgrad(sc.t0, a.output_proj_w, x.dsamp, M, C, C, 0.f)) != AXVS_OK) return rc;
+  // the core op: gradients of the value, the locations and the weights; padded keys get none
+  if ((rc = axvs_msda_core_bwd(s.value, m.shapes, s.loc, s.aw, x.dsamp, x.dval, x.gloc, x.gaw, m.N, m.S, d.heads, d.D, m.S, m.L, m.P, c.st)) != AXVS_OK)
+    return rc;
+  if (mask) hipLaunchKernelGGL(md_zero_rows_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, x.dval, mask, M, C);
+  hipLaunchKernelGGL(md_head_bwd_kernel, dim3(blocks((size_t)M * d.heads)), dim3(256), 0, c.st, (const float*)x.gloc, (const float*)x.gaw, (const float*)s.aw,
+                     ref, m.ref_dim, x.doff, M, d.heads, m.lv);
+  // weight gradients of the three input Linears
+  const float* const xa = pos ? sc.a : src;
+  if (pos) c.add(src, pos, sc.a, MC);
+  if ((rc = c.wgrad(x.doff, xa, g.self_attn.sampling_offsets_w, M, 2 * HLP, C, g.self_attn.sampling_offsets_b, m.NO)) != AXVS_OK) return rc;
+  if ((rc = c.wgrad(x.doff + 2 * HLP, xa, g.self_attn.attention_weights_w, M, HLP, C, g.self_attn.attention_weights_b, m.NO)) != AXVS_OK) return rc;
+  if ((rc = c.wgrad(x.dval, src, g.self_attn.value_proj_w, M, C, C, g.self_attn.value_proj_b)) != AXVS_OK) return rc;
+  // t0 = d(src + pos) through the query path; d_src = d buf2 (residual) + dval Wv + t0;  d_pos = t0
+  if ((rc = md_concat_weights(c, m, a, x)) != AXVS_OK) return rc;
+  if ((rc = c.dgrad(x.doff, x.wcat, sc.t0, M, m.NO, C, 0.f)) != AXVS_OK) return rc;
+  if ((rc = c.dgrad(x.dval, a.value_proj_w, d_src, M, C, C, 0.f, 0, false, 1.f, sc.g1, sc.t0)) != AXVS_OK) return rc;
+  if (d_pos && hipMemcpyAsync(d_pos, sc.t0, MC * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
+    return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
+  return status();
 }
 
 }  // namespace
@@ -772,6 +955,62 @@ int axvs_traj_layer_train_bwd(const float* d_out, const float* src, const float*
   return status();
 }
 
+// ---- MSDeformAttnTransformerEncoderLayer, training tier ------------------------------------------------------------------------
+size_t axvs_msda_layer_train_saved_bytes(int N, int S, int C, int heads, int L, int P, int d_ffn) {
+  MdShape m;
+  if (make_md_shape(m, N, S, C, heads, L, P, d_ffn) != AXVS_OK) return 0;
+  Bump b(nullptr);
+  carve_md_saved(b, m);
+  return b.off;
+}
+size_t axvs_msda_layer_train_scratch_bytes(int N, int S, int C, int heads, int L, int P, int d_ffn, int backward) {
+  MdShape m;
+  if (make_md_shape(m, N, S, C, heads, L, P, d_ffn) != AXVS_OK) return 0;
+  Bump b(nullptr);
+  Scratch sc;
+  MdScratch x;
+  carve_md_scratch(b, m, backward != 0, sc, x);
+  return b.off;
+}
+int axvs_msda_layer_train_fwd(const float* src, const float* pos, const float* reference_points, int ref_dim, const unsigned char* padding_mask,
+                              const int* spatial_shapes, float* out, const AxvsMsdaLayerParams* params, int N, int S, int C, int heads, int L, int P,
+                              int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, void* saved, size_t saved_bytes, void* scratch,
+                              size_t scratch_bytes, void* stream) {
+  if (!src || !reference_points || !spatial_shapes || !out || !params || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
+  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  MdShape m;
+  Ctx c{};
+  MdSaved s;
+  MdScratch x;
+  int rc;
+  if ((rc = make_md_shape(m, N, S, C, heads, L, P, d_ffn)) != AXVS_OK || (rc = md_levels(m, ref_dim, spatial_shapes)) != AXVS_OK ||
+      (rc = check_ptrs(params, "AxvsMsdaLayerParams")) != AXVS_OK)
+    return rc;
+  if ((rc = md_setup(c, m, s, x, false, saved, saved_bytes, scratch, scratch_bytes, stream)) != AXVS_OK) return rc;
+  return md_forward(c, m, x, src, pos, reference_points, padding_mask, out, *params, s, p_dropout, p_attn_drop, seed);
+}
+int axvs_msda_layer_train_bwd(const float* d_out, const float* src, const float* pos, const float* reference_points, int ref_dim,
+                              const unsigned char* padding_mask, const int* spatial_shapes, const AxvsMsdaLayerParams* params,
+                              const AxvsMsdaLayerGrads* grads, float* d_src, float* d_pos, int N, int S, int C, int heads, int L, int P, int d_ffn,
+                              float p_dropout, float p_attn_drop, unsigned seed, int recompute, void* saved, size_t saved_bytes, void* scratch,
+                              size_t scratch_bytes, void* stream) {
+  if (!d_out || !src || !reference_points || !spatial_shapes || !params || !grads || !d_src || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
+  if (d_pos && !pos) return fail(AXVS_ERR_ARG, "d_pos wanted without pos");
+  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  MdShape m;
+  Ctx c{};
+  MdSaved s;
+  MdScratch x;
+  int rc;
+  if ((rc = make_md_shape(m, N, S, C, heads, L, P, d_ffn)) != AXVS_OK || (rc = md_levels(m, ref_dim, spatial_shapes)) != AXVS_OK ||
+      (rc = check_ptrs(params, "AxvsMsdaLayerParams")) != AXVS_OK || (rc = check_ptrs(grads, "AxvsMsdaLayerGrads")) != AXVS_OK)
+    return rc;
+  if ((rc = md_setup(c, m, s, x, true, saved, saved_bytes, scratch, scratch_bytes, stream)) != AXVS_OK) return rc;
+  if (recompute) {   // rebuild the activations from (src, pos, seed)
+    if ((rc = md_forward(c, m, x, src, pos, reference_points, padding_mask, c.sc.g0, *params, s, p_dropout, p_attn_drop, seed)) != AXVS_OK) return rc;
+  }
+  return md_backward(c, m, x, d_out, src, pos, reference_points, padding_mask, *params, *grads, d_src, d_pos, s, p_dropout, p_attn_drop, seed);
+}
 // ---- cross-clip tracking module, training tier (axvs_cc_train_host.h) ---------------------------------------------------------------
 size_t axvs_cc_module_train_saved_bytes(const AxvsCCTrainCfg* cfg) {
   CCShape s;

@@ -4,9 +4,11 @@ Reference: OPS = MaXTron_Video-kMaX/maxtron_deeplab/modeling/within_clip_trackin
   `MSDeformAttn` (OPS/modules/ms_deform_attn.py:35-125; Tube-Link uses mmcv's MultiScaleDeformableAttention with the same
   math), `MSDeformAttnFunction` / `ms_deform_attn_core_pytorch` (OPS/functions/ms_deform_attn_func.py:33-77).
 Same constructor, parameter names (state-dict keys), initialisation and forward signature; forward runs in libaxvs.so.
-eval(): the fused module kernels (`axvs_msda_fwd`, `axvs_msda_layer_fwd`).  train(): the reference module's own arithmetic under
-torch autograd around `MSDeformAttnFunction`, whose forward AND backward are the HIP kernels of the native op
-(`axvs_msda_core_fwd` / `axvs_msda_core_bwd` = the extension's ms_deform_attn_forward / _backward).  GPU only.
+eval(): the fused module kernels (`axvs_msda_fwd`, `axvs_msda_layer_fwd`).  train(): the encoder layer runs the library's training
+tier (`axvs_msda_layer_train_fwd` / `_bwd`, axial_vs_amd.training.msda_layer_train); the standalone module, and the layer where the tier
+does not apply, run the reference module's own arithmetic under torch autograd around `MSDeformAttnFunction`, whose forward AND backward
+are the HIP kernels of the native op (`axvs_msda_core_fwd` / `axvs_msda_core_bwd` = the extension's ms_deform_attn_forward / _backward).
+GPU only.
 """
 from __future__ import annotations
 
@@ -259,6 +261,12 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
         self.norm2 = nn.LayerNorm(d_model)
         self.d_model, self.d_ffn = d_model, d_ffn
         self.mfma_dtype = mfma_dtype
+        # train() mode (and gradients in eval mode) on the library's training tier (axial_vs_amd.training.msda_layer_train):
+        # recompute = True rebuilds the activations in the backward from (src, pos, seed) instead of keeping them; dropout_seed fixes
+        # the dropout masks (None: drawn from torch's CPU generator); amp_compute = False keeps split-precision products under autocast
+        self.recompute = False
+        self.dropout_seed: Optional[int] = None
+        self.amp_compute = True
         self._packed = None
         self._packed_key = None
 
@@ -302,11 +310,31 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
         self._packed, self._packed_key = buf, key
         return buf
 
+    def _train_tier_takes(self, src, pos, reference_points, spatial_shapes, padding_mask) -> bool:
+        """Whether the training tier (axvs_msda_layer_train_*) runs this call: the dimensions within the bounds its size function
+        reports, constant reference points, LayerNorm eps 1e-5, one dropout probability for dropout2 / dropout3."""
+        a = self.self_attn
+        if not src.is_cuda or src.dim() != 3 or reference_points.requires_grad or reference_points.shape[-1] not in (2, 4):
+            return False
+        if self.norm1.eps != 1e-5 or self.norm2.eps != 1e-5 or self.dropout2.p != self.dropout3.p:
+            return False
+        shp = _shapes_host(spatial_shapes)
+        N, S = int(src.shape[0]), int(src.shape[1])
+        if sum(h * w for h, w in shp) != S or tuple(reference_points.shape[:3]) != (N, S, len(shp)) or src.shape[-1] != self.d_model:
+            return False
+        if (pos is not None and pos.shape != src.shape) or (padding_mask is not None and tuple(padding_mask.shape) != (N, S)):
+            return False
+        return _lib.lib().axvs_msda_layer_train_saved_bytes(N, S, self.d_model, a.n_heads, len(shp), a.n_points, self.d_ffn) > 0
+
     @_guarded
     def forward(self, src, pos, reference_points, spatial_shapes, level_start_index=None, padding_mask=None):
         if self.training or (torch.is_grad_enabled() and src.requires_grad):
-            # train() mode: the reference layer's forward (WC/msdeformattn.py:203-216) under torch autograd; the deformable attention
-            # op inside runs (forward and backward) on the HIP kernels through MSDeformAttnFunction
+            if self._train_tier_takes(src, pos, reference_points, spatial_shapes, padding_mask):
+                from .training import msda_layer_train
+                return msda_layer_train(self, src, pos, reference_points, spatial_shapes, padding_mask, dropout=self.training,
+                                        recompute=self.recompute)
+            # what the tier does not cover: the reference layer's forward (WC/msdeformattn.py:203-216) under torch autograd; the
+            # deformable attention op inside runs (forward and backward) on the HIP kernels through MSDeformAttnFunction
             src2 = self.self_attn(self.with_pos_embed(src, pos), reference_points, src, spatial_shapes, level_start_index, padding_mask)
             src = self.norm1(src + self.dropout1(src2))
             src2 = self.linear2(self.dropout2(F.relu(self.linear1(src))))

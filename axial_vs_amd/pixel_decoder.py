@@ -342,7 +342,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
         from .glue_training import conv_gn_train
         """train() mode (WC/msdeformattn.py:404-437, :91-174 under autograd): the 1x1 convolutions + GroupNorm run the library's training tier
         (round 6: axial_vs_amd.glue_training, forward and backward in HIP; rounds 3 - 5 used torch's kernels here), the level embeddings are torch parameters added by torch; the sine embeddings come from the library's kernels (constants); the encoder's layers run
-        their training tiers (deformable attention: HIP forward / backward of the op; axial-trajectory layers: axvs_axial_layer_train_*)."""
+        their training tiers (deformable layers: axvs_msda_layer_train_*; axial-trajectory layers: axvs_axial_layer_train_*)."""
         order = self.transformer_spatial_in_features[::-1]
         xs = [features[f] for f in order]
         BT = xs[0].shape[0]

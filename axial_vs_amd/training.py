@@ -1,6 +1,8 @@
 """Training path of TemporalAxialTrajectoryAttentionLayer and of the full T*H*W TemporalTrajectoryAttentionLayer:
 autograd over libaxvs.so's training tier (``axvs_traj_layer_train_fwd`` / ``_bwd`` for the full layer: the same pass and tail code, one
-pass over all T*H*W tokens of a clip; frames longer than LDS holds run on chunked-key attention kernels).
+pass over all T*H*W tokens of a clip; frames longer than LDS holds run on chunked-key attention kernels), and of the deformable
+encoder layer MSDeformAttnTransformerEncoderLayer (``axvs_msda_layer_train_fwd`` / ``_bwd``, ``msda_layer_train``: the same tail and
+dropout hash, the deformable attention's sampling head and the library's fp32 core op).
 
 Reference: the layer in ``train()`` mode under autograd, WC/temporal_attention.py:187-220 (and TrajectoryAttention :35-76), as the
 shipped configs train it (``ATTN_DROP: 0.1``, AMP -- VK/configs/VIPSeg/.../maxtron_wc_convnext_large.yaml).  The forward and the
@@ -177,18 +179,26 @@ def _check_tail(layer) -> None:
         raise NotImplementedError("axial_vs_amd: LayerNorm eps must be 1e-5")
 
 
-def _apply(layer, src: Tensor, pos: Tensor, kind, dims, dropout: bool, recompute: bool, params: List[Tensor]) -> Tensor:
-    p_drop = float(layer.dropout2.p) if dropout else 0.0        # = the attention maps' dropout (reference :164-165) = dropout2 = dropout3
-    p_attn = float(layer.dropout1.p) if dropout else 0.0
+def _seed(layer, p_drop: float, p_attn: float) -> int:
     seed = getattr(layer, "dropout_seed", None)
     if seed is None:
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p_drop > 0 or p_attn > 0) else 0
-    args = (src, pos, kind, dims, p_drop, p_attn, int(seed), bool(recompute), *params)
+    return int(seed)
+
+
+def _call(layer, fn, args) -> Tensor:
     if torch.is_autocast_enabled():
         amp = _lib.autocast_mode(layer)       # (read before autocast is switched off for the call)
         with torch.autocast(device_type="cuda", enabled=False), _lib.train_amp(amp):
-            return _LayerTrain.apply(*args)
-    return _LayerTrain.apply(*args)
+            return fn.apply(*args)
+    return fn.apply(*args)
+
+
+def _apply(layer, src: Tensor, pos: Tensor, kind, dims, dropout: bool, recompute: bool, params: List[Tensor]) -> Tensor:
+    p_drop = float(layer.dropout2.p) if dropout else 0.0        # = the attention maps' dropout (reference :164-165) = dropout2 = dropout3
+    p_attn = float(layer.dropout1.p) if dropout else 0.0
+    args = (src, pos, kind, dims, p_drop, p_attn, _seed(layer, p_drop, p_attn), bool(recompute), *params)
+    return _call(layer, _LayerTrain, args)
 
 
 def axial_layer_train(layer, src: Tensor, pos: Tensor, dropout: bool = True, recompute: bool = True) -> Tensor:
@@ -215,3 +225,144 @@ def traj_layer_train(layer, src: Tensor, pos: Tensor, dropout: bool = True, reco
         raise RuntimeError(f"src {tuple(src.shape)} does not match pos {tuple(pos.shape)}")
     dims = (int(B), int(T), int(H * W), int(C_), int(layer.n_heads), int(layer.linear1.out_features))
     return _apply(layer, src, pos, _FULL, dims, dropout, recompute, traj_layer_parameters(layer))
+
+
+# ---- MSDeformAttnTransformerEncoderLayer (WC/msdeformattn.py:177-216): axvs_msda_layer_train_fwd / _bwd ----------------------------------
+_MSDA = ("value_proj", "sampling_offsets", "attention_weights", "output_proj")
+
+
+def msda_layer_parameters(layer) -> List[Tensor]:
+    """An MSDeformAttnTransformerEncoderLayer's parameters in AxvsMsdaLayerParams field order (include/axvs.h)."""
+    ps: List[Tensor] = []
+    for n in _MSDA:
+        m = getattr(layer.self_attn, n)
+        ps += [m.weight, m.bias]
+    for n in _TAIL:
+        m = getattr(layer, n)
+        ps += [m.weight, m.bias]
+    return ps
+
+
+def _msda_struct(ptrs: List[int]) -> _lib.AxvsMsdaLayerParams:
+    s = _lib.AxvsMsdaLayerParams()
+    s.self_attn = _lib.AxvsMsdaParams(*ptrs[0:8])
+    for name, p in zip(("norm1_w", "norm1_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b", "norm2_w", "norm2_b"), ptrs[8:16]):
+        setattr(s, name, p)
+    return s
+
+
+class _MsdaLayerTrain(torch.autograd.Function):
+    """forward / backward of one deformable encoder layer through the library's training tier.  reference_points, the padding
+    mask and the spatial shapes are constants (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, src, pos, ref, mask, shapes, dims, p_dropout, p_attn_drop, seed, recompute, *params):
+        from .modules import _stream, _workspace
+        if not src.is_cuda:
+            raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
+        s, r = _f32c(src), _f32c(ref)
+        p = _f32c(pos) if pos is not None else None
+        ws = [_f32c(w) for w in params]
+        L = _lib.lib()
+        dev = s.device
+        nsaved = L.axvs_msda_layer_train_saved_bytes(*dims)
+        if nsaved == 0:
+            raise RuntimeError("axvs_msda_layer_train_saved_bytes: " + L.axvs_last_error().decode())
+        arr = (C.c_int * (2 * len(shapes)))(*[v for hw in shapes for v in hw])
+        with torch.cuda.device(dev):
+            out = torch.empty_like(s)
+            nscr = L.axvs_msda_layer_train_scratch_bytes(*dims, 0)
+            if recompute:
+                buf = _workspace(dev, nscr + nsaved)
+                scratch_ptr, saved_ptr, saved = buf.data_ptr(), buf.data_ptr() + nscr, None
+            else:
+                saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
+                buf = _workspace(dev, nscr)
+                scratch_ptr, saved_ptr = buf.data_ptr(), saved.data_ptr()
+            st = _msda_struct([w.data_ptr() for w in ws])
+            _lib.check(L.axvs_msda_layer_train_fwd(s.data_ptr(), p.data_ptr() if p is not None else None, r.data_ptr(), r.shape[-1],
+                                                   mask.data_ptr() if mask is not None else None, arr, out.data_ptr(), C.byref(st), *dims,
+                                                   float(p_dropout), float(p_attn_drop), int(seed), saved_ptr, nsaved, scratch_ptr, nscr,
+                                                   _stream(dev)), "axvs_msda_layer_train_fwd")
+        ctx.save_for_backward(s, p, r, mask, *ws)
+        ctx.amp = _lib.current_amp()
+        ctx.cfg = (arr, dims, float(p_dropout), float(p_attn_drop), int(seed), bool(recompute))
+        ctx.saved_buf = saved
+        ctx.in_dtypes = (src.dtype, pos.dtype if pos is not None else None, [w.dtype for w in params])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        from .modules import _stream, _workspace
+        s, p, r, mask, *ws = ctx.saved_tensors
+        arr, dims, p_dropout, p_attn_drop, seed, recompute = ctx.cfg
+        L = _lib.lib()
+        dev = s.device
+        with torch.cuda.device(dev):
+            g = _f32c(d_out)
+            d_src = torch.empty_like(s)
+            want_pos = p is not None and ctx.needs_input_grad[1]
+            d_pos = torch.empty_like(p) if want_pos else None
+            sizes = [w.numel() for w in ws]
+            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+            grads, off = [], 0
+            for w, n in zip(ws, sizes):
+                grads.append(flat[off:off + n].view(w.shape))
+                off += n
+            nsaved = L.axvs_msda_layer_train_saved_bytes(*dims)
+            nscr = L.axvs_msda_layer_train_scratch_bytes(*dims, 1)
+            if recompute:
+                buf = _workspace(dev, nscr + nsaved)
+                scratch_ptr, saved_ptr = buf.data_ptr(), buf.data_ptr() + nscr
+            else:
+                buf = _workspace(dev, nscr)
+                scratch_ptr, saved_ptr = buf.data_ptr(), ctx.saved_buf.data_ptr()
+            st = _msda_struct([w.data_ptr() for w in ws])
+            gs = _msda_struct([t.data_ptr() for t in grads])       # (the gradient struct has the parameter struct's layout)
+            with _lib.train_amp(ctx.amp):
+                _lib.check(L.axvs_msda_layer_train_bwd(g.data_ptr(), s.data_ptr(), p.data_ptr() if p is not None else None, r.data_ptr(),
+                                                       r.shape[-1], mask.data_ptr() if mask is not None else None, arr, C.byref(st),
+                                                       C.byref(gs), d_src.data_ptr(), d_pos.data_ptr() if want_pos else None, *dims,
+                                                       p_dropout, p_attn_drop, seed, int(recompute), saved_ptr, nsaved, scratch_ptr, nscr,
+                                                       _stream(dev)), "axvs_msda_layer_train_bwd")
+        sd, pd, wd = ctx.in_dtypes
+        out_grads = [gr.to(dt) for gr, dt in zip(grads, wd)]
+        return (d_src.to(sd), d_pos.to(pd) if want_pos else None, None, None, None, None, None, None, None, None, *out_grads)
+
+
+def msda_layer_dims(layer, src: Tensor, shapes) -> tuple:
+    a = layer.self_attn
+    return (int(src.shape[0]), int(src.shape[1]), int(layer.d_model), int(a.n_heads), int(len(shapes)), int(a.n_points), int(layer.d_ffn))
+
+
+def msda_layer_train(layer, src: Tensor, pos, reference_points: Tensor, spatial_shapes, padding_mask=None, dropout: bool = True,
+                     recompute: bool = False) -> Tensor:
+    """Differentiable forward of an MSDeformAttnTransformerEncoderLayer (WC/msdeformattn.py:177-216) through the training tier.
+    src [N,S,C]; pos [N,S,C] or None; reference_points [N,S,L,2 | 4] (constants: no gradient); spatial_shapes [(H_l, W_l)]; padding_mask
+    [N,S] bool or None -> out like src (fp32).  dropout=False: probabilities forced to 0 (gradients in eval mode).  Dropout sites 7 / 8 / 9
+    of include/axvs.h (dropout1 / dropout2 / dropout3), seeded by ``layer.dropout_seed`` or torch's CPU generator."""
+    from .msda import _shapes_host
+    if layer.norm1.eps != 1e-5 or layer.norm2.eps != 1e-5:
+        raise NotImplementedError("axial_vs_amd: LayerNorm eps must be 1e-5")
+    if dropout and layer.dropout2.p != layer.dropout3.p:
+        raise NotImplementedError("axial_vs_amd: the training tier takes one probability for dropout2 and dropout3")
+    shapes = _shapes_host(spatial_shapes)
+    if reference_points.requires_grad:
+        raise NotImplementedError("axial_vs_amd: reference_points are constants in the training tier (no gradient)")
+    if pos is not None and pos.shape != src.shape:
+        raise RuntimeError(f"pos {tuple(pos.shape)} does not match src {tuple(src.shape)}")
+    if tuple(reference_points.shape[:3]) != (src.shape[0], src.shape[1], len(shapes)):
+        raise RuntimeError(f"reference_points {tuple(reference_points.shape)} do not match src {tuple(src.shape)} and {len(shapes)} levels")
+    mask = None
+    if padding_mask is not None:
+        if not padding_mask.is_cuda:
+            raise RuntimeError("axial_vs_amd: padding_mask must be a CUDA tensor (no CPU fallback)")
+        if tuple(padding_mask.shape) != tuple(src.shape[:2]):
+            raise RuntimeError(f"padding_mask {tuple(padding_mask.shape)} does not match src {tuple(src.shape)}")
+        mask = padding_mask.to(torch.uint8).contiguous()
+    p_drop = float(layer.dropout2.p) if dropout else 0.0
+    p_attn = float(layer.dropout1.p) if dropout else 0.0
+    args = (src, pos, reference_points.detach(), mask, shapes, msda_layer_dims(layer, src, shapes), p_drop, p_attn,
+            _seed(layer, p_drop, p_attn), bool(recompute), *msda_layer_parameters(layer))
+    return _call(layer, _MsdaLayerTrain, args)

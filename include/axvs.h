@@ -361,6 +361,42 @@ int axvs_msda_core_bwd(const float* value, const int* spatial_shapes, const floa
                        const float* grad_output, float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M,
                        int D, int Lq, int L, int P, void* stream);
 
+/* ---- Training tier of MSDeformAttnTransformerEncoderLayer: WC/msdeformattn.py:177-216 in train() mode under autograd --
+ *      value_proj(src) with the rows of padded keys zeroed, one GEMM for sampling_offsets | attention_weights on src + pos, the
+ *      softmax over each (query, head)'s L*P logits and the sampling locations (OPS/modules/ms_deform_attn.py:98-117, both
+ *      reference-point forms), the fp32 core op above (forward and backward), output_proj, dropout1 + residual, norm1, FFN, norm2.
+ *      fp32 activations, split-precision GEMMs and the counter-based dropout of the trajectory layers' tier (see above).
+ *      Dropout sites (element index = the element's offset in the reference's tensor at that site):
+ *        7  dropout1 (p_attn_drop), the attention output [N, S, C]        (:210)
+ *        8  dropout2 (p_dropout), the FFN hidden [N, S, d_ffn]            (:202)
+ *        9  dropout3 (p_dropout), the FFN output [N, S, C]                (:204)
+ *      Bounds (the size functions return 0 and axvs_last_error() names the bound): head_dim in {8,16,32,64}, n_levels <= 8,
+ *      n_levels * n_points <= 32, n_heads * n_levels * n_points a multiple of 8, d_ffn a multiple of 8, N*S < 2^31.
+ *      reference_points are constants: they get no gradient. */
+typedef struct AxvsMsdaGrads {        /* same field order as AxvsMsdaParams */
+  float *value_proj_w, *value_proj_b, *sampling_offsets_w, *sampling_offsets_b, *attention_weights_w, *attention_weights_b,
+      *output_proj_w, *output_proj_b;
+} AxvsMsdaGrads;
+typedef struct AxvsMsdaLayerGrads {   /* same field order as AxvsMsdaLayerParams; every buffer is WRITTEN (not accumulated) */
+  AxvsMsdaGrads self_attn;
+  float *norm1_w, *norm1_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b, *norm2_w, *norm2_b;
+} AxvsMsdaLayerGrads;
+size_t axvs_msda_layer_train_saved_bytes(int N, int S, int C, int heads, int L, int P, int d_ffn);
+size_t axvs_msda_layer_train_scratch_bytes(int N, int S, int C, int heads, int L, int P, int d_ffn, int backward);
+/* src fp32 [N,S,C]; pos fp32 [N,S,C] or NULL; reference_points fp32 [N,S,L,ref_dim], ref_dim 2 or 4; padding_mask NULL or bytes
+ * [N,S] (non-zero = padding); spatial_shapes HOST ints [L][2] = (H_l, W_l), sum H_l*W_l == S; out fp32 [N,S,C]. */
+int axvs_msda_layer_train_fwd(const float* src, const float* pos, const float* reference_points, int ref_dim, const unsigned char* padding_mask,
+                              const int* spatial_shapes, float* out, const AxvsMsdaLayerParams* params, int N, int S, int C, int heads, int L, int P,
+                              int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, void* saved, size_t saved_bytes, void* scratch,
+                              size_t scratch_bytes, void* stream);
+/* d_out: gradient of `out`.  Writes d_src, d_pos (NULL: not wanted; needs pos) and every buffer of `grads`.  recompute != 0: `saved`
+ * is rebuilt from (src, pos, params, seed) first. */
+int axvs_msda_layer_train_bwd(const float* d_out, const float* src, const float* pos, const float* reference_points, int ref_dim,
+                              const unsigned char* padding_mask, const int* spatial_shapes, const AxvsMsdaLayerParams* params,
+                              const AxvsMsdaLayerGrads* grads, float* d_src, float* d_pos, int N, int S, int C, int heads, int L, int P, int d_ffn,
+                              float p_dropout, float p_attn_drop, unsigned seed, int recompute, void* saved, size_t saved_bytes, void* scratch,
+                              size_t scratch_bytes, void* stream);
+
 /* ---- Pixel-decoder glue: nn.Sequential(Conv2d(k=1), GroupNorm) between backbone NCHW maps and token rows
  *      (WC/msdeformattn.py:349-375 input_proj / output_proj; used at :412 and :434), PositionEmbeddingSine
  *      (WC/pos_embeddings.py:12-53) in token form. */
