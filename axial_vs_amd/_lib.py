@@ -80,6 +80,14 @@ class AxvsTLHeadParams(C.Structure):
                                    "cls_embed_b")] + [("mask_embed_w", _fp * 3), ("mask_embed_b", _fp * 3)]
 
 
+class AxvsTLHeadGrads(C.Structure):      # field order of AxvsTLHeadParams
+    _fields_ = AxvsTLHeadParams._fields_
+
+
+class AxvsTLHeadTrainCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "Q", "Tc", "frames_per_clip", "h", "w", "K1", "Cm", "num_layers")]
+
+
 class AxvsMsdaParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
                                    "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
@@ -202,6 +210,12 @@ SIGNATURES = {
     "axvs_tl_heads_pack": (C.c_int, [C.POINTER(AxvsTLHeadParams), _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "axvs_tl_heads_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "axvs_tl_heads_fwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp] + [C.c_int] * 9 + [_fp, C.c_size_t, _fp]),
+    "axvs_tl_heads_train_saved_bytes": (C.c_size_t, [C.POINTER(AxvsTLHeadTrainCfg)]),
+    "axvs_tl_heads_train_scratch_bytes": (C.c_size_t, [C.POINTER(AxvsTLHeadTrainCfg), C.c_int]),
+    "axvs_tl_heads_train_fwd": (C.c_int, [_fp] * 4 + [C.POINTER(AxvsTLHeadParams), C.POINTER(AxvsTLHeadTrainCfg), _fp, C.c_size_t, _fp,
+                                          C.c_size_t, _fp]),
+    "axvs_tl_heads_train_bwd": (C.c_int, [_fp] * 4 + [C.POINTER(AxvsTLHeadParams), C.POINTER(AxvsTLHeadGrads), _fp, _fp,
+                                          C.POINTER(AxvsTLHeadTrainCfg), _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
     "axvs_pos3d": (C.c_int, [_fp] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_pos3d_masked": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_scaled_residual": (C.c_int, [_fp, _fp, _fp, _fp, C.c_size_t, C.c_int, _fp]),

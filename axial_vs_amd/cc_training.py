@@ -12,6 +12,10 @@ running-statistics update of the four BatchNorm sites (momentum arithmetic on [C
 * dropout masks are the same counter-based hash as the layer's training tier (sites 10 + 2 l: attention maps of layer l, 11 + 2 l:
   ASPP ``_proj_drop``); ``seed`` from torch's CPU generator or ``module.dropout_seed``.
 * no gradient is produced for ``panoptic_features`` (the frozen segmenter's pixel features).
+
+Tube-Link's ``TubeLinkCrossClipHead`` trains through two calls: the layer chain alone (``cc_layers_train``, ``axvs_cc_layers_train_*``)
+and the prediction heads of all layers at once (``tl_heads_train``, ``axvs_tl_heads_train_*``: post_norm, class pooling, cls_embed, the
+mask MLP, the per-clip mask einsum); its ``mask_features`` get a gradient when they ask for one.
 """
 from __future__ import annotations
 
@@ -275,7 +279,7 @@ def cc_module_train(mod, clip_query: Tensor, panoptic_features: Tensor):
     return logits, masks
 
 
-# ---- the layer chain alone: the Tube-Link head's train() mode (its prediction heads are torch modules around it) ----------------------
+# ---- the layer chain alone: the first half of the Tube-Link head's train() mode (its prediction heads follow: tl_heads_train below) ------
 def chain_parameters(mod, num_layers: int) -> List[Tensor]:
     ps: List[Tensor] = []
     for i in range(num_layers):
@@ -372,3 +376,106 @@ def cc_layers_train(mod, clip_query: Tensor, num_layers: int, rates, p_attn: flo
         with torch.autocast(device_type="cuda", enabled=False), _lib.train_amp(amp):
             return _CCLayersTrain.apply(*args)
     return _CCLayersTrain.apply(*args)
+
+
+# ---- the Tube-Link head's prediction heads, all layers at once (axvs_tl_heads_train_*) ------------------------------------------------
+def tl_heads_parameters(mod) -> List[Tensor]:
+    """The head's trainable tensors in AxvsTLHeadParams field order: post_norm, activation_proj, cls_embed, the three mask_embed weights,
+    the three mask_embed biases."""
+    pn, me = mod.transformer_decoder.post_norm, mod.mask_embed
+    return [pn.weight, pn.bias, mod.activation_proj.weight, mod.activation_proj.bias, mod.cls_embed.weight, mod.cls_embed.bias,
+            me[0].weight, me[2].weight, me[4].weight, me[0].bias, me[2].bias, me[4].bias]
+
+
+def _tl_struct(ptrs: List[int], cls=_lib.AxvsTLHeadParams):
+    s = cls()
+    s.post_norm_w, s.post_norm_b, s.activation_proj_w, s.activation_proj_b, s.cls_embed_w, s.cls_embed_b = ptrs[:6]
+    for k in range(3):
+        s.mask_embed_w[k], s.mask_embed_b[k] = ptrs[6 + k], ptrs[9 + k]
+    return s
+
+
+def tl_heads_cfg(nl: int, B: int, Q: int, Tc: int, fpc: int, h: int, w: int, K1: int, Cm: int) -> _lib.AxvsTLHeadTrainCfg:
+    return _lib.AxvsTLHeadTrainCfg(int(B), int(Q), int(Tc), int(fpc), int(h), int(w), int(K1), int(Cm), int(nl))
+
+
+def tl_heads_supported(cfg: _lib.AxvsTLHeadTrainCfg) -> bool:
+    """True when the library's bounds take this configuration (else axvs_last_error() names the bound)."""
+    return _lib.lib().axvs_tl_heads_train_saved_bytes(C.byref(cfg)) > 0
+
+
+class _TLHeadsTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, queries, mask_features, dims, *params):
+        from .modules import _stream
+        if not queries.is_cuda:
+            raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
+        nl, B, Q, Tc, fpc, h, w, K1, Cm = dims
+        qs, mf = _f32c(queries), _f32c(mask_features)
+        ws = [_f32c(p) for p in params]
+        L = _lib.lib()
+        dev = qs.device
+        with torch.cuda.device(dev):
+            c = tl_heads_cfg(*dims)
+            nsaved = L.axvs_tl_heads_train_saved_bytes(C.byref(c))
+            nscr = L.axvs_tl_heads_train_scratch_bytes(C.byref(c), 0)
+            if nsaved == 0 or nscr == 0:
+                raise RuntimeError("axvs_tl_heads_train_saved_bytes: " + L.axvs_last_error().decode())
+            saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
+            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
+            cls = torch.empty(nl, B, Q, K1, dtype=torch.float32, device=dev)
+            masks = torch.empty(nl, B, Tc * fpc, Q, h, w, dtype=torch.float32, device=dev)
+            hp = _tl_struct([t.data_ptr() for t in ws])
+            _lib.check(L.axvs_tl_heads_train_fwd(qs.data_ptr(), mf.data_ptr(), cls.data_ptr(), masks.data_ptr(), C.byref(hp), C.byref(c),
+                                                 saved.data_ptr(), nsaved, scratch.data_ptr(), nscr, _stream(dev)), "axvs_tl_heads_train_fwd")
+        ctx.save_for_backward(qs, mf, *ws)
+        ctx.amp = _lib.current_amp()
+        ctx.dims = dims
+        ctx.saved_buf = saved
+        ctx.in_dtypes = (queries.dtype, mask_features.dtype, [p.dtype for p in params])
+        return cls, masks
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_cls, d_masks):
+        from .modules import _stream
+        qs, mf, *ws = ctx.saved_tensors
+        nl, B, Q, Tc, fpc, h, w, K1, Cm = ctx.dims
+        L = _lib.lib()
+        dev = qs.device
+        with torch.cuda.device(dev):
+            gc = _f32c(d_cls) if d_cls is not None else torch.zeros(nl, B, Q, K1, dtype=torch.float32, device=dev)
+            gm = _f32c(d_masks) if d_masks is not None else torch.zeros(nl, B, Tc * fpc, Q, h, w, dtype=torch.float32, device=dev)
+            c = tl_heads_cfg(*ctx.dims)
+            nsaved = L.axvs_tl_heads_train_saved_bytes(C.byref(c))
+            nscr = L.axvs_tl_heads_train_scratch_bytes(C.byref(c), 1)
+            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
+            sizes = [p.numel() for p in ws]
+            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+            grads, off = [], 0
+            for p, n in zip(ws, sizes):
+                grads.append(flat[off:off + n].view(p.shape))
+                off += n
+            d_q = torch.empty_like(qs)
+            d_mf = torch.empty_like(mf) if ctx.needs_input_grad[1] else None
+            hp = _tl_struct([p.data_ptr() for p in ws])
+            hg = _tl_struct([g.data_ptr() for g in grads], _lib.AxvsTLHeadGrads)
+            with _lib.train_amp(ctx.amp):
+                _lib.check(L.axvs_tl_heads_train_bwd(gc.data_ptr(), gm.data_ptr(), qs.data_ptr(), mf.data_ptr(), C.byref(hp), C.byref(hg), d_q.data_ptr(),
+                                                     d_mf.data_ptr() if d_mf is not None else None, C.byref(c), ctx.saved_buf.data_ptr(), nsaved,
+                                                     scratch.data_ptr(), nscr, _stream(dev)), "axvs_tl_heads_train_bwd")
+        qd, md, wd = ctx.in_dtypes
+        return (d_q.to(qd), d_mf.to(md) if d_mf is not None else None, None, *[g.to(dt) for g, dt in zip(grads, wd)])
+
+
+def tl_heads_train(mod, queries: Tensor, mask_features: Tensor, cfg: _lib.AxvsTLHeadTrainCfg):
+    """Differentiable prediction heads of a TubeLinkCrossClipHead for every layer: queries [nl,B,Q,Tc,256] (cc_layers_train's output),
+    mask_features [B,Tc*fpc,Cm,h,w] -> (class logits [nl,B,Q,K1], mask logits [nl,B,Tc*fpc,Q,h,w]).  `cfg` from tl_heads_cfg, accepted
+    by tl_heads_supported."""
+    dims = (cfg.num_layers, cfg.B, cfg.Q, cfg.Tc, cfg.frames_per_clip, cfg.h, cfg.w, cfg.K1, cfg.Cm)
+    args = (queries, mask_features, dims, *tl_heads_parameters(mod))
+    if torch.is_autocast_enabled():
+        amp = _lib.autocast_mode(mod)       # (read before autocast is switched off for the call)
+        with torch.autocast(device_type="cuda", enabled=False), _lib.train_amp(amp):
+            return _TLHeadsTrain.apply(*args)
+    return _TLHeadsTrain.apply(*args)

@@ -284,6 +284,8 @@ class TubeLinkCrossClipHead(nn.Module):
 
     forward(clip_query [B,Tc,Q,256] (the matched clip queries, TLCC:919), mask_features [B,T,Cm,h,w], T = Tc*frames_per_clip)
         -> (tuple of class logits [B,Q,K+1] per layer, tuple of mask logits [B,T,Q,h,w] per layer)
+    eval(): one library call (axvs_tl_cc_module_fwd); train(): the layer chain and then the prediction heads of all layers on the
+    training tier (cc_training.cc_layers_train + tl_heads_train)
     """
 
     def __init__(self, *, num_classes: int, feat_channels: int = 256, out_channels: int = 256, num_cc_layers: int = 6,
@@ -350,17 +352,26 @@ class TubeLinkCrossClipHead(nn.Module):
 
     def _forward_train(self, clip_query: Tensor, mask_features: Tensor):
         """train() mode (TLCC:925-947 with forward_head_clips :761-781 and pred_class :783-797 under autograd): the layer chain on the
-        library's training tier (axvs_cc_layers_train_fwd / _bwd), the prediction heads -- post_norm, class pooling, the mask MLP,
-        the per-clip einsum -- as the reference's torch modules."""
-        from .cc_training import cc_layers_train
+        library's training tier (axvs_cc_layers_train_fwd / _bwd), then the prediction heads of all layers -- post_norm, class pooling,
+        the mask MLP, the per-clip einsum -- in one call of the heads' tier (axvs_tl_heads_train_fwd / _bwd).  A configuration outside
+        the heads' bounds (include/axvs.h) keeps them as the reference's torch modules."""
+        from .cc_training import cc_layers_train, tl_heads_cfg, tl_heads_supported, tl_heads_train
         B, Tc, Q, _ = clip_query.shape
         T = mask_features.shape[1]
         fpc = T // Tc
         trj = self.transformer_trajectory_self_attention_layers[0].self_attn.attn_drop.p
         asp = self.conv_short_aggregate_layers[0]._proj_drop.p
         queries = cc_layers_train(self, clip_query.permute(0, 2, 1, 3).contiguous(), self.num_cc_layers, self.atrous_rates, trj, asp)
+        nl = self.num_cc_layers
+        K1, Cm = self.cls_embed.weight.shape[0], self.mask_embed[4].weight.shape[0]
+        if mask_features.dim() == 5 and T == Tc * fpc and mask_features.shape[0] == B and mask_features.shape[2] == Cm:
+            cfg = tl_heads_cfg(nl, B, Q, Tc, fpc, mask_features.shape[3], mask_features.shape[4], K1, Cm)
+            if tl_heads_supported(cfg):
+                cls, masks = tl_heads_train(self, queries, mask_features, cfg)
+                # unbind: one autograd node that stacks the per-layer gradients once
+                return tuple(cls.unbind(0)), tuple(masks.unbind(0))
         cls_all, mask_all = [], []
-        for i in range(self.num_cc_layers):
+        for i in range(nl):
             xn = self.transformer_decoder.post_norm(queries[i]).permute(0, 2, 1, 3)              # [B,Tc,Q,C]   TLCC:768-769
             act = torch.softmax(self.activation_proj(xn), dim=1)                                  # softmax over the clips, :789-791
             cls_all.append(self.cls_embed((xn * act).sum(dim=1)))

@@ -376,6 +376,78 @@ __global__ __launch_bounds__(256) void cct_act_pool_bwd_kernel(const float* __re
   }
 }
 
+// ---- Tube-Link class pooling (TLCC:789-791): per group g = (layer, b, q), softmax over its Tc clips ONLY of a = xn . wa + ba,
+//      pooled[g][c] = sum_t p_t xn[g Tc + t][c].  The Tc rows of a group are contiguous (rows (layer, b, q, t)).  One block per
+//      group; C <= 1024, Tc <= 16.
+__global__ __launch_bounds__(256) void tlt_pool_fwd_kernel(const float* __restrict__ xn, const float* __restrict__ wa, const float* __restrict__ ba,
+                                                            float* __restrict__ p_out, float* __restrict__ pooled, int Tc, int C) {
+  __shared__ float sp[16];
+  const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* xg = xn + (size_t)g * Tc * C;
+  for (int t = wave; t < Tc; t += 4) {
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += xg[(size_t)t * C + c] * wa[c];
+    s = wave_total(s);
+    if (lane == 0) sp[t] = s + ba[0];
+  }
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int t = 0; t < Tc; ++t) mx = fmaxf(mx, sp[t]);
+  float den = 0.f;
+  for (int t = 0; t < Tc; ++t) den += expf(sp[t] - mx);
+  const float inv = 1.f / den;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float acc = 0.f;
+    for (int t = 0; t < Tc; ++t) acc += expf(sp[t] - mx) * inv * xg[(size_t)t * C + c];
+    pooled[(size_t)g * C + c] = acc;
+  }
+  if ((int)threadIdx.x < Tc) p_out[(size_t)g * Tc + threadIdx.x] = expf(sp[threadIdx.x] - mx) * inv;
+}
+
+// backward: dxn[row_t][c] += p_t dpool[c] + da_t wa[c], da_t = p_t (dp_t - sum_t' p_t' dp_t'), dp_t = dpool . xn[row_t];
+// part_wa[g][c] = sum_t da_t xn[row_t][c], part_ba[g] = sum_t da_t (reduced over the groups by the caller, in a fixed order)
+__global__ __launch_bounds__(256) void tlt_pool_bwd_kernel(const float* __restrict__ xn, const float* __restrict__ wa, const float* __restrict__ p,
+                                                            const float* __restrict__ dpool, float* __restrict__ dxn, float* __restrict__ part_wa,
+                                                            float* __restrict__ part_ba, int Tc, int C) {
+  __shared__ float sd[16];
+  const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* xg = xn + (size_t)g * Tc * C;
+  const float* pg = p + (size_t)g * Tc;
+  const float* dpl = dpool + (size_t)g * C;
+  for (int t = wave; t < Tc; t += 4) {
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += xg[(size_t)t * C + c] * dpl[c];
+    s = wave_total(s);
+    if (lane == 0) sd[t] = s;
+  }
+  __syncthreads();
+  float sdp = 0.f;
+  for (int t = 0; t < Tc; ++t) sdp += pg[t] * sd[t];
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float acc = 0.f;
+    for (int t = 0; t < Tc; ++t) {
+      const float pt = pg[t], da = pt * (sd[t] - sdp);
+      dxn[((size_t)g * Tc + t) * C + c] += pt * dpl[c] + da * wa[c];
+      acc += da * xg[(size_t)t * C + c];
+    }
+    part_wa[(size_t)g * C + c] = acc;
+  }
+  if (threadIdx.x == 0) {
+    float sba = 0.f;
+    for (int t = 0; t < Tc; ++t) sba += pg[t] * (sd[t] - sdp);
+    part_ba[g] = sba;
+  }
+}
+
+// out[i] = sum_l part[l n + i], l = 0 .. G-1 in order (the layers' shares of the mask-feature gradient); any n
+__global__ __launch_bounds__(256) void tlt_sum_layers_kernel(const float* __restrict__ part, size_t n, int G, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float s = 0.f;
+  for (int l = 0; l < G; ++l) s += part[(size_t)l * n + i];
+  out[i] = s;
+}
+
 // ---- small Linear with any output width (the class head: K1 = classes + 1 is not a multiple of 4): one wave per output -------
 // y[r][k] = x[r] . w[k] + b[k] + (k == K1 - 1 ? last_bias : 0)        (add_bias_towards_void, CC:52)
 __global__ __launch_bounds__(256) void cct_small_linear_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,

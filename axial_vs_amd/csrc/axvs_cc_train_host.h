@@ -478,3 +478,209 @@ int cc_setup(CCCtx& k, const AxvsCCTrainCfg* cfg, void* scratch, size_t scratch_
   k.rm = RowMap{k.s.Tc * k.s.Q, k.s.Q, 1, (long long)k.s.Q * k.s.Tc, 1, k.s.Tc, 0};
   return k.c.g.init(k.st);
 }
+
+// ---- Tube-Link cross-clip head: the prediction heads of ALL layers, train() mode ------------------------------------------------------
+// TLCC = MaXTron_Tube-Link/models/video/tube_link_vis/mask2former_video_cc_head.py: forward_head_clips (:761-781) + pred_class
+// (:783-797) for every layer's clip queries at once (the heads share their weights across layers).  Input: what
+// axvs_cc_layers_train_fwd writes, [nl][B][Q][Tc][256]; rows r = ((l B + b) Q + q) Tc + t, so a group g = (l, b, q) owns Tc
+// consecutive rows.  post_norm LayerNorm, class pooling (softmax over the Tc clips of a group), cls_embed, the three-Linear
+// mask_embed MLP, and per (b, frame) ONE einsum GEMM whose rows are (layer, query): the frame's pixel features are read once for all
+// layers and the logits go straight into [nl][B][T][Q][h w].  The backward never reads the mask logits.
+constexpr int kTlhWSplits = 16;            // row splits of the cls_embed weight gradient
+constexpr long long kTlhMaxHW = 1LL << 26; // pixels per frame
+
+struct TLHShape {
+  int B, Q, Tc, fpc, T, h, w, K1, Cm, nl;
+  long long R, NG, HW;   // rows (l, b, q, t), groups (l, b, q), pixels per frame
+};
+
+int make_tlh_shape(TLHShape& s, const AxvsTLHeadTrainCfg* cfg) {
+  if (!cfg) return fail(AXVS_ERR_ARG, "null configuration");
+  if (cfg->B <= 0 || cfg->Q <= 0 || cfg->Tc <= 0 || cfg->frames_per_clip <= 0 || cfg->h <= 0 || cfg->w <= 0 || cfg->K1 <= 0 || cfg->Cm <= 0 ||
+      cfg->num_layers <= 0)
+    return fail(AXVS_ERR_ARG, "non-positive dimension");
+  if (cfg->Cm != 128 && cfg->Cm != 256) return fail(AXVS_ERR_ARG, "Tube-Link heads training: Cm=%d (mask channels must be 128 or 256)", cfg->Cm);
+  if (cfg->num_layers > kCcMaxLayers) return fail(AXVS_ERR_ARG, "Tube-Link heads training: num_layers=%d > %d", cfg->num_layers, kCcMaxLayers);
+  if (cfg->Tc > 16) return fail(AXVS_ERR_ARG, "Tube-Link heads training: Tc=%d > 16 clips not built", cfg->Tc);
+  if (cfg->Q % 4) return fail(AXVS_ERR_ARG, "Tube-Link heads training: Q=%d must be a multiple of 4", cfg->Q);
+  const long long HW = (long long)cfg->h * cfg->w;
+  if (HW > kTlhMaxHW) return fail(AXVS_ERR_ARG, "Tube-Link heads training: h*w=%lld > %lld pixels per frame", HW, kTlhMaxHW);
+  const long long R = (long long)cfg->num_layers * cfg->B * cfg->Q * cfg->Tc;
+  if (R * kCcC > INT32_MAX || (long long)cfg->num_layers * cfg->B * cfg->Q * cfg->K1 > INT32_MAX)
+    return fail(AXVS_ERR_ARG, "Tube-Link heads training: num_layers*B*Q*Tc*256=%lld > 2^31", R * kCcC);
+  s.B = cfg->B; s.Q = cfg->Q; s.Tc = cfg->Tc; s.fpc = cfg->frames_per_clip; s.T = s.Tc * s.fpc; s.h = cfg->h; s.w = cfg->w;
+  s.K1 = cfg->K1; s.Cm = cfg->Cm; s.nl = cfg->num_layers;
+  s.R = R; s.NG = (long long)s.nl * s.B * s.Q; s.HW = HW;
+  return AXVS_OK;
+}
+
+struct TLHSaved {
+  float *mean, *rstd, *xn, *p, *pooled, *h1, *h2, *me;   // LayerNorm statistics / output, pooling weights, pooled rows, MLP activations
+};
+TLHSaved carve_tlh_saved(Bump& b, const TLHShape& s) {
+  TLHSaved v{};
+  const size_t RC = (size_t)s.R * kCcC;
+  v.mean = b.f(s.R); v.rstd = b.f(s.R);
+  v.xn = b.f(RC);
+  v.p = b.f(s.R);
+  v.pooled = b.f((size_t)s.NG * kCcC);
+  v.h1 = b.f(RC); v.h2 = b.f(RC);
+  v.me = b.f((size_t)s.R * s.Cm);
+  return v;
+}
+
+struct TLHScratch {
+  float *kt;                                                   // forward: mask embeddings, contraction-major per (b, clip)
+  float *dkpart, *dk, *dme, *dh, *dh1, *dxn, *dpooled, *part_wa, *part_ba, *part_cls, *mfpart;
+  int ks, z;                                                   // split-K plan of d_me: k-steps per split, splits per frame
+};
+
+// split-K plan of d_me (Q rows x Cm columns, contraction over a frame's h w pixels): ~256 workgroups per frame's GEMM
+void tlh_plan(const TLHShape& s, int* ks, int* z) {
+  const int nk = (int)((s.HW + kGK - 1) / kGK);
+  const int tiles = (int)((s.Q + kGT - 1) / kGT) * ((s.Cm + kGT - 1) / kGT);
+  int want = 256 / tiles;
+  want = want < 1 ? 1 : want;
+  int k = (nk + want - 1) / want;
+  k = k < 4 ? 4 : k;
+  *ks = k;
+  *z = (nk + k - 1) / k;
+}
+
+TLHScratch carve_tlh_scratch(Bump& b, const TLHShape& s, bool backward, Scratch* sc) {
+  TLHScratch x{};
+  const size_t RC = (size_t)s.R * kCcC, RM = (size_t)s.R * s.Cm;
+  x.kt = b.f(RM);
+  tlh_plan(s, &x.ks, &x.z);
+  if (!backward) return x;
+  x.dkpart = b.f((size_t)s.fpc * x.z * s.Q * s.Cm);
+  x.dk = b.f(RM); x.dme = b.f(RM);
+  x.dh = b.f(RC); x.dh1 = b.f(RC); x.dxn = b.f(RC);
+  x.dpooled = b.f((size_t)s.NG * kCcC);
+  x.part_wa = b.f((size_t)s.NG * kCcC);
+  x.part_ba = b.f((size_t)s.NG);
+  x.part_cls = b.f((size_t)kTlhWSplits * s.K1 * (kCcC + 1));
+  x.mfpart = s.nl > 1 ? b.f((size_t)s.nl * s.Cm * s.HW) : nullptr;    // the layers' shares of one frame's d_mask_feature
+  // the Ctx's buffers for colsum / wgrad / dgrad (widest weight: 256 x 256)
+  sc->part_a = b.f((size_t)kColsumBlocks * kCcC);
+  sc->part_b = b.f((size_t)kColsumBlocks * kCcC);
+  sc->wpart = b.f((size_t)(Gemm::kSplit + 1) * kCcC * kCcC);
+  sc->wt = b.f((size_t)kCcC * kCcC);
+  return x;
+}
+
+int tlh_setup(Ctx& c, TLHShape& s, TLHSaved& sv, TLHScratch& x, const AxvsTLHeadTrainCfg* cfg, void* saved, size_t saved_bytes, void* scratch,
+              size_t scratch_bytes, bool backward, void* stream) {
+  int rc;
+  if ((rc = make_tlh_shape(s, cfg)) != AXVS_OK) return rc;
+  Bump sb(saved), cb(scratch);
+  sv = carve_tlh_saved(sb, s);
+  x = carve_tlh_scratch(cb, s, backward, &c.sc);
+  if (sb.off > saved_bytes || cb.off > scratch_bytes)
+    return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
+  c.st = static_cast<hipStream_t>(stream);
+  return c.g.init(c.st);
+}
+
+int tlh_forward(const Ctx& c, const TLHShape& s, const float* X, const float* mf, float* cls, float* masks, const AxvsTLHeadParams& p,
+                const TLHSaved& sv, const TLHScratch& x) {
+  const int C = kCcC, Cm = s.Cm;
+  const long long R = s.R;
+  const bool ex = g_train_exact != 0;
+  const Drop none = make_drop(0.f, 0, 0);
+  int rc;
+  // post_norm (TLCC:767-769)
+  hipLaunchKernelGGL(tr_ln_fwd_kernel, dim3(blocks(R, 4)), dim3(256), 0, c.st, X, p.post_norm_w, p.post_norm_b, sv.xn, sv.mean, sv.rstd, R, C, 1e-5f);
+  // pred_class (:783-797): activation_proj, softmax over the clips, weighted sum, cls_embed (no void bias)
+  hipLaunchKernelGGL(tlt_pool_fwd_kernel, dim3((unsigned)s.NG), dim3(256), 0, c.st, (const float*)sv.xn, p.activation_proj_w, p.activation_proj_b, sv.p,
+                     sv.pooled, s.Tc, C);
+  hipLaunchKernelGGL(cct_small_linear_fwd_kernel, dim3(blocks((size_t)s.NG * s.K1, 4)), dim3(256), 0, c.st, (const float*)sv.pooled, p.cls_embed_w,
+                     p.cls_embed_b, cls, (int)s.NG, C, s.K1, 0.f);
+  // mask_embed (:771): Linear + ReLU, Linear + ReLU, Linear
+  const GemmEpi e0{p.mask_embed_b[0], 1.f, 1, none, 0.f}, e1{p.mask_embed_b[1], 1.f, 1, none, 0.f}, e2{p.mask_embed_b[2], 1.f, 0, none, 0.f};
+  if ((rc = c.g.fwd(sv.xn, p.mask_embed_w[0], sv.h1, R, C, C, 0.f, &e0, ex)) != AXVS_OK) return rc;
+  if ((rc = c.g.fwd(sv.h1, p.mask_embed_w[1], sv.h2, R, C, C, 0.f, &e1, ex)) != AXVS_OK) return rc;
+  if ((rc = c.g.fwd(sv.h2, p.mask_embed_w[2], sv.me, R, Cm, C, 0.f, &e2, ex)) != AXVS_OK) return rc;
+  // 'bqc,btchw->btqhw' per clip (:774-778): per (b, frame) one GEMM over the rows (layer, query) of the frame's clip
+  hipLaunchKernelGGL(cct_kern_pack_kernel, dim3(eblocks((size_t)R * Cm)), dim3(256), 0, c.st, (const float*)sv.me, x.kt, s.nl, s.B, s.Q, s.Tc, Cm);
+  const int GQ = s.nl * s.Q;
+  const long long HW = s.HW;
+  const int al_mf = row_align(mf, HW, HW), al_o = row_align(masks, HW, HW);
+  const long long grp_ld = (long long)s.B * s.T * s.Q * HW;        // one layer's logits
+  for (int b = 0; b < s.B; ++b)
+    for (int f = 0; f < s.T; ++f) {
+      const int t = f / s.fpc;
+      if ((rc = c.g.tn_direct(x.kt + ((size_t)b * s.Tc + t) * Cm * GQ, mf + ((size_t)b * s.T + f) * Cm * HW, masks + ((size_t)b * s.T + f) * s.Q * HW, Cm, GQ,
+                              (int)HW, GQ, HW, HW, al_mf, al_o, nullptr, s.Q, grp_ld)) != AXVS_OK)
+        return rc;
+    }
+  return status();
+}
+
+int tlh_backward(const Ctx& c, const TLHShape& s, const float* d_cls, const float* d_masks, const float* X, const float* mf, const AxvsTLHeadParams& p,
+                 const AxvsTLHeadGrads& g, float* d_q, float* d_mf, const TLHSaved& sv, const TLHScratch& x) {
+  const int C = kCcC, Cm = s.Cm;
+  const long long R = s.R, HW = s.HW;
+  int rc;
+  // d_me[(l, b, q, t)] = sum over the clip's frames and pixels of d_masks[l, b, f, q] mf[b, f]: split-K partials of the clip's fpc frames,
+  // summed in a fixed order (no atomics)
+  const GemmEpi plain{nullptr, 1.f, 0, make_drop(0.f, 0, 0), 0.f};
+  GemmLd ldk{HW, HW, Cm, x.ks};
+  ldk.al_a = row_align(d_masks, HW, HW);
+  ldk.al_b = row_align(mf, HW, HW);
+  const size_t nqc = (size_t)s.Q * Cm;
+  for (int l = 0; l < s.nl; ++l)
+    for (int b = 0; b < s.B; ++b)
+      for (int t = 0; t < s.Tc; ++t) {
+        for (int j = 0; j < s.fpc; ++j) {
+          const int f = t * s.fpc + j;
+          if ((rc = c.g.nt(d_masks + (((size_t)l * s.B + b) * s.T + f) * s.Q * HW, mf + ((size_t)b * s.T + f) * Cm * HW, x.dkpart + (size_t)j * x.z * nqc, s.Q,
+                           Cm, (int)HW, ldk, plain, false, x.z)) != AXVS_OK)
+            return rc;
+        }
+        hipLaunchKernelGGL(tr_colsum_final_kernel, dim3(blocks(nqc, 256)), dim3(256), 0, c.st, (const float*)x.dkpart, s.fpc * x.z, nqc,
+                           x.dk + ((((size_t)b * s.Tc + t) * s.nl + l) * s.Q) * Cm);
+      }
+  hipLaunchKernelGGL(cct_kern_unpack_kernel, dim3(eblocks((size_t)R * Cm)), dim3(256), 0, c.st, (const float*)x.dk, x.dme, s.nl, s.B, s.Q, s.Tc, Cm);
+  // d_mask_feature[b, f] = sum_l sum_q me[l, b, q, clip(f)] d_masks[l, b, f, q]: one contraction over Q per layer, the layers added in order
+  if (d_mf) {
+    const int al_d = row_align(d_masks, HW, HW);
+    for (int b = 0; b < s.B; ++b)
+      for (int f = 0; f < s.T; ++f) {
+        const int t = f / s.fpc;
+        float* const out = d_mf + ((size_t)b * s.T + f) * Cm * HW;
+        for (int l = 0; l < s.nl; ++l) {
+          float* const dst = s.nl > 1 ? x.mfpart + (size_t)l * Cm * HW : out;
+          if ((rc = c.g.tn_direct(sv.me + ((((size_t)l * s.B + b) * s.Q) * s.Tc + t) * Cm, d_masks + (((size_t)l * s.B + b) * s.T + f) * s.Q * HW, dst, s.Q, Cm,
+                                  (int)HW, (long long)s.Tc * Cm, HW, HW, al_d, row_align(dst, HW, HW))) != AXVS_OK)
+            return rc;
+        }
+        if (s.nl > 1)
+          hipLaunchKernelGGL(tlt_sum_layers_kernel, dim3(eblocks((size_t)Cm * HW)), dim3(256), 0, c.st, (const float*)x.mfpart, (size_t)Cm * HW, s.nl, out);
+      }
+  }
+  // mask_embed backward (ReLU masks from the stored post-activation values)
+  if ((rc = c.wgrad(x.dme, sv.h2, g.mask_embed_w[2], R, Cm, C, g.mask_embed_b[2])) != AXVS_OK) return rc;
+  if ((rc = c.dgrad(x.dme, p.mask_embed_w[2], x.dh, R, Cm, C, 0.f)) != AXVS_OK) return rc;
+  hipLaunchKernelGGL(tr_relu_drop_bwd_kernel, dim3(blocks((size_t)R * C / 4)), dim3(256), 0, c.st, x.dh, (const float*)sv.h2, (size_t)R * C / 4, 1.f);
+  if ((rc = c.wgrad(x.dh, sv.h1, g.mask_embed_w[1], R, C, C, g.mask_embed_b[1])) != AXVS_OK) return rc;
+  if ((rc = c.dgrad(x.dh, p.mask_embed_w[1], x.dh1, R, C, C, 0.f)) != AXVS_OK) return rc;
+  hipLaunchKernelGGL(tr_relu_drop_bwd_kernel, dim3(blocks((size_t)R * C / 4)), dim3(256), 0, c.st, x.dh1, (const float*)sv.h1, (size_t)R * C / 4, 1.f);
+  if ((rc = c.wgrad(x.dh1, sv.xn, g.mask_embed_w[0], R, C, C, g.mask_embed_b[0])) != AXVS_OK) return rc;
+  if ((rc = c.dgrad(x.dh1, p.mask_embed_w[0], x.dxn, R, C, C, 0.f)) != AXVS_OK) return rc;
+  // cls_embed, then the pooling (adds its share into dxn)
+  hipLaunchKernelGGL(cct_small_linear_bwd_w_kernel, dim3(s.K1, kTlhWSplits), dim3(256), 0, c.st, d_cls, (const float*)sv.pooled, x.part_cls, (int)s.NG, C, s.K1);
+  hipLaunchKernelGGL(cct_small_linear_bwd_w_final_kernel, dim3(s.K1), dim3(256), 0, c.st, (const float*)x.part_cls, g.cls_embed_w, g.cls_embed_b, kTlhWSplits, C,
+                     s.K1);
+  hipLaunchKernelGGL(cct_small_linear_bwd_x_kernel, dim3((unsigned)s.NG), dim3(256), 0, c.st, d_cls, p.cls_embed_w, x.dpooled, (int)s.NG, C, s.K1);
+  hipLaunchKernelGGL(tlt_pool_bwd_kernel, dim3((unsigned)s.NG), dim3(256), 0, c.st, (const float*)sv.xn, p.activation_proj_w, (const float*)sv.p,
+                     (const float*)x.dpooled, x.dxn, x.part_wa, x.part_ba, s.Tc, C);
+  hipLaunchKernelGGL(tr_colsum_final_kernel, dim3(blocks(C, 256)), dim3(256), 0, c.st, (const float*)x.part_wa, (int)s.NG, (size_t)C, g.activation_proj_w);
+  hipLaunchKernelGGL(cct_reduce_groups_kernel, dim3(1, 1), dim3(256), 0, c.st, (const float*)x.part_ba, (int)s.NG, 1, g.activation_proj_b, (float*)nullptr,
+                     (float*)nullptr, 0.f);
+  // post_norm
+  c.colsum(x.dxn, R, C, g.post_norm_b, X, sv.mean, sv.rstd, g.post_norm_w);
+  hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(blocks(R, 4)), dim3(256), 0, c.st, (const float*)x.dxn, X, p.post_norm_w, (const float*)sv.mean,
+                     (const float*)sv.rstd, d_q, R, C);
+  return status();
+}

@@ -64,6 +64,10 @@ struct GemmLd {     // row strides (floats, multiples of 4) of A, B, C; ksteps >
   float* stat_part = nullptr;
   const float* stat_shift = nullptr;
   int stat_nblk = 0, stat_blk0 = 0, stat_rows = 0;
+  // tr_gemm_tn_kernel<.., GRP>: output row n starts at (n / c_grp_rows) c_grp_ld + (n % c_grp_rows) c -- rows (layer, query)
+  // of the Tube-Link mask einsum written straight into [layer][B][T][Q][pixels]
+  int c_grp_rows = 0;
+  long long c_grp_ld = 0;
 };
 
 inline bool gemm_nt_general(const GemmLd& ld, int K) { return !(ld.al_a == 4 && ld.al_b == 4 && (K & 3) == 0); }

@@ -49,6 +49,8 @@ struct Gemm {
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false, 1>))) return rc;
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false, 2>))) return rc;
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<true>))) return rc;
+    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false, 0, false, true>))) return rc;
+    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<true, 0, false, true>))) return rc;
     return ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false>));
   }
   // row-major:  Y[M,N] = beta Y + epilogue(X[M,K] W[N,K]^T); epilogue (optional): + bias, * mul, ReLU, dropout by element index
@@ -116,14 +118,24 @@ struct Gemm {
   // CC:55) in one split, straight into the caller's tensor
   // al_x / al_o: alignment (floats) of the rows of X and P -- K is a pixel count and need not be a multiple of anything
   // stat (nullable): GemmLd with the stat_* fields set -- the tile sums of P for the BatchNorm behind the einsum (STATS instantiation)
+  // grp_rows > 0: output row n at P + (n / grp_rows) grp_ld + (n % grp_rows) ldo (GemmLd::c_grp_rows)
   int tn_direct(const float* A, const float* X, float* P, int Mc, int N, int K, long long lda, long long ldx, long long ldo, int al_x, int al_o,
-                const GemmLd* stat = nullptr) const {
+                const GemmLd* stat = nullptr, int grp_rows = 0, long long grp_ld = 0) const {
     if (N % 4 || lda % 4) return fail(AXVS_ERR_ARG, "einsum GEMM: N=%d must be a multiple of 4", N);
     const dim3 grid((unsigned)(((N + kGT - 1) / kGT) * ((K + kGT - 1) / kGT)), 1u);
     const long long chunk = (Mc + kGK - 1) / kGK * kGK;
     GemmLd ld{lda, ldx, ldo, 0};
     ld.al_b = al_x;
     ld.al_c = al_o;
+    ld.c_grp_rows = grp_rows;
+    ld.c_grp_ld = grp_ld;
+    if (grp_rows > 0) {
+      if (stat) return fail(AXVS_ERR_ARG, "einsum GEMM: grouped output rows take no statistics");
+      if (al_x == 4 && al_o == 4 && K % 4 == 0)
+        hipLaunchKernelGGL((tr_gemm_tn_kernel<false, 0, false, true>), grid, dim3(512), kGemmLds, st, A, X, P, (long long)Mc, N, K, chunk, (float*)nullptr, ld);
+      else hipLaunchKernelGGL((tr_gemm_tn_kernel<true, 0, false, true>), grid, dim3(512), kGemmLds, st, A, X, P, (long long)Mc, N, K, chunk, (float*)nullptr, ld);
+      return AXVS_OK;
+    }
     if (stat) {
       ld.stat_part = stat->stat_part; ld.stat_shift = stat->stat_shift; ld.stat_nblk = stat->stat_nblk; ld.stat_blk0 = stat->stat_blk0;
       ld.stat_rows = stat->stat_rows;
@@ -1101,6 +1113,53 @@ int axvs_cc_layers_train_bwd(const float* d_queries, const float* clip_query, co
   const size_t n = (size_t)k.s.nl * k.s.M * kCcC;            // the chain adds the next layer's input gradient into this buffer
   if (hipMemcpyAsync(k.x.dx2h, d_queries, n * sizeof(float), hipMemcpyDeviceToDevice, k.st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
   return cc_chain_backward(k, clip_query, layers, layer_grads, d_clip_query, sv);
+}
+
+// ---- the Tube-Link cross-clip head's prediction heads (axvs_cc_train_host.h) -----------------------------------------------------------
+size_t axvs_tl_heads_train_saved_bytes(const AxvsTLHeadTrainCfg* cfg) {
+  TLHShape s;
+  if (make_tlh_shape(s, cfg) != AXVS_OK) return 0;
+  Bump b(nullptr);
+  carve_tlh_saved(b, s);
+  return b.off;
+}
+
+size_t axvs_tl_heads_train_scratch_bytes(const AxvsTLHeadTrainCfg* cfg, int backward) {
+  TLHShape s;
+  if (make_tlh_shape(s, cfg) != AXVS_OK) return 0;
+  Bump b(nullptr);
+  Scratch sc{};
+  carve_tlh_scratch(b, s, backward != 0, &sc);
+  return b.off;
+}
+
+int axvs_tl_heads_train_fwd(const float* queries, const float* mask_feature, float* cls_logits, float* mask_logits, const AxvsTLHeadParams* params,
+                            const AxvsTLHeadTrainCfg* cfg, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!queries || !mask_feature || !cls_logits || !mask_logits || !params || !cfg || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
+  Ctx c{};
+  TLHShape s;
+  TLHSaved sv;
+  TLHScratch x;
+  int rc;
+  if ((rc = cc_check_ptrs(params, sizeof(AxvsTLHeadParams), "AxvsTLHeadParams")) != AXVS_OK) return rc;
+  if ((rc = tlh_setup(c, s, sv, x, cfg, saved, saved_bytes, scratch, scratch_bytes, false, stream)) != AXVS_OK) return rc;
+  return tlh_forward(c, s, queries, mask_feature, cls_logits, mask_logits, *params, sv, x);
+}
+
+int axvs_tl_heads_train_bwd(const float* d_cls, const float* d_masks, const float* queries, const float* mask_feature, const AxvsTLHeadParams* params,
+                            const AxvsTLHeadGrads* grads, float* d_queries, float* d_mask_feature, const AxvsTLHeadTrainCfg* cfg, void* saved,
+                            size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!d_cls || !d_masks || !queries || !mask_feature || !params || !grads || !d_queries || !cfg || !saved || !scratch)
+    return fail(AXVS_ERR_ARG, "null pointer");
+  Ctx c{};
+  TLHShape s;
+  TLHSaved sv;
+  TLHScratch x;
+  int rc;
+  if ((rc = cc_check_ptrs(params, sizeof(AxvsTLHeadParams), "AxvsTLHeadParams")) != AXVS_OK) return rc;
+  if ((rc = cc_check_ptrs(grads, sizeof(AxvsTLHeadGrads), "AxvsTLHeadGrads")) != AXVS_OK) return rc;
+  if ((rc = tlh_setup(c, s, sv, x, cfg, saved, saved_bytes, scratch, scratch_bytes, true, stream)) != AXVS_OK) return rc;
+  return tlh_backward(c, s, d_cls, d_masks, queries, mask_feature, *params, *grads, d_queries, d_mask_feature, sv, x);
 }
 
 // ---- 1x1 convolution + GroupNorm, train() mode (WC/msdeformattn.py:349-375 under autograd) ----

@@ -68,7 +68,8 @@ __device__ __forceinline__ u16x8 tn_frag(const u16* tile, int col0, int fi, int 
 // softmax -- so it does not go through the bf16 split) and reduced over the 32 staging rows through LDS in a fixed order.
 // AMP = 1 / 2 (option train_amp, under torch.autocast): ONE bf16 / fp16 piece per operand, as in tr_gemm_nt_kernel<1>.
 // STATS: GemmLd::stat_* -- sums of the output tile for the BatchNorm that follows the mask einsum
-template <bool GEN, int AMP = 0, bool STATS = false>      // GEN: rows at any 4-byte boundary / extents that are not multiples of 4 (see tr_gemm_nt_kernel)
+// GRP: output rows in groups (GemmLd::c_grp_rows / c_grp_ld) -- its own instantiation, so the other kernels carry none of that addressing
+template <bool GEN, int AMP = 0, bool STATS = false, bool GRP = false>      // GEN: rows at any 4-byte boundary / extents that are not multiples of 4 (see tr_gemm_nt_kernel)
 __global__ __launch_bounds__(512, 4) void tr_gemm_tn_kernel(const float* __restrict__ dY, const float* __restrict__ X, float* __restrict__ part,
                                                             long long M, int N, int K, long long rows_per_split,
                                                             float* __restrict__ part_b, GemmLd ld) {
@@ -178,10 +179,12 @@ __global__ __launch_bounds__(512, 4) void tr_gemm_tn_kernel(const float* __restr
     const int idx = tid + 512 * i, row = idx >> 5, c4 = idx & 31;
     const int n = n0 + row, k = k0 + 4 * c4;
     const float4 o4 = *reinterpret_cast<const float4*>(stg + row * kGLd + 4 * c4);
+    size_t orow = (size_t)n * ld.c;
+    if constexpr (GRP) orow = (size_t)(n / ld.c_grp_rows) * ld.c_grp_ld + (size_t)(n % ld.c_grp_rows) * ld.c;
     if constexpr (!GEN) {
-      if (n < N && k < K) *reinterpret_cast<float4*>(out + (size_t)n * ld.c + k) = o4;
+      if (n < N && k < K) *reinterpret_cast<float4*>(out + orow + k) = o4;
     } else if (n < N) {
-      stg4(out + (size_t)n * ld.c + k, o4, K - k, ld.al_c);
+      stg4(out + orow + k, o4, K - k, ld.al_c);
     }
     if constexpr (STATS) {
       const float ov[4] = {o4.x, o4.y, o4.z, o4.w};

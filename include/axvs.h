@@ -593,6 +593,38 @@ int axvs_cc_layers_train_bwd(const float* d_queries, const float* clip_query, co
                              float* d_clip_query, const AxvsCCTrainCfg* cfg, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
                              void* stream);
 
+/* Training tier of the Tube-Link cross-clip head's prediction heads (TLCC:761-797 under autograd) for ALL layers at once:
+ * post_norm LayerNorm (eps 1e-5), class pooling (activation_proj, softmax over the Tc clips of each (layer, b, q), weighted sum),
+ * cls_embed (no void bias), the three-Linear mask_embed MLP and the per-clip 'bqc,btchw->btqhw' einsum.  The parameters are shared
+ * by the layers (AxvsTLHeadParams, the fp32 nn.Parameter storages).  Split-precision GEMMs as in the chain (16-bit products under
+ * option train_amp); no atomics: a step is bit-reproducible.
+ * Bounds (the size functions return 0 and axvs_last_error() names the bound): C = 256 (the queries), Cm in {128, 256}, Q a multiple
+ * of 4, Tc <= 16, num_layers <= 16, h*w <= 2^26 (any h, w: rows of pixels need no alignment), num_layers*B*Q*Tc*256 < 2^31; any B,
+ * frames_per_clip, K1.  Buffers: `saved` (forward -> backward) and `scratch` sized by the functions below; the backward scratch
+ * holds num_layers shares of one frame's mask-feature gradient (num_layers*Cm*h*w floats) when num_layers > 1. */
+typedef struct AxvsTLHeadGrads {      /* field order of AxvsTLHeadParams; every buffer is WRITTEN (not accumulated) */
+  float *post_norm_w, *post_norm_b;
+  float *activation_proj_w, *activation_proj_b;
+  float *cls_embed_w, *cls_embed_b;
+  float* mask_embed_w[3];
+  float* mask_embed_b[3];
+} AxvsTLHeadGrads;
+typedef struct AxvsTLHeadTrainCfg {
+  int B, Q, Tc, frames_per_clip, h, w, K1, Cm, num_layers;
+} AxvsTLHeadTrainCfg;
+size_t axvs_tl_heads_train_saved_bytes(const AxvsTLHeadTrainCfg* cfg);
+size_t axvs_tl_heads_train_scratch_bytes(const AxvsTLHeadTrainCfg* cfg, int backward);
+/* queries fp32 [nl,B,Q,Tc,256] (what axvs_cc_layers_train_fwd writes); mask_feature fp32 [B,Tc*fpc,Cm,h,w];
+ * cls_logits fp32 [nl,B,Q,K1]; mask_logits fp32 [nl,B,Tc*fpc,Q,h,w]. */
+int axvs_tl_heads_train_fwd(const float* queries, const float* mask_feature, float* cls_logits, float* mask_logits, const AxvsTLHeadParams* params,
+                            const AxvsTLHeadTrainCfg* cfg, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream);
+/* d_cls / d_masks: gradients of cls_logits / mask_logits; `saved` as the forward left it (the mask logits are not read).  Writes
+ * d_queries [nl,B,Q,Tc,256] (the d_queries of axvs_cc_layers_train_bwd), every buffer of `grads`, and d_mask_feature
+ * [B,Tc*fpc,Cm,h,w] when it is not NULL. */
+int axvs_tl_heads_train_bwd(const float* d_cls, const float* d_masks, const float* queries, const float* mask_feature, const AxvsTLHeadParams* params,
+                            const AxvsTLHeadGrads* grads, float* d_queries, float* d_mask_feature, const AxvsTLHeadTrainCfg* cfg, void* saved,
+                            size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
