@@ -102,6 +102,19 @@ class AxvsConvGnParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("conv_w", "conv_b", "gn_w", "gn_b")]
 
 
+class AxvsTestGemm(C.Structure):      # test hook (include/axvs.h): one call of the training tier's GEMM dispatch
+    _fields_ = [("op", C.c_int), ("a", _fp), ("b", _fp), ("c", _fp), ("M", C.c_longlong), ("N", C.c_int), ("K", C.c_int),
+                ("lda", C.c_longlong), ("ldb", C.c_longlong), ("ldc", C.c_longlong), ("al_a", C.c_int), ("al_b", C.c_int), ("al_c", C.c_int),
+                ("a2", _fp), ("aff", _fp), ("aff_rows", C.c_int), ("ksteps", C.c_int), ("zsplits", C.c_int), ("bias", _fp), ("mul", C.c_float),
+                ("relu", C.c_int), ("drop_seed", C.c_uint), ("drop_site", C.c_uint), ("drop_thr", C.c_uint), ("drop_scale", C.c_float),
+                ("beta", C.c_float), ("res", _fp), ("res2", _fp), ("out16", _fp), ("kind16", C.c_int), ("zero_rows", _fp), ("db", _fp),
+                ("exact", C.c_int), ("stat_part", _fp), ("stat_shift", _fp), ("stat_nblk", C.c_int), ("stat_blk0", C.c_int),
+                ("stat_rows", C.c_int), ("grp_rows", C.c_int), ("grp_ld", C.c_longlong), ("variant", C.c_int)]
+
+
+TEST_GEMM_OPS = {"nt": 0, "fwd": 1, "wgrad": 2, "dgrad": 3, "tn_direct": 4}
+
+
 # name -> (restype, argtypes); must list every symbol of include/axvs.h
 SIGNATURES = {
     "axvs_version": (C.c_int, []),
@@ -219,6 +232,8 @@ SIGNATURES = {
     "axvs_pos3d": (C.c_int, [_fp] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_pos3d_masked": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_scaled_residual": (C.c_int, [_fp, _fp, _fp, _fp, C.c_size_t, C.c_int, _fp]),
+    "axvs_test_train_gemm_scratch_bytes": (C.c_size_t, [C.POINTER(AxvsTestGemm)]),
+    "axvs_test_train_gemm": (C.c_int, [C.POINTER(AxvsTestGemm), _fp, _fp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -26,6 +26,10 @@ struct Bump {   // bump allocator over a caller-owned buffer (nullptr: size only
 };
 
 // ---- the Linear layers' GEMMs: split-precision bf16 MFMA kernels (axvs_train_gemm.h) ------------------------------------------------
+// The instantiation the last Gemm launch of this thread ran (include/axvs.h, AxvsTestGemm::variant, has the encoding): set in
+// launch_nt / launch_tn, the only places that launch the GEMM kernels, and reported by axvs_test_train_gemm.
+thread_local int t_gemm_variant = 0;
+
 struct Gemm {
   hipStream_t st = nullptr;
   int init(hipStream_t s) {
@@ -53,41 +57,70 @@ struct Gemm {
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<true, 0, false, true>))) return rc;
     return ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false>));
   }
+  // The argument checks of nt(), wgrad_partials() and tn_direct(): they run before anything touches the device (axvs_test_train_gemm
+  // calls them ahead of init(), so a refused call needs no GPU).
+  static int check_nt(int N, int K, const GemmLd& ld) {
+    if (N % 4 || ld.c % 4 || (ld.al_a == 4 && ld.a % 4) || (ld.al_b == 4 && ld.b % 4))
+      return fail(AXVS_ERR_ARG, "training GEMM: N=%d and the row strides must be multiples of 4 (K=%d)", N, K);
+    if (ld.aff && !ld.a2) return fail(AXVS_ERR_ARG, "training GEMM: the affine loader needs its second operand");
+    return AXVS_OK;
+  }
+  // (the weight-gradient kernel always runs its 16-byte loader: both row strides must keep every row 16-byte aligned)
+  static int check_wgrad(int N, int K, long long ldy, long long ldx) {
+    if (N % 8 || K % 8 || ldy % 4 || ldx % 4)
+      return fail(AXVS_ERR_ARG, "training GEMM: N=%d and K=%d must be multiples of 8, the row strides ldy=%lld and ldx=%lld multiples of 4", N, K,
+                  ldy, ldx);
+    return AXVS_OK;
+  }
+  static int check_tn(int N, long long lda, bool stat, int grp_rows) {
+    if (N % 4 || lda % 4) return fail(AXVS_ERR_ARG, "einsum GEMM: N=%d must be a multiple of 4", N);
+    if (grp_rows > 0 && stat) return fail(AXVS_ERR_ARG, "einsum GEMM: grouped output rows take no statistics");
+    return AXVS_OK;
+  }
+  template <int NS, bool GEN = false, bool ADD = false, bool F16 = false, bool AFF = false>
+  void launch_nt(dim3 grid, const float* X, const float* W, float* Y, long long M, int N, int K, const GemmLd& ld, const GemmEpi& e) const {
+    t_gemm_variant = 0x100 | NS | GEN << 2 | ADD << 3 | F16 << 4 | AFF << 5;
+    hipLaunchKernelGGL((tr_gemm_nt_kernel<NS, 0, GEN, ADD, F16, AFF>), grid, dim3(512), gemm_nt_lds<NS>(), st, X, W, Y, M, N, K, ld, e);
+  }
+  template <bool GEN, int AMP = 0, bool STATS = false, bool GRP = false>
+  void launch_tn(dim3 grid, const float* dY, const float* X, float* part, long long M, int N, int K, long long chunk, float* part_b,
+                 const GemmLd& ld) const {
+    t_gemm_variant = 0x200 | GEN | AMP << 1 | STATS << 3 | GRP << 4;
+    hipLaunchKernelGGL((tr_gemm_tn_kernel<GEN, AMP, STATS, GRP>), grid, dim3(512), kGemmLds, st, dY, X, part, M, N, K, chunk, part_b, ld);
+  }
   // row-major:  Y[M,N] = beta Y + epilogue(X[M,K] W[N,K]^T); epilogue (optional): + bias, * mul, ReLU, dropout by element index
   // exact: three bf16 pieces per operand (fp32 accuracy) -- for the GEMM in front of the ReLU (see tr_gemm_nt_kernel)
   // ld (optional): row strides of X, W, Y (sub-matrices of wider buffers); ld.ksteps > 0 with zsplits: split-K partials [z][M][ld.c]
   int nt(const float* X, const float* W, float* Y, long long M, int N, int K, GemmLd ld, const GemmEpi& e, bool exact, int zsplits = 1) const {
-    if (N % 4 || ld.c % 4 || (ld.al_a == 4 && ld.a % 4) || (ld.al_b == 4 && ld.b % 4))
-      return fail(AXVS_ERR_ARG, "training GEMM: N=%d and the row strides must be multiples of 4 (K=%d)", N, K);
+    if (int rc = check_nt(N, K, ld)) return rc;
     if (M <= 0) return AXVS_OK;
     const dim3 grid((unsigned)((M + kGT - 1) / kGT), (unsigned)((N + kGT - 1) / kGT), (unsigned)zsplits);
     // (a deeper register prefetch for grids of a few workgroups was measured and does not pay: these launches are bound by their
     //  fixed cost -- ~11 us whatever K -- not by the load round trips of the k-loop)
     const bool gen = gemm_nt_general(ld, K), add = ld.a2 != nullptr;   // (the general loader takes the addend at run time)
     if (ld.aff) {                     // affine A operand (two-piece products: an input-gradient GEMM)
-      if (!ld.a2) return fail(AXVS_ERR_ARG, "training GEMM: the affine loader needs its second operand");
-      if (gen) hipLaunchKernelGGL((tr_gemm_nt_kernel<2, 0, true, false, false, true>), grid, dim3(512), gemm_nt_lds<2>(), st, X, W, Y, M, N, K, ld, e);
-      else hipLaunchKernelGGL((tr_gemm_nt_kernel<2, 0, false, false, false, true>), grid, dim3(512), gemm_nt_lds<2>(), st, X, W, Y, M, N, K, ld, e);
+      if (gen) launch_nt<2, true, false, false, true>(grid, X, W, Y, M, N, K, ld, e);
+      else launch_nt<2, false, false, false, true>(grid, X, W, Y, M, N, K, ld, e);
       return AXVS_OK;
     }
     if (g_train_amp) {                // torch.autocast: one 16-bit piece per operand (1: bf16, 2: fp16), whatever the caller's `exact`
-#define AXVS_NT1(F16_)                                                                                                                              \
-  do {                                                                                                                                              \
-    if (gen) hipLaunchKernelGGL((tr_gemm_nt_kernel<1, 0, true, false, F16_>), grid, dim3(512), gemm_nt_lds<1>(), st, X, W, Y, M, N, K, ld, e);      \
-    else if (add) hipLaunchKernelGGL((tr_gemm_nt_kernel<1, 0, false, true, F16_>), grid, dim3(512), gemm_nt_lds<1>(), st, X, W, Y, M, N, K, ld, e); \
-    else hipLaunchKernelGGL((tr_gemm_nt_kernel<1, 0, false, false, F16_>), grid, dim3(512), gemm_nt_lds<1>(), st, X, W, Y, M, N, K, ld, e);         \
-  } while (0)
-      if (g_train_amp == 2) AXVS_NT1(true);
-      else AXVS_NT1(false);
-#undef AXVS_NT1
+      if (g_train_amp == 2) {
+        if (gen) launch_nt<1, true, false, true>(grid, X, W, Y, M, N, K, ld, e);
+        else if (add) launch_nt<1, false, true, true>(grid, X, W, Y, M, N, K, ld, e);
+        else launch_nt<1, false, false, true>(grid, X, W, Y, M, N, K, ld, e);
+      } else {
+        if (gen) launch_nt<1, true>(grid, X, W, Y, M, N, K, ld, e);
+        else if (add) launch_nt<1, false, true>(grid, X, W, Y, M, N, K, ld, e);
+        else launch_nt<1>(grid, X, W, Y, M, N, K, ld, e);
+      }
       return AXVS_OK;
     }
-    if (exact && gen) hipLaunchKernelGGL((tr_gemm_nt_kernel<3, 0, true>), grid, dim3(512), gemm_nt_lds<3>(), st, X, W, Y, M, N, K, ld, e);
-    else if (exact && add) hipLaunchKernelGGL((tr_gemm_nt_kernel<3, 0, false, true>), grid, dim3(512), gemm_nt_lds<3>(), st, X, W, Y, M, N, K, ld, e);
-    else if (exact) hipLaunchKernelGGL(tr_gemm_nt_kernel<3>, grid, dim3(512), gemm_nt_lds<3>(), st, X, W, Y, M, N, K, ld, e);
-    else if (gen) hipLaunchKernelGGL((tr_gemm_nt_kernel<2, 0, true>), grid, dim3(512), gemm_nt_lds<2>(), st, X, W, Y, M, N, K, ld, e);
-    else if (add) hipLaunchKernelGGL((tr_gemm_nt_kernel<2, 0, false, true>), grid, dim3(512), gemm_nt_lds<2>(), st, X, W, Y, M, N, K, ld, e);
-    else hipLaunchKernelGGL(tr_gemm_nt_kernel<2>, grid, dim3(512), gemm_nt_lds<2>(), st, X, W, Y, M, N, K, ld, e);
+    if (exact && gen) launch_nt<3, true>(grid, X, W, Y, M, N, K, ld, e);
+    else if (exact && add) launch_nt<3, false, true>(grid, X, W, Y, M, N, K, ld, e);
+    else if (exact) launch_nt<3>(grid, X, W, Y, M, N, K, ld, e);
+    else if (gen) launch_nt<2, true>(grid, X, W, Y, M, N, K, ld, e);
+    else if (add) launch_nt<2, false, true>(grid, X, W, Y, M, N, K, ld, e);
+    else launch_nt<2>(grid, X, W, Y, M, N, K, ld, e);
     return AXVS_OK;
   }
   // X2 (nullable): added to X element-wise in the loader (q = k = Linear(x + pos) without an x + pos buffer)
@@ -102,15 +135,15 @@ struct Gemm {
   static constexpr int kSplit = 64;
   int wgrad_partials(const float* dY, const float* X, float* part, long long M, int N, int K, int* nparts, float* part_b = nullptr,
                      long long ldy = 0, long long ldx = 0) const {
-    if (N % 8 || K % 8) return fail(AXVS_ERR_ARG, "training GEMM: N=%d and K=%d must be multiples of 8", N, K);
+    const GemmLd ld{ldy ? ldy : N, ldx ? ldx : K, K, 0};
+    if (int rc = check_wgrad(N, K, ld.a, ld.b)) return rc;
     long long chunk = (M + kSplit - 1) / kSplit;
     chunk = (chunk + kGK - 1) / kGK * kGK;                 // whole k-steps per split
     const int np = (int)((M + chunk - 1) / chunk);
     const dim3 grid((unsigned)(((N + kGT - 1) / kGT) * ((K + kGT - 1) / kGT)), (unsigned)np);
-    const GemmLd ld{ldy ? ldy : N, ldx ? ldx : K, K, 0};
-    if (g_train_amp == 1) hipLaunchKernelGGL((tr_gemm_tn_kernel<false, 1>), grid, dim3(512), kGemmLds, st, dY, X, part, M, N, K, chunk, part_b, ld);
-    else if (g_train_amp == 2) hipLaunchKernelGGL((tr_gemm_tn_kernel<false, 2>), grid, dim3(512), kGemmLds, st, dY, X, part, M, N, K, chunk, part_b, ld);
-    else hipLaunchKernelGGL(tr_gemm_tn_kernel<false>, grid, dim3(512), kGemmLds, st, dY, X, part, M, N, K, chunk, part_b, ld);
+    if (g_train_amp == 1) launch_tn<false, 1>(grid, dY, X, part, M, N, K, chunk, part_b, ld);
+    else if (g_train_amp == 2) launch_tn<false, 2>(grid, dY, X, part, M, N, K, chunk, part_b, ld);
+    else launch_tn<false>(grid, dY, X, part, M, N, K, chunk, part_b, ld);
     *nparts = np;
     return AXVS_OK;
   }
@@ -121,7 +154,7 @@ struct Gemm {
   // grp_rows > 0: output row n at P + (n / grp_rows) grp_ld + (n % grp_rows) ldo (GemmLd::c_grp_rows)
   int tn_direct(const float* A, const float* X, float* P, int Mc, int N, int K, long long lda, long long ldx, long long ldo, int al_x, int al_o,
                 const GemmLd* stat = nullptr, int grp_rows = 0, long long grp_ld = 0) const {
-    if (N % 4 || lda % 4) return fail(AXVS_ERR_ARG, "einsum GEMM: N=%d must be a multiple of 4", N);
+    if (int rc = check_tn(N, lda, stat != nullptr, grp_rows)) return rc;
     const dim3 grid((unsigned)(((N + kGT - 1) / kGT) * ((K + kGT - 1) / kGT)), 1u);
     const long long chunk = (Mc + kGK - 1) / kGK * kGK;
     GemmLd ld{lda, ldx, ldo, 0};
@@ -129,23 +162,21 @@ struct Gemm {
     ld.al_c = al_o;
     ld.c_grp_rows = grp_rows;
     ld.c_grp_ld = grp_ld;
+    const bool gen = !(al_x == 4 && al_o == 4 && K % 4 == 0);
     if (grp_rows > 0) {
-      if (stat) return fail(AXVS_ERR_ARG, "einsum GEMM: grouped output rows take no statistics");
-      if (al_x == 4 && al_o == 4 && K % 4 == 0)
-        hipLaunchKernelGGL((tr_gemm_tn_kernel<false, 0, false, true>), grid, dim3(512), kGemmLds, st, A, X, P, (long long)Mc, N, K, chunk, (float*)nullptr, ld);
-      else hipLaunchKernelGGL((tr_gemm_tn_kernel<true, 0, false, true>), grid, dim3(512), kGemmLds, st, A, X, P, (long long)Mc, N, K, chunk, (float*)nullptr, ld);
+      if (gen) launch_tn<true, 0, false, true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
+      else launch_tn<false, 0, false, true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
       return AXVS_OK;
     }
     if (stat) {
       ld.stat_part = stat->stat_part; ld.stat_shift = stat->stat_shift; ld.stat_nblk = stat->stat_nblk; ld.stat_blk0 = stat->stat_blk0;
       ld.stat_rows = stat->stat_rows;
-      if (al_x == 4 && al_o == 4 && K % 4 == 0)
-        hipLaunchKernelGGL((tr_gemm_tn_kernel<false, 0, true>), grid, dim3(512), kGemmLds, st, A, X, P, (long long)Mc, N, K, chunk, (float*)nullptr, ld);
-      else hipLaunchKernelGGL((tr_gemm_tn_kernel<true, 0, true>), grid, dim3(512), kGemmLds, st, A, X, P, (long long)Mc, N, K, chunk, (float*)nullptr, ld);
+      if (gen) launch_tn<true, 0, true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
+      else launch_tn<false, 0, true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
       return AXVS_OK;
     }
-    if (al_x == 4 && al_o == 4 && K % 4 == 0) hipLaunchKernelGGL(tr_gemm_tn_kernel<false>, grid, dim3(512), kGemmLds, st, A, X, P, (long long)Mc, N, K, chunk, (float*)nullptr, ld);
-    else hipLaunchKernelGGL(tr_gemm_tn_kernel<true>, grid, dim3(512), kGemmLds, st, A, X, P, (long long)Mc, N, K, chunk, (float*)nullptr, ld);
+    if (gen) launch_tn<true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
+    else launch_tn<false>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
     return AXVS_OK;
   }
 };
@@ -331,11 +362,13 @@ struct Ctx {
   // mul: dX = mul * dY W; res / res2 (nullable, [M][K]): added in the epilogue
   int dgrad(const float* dY, const float* W, float* dX, long long M, int N, int K, float beta, long long ldy = 0, bool exact = false,
             float mul = 1.f, const float* res = nullptr, const float* res2 = nullptr) const {
+    const GemmLd ld{ldy ? ldy : N, N, K, 0};
+    if (int rc = Gemm::check_nt(K, N, ld)) return rc;      // (before the transpose: a refused call launches nothing)
     hipLaunchKernelGGL(tr_transpose_kernel, dim3((K + 31) / 32, (N + 31) / 32), dim3(256), 0, st, W, sc.wt, N, K);
     GemmEpi e{nullptr, mul, 0, Drop{0u, 0u, 0u, 1.f}, beta};
     e.res = res;
     e.res2 = res2;
-    return g.nt(dY, sc.wt, dX, M, K, N, GemmLd{ldy ? ldy : N, N, K, 0}, e, exact || g_train_exact >= 2);
+    return g.nt(dY, sc.wt, dX, M, K, N, ld, e, exact || g_train_exact >= 2);
   }
   int spatial_lds(const void* fn, size_t bytes) const { return bytes > 64 * 1024 ? ensure_max_lds(fn) : AXVS_OK; }
 };
@@ -1268,6 +1301,75 @@ int axvs_conv1x1_gn_train_bwd(const float* d_out, int out_layout, long long out_
       return fail(AXVS_ERR_ARG, "conv1x1 + GroupNorm backward: an input gradient in strided token rows is not built (pass contiguous rows or NCHW)");
     }
   }
+  return status();
+}
+
+// ---- test hooks: one call of the GEMM dispatch above (include/axvs.h) --------------------------------------------------------------
+size_t axvs_test_train_gemm_scratch_bytes(const AxvsTestGemm* t) {
+  if (!t) return 0;
+  Bump b(nullptr);
+  if (t->op == AXVS_TEST_GEMM_WGRAD) {
+    b.f((size_t)(Gemm::kSplit + 1) * t->N * t->K);     // Ctx::sc.wpart
+    b.f((size_t)Gemm::kSplit * t->N);                 // Ctx::sc.part_a (the bias partials)
+  } else if (t->op == AXVS_TEST_GEMM_DGRAD) {
+    b.f((size_t)t->N * t->K);                         // Ctx::sc.wt
+  }
+  return b.off;
+}
+
+int axvs_test_train_gemm(AxvsTestGemm* t, void* scratch, void* stream) {
+  if (!t || !t->a || !t->b || !t->c) return fail(AXVS_ERR_ARG, "null pointer");
+  t->variant = 0;
+  if (t->M <= 0 || t->N <= 0 || t->K <= 0) return fail(AXVS_ERR_ARG, "non-positive dimension");
+  GemmLd ld{t->lda, t->ldb, t->ldc, t->ksteps, t->a2};
+  ld.al_a = t->al_a; ld.al_b = t->al_b; ld.al_c = t->al_c;
+  ld.aff = t->aff; ld.aff_rows = t->aff_rows;
+  GemmEpi e{t->bias, t->mul, t->relu, Drop{t->drop_seed, t->drop_site, t->drop_thr, t->drop_scale}, t->beta};
+  e.res = t->res; e.res2 = t->res2;
+  e.out16 = t->out16; e.kind16 = t->kind16; e.zero_rows = t->zero_rows;
+  GemmLd stat{0, 0, 0, 0};
+  stat.stat_part = t->stat_part; stat.stat_shift = t->stat_shift; stat.stat_nblk = t->stat_nblk; stat.stat_blk0 = t->stat_blk0;
+  stat.stat_rows = t->stat_rows;
+  // the host-side refusals first: they need no device
+  int rc;
+  switch (t->op) {
+    case AXVS_TEST_GEMM_NT: rc = Gemm::check_nt(t->N, t->K, ld); break;
+    case AXVS_TEST_GEMM_FWD: rc = Gemm::check_nt(t->N, t->K, GemmLd{t->K, t->K, t->N, 0, t->a2}); break;
+    case AXVS_TEST_GEMM_WGRAD: rc = Gemm::check_wgrad(t->N, t->K, t->lda ? t->lda : t->N, t->ldb ? t->ldb : t->K); break;
+    case AXVS_TEST_GEMM_DGRAD: rc = Gemm::check_nt(t->K, t->N, GemmLd{t->lda ? t->lda : t->N, t->N, t->K, 0}); break;
+    case AXVS_TEST_GEMM_TN_DIRECT:
+      if (t->M > INT32_MAX) return fail(AXVS_ERR_ARG, "einsum GEMM: Mc=%lld rows > 2^31 - 1", t->M);
+      rc = Gemm::check_tn(t->N, t->lda, t->stat_part != nullptr, t->grp_rows);
+      break;
+    default: return fail(AXVS_ERR_ARG, "test GEMM: unknown op %d", t->op);
+  }
+  if (rc) return rc;
+  if ((t->op == AXVS_TEST_GEMM_WGRAD || t->op == AXVS_TEST_GEMM_DGRAD) && !scratch) return fail(AXVS_ERR_ARG, "null scratch");
+  Ctx c{};
+  c.st = static_cast<hipStream_t>(stream);
+  if ((rc = c.g.init(c.st))) return rc;
+  Bump b(scratch);
+  if (t->op == AXVS_TEST_GEMM_WGRAD) {
+    c.sc.wpart = b.f((size_t)(Gemm::kSplit + 1) * t->N * t->K);
+    c.sc.part_a = b.f((size_t)Gemm::kSplit * t->N);
+  } else if (t->op == AXVS_TEST_GEMM_DGRAD) {
+    c.sc.wt = b.f((size_t)t->N * t->K);
+  }
+  t_gemm_variant = 0;
+  switch (t->op) {
+    case AXVS_TEST_GEMM_NT: rc = c.g.nt(t->a, t->b, t->c, t->M, t->N, t->K, ld, e, t->exact != 0, t->zsplits > 0 ? t->zsplits : 1); break;
+    case AXVS_TEST_GEMM_FWD: rc = c.g.fwd(t->a, t->b, t->c, t->M, t->N, t->K, t->beta, &e, t->exact != 0, t->a2); break;
+    case AXVS_TEST_GEMM_WGRAD: rc = c.wgrad(t->a, t->b, t->c, t->M, t->N, t->K, t->db, t->lda, t->ldb, t->mul); break;
+    case AXVS_TEST_GEMM_DGRAD:
+      rc = c.dgrad(t->a, t->b, t->c, t->M, t->N, t->K, t->beta, t->lda, t->exact != 0, t->mul, t->res, t->res2);
+      break;
+    default:
+      rc = c.g.tn_direct(t->a, t->b, t->c, (int)t->M, t->N, t->K, t->lda, t->ldb, t->ldc, t->al_b, t->al_c, t->stat_part ? &stat : nullptr,
+                         t->grp_rows, t->grp_ld);
+      break;
+  }
+  t->variant = t_gemm_variant;
+  if (rc) return rc;
   return status();
 }
 

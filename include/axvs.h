@@ -625,6 +625,67 @@ int axvs_tl_heads_train_bwd(const float* d_cls, const float* d_masks, const floa
                             const AxvsTLHeadGrads* grads, float* d_queries, float* d_mask_feature, const AxvsTLHeadTrainCfg* cfg, void* saved,
                             size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- test hooks, not part of the drop-in surface ----------------------------------------------------------------------------------
+ * One call of the training tier's split-precision GEMM dispatch (tr_gemm_nt_kernel / tr_gemm_tn_kernel behind the host code every
+ * training entry point above uses), with every operand, stride and epilogue field explicit: what tests/test_hip_train_gemm.py holds
+ * against float64.  The call goes through the same host functions as the training tiers, so the choice of kernel instantiation is part
+ * of what it exercises; option "train_amp" applies as it does there (under it `exact` is ignored).
+ *   op AXVS_TEST_GEMM_NT         c[M,N] (row stride ldc; with ksteps > 0 the zsplits split-K partials [z][M][ldc]) = epilogue(A B^T), A = a[M,K] (lda, +a2,
+ *                                or with aff the per-row-group affine form of a and a2, aff_rows rows per group), B = b[N,K] (ldb); rows at al_a / al_b floats
+ *      AXVS_TEST_GEMM_FWD        the same on contiguous rows (strides, alignments, aff and split-K ignored)
+ *      AXVS_TEST_GEMM_WGRAD      c[N,K] = mul a[M,N]^T b[M,K] (row strides lda / ldb, 0: N / K) and, when db != NULL, db[N] = mul (column sums of a):
+ *                                the 64-way row-split partials and their deterministic reduction
+ *      AXVS_TEST_GEMM_DGRAD      c[M,K] = beta c + mul a[M,N] b[N,K] + res + res2 (a's row stride lda, 0: N): transpose, then the nt form
+ *      AXVS_TEST_GEMM_TN_DIRECT  c[N,K] (row stride ldc) = a[M,N]^T b[M,K] (lda, ldb), M <= 2^31 - 1 rows in one split; rows of b / c at al_b / al_c floats;
+ *                                stat_part != NULL: the tile statistics (stat_* as GemmLd, axvs_gemm_nt.h); grp_rows > 0: output row n at
+ *                                c + (n / grp_rows) grp_ld + (n % grp_rows) ldc
+ *   Epilogue of NT / FWD: (acc + bias) * mul, ReLU, dropout of element row * N + col (drop_thr = floor(p 2^24), drop_scale = 1 / (1 - p); 0: none),
+ *   + beta c, + res, + res2 (both [M][ldc]); out16 != NULL: one f16 (kind16 1) / bf16 (2) value per element in the blocked layout [ceil(N/32)][M][32]
+ *   instead, rows with zero_rows[row] != 0 written as zeros.
+ *   variant (out): the instantiation launched last, 0x100 | NS | GEN << 2 | ADD << 3 | F16 << 4 | AFF << 5 for tr_gemm_nt_kernel<NS, 0, GEN, ADD, F16, AFF>,
+ *   0x200 | GEN | AMP << 1 | STATS << 3 | GRP << 4 for tr_gemm_tn_kernel<GEN, AMP, STATS, GRP>; 0 when nothing was launched.
+ *   scratch: axvs_test_train_gemm_scratch_bytes(t) bytes (0 for NT, FWD and TN_DIRECT).  Refusals before any device work return AXVS_ERR_ARG. */
+#define AXVS_TEST_GEMM_NT 0
+#define AXVS_TEST_GEMM_FWD 1
+#define AXVS_TEST_GEMM_WGRAD 2
+#define AXVS_TEST_GEMM_DGRAD 3
+#define AXVS_TEST_GEMM_TN_DIRECT 4
+typedef struct AxvsTestGemm {
+  int op;
+  const float* a;
+  const float* b;
+  float* c;
+  long long M;
+  int N, K;
+  long long lda, ldb, ldc;
+  int al_a, al_b, al_c;
+  const float* a2;
+  const float* aff;
+  int aff_rows;
+  int ksteps, zsplits;
+  const float* bias;
+  float mul;
+  int relu;
+  unsigned drop_seed, drop_site, drop_thr;
+  float drop_scale;
+  float beta;
+  const float* res;
+  const float* res2;
+  unsigned short* out16;
+  int kind16;
+  const unsigned char* zero_rows;
+  float* db;
+  int exact;
+  float* stat_part;
+  const float* stat_shift;
+  int stat_nblk, stat_blk0, stat_rows;
+  int grp_rows;
+  long long grp_ld;
+  int variant;
+} AxvsTestGemm;
+size_t axvs_test_train_gemm_scratch_bytes(const AxvsTestGemm* t);
+int axvs_test_train_gemm(AxvsTestGemm* t, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
