@@ -102,6 +102,14 @@ class AxvsConvGnParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("conv_w", "conv_b", "gn_w", "gn_b")]
 
 
+class AxvsFfnParams(C.Structure):
+    _fields_ = [(n, _fp) for n in ("norm1_w", "norm1_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b", "norm2_w", "norm2_b")]
+
+
+class AxvsFpnLevelParams(C.Structure):
+    _fields_ = [(n, _fp) for n in ("lateral_w", "lateral_gn_w", "lateral_gn_b", "output_w", "output_gn_w", "output_gn_b", "mask_w", "mask_b")]
+
+
 class AxvsTestGemm(C.Structure):      # test hook (include/axvs.h): one call of the training tier's GEMM dispatch
     _fields_ = [("op", C.c_int), ("a", _fp), ("b", _fp), ("c", _fp), ("M", C.c_longlong), ("N", C.c_int), ("K", C.c_int),
                 ("lda", C.c_longlong), ("ldb", C.c_longlong), ("ldc", C.c_longlong), ("al_a", C.c_int), ("al_b", C.c_int), ("al_c", C.c_int),
@@ -178,6 +186,14 @@ SIGNATURES = {
     "axvs_cc_heads_pack": (C.c_int, [C.POINTER(AxvsCCHeadParams), _fp, C.c_int, C.c_int, _fp]),
     "axvs_cc_heads_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "axvs_cc_heads_fwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp] + [C.c_int] * 8 + [_fp, C.c_size_t, _fp]),
+    "axvs_ffn_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "axvs_ffn_pack": (C.c_int, [C.POINTER(AxvsFfnParams), _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    "axvs_ffn_packed_fwd": (C.c_int, [_fp, _fp, _fp, C.c_longlong, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp]),
+    "axvs_fpn_level_packed_bytes": (C.c_size_t, [C.c_int] * 3),
+    "axvs_fpn_level_pack": (C.c_int, [C.POINTER(AxvsFpnLevelParams), _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "axvs_fpn_level_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "axvs_fpn_level_fwd": (C.c_int, [_fp, _fp, C.c_longlong, C.c_longlong, C.c_int, C.c_int, _fp, _fp, _fp] + [C.c_int] * 7 +
+                           [C.c_float, C.c_int, _fp, C.c_size_t, _fp]),
     "axvs_conv1x1_gn_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "axvs_conv1x1_gn_pack": (C.c_int, [C.POINTER(AxvsConvGnParams), _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "axvs_conv1x1_gn_workspace_bytes": (C.c_size_t, [C.c_int] * 4),

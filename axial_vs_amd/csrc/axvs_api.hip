@@ -11,6 +11,7 @@
 #include "axvs_cc.h"
 #include "axvs_msda.h"
 #include "axvs_glue.h"
+#include "axvs_fpn.h"
 #include "axvs_lsap.h"
 #include "axvs_common.h"
 #include "axvs_fused.h"
@@ -2283,6 +2284,217 @@ int axvs_scaled_residual(const float* a, const float* b, const float* gamma, flo
   if (!a || !b || !gamma || !out || C <= 0) return fail(AXVS_ERR_ARG, "bad argument");
   hipLaunchKernelGGL(scaled_residual_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      a, b, gamma, out, n, C);
+  return last_launch_status();
+}
+
+// ---- Tube-Link MSDeformAttnPixelDecoder (TL/mmdet/models/plugins/msdeformattn_pixel_decoder.py): encoder-layer FFN tail and FPN tail ----
+size_t axvs_ffn_packed_bytes(int C, int d_ffn) {
+  Carver c(nullptr);
+  carve_ffn(c, C, d_ffn);
+  return c.off;
+}
+
+int axvs_ffn_pack(const AxvsFfnParams* p, void* packed, int C, int d_ffn, int dtype, void* stream) {
+  if (int rcd = check_dtype(dtype)) return rcd;
+  if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
+  if (int rc = check_cfg(C, C / 32 > 0 ? C / 32 : 1)) return rc;
+  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
+  Carver c(packed);
+  LayerPacked l = carve_ffn(c, C, d_ffn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == AXVS_BF16) pack_ffn<kBF>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
+  else pack_ffn<false>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
+  return last_launch_status();
+}
+
+int axvs_ffn_packed_fwd(const float* x, float* out, const void* packed_ffn, long long M, int C, int d_ffn, int dtype, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  if (int rcd = check_dtype(dtype)) return rcd;
+  if (!x || !out || !packed_ffn || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
+  if (M <= 0) return fail(AXVS_ERR_ARG, "empty input");
+  const int heads = C / 32 > 0 ? C / 32 : 1;      // head_dim 32: the fused FFN tier's configuration at C = 256 (heads only select the tier here)
+  if (int rc = check_cfg(C, heads)) return rc;
+  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
+  if (workspace_bytes < axvs_ffn_workspace_bytes(M, C, d_ffn)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Carver pc(const_cast<void*>(packed_ffn));
+  LayerPacked p = carve_ffn(pc, C, d_ffn);
+  Carver wc(workspace);
+  float* xin = wc.take<float>((size_t)M * C);
+  float* tmp = wc.take<float>((size_t)M * C);
+  u16* y16 = wc.take<u16>((size_t)M * C);
+  u16* h16 = wc.take<u16>((size_t)M * d_ffn);
+  if (hipMemcpyAsync(xin, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return fail(AXVS_ERR_LAUNCH, "copy failed");
+  g_prof_next = 0;
+  int rc = dtype == AXVS_BF16 ? run_ffn<kBF>(xin, out, p, M, C, heads, d_ffn, tmp, y16, h16, st)
+                              : run_ffn<false>(xin, out, p, M, C, heads, d_ffn, tmp, y16, h16, st);
+  return rc != AXVS_OK ? rc : last_launch_status();
+}
+
+namespace {
+struct FpnPacked {
+  u16 *lat_w3, *out_w, *mask_w;
+  float *lat_wf, *lat_g, *lat_b, *out_g, *out_b, *mask_b;
+};
+FpnPacked carve_fpn(Carver& c, int Cin, int C, int Cm) {
+  FpnPacked f{};
+  f.lat_w3 = c.take<u16>(3 * (size_t)Cin * ((C + 15) & ~15));
+  f.lat_wf = c.take<float>((size_t)C * Cin);
+  f.lat_g = c.take<float>(C);
+  f.lat_b = c.take<float>(C);
+  f.out_w = c.take<u16>(9 * (size_t)C * C);
+  f.out_g = c.take<float>(C);
+  f.out_b = c.take<float>(C);
+  if (Cm > 0) {
+    f.mask_w = c.take<u16>((size_t)C * Cm);
+    f.mask_b = c.take<float>(Cm);
+  }
+  return f;
+}
+struct FpnWs {
+  float *tok, *lat, *gpart, *stats1, *cpart, *stats2;
+  u16* m16;
+};
+FpnWs carve_fpn_ws(Carver& c, int N, int H, int W, int Cin, int C, int groups) {
+  const size_t M = (size_t)N * H * W;
+  const size_t nblk = (size_t)(H * W + 63) / 64, tiles = (size_t)((W + kFpnTW - 1) / kFpnTW) * ((H + kFpnTH - 1) / kFpnTH);
+  FpnWs w{};
+  w.tok = c.take<float>(M * Cin);            // token-row copy of the NCHW lateral input (128 x 128 GEMM path)
+  w.lat = c.take<float>(M * C);              // raw lateral conv output, then the raw 3x3 conv output
+  w.m16 = c.take<u16>(M * C);                // merged map, f16 channels-last rows
+  w.gpart = c.take<float>((size_t)N * nblk * groups * 2);
+  w.cpart = c.take<float>((size_t)N * tiles * C * 2);
+  w.stats1 = c.take<float>((size_t)N * groups * 2);
+  w.stats2 = c.take<float>((size_t)N * groups * 2);
+  return w;
+}
+int fpn_check(int Cin, int C, int Cm) {
+  if (Cin <= 0 || Cin % 32 || C <= 0 || C % 32 || C > 4096 || Cm < 0 || Cm % 32)
+    return fail(AXVS_ERR_ARG, "Cin=%d and C=%d must be positive multiples of 32 (C <= 4096), Cm=%d a multiple of 32 (0: no mask_feature)", Cin, C, Cm);
+  return AXVS_OK;
+}
+}  // namespace
+
+size_t axvs_fpn_level_packed_bytes(int Cin, int C, int Cm) {
+  Carver c(nullptr);
+  carve_fpn(c, Cin, C, Cm);
+  return c.off;
+}
+
+int axvs_fpn_level_pack(const AxvsFpnLevelParams* p, void* packed, int Cin, int C, int Cm, int dtype, void* stream) {
+  if (int rcd = check_dtype(dtype)) return rcd;
+  if (!p || !packed || !p->lateral_w || !p->lateral_gn_w || !p->lateral_gn_b || !p->output_w || !p->output_gn_w || !p->output_gn_b)
+    return fail(AXVS_ERR_ARG, "null pointer");
+  if (int rc = fpn_check(Cin, C, Cm)) return rc;
+  if (Cm > 0 && (!p->mask_w || !p->mask_b)) return fail(AXVS_ERR_ARG, "null pointer (mask_feature weights with Cm=%d)", Cm);
+  Carver c(packed);
+  const FpnPacked f = carve_fpn(c, Cin, C, Cm);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  PackDim nd{C, C, 0, 0, 0}, kd{Cin, Cin, 0, 0, 0}, md{Cm, Cm, 0, 0, 0}, cd{C, C, 0, 0, 0};
+  const long long w3 = 9LL * C * C;
+  if (dtype == AXVS_BF16) {
+    pack_w3<kBF>(p->lateral_w, f.lat_w3, nd, kd, st);
+    hipLaunchKernelGGL((fpn_pack3x3_kernel<kBF>), dim3((unsigned)((w3 + 255) / 256)), dim3(256), 0, st, p->output_w, f.out_w, C, C);
+    if (Cm > 0) pack_w<kBF>(p->mask_w, f.mask_w, md, cd, st);
+  } else {
+    pack_w3<false>(p->lateral_w, f.lat_w3, nd, kd, st);
+    hipLaunchKernelGGL((fpn_pack3x3_kernel<false>), dim3((unsigned)((w3 + 255) / 256)), dim3(256), 0, st, p->output_w, f.out_w, C, C);
+    if (Cm > 0) pack_w<false>(p->mask_w, f.mask_w, md, cd, st);
+  }
+  if (hipMemcpyAsync(f.lat_wf, p->lateral_w, (size_t)C * Cin * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return fail(AXVS_ERR_LAUNCH, "copy failed");
+  copy_f32(p->lateral_gn_w, f.lat_g, C, st);
+  copy_f32(p->lateral_gn_b, f.lat_b, C, st);
+  copy_f32(p->output_gn_w, f.out_g, C, st);
+  copy_f32(p->output_gn_b, f.out_b, C, st);
+  if (Cm > 0) copy_f32(p->mask_b, f.mask_b, Cm, st);
+  return last_launch_status();
+}
+
+size_t axvs_fpn_level_workspace_bytes(int N, int H, int W, int Cin, int C, int groups) {
+  Carver c(nullptr);
+  carve_fpn_ws(c, N, H, W, Cin, C, groups);
+  return c.off;
+}
+
+int axvs_fpn_level_fwd(const float* x, const float* up, long long up_batch_stride, long long up_ld, int Hu, int Wu, float* y,
+                       float* mask_feature, const void* packed, int N, int H, int W, int Cin, int C, int Cm, int groups, float eps, int dtype,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rcd = check_dtype(dtype)) return rcd;
+  if (!x || !up || !packed || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
+  if (!y && !mask_feature) return fail(AXVS_ERR_ARG, "null pointer: neither y nor mask_feature requested");
+  if (mask_feature && Cm <= 0) return fail(AXVS_ERR_ARG, "mask_feature requested from a pack without mask_feature weights (Cm=%d)", Cm);
+  if (int rc = fpn_check(Cin, C, Cm)) return rc;
+  if (N <= 0 || H <= 0 || W <= 0 || Hu <= 0 || Wu <= 0) return fail(AXVS_ERR_ARG, "empty shape");
+  if (N > 65535) return fail(AXVS_ERR_ARG, "N=%d frames: at most 65535 (grid dimension)", N);
+  if (groups <= 0 || C % groups) return fail(AXVS_ERR_ARG, "groups=%d must divide C=%d", groups, C);
+  if ((long long)N * H * W > 2147483647LL / 64) return fail(AXVS_ERR_ARG, "N*H*W=%lld too large for 32-bit row indices", (long long)N * H * W);
+  if (up_ld < C || up_ld % 4 || up_batch_stride % 4 || up_batch_stride < (long long)Hu * Wu * up_ld - (up_ld - C) ||
+      (reinterpret_cast<uintptr_t>(up) & 15))
+    return fail(AXVS_ERR_ARG, "up: row stride %lld / batch stride %lld must be multiples of 4 floats covering [Hu*Wu, C] rows, pointer 16-byte aligned",
+                up_ld, up_batch_stride);
+  if (workspace_bytes < axvs_fpn_level_workspace_bytes(N, H, W, Cin, C, groups)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Carver pc(const_cast<void*>(packed));
+  const FpnPacked f = carve_fpn(pc, Cin, C, Cm);
+  Carver wc(workspace);
+  const FpnWs w = carve_fpn_ws(wc, N, H, W, Cin, C, groups);
+  const int HW = H * W;
+  const long long M = (long long)N * HW;
+  const int nblk = (HW + 63) / 64, ntx = (W + kFpnTW - 1) / kFpnTW, tiles = ntx * ((H + kFpnTH - 1) / kFpnTH);
+  const bool bf = dtype == AXVS_BF16;
+  g_prof_next = 0;
+  mark(st, "begin");
+  // 1. lateral 1x1 conv (no bias: use_bias = norm_cfg is None, TL:136) -> raw fp32 rows; the GEMMs of axvs_conv1x1_gn_fwd
+  if (g_msda_gemm && g_conv_nt128 && ((M + 127) / 128) * ((C + 127) / 128) >= g_conv_nt128_nchw) {
+    hipLaunchKernelGGL(nchw_to_tokens_kernel, dim3((unsigned)((HW + 63) / 64), (unsigned)((Cin + 63) / 64), N), dim3(256), 0, st, x, w.tok, Cin, HW);
+    const tr::GemmEpi e{nullptr, 1.f, 0, tr::Drop{0, 0, 0, 1.f}, 0.f};
+    if (int rc = launch_nt128(w.tok, nullptr, f.lat_wf, w.lat, M, C, Cin, e, st, g_conv_nt128_exact != 0)) return rc;
+  } else {
+    const EpiRowsF32 ey{w.lat, nullptr, nullptr, identity_map(M), C, 1.f};
+    if (bf) launch_gemm<kBF>(ALoadNCHWSplit3<kBF>{x, (int)M, Cin, HW}, f.lat_w3, ey, (int)M, C, 3 * Cin, st);
+    else launch_gemm<false>(ALoadNCHWSplit3<false>{x, (int)M, Cin, HW}, f.lat_w3, ey, (int)M, C, 3 * Cin, st);
+  }
+  mark(st, "fpn.lateral");
+  {
+    const int n4 = C / 4, lanes = n4 < 256 ? n4 : 256, rg = 256 / lanes;
+    hipLaunchKernelGGL(gn_stats_kernel, dim3((unsigned)nblk, N), dim3(256), 2 * (size_t)rg * C * sizeof(float), st, (const float*)w.lat, w.gpart, HW, C, groups);
+    hipLaunchKernelGGL(fpn_gn_finalize_kernel, dim3(groups, N), dim3(256), 0, st, (const float*)w.gpart, nblk, groups, 1, groups,
+                       (double)HW * (C / groups), eps, w.stats1);
+  }
+  // 2. GroupNorm apply + bilinear(up) -> merged f16 rows (TL:314-318)
+  {
+    const long long tot = M * (C / 4);
+    if (bf) hipLaunchKernelGGL((fpn_merge_kernel<kBF>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)w.lat, (const float*)w.stats1, (const float*)f.lat_g,
+                               (const float*)f.lat_b, up, up_batch_stride, up_ld, Hu, Wu, w.m16, N, H, W, C, groups);
+    else hipLaunchKernelGGL((fpn_merge_kernel<false>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)w.lat, (const float*)w.stats1, (const float*)f.lat_g,
+                            (const float*)f.lat_b, up, up_batch_stride, up_ld, Hu, Wu, w.m16, N, H, W, C, groups);
+  }
+  mark(st, "fpn.merge");
+  // 3. 3x3 conv (implicit GEMM) + per-tile partial sums -> GroupNorm statistics (TL:319)
+  {
+    const dim3 grid((unsigned)tiles, (unsigned)((C + 255) / 256), (unsigned)N);
+    if (bf) hipLaunchKernelGGL((fpn_conv3x3_kernel<kBF>), grid, dim3(256), 0, st, (const u16*)w.m16, (const u16*)f.out_w, w.lat, w.cpart, H, W, C, C, ntx);
+    else hipLaunchKernelGGL((fpn_conv3x3_kernel<false>), grid, dim3(256), 0, st, (const u16*)w.m16, (const u16*)f.out_w, w.lat, w.cpart, H, W, C, C, ntx);
+    mark(st, "fpn.conv3x3");
+    hipLaunchKernelGGL(fpn_gn_finalize_kernel, dim3(groups, N), dim3(256), 0, st, (const float*)w.cpart, tiles, C, C / groups, groups,
+                       (double)HW * (C / groups), eps, w.stats2);
+  }
+  // 4. the level's output ReLU(GN(c)) as fp32 rows, when asked for
+  if (y) {
+    const long long tot = M * (C / 4);
+    hipLaunchKernelGGL(fpn_gn_relu_rows_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)w.lat, (const float*)w.stats2,
+                       (const float*)f.out_g, (const float*)f.out_b, y, M, HW, C, groups);
+    mark(st, "fpn.gn_relu");
+  }
+  // 5. mask_feature = conv1x1(ReLU(GN(c))) + bias (TL:324), GroupNorm + ReLU in the A loader, NCHW fp32 out
+  if (mask_feature) {
+    const EpiNCHWBias em{mask_feature, f.mask_b, HW, Cm};
+    if (bf) launch_gemm<kBF>(ALoadGnRelu<kBF>{w.lat, w.stats2, f.out_g, f.out_b, (int)M, C, HW, groups}, f.mask_w, em, (int)M, Cm, C, st);
+    else launch_gemm<false>(ALoadGnRelu<false>{w.lat, w.stats2, f.out_g, f.out_b, (int)M, C, HW, groups}, f.mask_w, em, (int)M, Cm, C, st);
+    mark(st, "fpn.mask_feature");
+  }
   return last_launch_status();
 }
 

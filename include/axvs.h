@@ -219,6 +219,49 @@ size_t axvs_ffn_workspace_bytes(long long M, int C, int d_ffn);
 int axvs_ffn_fwd(const float* x, float* out, const void* packed_layer, long long M, int C, int heads, int d_ffn,
                  int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The same feed-forward tail from its own four parameter pairs: mmcv BaseTransformerLayer with operation_order
+ *      ('self_attn', 'norm', 'ffn', 'norm') after the attention, as in every layer of Tube-Link's MSDeformAttnPixelDecoder encoder
+ *      (TL/mmdet/models/plugins/msdeformattn_pixel_decoder.py:63-88): norms[0] -> ffns[0] (x + fc2(relu(fc1(x))), mmcv FFN with
+ *      add_identity) -> norms[1], LayerNorm eps 1e-5.  norm1 / norm2 = norms[0] / norms[1], linear1 / linear2 = ffns[0].layers[0][0] /
+ *      ffns[0].layers[1].  x / out fp32 [M, C] (out may be x: x is copied first); C a multiple of 32; workspace axvs_ffn_workspace_bytes(M, C, d_ffn). */
+typedef struct AxvsFfnParams {
+  const float *norm1_w, *norm1_b;       /* [C] */
+  const float *linear1_w, *linear1_b;   /* [F,C], [F] */
+  const float *linear2_w, *linear2_b;   /* [C,F], [C] */
+  const float *norm2_w, *norm2_b;       /* [C] */
+} AxvsFfnParams;
+size_t axvs_ffn_packed_bytes(int C, int d_ffn);
+int axvs_ffn_pack(const AxvsFfnParams* p, void* packed, int C, int d_ffn, int dtype, void* stream);
+int axvs_ffn_packed_fwd(const float* x, float* out, const void* packed_ffn, long long M, int C, int d_ffn, int dtype, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ---- FPN tail of Tube-Link's MSDeformAttnPixelDecoder for one level the encoder does not see (TL:311-325, stride 4 in every
+ *      shipped config), lateral_convs[i] / output_convs[i] ConvModules with GroupNorm and no conv bias (use_bias = norm_cfg is None, TL:136):
+ *        m = GN(conv1x1(x)) + F.interpolate(up, size = (H, W), mode = 'bilinear', align_corners = False)      TL:313-318
+ *        c = ReLU(GN(conv3x3(m, padding = 1)))                                                                  TL:319
+ *        mask_feature = conv1x1(c) + bias  (the mask_feature Conv2d, TL:324; only for the last level)
+ *      x: backbone map, NCHW fp32 [N, Cin, H, W].  up: the next-coarser level's output as fp32 token rows, row (n, y*Wu + x) at
+ *      up + n*up_batch_stride + (y*Wu + x)*up_ld (a level slice of the encoder's [N, S, C] buffer, read where it lies; any size ratio).
+ *      y (NULL: not written): ReLU(GN(conv3x3(m))) as fp32 token rows [N, H*W, C].  mask_feature (NULL: not computed): NCHW fp32
+ *      [N, Cm, H, W].  m is stored once as f16 channels-last rows (the 3x3 conv's operand type); the 3x3 conv is an implicit GEMM on
+ *      16x16x32 f16 (bf16) MFMAs with fp32 accumulation, writes fp32 rows and per-tile partial sums; the GroupNorm statistics are reduced in
+ *      a fixed order (bit-identical run to run); the mask_feature GEMM normalises c in its operand loader.
+ *      Bounds: H, W, Hu, Wu >= 1; Cin, C multiples of 32 (C <= 4096); Cm a multiple of 32 (0: the pack holds no mask_feature weights);
+ *      groups divides C; N <= 65535; N*H*W < 2^31 / 64 (the 32-bit row indices of the GEMMs); up_ld / up_batch_stride multiples of 4, up 16-byte aligned.  Otherwise AXVS_ERR_ARG. */
+typedef struct AxvsFpnLevelParams {
+  const float* lateral_w;                        /* lateral_convs[i].conv.weight [C, Cin, 1, 1] */
+  const float *lateral_gn_w, *lateral_gn_b;      /* lateral_convs[i].gn [C] */
+  const float* output_w;                         /* output_convs[i].conv.weight [C, C, 3, 3] */
+  const float *output_gn_w, *output_gn_b;        /* output_convs[i].gn [C] */
+  const float *mask_w, *mask_b;                  /* mask_feature [Cm, C, 1, 1], [Cm]; may be NULL when Cm = 0 */
+} AxvsFpnLevelParams;
+size_t axvs_fpn_level_packed_bytes(int Cin, int C, int Cm);
+int axvs_fpn_level_pack(const AxvsFpnLevelParams* p, void* packed, int Cin, int C, int Cm, int dtype, void* stream);
+size_t axvs_fpn_level_workspace_bytes(int N, int H, int W, int Cin, int C, int groups);
+int axvs_fpn_level_fwd(const float* x, const float* up, long long up_batch_stride, long long up_ld, int Hu, int Wu, float* y,
+                       float* mask_feature, const void* packed, int N, int H, int W, int Cin, int C, int Cm, int groups, float eps, int dtype,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* =====================================================================================================
  * Cross-clip tracking module (CC/maxtron_cross_clip_tracking_module.py), d_model = 256, 8 heads, norm_fn = 'ln'.
  * ===================================================================================================== */
