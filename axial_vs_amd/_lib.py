@@ -110,6 +110,29 @@ class AxvsFpnLevelParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("lateral_w", "lateral_gn_w", "lateral_gn_b", "output_w", "output_gn_w", "output_gn_b", "mask_w", "mask_b")]
 
 
+def fill(cls, ptrs):
+    """A `cls` with `ptrs` assigned to its fields in declaration order: a nested Structure is filled recursively, a ctypes array takes
+    as many pointers as it has elements.  A gradient struct has its parameter struct's layout (include/axvs.h), so this fills both."""
+    ptrs = list(ptrs)
+    s, n = _fill(cls, ptrs, 0)
+    if n != len(ptrs):
+        raise ValueError(f"{cls.__name__} takes {n} pointers, got {len(ptrs)}")
+    return s
+
+
+def _fill(cls, ptrs, i):
+    s = cls()
+    for name, t in cls._fields_:
+        if issubclass(t, C.Structure):
+            v, i = _fill(t, ptrs, i)
+        elif issubclass(t, C.Array):
+            v, i = t(*ptrs[i:i + t._length_]), i + t._length_
+        else:
+            v, i = ptrs[i], i + 1
+        setattr(s, name, v)
+    return s, i
+
+
 class AxvsTestGemm(C.Structure):      # test hook (include/axvs.h): one call of the training tier's GEMM dispatch
     _fields_ = [("op", C.c_int), ("a", _fp), ("b", _fp), ("c", _fp), ("M", C.c_longlong), ("N", C.c_int), ("K", C.c_int),
                 ("lda", C.c_longlong), ("ldb", C.c_longlong), ("ldc", C.c_longlong), ("al_a", C.c_int), ("al_b", C.c_int), ("al_c", C.c_int),

@@ -27,9 +27,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from . import _lib
-from .training import _f32c
-
-_BN_SITES = ("_class_embedding_projection", "_mask_embedding_projection")
+from ._autograd import apply, cast, draw_seed, f32c, grad_buffer, nbytes, place, require_gpu
 
 
 def _bn_modules(mod):
@@ -37,10 +35,9 @@ def _bn_modules(mod):
             mod._predictor._pixel_space_mask_batch_norm]
 
 
-def module_parameters(mod) -> List[Tensor]:
-    """Every trainable tensor of the module, in the order the autograd Function returns gradients."""
+def chain_parameters(mod, num_layers: int) -> List[Tensor]:
     ps: List[Tensor] = []
-    for i in range(mod.num_layers):
+    for i in range(num_layers):
         lay, asp, cn = mod.transformer_trajectory_self_attention_layers[i], mod.conv_short_aggregate_layers[i], mod.conv_norms[i]
         at = lay.self_attn
         ps += [at.qkv.weight, at.qkv.bias, at.proj_q.weight, at.proj_q.bias, at.proj_kv.weight, at.proj_kv.bias, at.proj.weight, at.proj.bias,
@@ -49,6 +46,12 @@ def module_parameters(mod) -> List[Tensor]:
             conv = getattr(asp, f"_aspp_conv{k}")
             ps += [conv.weight, conv.bias]
         ps += [asp._proj_conv_bn_act.conv.weight, asp._proj_conv_bn_act.norm.weight, asp._proj_conv_bn_act.norm.bias, cn.weight, cn.bias]
+    return ps
+
+
+def module_parameters(mod) -> List[Tensor]:
+    """Every trainable tensor of the module, in the order the autograd Function returns gradients."""
+    ps = chain_parameters(mod, mod.num_layers)
     pr = mod._predictor
     ps += [mod._class_embedding_projection.conv.weight, mod._class_embedding_projection.norm.weight, mod._class_embedding_projection.norm.bias,
            mod._mask_embedding_projection.conv.weight, mod._mask_embedding_projection.norm.weight, mod._mask_embedding_projection.norm.bias,
@@ -60,7 +63,6 @@ def module_parameters(mod) -> List[Tensor]:
 
 
 _PER_LAYER = 21
-_HEAD = 15
 
 
 def _layer_struct(ptrs: List[int], Cc: int = 256):
@@ -75,6 +77,11 @@ def _layer_struct(ptrs: List[int], Cc: int = 256):
     return s
 
 
+def _layers(ptrs: List[int], nl: int):
+    """The AxvsCCLayerParams (or AxvsCCLayerGrads) array of `nl` layers from the chain's tensors."""
+    return (_lib.AxvsCCLayerParams * nl)(*[_layer_struct(ptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
+
+
 def _head_struct(ptrs: List[int], running) -> _lib.AxvsCCHeadParams:
     h = _lib.AxvsCCHeadParams()
     h.class_proj_w, h.class_proj_bn = ptrs[0], _lib.AxvsBN(ptrs[1], ptrs[2], running[0][0], running[0][1])
@@ -82,16 +89,6 @@ def _head_struct(ptrs: List[int], running) -> _lib.AxvsCCHeadParams:
     h.mask_head_w, h.mask_head_bn = ptrs[6], _lib.AxvsBN(ptrs[7], ptrs[8], running[2][0], running[2][1])
     h.class_head_w, h.class_head_b, h.act_head_w, h.act_head_b = ptrs[9:13]
     h.pixel_bn = _lib.AxvsBN(ptrs[13], ptrs[14], running[3][0], running[3][1])
-    return h
-
-
-def _head_grads(ptrs: List[int]) -> _lib.AxvsCCHeadGrads:
-    h = _lib.AxvsCCHeadGrads()
-    h.class_proj_w, h.class_proj_bn = ptrs[0], _lib.AxvsBNGrads(ptrs[1], ptrs[2])
-    h.mask_proj_w, h.mask_proj_bn = ptrs[3], _lib.AxvsBNGrads(ptrs[4], ptrs[5])
-    h.mask_head_w, h.mask_head_bn = ptrs[6], _lib.AxvsBNGrads(ptrs[7], ptrs[8])
-    h.class_head_w, h.class_head_b, h.act_head_w, h.act_head_b = ptrs[9:13]
-    h.pixel_bn = _lib.AxvsBNGrads(ptrs[13], ptrs[14])
     return h
 
 
@@ -138,34 +135,29 @@ class _CCModuleTrain(torch.autograd.Function):
     def forward(ctx, clip_query, panoptic_features, cfg, running, *params):
         from .modules import _stream
         dims, rates, p_attn, p_aspp, seed = cfg
-        if not clip_query.is_cuda:
-            raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
+        require_gpu(clip_query)
         B, Q, Tc, V, H, W, K1, nl = dims
-        cq, pf = _f32c(clip_query), _f32c(panoptic_features)
-        ws = [_f32c(w) for w in params]
-        rn = [(_f32c(m), _f32c(v)) for m, v in running]
-        L = _lib.lib()
+        cq, pf = f32c(clip_query), f32c(panoptic_features)
+        ws = [f32c(w) for w in params]
+        rn = [(f32c(m), f32c(v)) for m, v in running]
         dev = cq.device
         group = _sync_group()
         with torch.cuda.device(dev):
             probe = _cfg(dims, rates, p_attn, p_aspp, seed, None)
-            nsaved = L.axvs_cc_module_train_saved_bytes(C.byref(probe))
-            nscr = L.axvs_cc_module_train_scratch_bytes(C.byref(probe), 0)
-            nstat = L.axvs_cc_module_train_bn_stats_floats(C.byref(probe))
-            if nsaved == 0 or nscr == 0:
-                raise RuntimeError("axvs_cc_module_train_saved_bytes: " + L.axvs_last_error().decode())
-            saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
+            nsaved = nbytes("axvs_cc_module_train_saved_bytes", C.byref(probe))
+            nscr = nbytes("axvs_cc_module_train_scratch_bytes", C.byref(probe), 0)
+            nstat = _lib.lib().axvs_cc_module_train_bn_stats_floats(C.byref(probe))
+            saved, _, scratch = place(dev, nsaved, nscr, shared=False)       # (the SyncBatchNorm hook checks its buffers lie in `scratch`)
             logits = torch.empty(nl, 1, Q, K1, dtype=torch.float32, device=dev)
             masks = torch.empty(nl, B, Q, Tc * V, H, W, dtype=torch.float32, device=dev)
             stats = torch.empty(nstat, dtype=torch.float32, device=dev)
             hook = _AllReduce(scratch, group) if group is not None else None
             c = _cfg(dims, rates, p_attn, p_aspp, seed, hook)
             ptrs = [w.data_ptr() for w in ws]
-            layers = (_lib.AxvsCCLayerParams * nl)(*[_layer_struct(ptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
             heads = _head_struct(ptrs[nl * _PER_LAYER:], [(m.data_ptr(), v.data_ptr()) for m, v in rn])
-            rc = L.axvs_cc_module_train_fwd(cq.data_ptr(), pf.data_ptr(), logits.data_ptr(), masks.data_ptr(), stats.data_ptr(), layers,
-                                            C.byref(heads), C.byref(c), saved.data_ptr(), nsaved, scratch.data_ptr(), nscr, _stream(dev))
+            rc = _lib.lib().axvs_cc_module_train_fwd(cq.data_ptr(), pf.data_ptr(), logits.data_ptr(), masks.data_ptr(), stats.data_ptr(),
+                                                     _layers(ptrs, nl), C.byref(heads), C.byref(c), saved.data_ptr(), nsaved,
+                                                     scratch.data_ptr(), nscr, _stream(dev))
             if hook is not None and hook.error is not None:
                 raise hook.error
             _lib.check(rc, "axvs_cc_module_train_fwd")
@@ -174,7 +166,7 @@ class _CCModuleTrain(torch.autograd.Function):
         ctx.running = rn
         ctx.cfg = cfg
         ctx.saved_buf = saved
-        ctx.in_dtypes = (clip_query.dtype, [w.dtype for w in params])
+        ctx.in_dtypes = [t.dtype for t in (clip_query, *params)]
         ctx.mark_non_differentiable(stats)
         return logits, masks, stats
 
@@ -185,40 +177,31 @@ class _CCModuleTrain(torch.autograd.Function):
         cq, pf, *ws = ctx.saved_tensors
         dims, rates, p_attn, p_aspp, seed = ctx.cfg
         B, Q, Tc, V, H, W, K1, nl = dims
-        L = _lib.lib()
         dev = cq.device
         group = _sync_group()
         with torch.cuda.device(dev):
-            gl = _f32c(d_logits) if d_logits is not None else torch.zeros(nl, 1, Q, K1, dtype=torch.float32, device=dev)
-            gm = _f32c(d_masks) if d_masks is not None else torch.zeros(nl, B, Q, Tc * V, H, W, dtype=torch.float32, device=dev)
+            gl = f32c(d_logits) if d_logits is not None else torch.zeros(nl, 1, Q, K1, dtype=torch.float32, device=dev)
+            gm = f32c(d_masks) if d_masks is not None else torch.zeros(nl, B, Q, Tc * V, H, W, dtype=torch.float32, device=dev)
             probe = _cfg(dims, rates, p_attn, p_aspp, seed, None)
-            nsaved = L.axvs_cc_module_train_saved_bytes(C.byref(probe))
-            nscr = L.axvs_cc_module_train_scratch_bytes(C.byref(probe), 1)
-            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
+            nsaved = nbytes("axvs_cc_module_train_saved_bytes", C.byref(probe))
+            nscr = nbytes("axvs_cc_module_train_scratch_bytes", C.byref(probe), 1)
+            _, saved_ptr, scratch = place(dev, nsaved, nscr, shared=False, saved=ctx.saved_buf)
             hook = _AllReduce(scratch, group) if group is not None else None
             c = _cfg(dims, rates, p_attn, p_aspp, seed, hook)
-            sizes = [w.numel() for w in ws]
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            grads, off = [], 0
-            for w, n in zip(ws, sizes):
-                grads.append(flat[off:off + n].view(w.shape))
-                off += n
+            grads = grad_buffer(ws, dev)
             d_cq = torch.empty_like(cq)
-            ptrs = [w.data_ptr() for w in ws]
-            gptrs = [g.data_ptr() for g in grads]
-            layers = (_lib.AxvsCCLayerParams * nl)(*[_layer_struct(ptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
-            lgrads = (_lib.AxvsCCLayerParams * nl)(*[_layer_struct(gptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
+            ptrs, gptrs = [w.data_ptr() for w in ws], [g.data_ptr() for g in grads]
             heads = _head_struct(ptrs[nl * _PER_LAYER:], [(m.data_ptr(), v.data_ptr()) for m, v in ctx.running])
-            hgrads = _head_grads(gptrs[nl * _PER_LAYER:])
+            hgrads = _lib.fill(_lib.AxvsCCHeadGrads, gptrs[nl * _PER_LAYER:])
             with _lib.train_amp(ctx.amp):
-                rc = L.axvs_cc_module_train_bwd(gl.data_ptr(), gm.data_ptr(), cq.data_ptr(), pf.data_ptr(), layers, C.byref(heads), lgrads,
-                                                C.byref(hgrads), d_cq.data_ptr(), C.byref(c), ctx.saved_buf.data_ptr(), nsaved, scratch.data_ptr(), nscr,
-                                                _stream(dev))
+                rc = _lib.lib().axvs_cc_module_train_bwd(gl.data_ptr(), gm.data_ptr(), cq.data_ptr(), pf.data_ptr(), _layers(ptrs, nl),
+                                                         C.byref(heads), _layers(gptrs, nl), C.byref(hgrads), d_cq.data_ptr(), C.byref(c),
+                                                         saved_ptr, nsaved, scratch.data_ptr(), nscr, _stream(dev))
             if hook is not None and hook.error is not None:
                 raise hook.error
             _lib.check(rc, "axvs_cc_module_train_bwd")
-        qd, wd = ctx.in_dtypes
-        return (d_cq.to(qd), None, None, None, *[g.to(dt) for g, dt in zip(grads, wd)])
+        d_cq, *grads = cast([d_cq, *grads], ctx.in_dtypes)
+        return (d_cq, None, None, None, *grads)
 
 
 def cc_module_train(mod, clip_query: Tensor, panoptic_features: Tensor):
@@ -241,18 +224,10 @@ def cc_module_train(mod, clip_query: Tensor, panoptic_features: Tensor):
     K1 = mod._predictor._transformer_class_head.conv.weight.shape[0]
     nl = mod.num_layers
     p_attn, p_aspp = float(mod.attn_drop), float(mod.aspp_drop)
-    seed = getattr(mod, "dropout_seed", None)
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p_attn > 0 or p_aspp > 0) else 0
-    cfg = ((int(B), int(Q), int(Tc), int(V), int(H), int(W), int(K1), int(nl)), tuple(int(r) for r in mod.atrous_rates), p_attn, p_aspp, int(seed))
+    cfg = ((int(B), int(Q), int(Tc), int(V), int(H), int(W), int(K1), int(nl)), tuple(int(r) for r in mod.atrous_rates), p_attn, p_aspp,
+           draw_seed(mod, p_attn, p_aspp))
     running = [(bn.running_mean, bn.running_var) for bn in bns]
-    args = (clip_query, panoptic_features, cfg, running, *module_parameters(mod))
-    if torch.is_autocast_enabled():
-        amp = _lib.autocast_mode(mod)       # (read before autocast is switched off for the call)
-        with torch.autocast(device_type="cuda", enabled=False), _lib.train_amp(amp):
-            logits, masks, stats = _CCModuleTrain.apply(*args)
-    else:
-        logits, masks, stats = _CCModuleTrain.apply(*args)
+    logits, masks, stats = apply(mod, _CCModuleTrain, clip_query, panoptic_features, cfg, running, *module_parameters(mod))
     # running statistics: one momentum step per layer call, in layer order (nn.BatchNorm semantics, momentum 0.01), folded into
     # one update per buffer: r <- (1-m)^nl r + sum_l m (1-m)^(nl-1-l) stat_l
     with torch.no_grad():
@@ -280,52 +255,32 @@ def cc_module_train(mod, clip_query: Tensor, panoptic_features: Tensor):
 
 
 # ---- the layer chain alone: the first half of the Tube-Link head's train() mode (its prediction heads follow: tl_heads_train below) ------
-def chain_parameters(mod, num_layers: int) -> List[Tensor]:
-    ps: List[Tensor] = []
-    for i in range(num_layers):
-        lay, asp, cn = mod.transformer_trajectory_self_attention_layers[i], mod.conv_short_aggregate_layers[i], mod.conv_norms[i]
-        at = lay.self_attn
-        ps += [at.qkv.weight, at.qkv.bias, at.proj_q.weight, at.proj_q.bias, at.proj_kv.weight, at.proj_kv.bias, at.proj.weight, at.proj.bias,
-               lay.norm.weight, lay.norm.bias]
-        for k in range(3):
-            conv = getattr(asp, f"_aspp_conv{k}")
-            ps += [conv.weight, conv.bias]
-        ps += [asp._proj_conv_bn_act.conv.weight, asp._proj_conv_bn_act.norm.weight, asp._proj_conv_bn_act.norm.bias, cn.weight, cn.bias]
-    return ps
-
-
 class _CCLayersTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, clip_query, cfg, *params):
         from .modules import _stream
         dims, rates, p_attn, p_aspp, seed = cfg
-        if not clip_query.is_cuda:
-            raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
+        require_gpu(clip_query)
         B, Q, Tc, nl = dims
-        cq = _f32c(clip_query)
-        ws = [_f32c(w) for w in params]
-        L = _lib.lib()
+        cq = f32c(clip_query)
+        ws = [f32c(w) for w in params]
         dev = cq.device
         full = (B, Q, Tc, 1, 1, 1, 1, nl)
         with torch.cuda.device(dev):
             c = _cfg(full, rates, p_attn, p_aspp, seed, None)
             c.chain_only = 1
-            nsaved = L.axvs_cc_module_train_saved_bytes(C.byref(c))
-            nscr = L.axvs_cc_module_train_scratch_bytes(C.byref(c), 0)
-            if nsaved == 0 or nscr == 0:
-                raise RuntimeError("axvs_cc_module_train_saved_bytes: " + L.axvs_last_error().decode())
-            saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
+            nsaved = nbytes("axvs_cc_module_train_saved_bytes", C.byref(c))
+            nscr = nbytes("axvs_cc_module_train_scratch_bytes", C.byref(c), 0)
+            saved, _, scratch = place(dev, nsaved, nscr, shared=False)
             out = torch.empty(nl, B, Q, Tc, 256, dtype=torch.float32, device=dev)
-            ptrs = [w.data_ptr() for w in ws]
-            layers = (_lib.AxvsCCLayerParams * nl)(*[_layer_struct(ptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
-            _lib.check(L.axvs_cc_layers_train_fwd(cq.data_ptr(), out.data_ptr(), layers, C.byref(c), saved.data_ptr(), nsaved, scratch.data_ptr(), nscr,
-                                                  _stream(dev)), "axvs_cc_layers_train_fwd")
+            _lib.check(_lib.lib().axvs_cc_layers_train_fwd(cq.data_ptr(), out.data_ptr(), _layers([w.data_ptr() for w in ws], nl), C.byref(c),
+                                                           saved.data_ptr(), nsaved, scratch.data_ptr(), nscr, _stream(dev)),
+                       "axvs_cc_layers_train_fwd")
         ctx.save_for_backward(cq, *ws)
         ctx.amp = _lib.current_amp()
         ctx.cfg = (full, rates, p_attn, p_aspp, seed)
         ctx.saved_buf = saved
-        ctx.in_dtypes = (clip_query.dtype, [w.dtype for w in params])
+        ctx.in_dtypes = [t.dtype for t in (clip_query, *params)]
         return out
 
     @staticmethod
@@ -335,30 +290,23 @@ class _CCLayersTrain(torch.autograd.Function):
         cq, *ws = ctx.saved_tensors
         full, rates, p_attn, p_aspp, seed = ctx.cfg
         nl = full[-1]
-        L = _lib.lib()
         dev = cq.device
         with torch.cuda.device(dev):
-            g = _f32c(d_out)
+            g = f32c(d_out)
             c = _cfg(full, rates, p_attn, p_aspp, seed, None)
             c.chain_only = 1
-            nsaved = L.axvs_cc_module_train_saved_bytes(C.byref(c))
-            nscr = L.axvs_cc_module_train_scratch_bytes(C.byref(c), 1)
-            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
-            sizes = [w.numel() for w in ws]
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            grads, off = [], 0
-            for w, n in zip(ws, sizes):
-                grads.append(flat[off:off + n].view(w.shape))
-                off += n
+            nsaved = nbytes("axvs_cc_module_train_saved_bytes", C.byref(c))
+            nscr = nbytes("axvs_cc_module_train_scratch_bytes", C.byref(c), 1)
+            _, saved_ptr, scratch = place(dev, nsaved, nscr, shared=False, saved=ctx.saved_buf)
+            grads = grad_buffer(ws, dev)
             d_cq = torch.empty_like(cq)
-            ptrs, gptrs = [w.data_ptr() for w in ws], [t.data_ptr() for t in grads]
-            layers = (_lib.AxvsCCLayerParams * nl)(*[_layer_struct(ptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
-            lgrads = (_lib.AxvsCCLayerParams * nl)(*[_layer_struct(gptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
             with _lib.train_amp(ctx.amp):
-                _lib.check(L.axvs_cc_layers_train_bwd(g.data_ptr(), cq.data_ptr(), layers, lgrads, d_cq.data_ptr(), C.byref(c), ctx.saved_buf.data_ptr(),
-                                                      nsaved, scratch.data_ptr(), nscr, _stream(dev)), "axvs_cc_layers_train_bwd")
-        qd, wd = ctx.in_dtypes
-        return (d_cq.to(qd), None, *[t.to(dt) for t, dt in zip(grads, wd)])
+                _lib.check(_lib.lib().axvs_cc_layers_train_bwd(g.data_ptr(), cq.data_ptr(), _layers([w.data_ptr() for w in ws], nl),
+                                                               _layers([t.data_ptr() for t in grads], nl), d_cq.data_ptr(), C.byref(c),
+                                                               saved_ptr, nsaved, scratch.data_ptr(), nscr, _stream(dev)),
+                           "axvs_cc_layers_train_bwd")
+        d_cq, *grads = cast([d_cq, *grads], ctx.in_dtypes)
+        return (d_cq, None, *grads)
 
 
 def cc_layers_train(mod, clip_query: Tensor, num_layers: int, rates, p_attn: float, p_aspp: float) -> Tensor:
@@ -366,16 +314,9 @@ def cc_layers_train(mod, clip_query: Tensor, num_layers: int, rates, p_attn: flo
     B, Q, Tc, Cq = clip_query.shape
     if Cq != 256:
         raise RuntimeError("clip_query must be [B,Q,Tc,256]")
-    seed = getattr(mod, "dropout_seed", None)
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p_attn > 0 or p_aspp > 0) else 0
-    cfg = ((int(B), int(Q), int(Tc), int(num_layers)), tuple(int(r) for r in rates), float(p_attn), float(p_aspp), int(seed))
-    args = (clip_query, cfg, *chain_parameters(mod, num_layers))
-    if torch.is_autocast_enabled():
-        amp = _lib.autocast_mode(mod)       # (read before autocast is switched off for the call)
-        with torch.autocast(device_type="cuda", enabled=False), _lib.train_amp(amp):
-            return _CCLayersTrain.apply(*args)
-    return _CCLayersTrain.apply(*args)
+    cfg = ((int(B), int(Q), int(Tc), int(num_layers)), tuple(int(r) for r in rates), float(p_attn), float(p_aspp),
+           draw_seed(mod, p_attn, p_aspp))
+    return apply(mod, _CCLayersTrain, clip_query, cfg, *chain_parameters(mod, num_layers))
 
 
 # ---- the Tube-Link head's prediction heads, all layers at once (axvs_tl_heads_train_*) ------------------------------------------------
@@ -385,14 +326,6 @@ def tl_heads_parameters(mod) -> List[Tensor]:
     pn, me = mod.transformer_decoder.post_norm, mod.mask_embed
     return [pn.weight, pn.bias, mod.activation_proj.weight, mod.activation_proj.bias, mod.cls_embed.weight, mod.cls_embed.bias,
             me[0].weight, me[2].weight, me[4].weight, me[0].bias, me[2].bias, me[4].bias]
-
-
-def _tl_struct(ptrs: List[int], cls=_lib.AxvsTLHeadParams):
-    s = cls()
-    s.post_norm_w, s.post_norm_b, s.activation_proj_w, s.activation_proj_b, s.cls_embed_w, s.cls_embed_b = ptrs[:6]
-    for k in range(3):
-        s.mask_embed_w[k], s.mask_embed_b[k] = ptrs[6 + k], ptrs[9 + k]
-    return s
 
 
 def tl_heads_cfg(nl: int, B: int, Q: int, Tc: int, fpc: int, h: int, w: int, K1: int, Cm: int) -> _lib.AxvsTLHeadTrainCfg:
@@ -408,31 +341,27 @@ class _TLHeadsTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, queries, mask_features, dims, *params):
         from .modules import _stream
-        if not queries.is_cuda:
-            raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
+        require_gpu(queries)
         nl, B, Q, Tc, fpc, h, w, K1, Cm = dims
-        qs, mf = _f32c(queries), _f32c(mask_features)
-        ws = [_f32c(p) for p in params]
-        L = _lib.lib()
+        qs, mf = f32c(queries), f32c(mask_features)
+        ws = [f32c(p) for p in params]
         dev = qs.device
         with torch.cuda.device(dev):
             c = tl_heads_cfg(*dims)
-            nsaved = L.axvs_tl_heads_train_saved_bytes(C.byref(c))
-            nscr = L.axvs_tl_heads_train_scratch_bytes(C.byref(c), 0)
-            if nsaved == 0 or nscr == 0:
-                raise RuntimeError("axvs_tl_heads_train_saved_bytes: " + L.axvs_last_error().decode())
-            saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
+            nsaved = nbytes("axvs_tl_heads_train_saved_bytes", C.byref(c))
+            nscr = nbytes("axvs_tl_heads_train_scratch_bytes", C.byref(c), 0)
+            saved, _, scratch = place(dev, nsaved, nscr, shared=False)
             cls = torch.empty(nl, B, Q, K1, dtype=torch.float32, device=dev)
             masks = torch.empty(nl, B, Tc * fpc, Q, h, w, dtype=torch.float32, device=dev)
-            hp = _tl_struct([t.data_ptr() for t in ws])
-            _lib.check(L.axvs_tl_heads_train_fwd(qs.data_ptr(), mf.data_ptr(), cls.data_ptr(), masks.data_ptr(), C.byref(hp), C.byref(c),
-                                                 saved.data_ptr(), nsaved, scratch.data_ptr(), nscr, _stream(dev)), "axvs_tl_heads_train_fwd")
+            hp = _lib.fill(_lib.AxvsTLHeadParams, [t.data_ptr() for t in ws])
+            _lib.check(_lib.lib().axvs_tl_heads_train_fwd(qs.data_ptr(), mf.data_ptr(), cls.data_ptr(), masks.data_ptr(), C.byref(hp), C.byref(c),
+                                                          saved.data_ptr(), nsaved, scratch.data_ptr(), nscr, _stream(dev)),
+                       "axvs_tl_heads_train_fwd")
         ctx.save_for_backward(qs, mf, *ws)
         ctx.amp = _lib.current_amp()
         ctx.dims = dims
         ctx.saved_buf = saved
-        ctx.in_dtypes = (queries.dtype, mask_features.dtype, [p.dtype for p in params])
+        ctx.in_dtypes = [t.dtype for t in (queries, mask_features, *params)]
         return cls, masks
 
     @staticmethod
@@ -441,31 +370,26 @@ class _TLHeadsTrain(torch.autograd.Function):
         from .modules import _stream
         qs, mf, *ws = ctx.saved_tensors
         nl, B, Q, Tc, fpc, h, w, K1, Cm = ctx.dims
-        L = _lib.lib()
         dev = qs.device
         with torch.cuda.device(dev):
-            gc = _f32c(d_cls) if d_cls is not None else torch.zeros(nl, B, Q, K1, dtype=torch.float32, device=dev)
-            gm = _f32c(d_masks) if d_masks is not None else torch.zeros(nl, B, Tc * fpc, Q, h, w, dtype=torch.float32, device=dev)
+            gc = f32c(d_cls) if d_cls is not None else torch.zeros(nl, B, Q, K1, dtype=torch.float32, device=dev)
+            gm = f32c(d_masks) if d_masks is not None else torch.zeros(nl, B, Tc * fpc, Q, h, w, dtype=torch.float32, device=dev)
             c = tl_heads_cfg(*ctx.dims)
-            nsaved = L.axvs_tl_heads_train_saved_bytes(C.byref(c))
-            nscr = L.axvs_tl_heads_train_scratch_bytes(C.byref(c), 1)
-            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
-            sizes = [p.numel() for p in ws]
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            grads, off = [], 0
-            for p, n in zip(ws, sizes):
-                grads.append(flat[off:off + n].view(p.shape))
-                off += n
+            nsaved = nbytes("axvs_tl_heads_train_saved_bytes", C.byref(c))
+            nscr = nbytes("axvs_tl_heads_train_scratch_bytes", C.byref(c), 1)
+            _, saved_ptr, scratch = place(dev, nsaved, nscr, shared=False, saved=ctx.saved_buf)
+            grads = grad_buffer(ws, dev)
             d_q = torch.empty_like(qs)
             d_mf = torch.empty_like(mf) if ctx.needs_input_grad[1] else None
-            hp = _tl_struct([p.data_ptr() for p in ws])
-            hg = _tl_struct([g.data_ptr() for g in grads], _lib.AxvsTLHeadGrads)
+            hp = _lib.fill(_lib.AxvsTLHeadParams, [p.data_ptr() for p in ws])
+            hg = _lib.fill(_lib.AxvsTLHeadGrads, [g.data_ptr() for g in grads])
             with _lib.train_amp(ctx.amp):
-                _lib.check(L.axvs_tl_heads_train_bwd(gc.data_ptr(), gm.data_ptr(), qs.data_ptr(), mf.data_ptr(), C.byref(hp), C.byref(hg), d_q.data_ptr(),
-                                                     d_mf.data_ptr() if d_mf is not None else None, C.byref(c), ctx.saved_buf.data_ptr(), nsaved,
-                                                     scratch.data_ptr(), nscr, _stream(dev)), "axvs_tl_heads_train_bwd")
-        qd, md, wd = ctx.in_dtypes
-        return (d_q.to(qd), d_mf.to(md) if d_mf is not None else None, None, *[g.to(dt) for g, dt in zip(grads, wd)])
+                _lib.check(_lib.lib().axvs_tl_heads_train_bwd(gc.data_ptr(), gm.data_ptr(), qs.data_ptr(), mf.data_ptr(), C.byref(hp), C.byref(hg),
+                                                              d_q.data_ptr(), d_mf.data_ptr() if d_mf is not None else None, C.byref(c),
+                                                              saved_ptr, nsaved, scratch.data_ptr(), nscr, _stream(dev)),
+                           "axvs_tl_heads_train_bwd")
+        d_q, d_mf, *grads = cast([d_q, d_mf, *grads], ctx.in_dtypes)
+        return (d_q, d_mf, None, *grads)
 
 
 def tl_heads_train(mod, queries: Tensor, mask_features: Tensor, cfg: _lib.AxvsTLHeadTrainCfg):
@@ -473,9 +397,4 @@ def tl_heads_train(mod, queries: Tensor, mask_features: Tensor, cfg: _lib.AxvsTL
     mask_features [B,Tc*fpc,Cm,h,w] -> (class logits [nl,B,Q,K1], mask logits [nl,B,Tc*fpc,Q,h,w]).  `cfg` from tl_heads_cfg, accepted
     by tl_heads_supported."""
     dims = (cfg.num_layers, cfg.B, cfg.Q, cfg.Tc, cfg.frames_per_clip, cfg.h, cfg.w, cfg.K1, cfg.Cm)
-    args = (queries, mask_features, dims, *tl_heads_parameters(mod))
-    if torch.is_autocast_enabled():
-        amp = _lib.autocast_mode(mod)       # (read before autocast is switched off for the call)
-        with torch.autocast(device_type="cuda", enabled=False), _lib.train_amp(amp):
-            return _TLHeadsTrain.apply(*args)
-    return _TLHeadsTrain.apply(*args)
+    return apply(mod, _TLHeadsTrain, queries, mask_features, dims, *tl_heads_parameters(mod))

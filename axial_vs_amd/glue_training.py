@@ -14,23 +14,16 @@ import torch
 from torch import Tensor
 
 from . import _lib
-
-
-def _f32c(t: Tensor) -> Tensor:
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
+from ._autograd import cast, f32c, place, require_gpu
 
 
 class _ConvGnTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, conv_w, conv_b, gn_w, gn_b, in_layout, out_layout, N, HW, Cin, Cout, groups, eps, hw):
-        from .modules import _stream, _workspace
-        if not x.is_cuda:
-            raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
-        xs = _f32c(x)
-        ws = [_f32c(w) for w in (conv_w, conv_b, gn_w, gn_b)]
+        from .modules import _stream
+        require_gpu(x)
+        xs = f32c(x)
+        ws = [f32c(w) for w in (conv_w, conv_b, gn_w, gn_b)]
         L = _lib.lib()
         dev = xs.device
         il, ol = (0 if in_layout == "nchw" else 1), (0 if out_layout == "nchw" else 1)
@@ -38,38 +31,37 @@ class _ConvGnTrain(torch.autograd.Function):
         obs, old = (0, 0) if ol == 0 else (HW * Cout, Cout)
         with torch.cuda.device(dev):
             out = torch.empty((N, Cout) + tuple(hw), dtype=torch.float32, device=dev) if ol == 0 else torch.empty(N, HW, Cout, dtype=torch.float32, device=dev)
-            saved = torch.empty(max(L.axvs_conv1x1_gn_train_saved_bytes(N, HW, Cin, Cout, groups, il, ibs, ild), 1), dtype=torch.uint8, device=dev)
-            scratch = _workspace(dev, L.axvs_conv1x1_gn_train_scratch_bytes(N, HW, Cin, Cout, groups, 1))
-            ps = _lib.AxvsConvGnParams(*[w.data_ptr() for w in ws])
+            # (the scratch is sized for the backward in both directions)
+            saved, _, scratch = place(dev, max(L.axvs_conv1x1_gn_train_saved_bytes(N, HW, Cin, Cout, groups, il, ibs, ild), 1),
+                                      L.axvs_conv1x1_gn_train_scratch_bytes(N, HW, Cin, Cout, groups, 1))
+            ps = _lib.fill(_lib.AxvsConvGnParams, [w.data_ptr() for w in ws])
             _lib.check(L.axvs_conv1x1_gn_train_fwd(xs.data_ptr(), il, ibs, ild, out.data_ptr(), ol, obs, old, C.byref(ps), N, HW, Cin, Cout, groups, eps,
                                                    saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(), _stream(dev)), "axvs_conv1x1_gn_train_fwd")
         ctx.save_for_backward(xs, saved, *ws)
         ctx.cfg = (il, ol, ibs, ild, obs, old, N, HW, Cin, Cout, groups)
-        ctx.in_dtypes = (x.dtype, conv_w.dtype, conv_b.dtype, gn_w.dtype, gn_b.dtype)
+        ctx.in_dtypes = [t.dtype for t in (x, conv_w, conv_b, gn_w, gn_b)]
         ctx.x_shape = tuple(x.shape)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        from .modules import _stream, _workspace
-        xs, saved, cw, cb, gw, gb = ctx.saved_tensors
+        from .modules import _stream
+        xs, saved, *ws = ctx.saved_tensors
         il, ol, ibs, ild, obs, old, N, HW, Cin, Cout, groups = ctx.cfg
         L = _lib.lib()
         dev = xs.device
-        d = _f32c(d_out)
+        d = f32c(d_out)
         with torch.cuda.device(dev):
-            grads = [torch.empty_like(w) for w in (cw, cb, gw, gb)]
-            need_dx = ctx.needs_input_grad[0]
-            dx = torch.empty_like(xs) if need_dx else None
-            scratch = _workspace(dev, L.axvs_conv1x1_gn_train_scratch_bytes(N, HW, Cin, Cout, groups, 1))
-            ps = _lib.AxvsConvGnParams(cw.data_ptr(), cb.data_ptr(), gw.data_ptr(), gb.data_ptr())
-            gs = _lib.AxvsConvGnParams(*[g.data_ptr() for g in grads])
-            _lib.check(L.axvs_conv1x1_gn_train_bwd(d.data_ptr(), ol, obs, old, xs.data_ptr(), il, ibs, ild, C.byref(ps), C.byref(gs), dx.data_ptr() if need_dx else None,
-                                                   N, HW, Cin, Cout, groups, saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(), _stream(dev)),
+            grads = [torch.empty_like(w) for w in ws]
+            dx = torch.empty_like(xs) if ctx.needs_input_grad[0] else None
+            _, _, scratch = place(dev, saved.numel(), L.axvs_conv1x1_gn_train_scratch_bytes(N, HW, Cin, Cout, groups, 1), saved=saved)
+            ps = _lib.fill(_lib.AxvsConvGnParams, [w.data_ptr() for w in ws])
+            gs = _lib.fill(_lib.AxvsConvGnParams, [g.data_ptr() for g in grads])
+            _lib.check(L.axvs_conv1x1_gn_train_bwd(d.data_ptr(), ol, obs, old, xs.data_ptr(), il, ibs, ild, C.byref(ps), C.byref(gs),
+                                                   dx.data_ptr() if dx is not None else None, N, HW, Cin, Cout, groups, saved.data_ptr(),
+                                                   saved.numel(), scratch.data_ptr(), scratch.numel(), _stream(dev)),
                        "axvs_conv1x1_gn_train_bwd")
-        dts = ctx.in_dtypes
-        out = [dx.reshape(ctx.x_shape).to(dts[0]) if need_dx else None] + [g.to(dt) for g, dt in zip(grads, dts[1:])]
-        return tuple(out) + (None,) * 9
+        return (*cast([dx.reshape(ctx.x_shape) if dx is not None else None, *grads], ctx.in_dtypes),) + (None,) * 9
 
 
 def conv_gn_train(x: Tensor, conv: torch.nn.Conv2d, gn: torch.nn.GroupNorm, out_layout: str = "nchw", hw: Optional[Tuple[int, int]] = None) -> Tensor:

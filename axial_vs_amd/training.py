@@ -31,6 +31,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._autograd import apply, cast, draw_seed, f32c, grad_buffer, nbytes, place, require_gpu
 
 _TRAJ = ("q", "k", "v", "proj_q", "proj_kv", "proj")
 _TAIL = ("norm1", "linear1", "linear2", "norm2")
@@ -61,33 +62,9 @@ def traj_layer_parameters(layer) -> List[Tensor]:
     return ps
 
 
-def _struct(ptrs: List[int]) -> _lib.AxvsAxialLayerParams:
-    s = _lib.AxvsAxialLayerParams()
-    s.height_attn = _lib.AxvsTrajParams(*ptrs[0:12])
-    s.width_attn = _lib.AxvsTrajParams(*ptrs[12:24])
-    for name, p in zip(("norm1_w", "norm1_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b", "norm2_w", "norm2_b"), ptrs[24:32]):
-        setattr(s, name, p)
-    return s
-
-
-def _traj_struct(ptrs: List[int]) -> _lib.AxvsTrajLayerParams:
-    s = _lib.AxvsTrajLayerParams()
-    s.temporal_attn = _lib.AxvsTrajParams(*ptrs[0:12])
-    for name, p in zip(("norm1_w", "norm1_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b", "norm2_w", "norm2_b"), ptrs[12:20]):
-        setattr(s, name, p)
-    return s
-
-
-# the two layers' entry points: (library symbol prefix, parameter struct builder); `dims` is the size argument list of each
-_AXIAL = ("axvs_axial_layer_train", _struct)
-_FULL = ("axvs_traj_layer_train", _traj_struct)
-
-
-def _f32c(t: Tensor) -> Tensor:
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
+# the two layers' entry points: (library symbol prefix, parameter struct); `dims` is the size argument list of each
+_AXIAL = ("axvs_axial_layer_train", _lib.AxvsAxialLayerParams)
+_FULL = ("axvs_traj_layer_train", _lib.AxvsTrajLayerParams)
 
 
 class _LayerTrain(torch.autograd.Function):
@@ -95,81 +72,58 @@ class _LayerTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src, pos, kind, dims, p_dropout, p_attn_drop, seed, recompute, *params):
-        from .modules import _stream, _workspace
-        name, make = kind
-        if not src.is_cuda:
-            raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
-        s, p = _f32c(src), _f32c(pos)
-        ws = [_f32c(w) for w in params]
-        L = _lib.lib()
+        from .modules import _stream
+        name, struct = kind
+        require_gpu(src)
+        s, p = f32c(src), f32c(pos)
+        ws = [f32c(w) for w in params]
         dev = s.device
-        nsaved = getattr(L, name + "_saved_bytes")(*dims)
-        if nsaved == 0:
-            raise RuntimeError(name + "_saved_bytes: " + L.axvs_last_error().decode())
+        nsaved = nbytes(name + "_saved_bytes", *dims)
         with torch.cuda.device(dev):
             out = torch.empty_like(s)
-            # with recompute the forward's activations are scratch too: they live in the shared workspace, after the scratch part
-            nscr = getattr(L, name + "_scratch_bytes")(*dims, 0)
-            if recompute:
-                buf = _workspace(dev, nscr + nsaved)
-                scratch_ptr, saved_ptr, saved = buf.data_ptr(), buf.data_ptr() + nscr, None
-            else:
-                saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
-                buf = _workspace(dev, nscr)
-                scratch_ptr, saved_ptr = buf.data_ptr(), saved.data_ptr()
-            st = make([w.data_ptr() for w in ws])
-            _lib.check(getattr(L, name + "_fwd")(s.data_ptr(), p.data_ptr(), out.data_ptr(), C.byref(st), *dims, float(p_dropout),
-                                                 float(p_attn_drop), int(seed), saved_ptr, nsaved, scratch_ptr, nscr, _stream(dev)),
+            nscr = nbytes(name + "_scratch_bytes", *dims, 0)
+            saved, saved_ptr, scratch = place(dev, nsaved, nscr, recompute)
+            st = _lib.fill(struct, [w.data_ptr() for w in ws])
+            _lib.check(getattr(_lib.lib(), name + "_fwd")(s.data_ptr(), p.data_ptr(), out.data_ptr(), C.byref(st), *dims, float(p_dropout),
+                                                          float(p_attn_drop), int(seed), saved_ptr, nsaved, scratch.data_ptr(), nscr,
+                                                          _stream(dev)),
                        name + "_fwd")
         ctx.save_for_backward(s, p, *ws)
         ctx.amp = _lib.current_amp()
         ctx.cfg = (kind, dims, float(p_dropout), float(p_attn_drop), int(seed), bool(recompute))
         ctx.saved_buf = saved
-        ctx.in_dtypes = (src.dtype, pos.dtype, [w.dtype for w in params])
+        ctx.in_dtypes = [t.dtype for t in (src, pos, *params)]
         ctx.shapes = (src.shape, pos.shape)
         return out.view(src.shape)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_out):
-        from .modules import _stream, _workspace
+        from .modules import _stream
         s, p, *ws = ctx.saved_tensors
-        kind, dims, p_dropout, p_attn_drop, seed, recompute = ctx.cfg
-        name, make = kind
-        L = _lib.lib()
+        (name, struct), dims, p_dropout, p_attn_drop, seed, recompute = ctx.cfg
         dev = s.device
         with torch.cuda.device(dev):
-            g = _f32c(d_out)
+            g = f32c(d_out)
             d_src = torch.empty_like(s)
-            want_pos = ctx.needs_input_grad[1]
-            d_pos = torch.empty_like(p) if want_pos else None
-            sizes = [w.numel() for w in ws]
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            grads, off = [], 0
-            for w, n in zip(ws, sizes):
-                grads.append(flat[off:off + n].view(w.shape))
-                off += n
-            nsaved = getattr(L, name + "_saved_bytes")(*dims)
-            nscr = getattr(L, name + "_scratch_bytes")(*dims, 1)
-            if recompute:
-                buf = _workspace(dev, nscr + nsaved)
-                scratch_ptr, saved_ptr = buf.data_ptr(), buf.data_ptr() + nscr
-            else:
-                buf = _workspace(dev, nscr)
-                scratch_ptr, saved_ptr = buf.data_ptr(), ctx.saved_buf.data_ptr()
-            st = make([w.data_ptr() for w in ws])
-            gs = make([t.data_ptr() for t in grads])       # (the gradient structs have the parameter structs' layout)
+            d_pos = torch.empty_like(p) if ctx.needs_input_grad[1] else None
+            grads = grad_buffer(ws, dev)
+            nsaved = nbytes(name + "_saved_bytes", *dims)
+            nscr = nbytes(name + "_scratch_bytes", *dims, 1)
+            _, saved_ptr, scratch = place(dev, nsaved, nscr, recompute, saved=ctx.saved_buf)
+            st = _lib.fill(struct, [w.data_ptr() for w in ws])
+            gs = _lib.fill(struct, [t.data_ptr() for t in grads])
             with _lib.train_amp(ctx.amp):
-                _lib.check(getattr(L, name + "_bwd")(g.data_ptr(), s.data_ptr(), p.data_ptr(), C.byref(st), C.byref(gs), d_src.data_ptr(),
-                                                     d_pos.data_ptr() if want_pos else None, *dims, p_dropout, p_attn_drop, seed,
-                                                     int(recompute), saved_ptr, nsaved, scratch_ptr, nscr, _stream(dev)),
+                _lib.check(getattr(_lib.lib(), name + "_bwd")(g.data_ptr(), s.data_ptr(), p.data_ptr(), C.byref(st), C.byref(gs),
+                                                              d_src.data_ptr(), d_pos.data_ptr() if d_pos is not None else None, *dims,
+                                                              p_dropout, p_attn_drop, seed, int(recompute), saved_ptr, nsaved,
+                                                              scratch.data_ptr(), nscr, _stream(dev)),
                            name + "_bwd")
         # (the saved activations stay with ctx until autograd releases it: a second backward through the same graph --
         #  retain_graph=True, shared subgraphs -- finds them again)
-        sd, pd, wd = ctx.in_dtypes
-        out_grads = [gr.to(dt) for gr, dt in zip(grads, wd)]
-        return (d_src.view(ctx.shapes[0]).to(sd), d_pos.view(ctx.shapes[1]).to(pd) if want_pos else None, None, None, None, None, None, None,
-                *out_grads)
+        d_src, d_pos, *grads = cast([d_src.view(ctx.shapes[0]), d_pos.view(ctx.shapes[1]) if d_pos is not None else None, *grads],
+                                    ctx.in_dtypes)
+        return (d_src, d_pos, None, None, None, None, None, None, *grads)
 
 
 def _check_tail(layer) -> None:
@@ -179,26 +133,10 @@ def _check_tail(layer) -> None:
         raise NotImplementedError("axial_vs_amd: LayerNorm eps must be 1e-5")
 
 
-def _seed(layer, p_drop: float, p_attn: float) -> int:
-    seed = getattr(layer, "dropout_seed", None)
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p_drop > 0 or p_attn > 0) else 0
-    return int(seed)
-
-
-def _call(layer, fn, args) -> Tensor:
-    if torch.is_autocast_enabled():
-        amp = _lib.autocast_mode(layer)       # (read before autocast is switched off for the call)
-        with torch.autocast(device_type="cuda", enabled=False), _lib.train_amp(amp):
-            return fn.apply(*args)
-    return fn.apply(*args)
-
-
 def _apply(layer, src: Tensor, pos: Tensor, kind, dims, dropout: bool, recompute: bool, params: List[Tensor]) -> Tensor:
     p_drop = float(layer.dropout2.p) if dropout else 0.0        # = the attention maps' dropout (reference :164-165) = dropout2 = dropout3
     p_attn = float(layer.dropout1.p) if dropout else 0.0
-    args = (src, pos, kind, dims, p_drop, p_attn, _seed(layer, p_drop, p_attn), bool(recompute), *params)
-    return _call(layer, _LayerTrain, args)
+    return apply(layer, _LayerTrain, src, pos, kind, dims, p_drop, p_attn, draw_seed(layer, p_drop, p_attn), bool(recompute), *params)
 
 
 def axial_layer_train(layer, src: Tensor, pos: Tensor, dropout: bool = True, recompute: bool = True) -> Tensor:
@@ -243,92 +181,61 @@ def msda_layer_parameters(layer) -> List[Tensor]:
     return ps
 
 
-def _msda_struct(ptrs: List[int]) -> _lib.AxvsMsdaLayerParams:
-    s = _lib.AxvsMsdaLayerParams()
-    s.self_attn = _lib.AxvsMsdaParams(*ptrs[0:8])
-    for name, p in zip(("norm1_w", "norm1_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b", "norm2_w", "norm2_b"), ptrs[8:16]):
-        setattr(s, name, p)
-    return s
-
-
 class _MsdaLayerTrain(torch.autograd.Function):
     """forward / backward of one deformable encoder layer through the library's training tier.  reference_points, the padding
     mask and the spatial shapes are constants (no gradient)."""
 
     @staticmethod
     def forward(ctx, src, pos, ref, mask, shapes, dims, p_dropout, p_attn_drop, seed, recompute, *params):
-        from .modules import _stream, _workspace
-        if not src.is_cuda:
-            raise RuntimeError("axial_vs_amd: the training tier needs GPU tensors; there is no CPU fallback")
-        s, r = _f32c(src), _f32c(ref)
-        p = _f32c(pos) if pos is not None else None
-        ws = [_f32c(w) for w in params]
-        L = _lib.lib()
+        from .modules import _stream
+        require_gpu(src)
+        s, p, r = f32c(src), f32c(pos), f32c(ref)
+        ws = [f32c(w) for w in params]
         dev = s.device
-        nsaved = L.axvs_msda_layer_train_saved_bytes(*dims)
-        if nsaved == 0:
-            raise RuntimeError("axvs_msda_layer_train_saved_bytes: " + L.axvs_last_error().decode())
+        nsaved = nbytes("axvs_msda_layer_train_saved_bytes", *dims)
         arr = (C.c_int * (2 * len(shapes)))(*[v for hw in shapes for v in hw])
         with torch.cuda.device(dev):
             out = torch.empty_like(s)
-            nscr = L.axvs_msda_layer_train_scratch_bytes(*dims, 0)
-            if recompute:
-                buf = _workspace(dev, nscr + nsaved)
-                scratch_ptr, saved_ptr, saved = buf.data_ptr(), buf.data_ptr() + nscr, None
-            else:
-                saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
-                buf = _workspace(dev, nscr)
-                scratch_ptr, saved_ptr = buf.data_ptr(), saved.data_ptr()
-            st = _msda_struct([w.data_ptr() for w in ws])
-            _lib.check(L.axvs_msda_layer_train_fwd(s.data_ptr(), p.data_ptr() if p is not None else None, r.data_ptr(), r.shape[-1],
-                                                   mask.data_ptr() if mask is not None else None, arr, out.data_ptr(), C.byref(st), *dims,
-                                                   float(p_dropout), float(p_attn_drop), int(seed), saved_ptr, nsaved, scratch_ptr, nscr,
-                                                   _stream(dev)), "axvs_msda_layer_train_fwd")
+            nscr = nbytes("axvs_msda_layer_train_scratch_bytes", *dims, 0)
+            saved, saved_ptr, scratch = place(dev, nsaved, nscr, recompute)
+            st = _lib.fill(_lib.AxvsMsdaLayerParams, [w.data_ptr() for w in ws])
+            _lib.check(_lib.lib().axvs_msda_layer_train_fwd(s.data_ptr(), p.data_ptr() if p is not None else None, r.data_ptr(), r.shape[-1],
+                                                            mask.data_ptr() if mask is not None else None, arr, out.data_ptr(), C.byref(st),
+                                                            *dims, float(p_dropout), float(p_attn_drop), int(seed), saved_ptr, nsaved,
+                                                            scratch.data_ptr(), nscr, _stream(dev)), "axvs_msda_layer_train_fwd")
         ctx.save_for_backward(s, p, r, mask, *ws)
         ctx.amp = _lib.current_amp()
         ctx.cfg = (arr, dims, float(p_dropout), float(p_attn_drop), int(seed), bool(recompute))
         ctx.saved_buf = saved
-        ctx.in_dtypes = (src.dtype, pos.dtype if pos is not None else None, [w.dtype for w in params])
+        ctx.in_dtypes = [t.dtype if t is not None else None for t in (src, pos, *params)]
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_out):
-        from .modules import _stream, _workspace
+        from .modules import _stream
         s, p, r, mask, *ws = ctx.saved_tensors
         arr, dims, p_dropout, p_attn_drop, seed, recompute = ctx.cfg
-        L = _lib.lib()
         dev = s.device
         with torch.cuda.device(dev):
-            g = _f32c(d_out)
+            g = f32c(d_out)
             d_src = torch.empty_like(s)
-            want_pos = p is not None and ctx.needs_input_grad[1]
-            d_pos = torch.empty_like(p) if want_pos else None
-            sizes = [w.numel() for w in ws]
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            grads, off = [], 0
-            for w, n in zip(ws, sizes):
-                grads.append(flat[off:off + n].view(w.shape))
-                off += n
-            nsaved = L.axvs_msda_layer_train_saved_bytes(*dims)
-            nscr = L.axvs_msda_layer_train_scratch_bytes(*dims, 1)
-            if recompute:
-                buf = _workspace(dev, nscr + nsaved)
-                scratch_ptr, saved_ptr = buf.data_ptr(), buf.data_ptr() + nscr
-            else:
-                buf = _workspace(dev, nscr)
-                scratch_ptr, saved_ptr = buf.data_ptr(), ctx.saved_buf.data_ptr()
-            st = _msda_struct([w.data_ptr() for w in ws])
-            gs = _msda_struct([t.data_ptr() for t in grads])       # (the gradient struct has the parameter struct's layout)
+            d_pos = torch.empty_like(p) if p is not None and ctx.needs_input_grad[1] else None
+            grads = grad_buffer(ws, dev)
+            nsaved = nbytes("axvs_msda_layer_train_saved_bytes", *dims)
+            nscr = nbytes("axvs_msda_layer_train_scratch_bytes", *dims, 1)
+            _, saved_ptr, scratch = place(dev, nsaved, nscr, recompute, saved=ctx.saved_buf)
+            st = _lib.fill(_lib.AxvsMsdaLayerParams, [w.data_ptr() for w in ws])
+            gs = _lib.fill(_lib.AxvsMsdaLayerParams, [t.data_ptr() for t in grads])
             with _lib.train_amp(ctx.amp):
-                _lib.check(L.axvs_msda_layer_train_bwd(g.data_ptr(), s.data_ptr(), p.data_ptr() if p is not None else None, r.data_ptr(),
-                                                       r.shape[-1], mask.data_ptr() if mask is not None else None, arr, C.byref(st),
-                                                       C.byref(gs), d_src.data_ptr(), d_pos.data_ptr() if want_pos else None, *dims,
-                                                       p_dropout, p_attn_drop, seed, int(recompute), saved_ptr, nsaved, scratch_ptr, nscr,
-                                                       _stream(dev)), "axvs_msda_layer_train_bwd")
-        sd, pd, wd = ctx.in_dtypes
-        out_grads = [gr.to(dt) for gr, dt in zip(grads, wd)]
-        return (d_src.to(sd), d_pos.to(pd) if want_pos else None, None, None, None, None, None, None, None, None, *out_grads)
+                _lib.check(_lib.lib().axvs_msda_layer_train_bwd(g.data_ptr(), s.data_ptr(), p.data_ptr() if p is not None else None,
+                                                                r.data_ptr(), r.shape[-1], mask.data_ptr() if mask is not None else None, arr,
+                                                                C.byref(st), C.byref(gs), d_src.data_ptr(),
+                                                                d_pos.data_ptr() if d_pos is not None else None, *dims, p_dropout, p_attn_drop,
+                                                                seed, int(recompute), saved_ptr, nsaved, scratch.data_ptr(), nscr,
+                                                                _stream(dev)), "axvs_msda_layer_train_bwd")
+        d_src, d_pos, *grads = cast([d_src, d_pos, *grads], ctx.in_dtypes)
+        return (d_src, d_pos, None, None, None, None, None, None, None, None, *grads)
 
 
 def msda_layer_dims(layer, src: Tensor, shapes) -> tuple:
@@ -363,6 +270,5 @@ def msda_layer_train(layer, src: Tensor, pos, reference_points: Tensor, spatial_
         mask = padding_mask.to(torch.uint8).contiguous()
     p_drop = float(layer.dropout2.p) if dropout else 0.0
     p_attn = float(layer.dropout1.p) if dropout else 0.0
-    args = (src, pos, reference_points.detach(), mask, shapes, msda_layer_dims(layer, src, shapes), p_drop, p_attn,
-            _seed(layer, p_drop, p_attn), bool(recompute), *msda_layer_parameters(layer))
-    return _call(layer, _MsdaLayerTrain, args)
+    return apply(layer, _MsdaLayerTrain, src, pos, reference_points.detach(), mask, shapes, msda_layer_dims(layer, src, shapes), p_drop,
+                 p_attn, draw_seed(layer, p_drop, p_attn), bool(recompute), *msda_layer_parameters(layer))

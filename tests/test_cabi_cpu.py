@@ -225,6 +225,50 @@ def test_training_buffer_sizes_and_argument_checks():
     assert L.axvs_axial_layer_train_saved_bytes(1, 17, 8, 8, 256, 8, 1024) == 0 and b"T=17" in L.axvs_last_error()
 
 
+def test_struct_fill_puts_each_pointer_in_its_field():
+    """_lib.fill walks a parameter / gradient struct in declaration order (nested structs recursively, arrays element by element):
+    pointer values 1..n land where the training tier's parameter lists put each tensor."""
+    from axial_vs_amd import _lib
+    traj = ["q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "proj_q_w", "proj_q_b", "proj_kv_w", "proj_kv_b", "proj_w", "proj_b"]
+    tail = ["norm1_w", "norm1_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b", "norm2_w", "norm2_b"]
+    msda = ["value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b", "attention_weights_w", "attention_weights_b",
+            "output_proj_w", "output_proj_b"]
+
+    def expect(cls, paths):
+        s = _lib.fill(cls, range(1, len(paths) + 1))
+        for v, path in enumerate(paths, 1):
+            obj = s
+            for part in path.split("."):
+                obj = obj[int(part)] if part.isdigit() else getattr(obj, part)
+            assert obj == v, (cls.__name__, path, obj, v)
+        with pytest.raises(ValueError):
+            _lib.fill(cls, range(1, len(paths) + 2))
+        return s
+
+    s = expect(_lib.AxvsAxialLayerParams, [f"height_attn.{n}" for n in traj] + [f"width_attn.{n}" for n in traj] + tail)
+    assert s.width_attn.q_w == 13 and s.norm2_b == 32
+    expect(_lib.AxvsTrajLayerParams, [f"temporal_attn.{n}" for n in traj] + tail)
+    expect(_lib.AxvsMsdaLayerParams, [f"self_attn.{n}" for n in msda] + tail)
+    s = expect(_lib.AxvsTLHeadParams, ["post_norm_w", "post_norm_b", "activation_proj_w", "activation_proj_b", "cls_embed_w", "cls_embed_b",
+                                       "mask_embed_w.0", "mask_embed_w.1", "mask_embed_w.2", "mask_embed_b.0", "mask_embed_b.1", "mask_embed_b.2"])
+    assert list(s.mask_embed_w) == [7, 8, 9] and list(s.mask_embed_b) == [10, 11, 12]
+    expect(_lib.AxvsCCHeadGrads, ["class_proj_w", "class_proj_bn.w", "class_proj_bn.b", "mask_proj_w", "mask_proj_bn.w", "mask_proj_bn.b",
+                                  "mask_head_w", "mask_head_bn.w", "mask_head_bn.b", "class_head_w", "class_head_b", "act_head_w",
+                                  "act_head_b", "pixel_bn.w", "pixel_bn.b"])
+
+
+def test_cross_clip_module_parameters_are_the_chain_then_the_heads():
+    import axial_vs_amd as ax
+    from axial_vs_amd.cc_training import chain_parameters, module_parameters
+    nl = 2
+    mod = ax.CrossClipTrackingModule(num_layers=nl, num_classes=3, attn_drop=0.0, aspp_drop=0.0, kernel_sizes=[3, 3, 3], atrous_rates=[1, 2, 3],
+                                     norm_fn="ln", num_clip_frames=1)
+    ps = module_parameters(mod)
+    assert len(ps) == nl * 21 + 15
+    assert all(a is b for a, b in zip(ps, chain_parameters(mod, nl)))
+    assert len({id(p) for p in ps}) == len(ps)
+
+
 def test_reference_extension_stand_in_exposes_the_two_entry_points():
     """`import MultiScaleDeformableAttention as MSDA` (OPS/functions/ms_deform_attn_func.py:22) resolves to the stand-in module and
     finds ms_deform_attn_forward / ms_deform_attn_backward with the extension's argument lists (OPS/src/ms_deform_attn.h:24-67)."""

@@ -111,6 +111,27 @@ def test_dropout_is_a_function_of_the_seed():
     assert not torch.equal(o1, o2) and torch.equal(o1, o3)
 
 
+@pytest.mark.parametrize("recompute", [True, False])
+def test_second_backward_through_a_retained_graph(recompute):
+    """backward(retain_graph=True), then backward again: the second finds the forward's activations (kept on ctx, or rebuilt under
+    recompute) and gives the same gradients, so every .grad ends up exactly twice the first one."""
+    B, T, C, H, W, F = 1, 2, 64, 6, 5, 128
+    w = orc.random_weights(orc.axial_layer_param_shapes(C, F), 3)
+    src, pos = orc.synthetic_clip(B, T, C, H, W, 3)
+    d_out = torch.randn(B * T, H * W, C, generator=torch.Generator().manual_seed(4)).cuda()
+    layer = make_layer(C, F, w, 0.1, 0.1, 7)
+    layer.recompute = recompute
+    s = src.float().cuda().requires_grad_(True)
+    p = pos.float().cuda().requires_grad_(True)
+    loss = (layer(s, p)[0] * d_out).sum()
+    leaves = [s, p, *layer.parameters()]
+    loss.backward(retain_graph=True)
+    first = [t.grad.clone() for t in leaves]
+    loss.backward()
+    for t, g in zip(leaves, first):
+        assert torch.equal(t.grad, 2 * g)
+
+
 def test_train_mode_without_dropout_matches_eval_tier():
     """p = 0: the fp32 training tier and the 16-bit MFMA inference tier compute the same function (to the inference tier's bar)."""
     B, T, C, H, W, F = 1, 4, 256, 16, 24, 1024
