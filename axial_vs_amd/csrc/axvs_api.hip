@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "axvs_host.h"
 #include "axvs_attn.h"
@@ -31,51 +32,31 @@ thread_local int g_prof_cap = 0;
 thread_local int g_prof_next = 0;
 constexpr int kMaxStages = 32;
 thread_local const char* g_stage_names[kMaxStages] = {};
-thread_local int g_generic_only = 0;
-constexpr int g_attn_waves = 0;
+constexpr int kMergeSmall = 128;         // 16-row-tile passes (T <= 4) of at most this many tiles run merged too (round 5, profiles/r5_merged_16row_tiles.txt)
+// ---- options (axvs_set_option; the comment above it is the list of the 15 keys) ----
+thread_local int g_generic_only = 0;     // option "generic_only": 1 = always use the shape-generic v1 kernels
 thread_local int* g_status = nullptr;     // axvs_set_status_buffer: word that kernels OR condition bits into (device memory, or pinned host memory)
 thread_local volatile int* g_status_host = nullptr;   // the same word when the HOST can read it (pinned host memory): the entry points of the
                                           // axial layer then refuse to run on top of a reported hand-off timeout (status_gate)
 thread_local unsigned g_sync_spin_limit = axvs::kSyncSpinLimit;   // option "sync_spin_limit": polls before a hand-off wait gives up (tests shorten it)
 thread_local long long g_row_span = 0;   // rows spanned by the layer's row-addressed tensors when their frames are strided (0: natural)
-thread_local int g_ffn_wide = 0;         // option "ffn_wide": 0 = 128-row FFN tiles when they save a round of the chip (ffn_wide_pays), 1 = always, 2 = never
-constexpr int g_merge_mid = 1;        // option "merge_mid": merged q/k/v + trajectory launch on 32-row tiles (T = 5 .. 8): 1 = while the pass fits one round of the chip, 0 never, 2 always
-thread_local int g_no_small_tiles = 0;   // option "no_small_tiles": never use the 16-row trajectory tiles
-constexpr int kSmallBelow = 65;          // problems with fewer 64-row tiles than this run the few-rows forms (16-row trajectory tiles, 3-way split q/k/v
-                                         // projection, chunk-per-workgroup FFN): their 4x workgroups fit one round of the 256 CUs up to 64 tiles, and from 65 on
-                                         // the 64-row forms (merged launch per pass, FFN riding in the width pass) are faster at every T -- round 5 sweep,
-                                         // profiles/r5_planner_threshold.txt (128 until then: [1,2,256,48,80] 93.4 -> 79.5 us, [1,5,256,24,40] 94.6 -> 82.8)
-constexpr int g_small_below = kSmallBelow;      // option "small_tiles_below" (A/B runs; <= 0 restores the default)
-thread_local int g_ffn_split_pairs = 1;  // option "ffn_split_pairs": 65 .. 128 tiles run the chunk-per-workgroup FFN with two chunks per workgroup (0: the one-workgroup-per-tile kernel)
-constexpr int g_ffn_split_below = kSmallBelow;  // option "ffn_split_below": the same switch for the stand-alone FFN alone (chunk-per-workgroup form below it)
+thread_local int g_ffn_wide = 0;         // option "plan_force" bits 2 / 4: 0 = 128-row FFN tiles when they save a round of the chip (ffn_wide_pays), 1 = always, 2 = never
+thread_local int g_no_small_tiles = 0;   // option "plan_force" bit 1: never use the 16-row trajectory tiles
+thread_local int g_ffn_split_pairs = 1;  // option "plan_force" bit 8 clears it: 65 .. 88 tiles run the chunk-per-workgroup FFN with two chunks per workgroup (0: the one-workgroup-per-tile kernel)
 thread_local int g_spatial_only = 0;     // option "spatial_only": 1 = the fused trajectory kernels return after QK^T / softmax / AV (timing only; outputs unwritten);
                                          // 2 = the merged q/k/v + trajectory kernels return after their q/k/v part (the two-launch kernels treat it as 1)
-constexpr int g_no_wt_stores = 0;     // option "no_wt_stores": plain instead of write-through (sc1) stores of inter-kernel tensors (tuning)
 thread_local int g_no_ffn_fusion = 0;    // option "no_ffn_fusion": keep the FFN in its own kernel
-thread_local int g_no_reassoc = 0;       // option "no_reassoc": generic tier computes k2, v2 = proj_kv(x) for every frame slot (the reference's form)
+thread_local int g_no_reassoc = 0;       // option "plan_force" bit 64: generic tier computes k2, v2 = proj_kv(x) for every frame slot (the reference's form)
 thread_local int g_ffn_gelu = 0;         // option "ffn_gelu": the layer's FFN activation is exact GELU (F.gelu) instead of ReLU -- set by the
                                          // host module around its calls for activation="gelu" (WC/temporal_attention.py:9-17): the FFN then runs on the
                                          // stand-alone fused kernels' GELU instantiation instead of riding in the width-pass kernel
-// option "msda_gemm": the deformable attention's three projections on the 128 x 128 split-precision GEMM of axvs_gemm_nt.h when the
-// level set has >= 2048 rows.  4 (the default of rounds 3 - 4): two bf16 pieces for value_proj (its output is rounded to 16 bits anyway) and for the
-// offset | weight projection, three pieces (fp32 accuracy) for output_proj, whose result enters the residual stream without a norm;
-// 2 (default since the end of round 5) / 3: two / three pieces everywhere; 0: the 64 x 64 kernels of axvs_gemm.h.
-// (Two pieces put 5e-6 on a projection; the free-running 16-bit stack's max-norm at BASELINE config 3 is chaotic in its 16-bit roundings either way -- 1.29e-3 with 2,
-//  1.38 - 1.48e-3 with 4, relative L2 5.7e-4 for both -- and 2 saves 2.5 % of the module: profiles/r5_planner_threshold.txt.)
-constexpr int g_msda_gemm = 2;
-constexpr int g_conv_nt128_nchw = 128;  // option "conv_nt128_nchw": the same for NCHW inputs (transposed to token rows first), tiles of the ONE launch over all frames
-constexpr int g_conv_nt128_exact = 0;  // option "conv_nt128_exact": 0 = two bf16 pieces per operand (5e-6 of the float64 projection + GroupNorm, 114 against 147 us at [32786 x 256 x 512]), 1 = three (9e-7)
-constexpr int g_conv_nt128_splitk = 1024; // option "conv_nt128_splitk": split-K for the NCHW projections with few row tiles and Cin >= this (0: never)
-constexpr int g_conv_nt128 = 192;     // option "conv_nt128": token-row 1x1 projections run the 128 x 128 three-piece GEMM from this many tiles per launch on (0: never)
 // Merged q/k/v + trajectory launches (temporal_fused_kernel<..., MQ>): one launch per axial pass.  The sibling row tiles of a
 // sequence hand K / V^T over inside the launch through arrival counters the CALLER provides (axvs_set_sync_buffer: device words
 // that are zero when registered; every launch leaves them zero) -- without a registered buffer the passes run as two launches.
 thread_local unsigned* g_sync = nullptr;
 thread_local size_t g_sync_words = 0;
 thread_local int g_merge_qkv_any = 0;    // option "merge_qkv_any": merged launches at every grid size (A/B; see run_traj)
-constexpr int g_qkv_split_upto = 64;  // option "qkv_split_upto": the stand-alone q/k/v kernel runs one workgroup per (tile, q | k | v) up to this many tiles of 64 rows
-constexpr int kMergeSmall = 128;         // 16-row-tile passes (T <= 4) of at most this many tiles run merged too (round 5, profiles/r5_merged_16row_tiles.txt)
-thread_local int g_merge_small = kMergeSmall;      // option "merge_small": 0 never, 1 at any size, n > 1: passes of at most n tiles of 16 rows, < 0: the default
+thread_local int g_merge_small = kMergeSmall;   // option "plan_force" bits 16 / 32: 0 never, 1 at any size, n > 1: passes of at most n tiles of 16 rows (kMergeSmall)
 thread_local int g_out_dtype = 0;        // option "layer_out_dtype": 0 = the layer's output rows are fp32 (the reference's type); 1 / 2 = the kernel that ends the layer
                                          // (norm2 epilogue of the FFN) writes them as f16 / bf16 -- the map a batch-sharded caller gathers over the links
                                          // (BASELINE config 5 is worded "bf16"), written once instead of cast by a second pass
@@ -86,8 +67,27 @@ thread_local int g_cc_last_only = 0;     // option "cc_last_heads_only": axvs_cc
                                          // (CC/...:283-318) and its inference path drops all but the last (maxtron_cc_model.py:301-: aux_outputs are read under
                                          // self.training only): an inference pipeline that does not want them saves 3/4 of the mask einsum's HBM writes
 thread_local int g_no_merge_qkv = 0;     // option "no_merge_qkv": keep qkv_fused_kernel + trajectory kernel as two launches (A/B, tests)
-thread_local int g_no_attn_fusion = 0;   // option "no_attn_fusion": keep spatial_attn_kernel + temporal kernel separate   // option "attn_waves": cap on waves per attention workgroup (tuning)
-   // option "generic_only": 1 = always use the shape-generic v1 kernels
+thread_local int g_no_attn_fusion = 0;   // option "no_attn_fusion": keep spatial_attn_kernel + temporal kernel separate
+
+// ---- planner constants (measured; settable in rounds 2 - 5, fixed since round 6) ----
+constexpr int kSmallBelow = 65;          // problems with fewer 64-row tiles than this run the few-rows forms (16-row trajectory tiles, 3-way split q/k/v
+                                         // projection, chunk-per-workgroup FFN): their 4x workgroups fit one round of the 256 CUs up to 64 tiles, and from 65 on
+                                         // the 64-row forms (merged launch per pass, FFN riding in the width pass) are faster at every T -- round 5 sweep,
+                                         // profiles/r5_planner_threshold.txt (128 until then: [1,2,256,48,80] 93.4 -> 79.5 us, [1,5,256,24,40] 94.6 -> 82.8)
+constexpr int kMergeMid = 1;             // merged q/k/v + trajectory launch on 32-row tiles (T = 5 .. 8): 1 = while the pass fits one round of the chip, 0 never,
+                                         // 2 always (profiles/r5_merged_32row_tiles.txt)
+constexpr int kQkvSplitUpto = 64;        // the stand-alone q/k/v kernel runs one workgroup per (tile, q | k | v) up to this many tiles of 64 rows
+// Pieces of the 128 x 128 split-precision GEMM of axvs_gemm_nt.h, which runs the deformable attention's three projections when the
+// level set has >= 2048 rows.  4 (rounds 3 - 4): two bf16 pieces for value_proj (its output is rounded to 16 bits anyway) and for the
+// offset | weight projection, three pieces (fp32 accuracy) for output_proj, whose result enters the residual stream without a norm;
+// 2 (since the end of round 5) / 3: two / three pieces everywhere; 0: the 64 x 64 kernels of axvs_gemm.h.
+// (Two pieces put 5e-6 on a projection; the free-running 16-bit stack's max-norm at BASELINE config 3 is chaotic in its 16-bit roundings either way -- 1.29e-3 with 2,
+//  1.38 - 1.48e-3 with 4, relative L2 5.7e-4 for both -- and 2 saves 2.5 % of the module: profiles/r5_planner_threshold.txt.)
+constexpr int kMsdaGemm = 2;
+constexpr int kConvNt128 = 192;          // token-row 1x1 projections run the 128 x 128 GEMM from this many tiles per launch on (0: never)
+constexpr int kConvNt128Nchw = 128;      // the same for NCHW inputs (transposed to token rows first), tiles of the ONE launch over all frames
+constexpr int kConvNt128Exact = 0;       // 0 = two bf16 pieces per operand (5e-6 of the float64 projection + GroupNorm, 114 against 147 us at [32786 x 256 x 512]), 1 = three (9e-7)
+constexpr int kConvNt128SplitK = 1024;   // split-K for the NCHW projections with few row tiles and Cin >= this (0: never)
 
 inline void mark(hipStream_t st, const char* name) {
   if (g_prof_next < kMaxStages) g_stage_names[g_prof_next] = name;
@@ -125,6 +125,20 @@ int check_dtype(int dtype) {
     return fail(AXVS_ERR_ARG, "the bf16 operand tier is not built into this library (it does not hold the 1e-3 parity bar; fp16 operands run at the same rate and do): rebuild with AXVS_WITH_BF16=1");
   }
   return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+}
+// f(std::bool_constant<BF>) for the operand type of a dtype that check_dtype has accepted
+template <class F>
+auto by_dtype(int dtype, F&& f) {
+  return dtype == AXVS_BF16 ? f(std::bool_constant<kBF>{}) : f(std::false_type{});
+}
+
+int check_ffn(int d_ffn) {
+  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
+  return AXVS_OK;
+}
+int check_ws(size_t have, size_t need) {
+  if (have < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %zu < %zu", have, need);
+  return AXVS_OK;
 }
 
 int cu_count() {
@@ -201,17 +215,10 @@ LayerPacked carve_ffn(Carver& c, int C, int F) {   // norm1 / linear1 / linear2 
 }
 
 LayerPacked carve_layer(Carver& c, int C, int heads, int F) {
-  LayerPacked l;
-  l.th = carve_traj(c, C, heads);
-  l.tw = carve_traj(c, C, heads);
-  l.w1 = c.take<u16>((size_t)F * C);
-  l.w2 = c.take<u16>((size_t)F * C);
-  l.b1 = c.take<float>(F);
-  l.b2 = c.take<float>(C);
-  l.g1 = c.take<float>(C);
-  l.be1 = c.take<float>(C);
-  l.g2 = c.take<float>(C);
-  l.be2 = c.take<float>(C);
+  const TrajPacked th = carve_traj(c, C, heads), tw = carve_traj(c, C, heads);
+  LayerPacked l = carve_ffn(c, C, F);
+  l.th = th;
+  l.tw = tw;
   return l;
 }
 
@@ -297,6 +304,42 @@ TrajWs carve_traj_ws(Carver& c, long long Mp, int T, int heads, bool lean = fals
   return w;
 }
 
+// rows the stand-alone FFN works on (x: its input, clobbered by the generic path) + the generic path's scratch
+struct FfnWs {
+  float *x, *tmp;
+  u16 *y16, *h16;
+};
+FfnWs carve_ffn_ws(Carver& c, long long M, int C, int F) {
+  FfnWs w{};
+  w.x = c.take<float>((size_t)M * C);
+  w.tmp = c.take<float>((size_t)M * C);
+  w.y16 = c.take<u16>((size_t)M * C);
+  w.h16 = c.take<u16>((size_t)M * F);
+  return w;
+}
+struct TrajAttnWs {
+  TrajWs tw;
+  float* zeros;      // [S T L][C]: the residual the fused kernels always add
+};
+TrajAttnWs carve_traj_attn_ws(Carver& c, int S, int T, int L, int C, int heads) {
+  const long long M = (long long)S * T * L;
+  TrajAttnWs w{};
+  w.tw = carve_traj_ws(c, M, T, heads, false, padded_rows(M, L));
+  w.zeros = c.take<float>((size_t)M * C);
+  return w;
+}
+struct TrajLayerWs {
+  TrajWs tw;
+  FfnWs f;
+};
+TrajLayerWs carve_traj_layer_ws(Carver& c, int B, int T, int HW, int C, int heads, int F) {
+  const long long M = (long long)B * T * HW;
+  TrajLayerWs w{};
+  w.tw = carve_traj_ws(c, M, T, heads, false, padded_rows(M, HW));
+  w.f = carve_ffn_ws(c, M, C, F);
+  return w;
+}
+
 // Full fusion (spatial half inside the temporal kernel, x never leaves LDS) needs: the fused kernels, no attention-map
 // output, 8..128 keys per frame (frames are padded to multiples of 16 rows in the q/k/v row space, V^T to 32-key steps: within 2x of
 // the padded rows for every L; below 8 keys the padding would more than double the work).  Any axis length: row tiles are cut
@@ -312,9 +355,8 @@ bool can_fuse_attn(int C, int heads, int T, int L, bool want_attn, long long row
 // The FFN rides in the width-pass kernel only when that kernel has more than 64 tiles (kSmallBelow): with fewer 64-row tiles every
 // workgroup's private 1 MB FFN weight stream is pure latency (43 us per pass whether 16 or 64 workgroups run), and a 16-row
 // trajectory kernel (4x the workgroups) + the stand-alone FFN kernel is faster (BASELINE config 3: res4 / res5 levels).
-inline int small_below(int /*T*/) { return g_small_below; }
 bool can_fuse_ffn_into_pass(int T, int F, long long M) {
-  return !g_no_ffn_fusion && !g_ffn_gelu && T <= 4 && F % 256 == 0 && F <= 4096 && (M >= (long long)small_below(T) * 64 || g_no_small_tiles);
+  return !g_no_ffn_fusion && !g_ffn_gelu && T <= 4 && F % 256 == 0 && F <= 4096 && (M >= (long long)kSmallBelow * 64 || g_no_small_tiles);
 }
 // (activation = gelu: the stand-alone fused FFN kernels have a GELU instantiation; only the width-pass kernel does not carry it)
 bool ffn_kernel_is_fused(int C, int heads, int F) { return !g_generic_only && C == 256 && heads == 8 && F % 256 == 0 && F <= 4096; }
@@ -324,14 +366,14 @@ bool ffn_kernel_is_fused(int C, int heads, int F) { return !g_generic_only && C 
 // one-workgroup-per-tile kernel leaves half the CUs idle behind a private 1 MB stream (only reached when the FFN does not ride in the width pass: T >= 5, GELU)
 int ffn_split_mode(int C, int heads, int F, long long M) {      // 0: no split, 1: one chunk per workgroup, 2: two
   if (!ffn_kernel_is_fused(C, heads, F) || g_no_small_tiles || F < 512) return 0;
-  if (M < (long long)g_ffn_split_below * 64) return 1;
+  if (M < (long long)kSmallBelow * 64) return 1;
   return (g_ffn_split_pairs && F % 512 == 0 && M <= 88 * 64) ? 2 : 0;      // measured: -2.4 us at 75 tiles, -0.5 .. -0.9 at 80 .. 84, +0.9 at 96, +4.5 at 128 (partials + finishing kernel)
 }
 bool ffn_split_applies(int C, int heads, int F, long long M) { return ffn_split_mode(C, heads, F, M) != 0; }
 
 // 64-row tiles (MT = 4) of the fused trajectory kernel: T <= 4, and either the FFN rides along or there are enough tiles to
 // fill the chip (few tiles take 16-row tiles: 4x the workgroups) -- the choice launch_temporal makes
-bool traj_mt4(int T, long long tiles64, bool with_ffn) { return T <= 4 && (with_ffn || tiles64 >= small_below(T) || g_no_small_tiles); }
+bool traj_mt4(int T, long long tiles64, bool with_ffn) { return T <= 4 && (with_ffn || tiles64 >= kSmallBelow || g_no_small_tiles); }
 long long traj_tiles64(long long Mp, int N) { return (Mp / N) * ((N + 63) / 64); }
 // what one axial layer's launch sequence touches in the workspace (the same predicates run_traj / run_ffn dispatch on)
 struct LayerPlan {
@@ -350,6 +392,32 @@ LayerPlan plan_layer(int B, int T, int H, int W, int C, int heads, int F, bool w
   return p;
 }
 
+bool sine_in_kernel(int C, int heads) { return !g_generic_only && C == 256 && heads == 8; }
+
+// members the plan does not need are null
+struct AxialWs {
+  TrajWs tw;
+  float *buf1, *buf2;   // height pass -> width pass -> FFN rows; buf1 doubles as the fp32 scratch of the generic FFN path
+  u16 *y16, *h16;
+  float* ffn_part;
+  float* pos;           // materialised sine positions (tiers without in-kernel evaluation)
+};
+// span: rows spanned by a row-addressed temporary (= M unless the frames are strided)
+AxialWs carve_axial_ws(Carver& c, const LayerPlan& plan, bool sine, long long span, int B, int T, int H, int W, int C, int heads, int F) {
+  const long long M = (long long)B * T * H * W;
+  AxialWs w{};
+  w.tw = carve_traj_ws(c, M, T, heads, plan.lean_traj, std::max(padded_rows(M, H), padded_rows(M, W)));      // q/k/v row space: frames padded to multiples of 16 rows
+  w.buf1 = c.take<float>((size_t)span * C);
+  if (plan.need_buf2) w.buf2 = c.take<float>((size_t)span * C);
+  if (plan.need_ffn_tmp) {
+    w.y16 = c.take<u16>((size_t)M * C);
+    w.h16 = c.take<u16>((size_t)M * F);
+  }
+  if (plan.need_ffn_part) w.ffn_part = c.take<float>((size_t)(F / 256) * M * C);
+  if (sine && !sine_in_kernel(C, heads)) w.pos = c.take<float>((size_t)M * C);
+  return w;
+}
+
 RowMap identity_map(long long rows) {
   int n = (int)(rows > 0 ? rows : 1);
   return RowMap{n, n, 1, 0, 0, 1, 0};
@@ -362,8 +430,7 @@ int launch_attn(const TrajWs& w, float* attn, int S, int N, int T, int L, int he
   const int tch = (int)((150 * 1024) / per_frame) < T ? (int)((150 * 1024) / per_frame) : T;
   const size_t lds = per_frame * tch;
   if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&spatial_attn_kernel<BF, NKS>))) return rc;
-  const int wcap = g_attn_waves > 0 ? g_attn_waves : 8;
-  const int nwaves = (N + 31) / 32 >= wcap ? wcap : (N + 31) / 32;  // 32 queries per wave, at most `wcap` waves
+  const int nwaves = (N + 31) / 32 >= 8 ? 8 : (N + 31) / 32;  // 32 queries per wave, at most 8 waves
   dim3 grid((N + 32 * nwaves - 1) / (32 * nwaves), heads, S);
   hipLaunchKernelGGL((spatial_attn_kernel<BF, NKS>), grid, dim3(64 * nwaves), lds, st, w.q16, w.k16, w.v16, w.x16, attn, N, T, L,
                      heads, Mp, tch);
@@ -375,12 +442,12 @@ template <bool BF>
 int launch_temporal(const TrajWs& w, const TrajPacked& p, const float* res, float* out, RowMap rm, long long Mp, int N, int L, int T,
                     float scale, hipStream_t st, int nks = 0, const FfnArgs* fa = nullptr, const OwnQkv* oq = nullptr) {
   // output rows are addressed through the RowMap: the largest byte offset is that of the natural [rows, 256] fp32 tensor
-  const int wt = ((!g_no_wt_stores && (g_row_span ? g_row_span : Mp) * 256 * 4 < (1ll << 32)) ? 1 : 0) | (g_spatial_only && nks > 0 ? (oq ? g_spatial_only : 1) << 1 : 0) |
+  const int wt = ((g_row_span ? g_row_span : Mp) * 256 * 4 < (1ll << 32) ? 1 : 0) | (g_spatial_only && nks > 0 ? (oq ? g_spatial_only : 1) << 1 : 0) |
                  (fa != nullptr && g_out_dtype ? (g_out_dtype == 1 ? kOutF16 : kOutBf16) : 0);
   // few rows (cross-clip queries: 512 per video): 16-row tiles give 4x the workgroups -- the spatial half is per-query work
   const long long tiles64 = nks > 0 ? traj_tiles64(Mp, N) : (Mp + 63) / 64;
   if (oq && !(nks > 0 && T <= 8)) return fail(AXVS_ERR_ARG, "internal: own q,k,v need the in-kernel spatial half and T <= 8");
-  if (fa == nullptr && (tiles64 < small_below(T) || T > 8) && !g_no_small_tiles) {       // (T > 8 exists on 16-row tiles only: fused_frames)
+  if (fa == nullptr && (tiles64 < kSmallBelow || T > 8) && !g_no_small_tiles) {       // (T > 8 exists on 16-row tiles only: fused_frames)
     switch (T) {
       case 1: return launch_temporal_n<BF, 1, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
       case 2: return launch_temporal_n<BF, 2, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
@@ -458,7 +525,7 @@ int run_traj(const float* qsrc, const float* ksrc, const float* vsrc, const floa
   // levels of 32 x 32 and below, the cross-clip queries).  Their merged form exists (MQ = 1 on 16-row tiles, bit-identical) but
   // every 16-row workgroup then streams the 384 KB of q/k/v weights itself, which costs what the launch and the q round trip save:
   // layer at [1,4,256,32,32] 59.0 vs 59.2 us, [1,4,256,16,16] 53.1 vs 56.0, [3,4,256,16,32] 105.3 vs 97.8 (768 tiles: siblings
-  // start staggered), cross-clip module 236.1 vs 237.3, BASELINE config 3 0.997 vs 0.989 ms -- off unless option "merge_small" (rounds 3 - 4).
+  // start staggered), cross-clip module 236.1 vs 237.3, BASELINE config 3 0.997 vs 0.989 ms -- off in rounds 3 - 4.
   // Round 5: with the few-rows forms ending at 64 tiles of 64 rows (kSmallBelow) every 16-row grid fits one round of the chip and the case that lost is gone:
   // back to back on warm weights the merged form gains at every size (-8 % per layer at 32 tiles of 16 rows, -7 % at 64, -3 % at 128, -1.5 % at 256), but in a
   // stack of layers with their own, cold weights only up to 128 tiles (-3 %; +3 % at 256: 256 workgroups x 384 KB of q/k/v weights from HBM) -- merged up to
@@ -469,9 +536,9 @@ int run_traj(const float* qsrc, const float* ksrc, const float* vsrc, const floa
   const int tps = (N + 63) / 64;
   // 32-row tiles (5 .. 8 frames per clip, more than 64 tiles of 64 rows; Tube-Link's T = 5 levels): the merged form exists too (MQ = 1, round 5).  Their x tile
   // (T * 16 KiB) leaves room for ONE workgroup per CU, so the siblings of a hand-off start together only while the pass fits one round of the chip: -4 .. -9 % per
-  // layer up to 256 tiles, +4 .. +15 % beyond (profiles/r5_merged_32row_tiles.txt) -- merged iff tiles <= CUs (option "merge_mid": 0 never, 2 always).
-  const bool mt2 = T > 4 && T <= 8 && (tiles >= small_below(T) || g_no_small_tiles);
-  const bool mid_ok = mt2 && g_merge_mid && (g_merge_mid == 2 || (long long)S * ((N + 31) / 32) <= cu_count());
+  // layer up to 256 tiles, +4 .. +15 % beyond (profiles/r5_merged_32row_tiles.txt) -- merged iff tiles <= CUs (kMergeMid).
+  const bool mt2 = T > 4 && T <= 8 && (tiles >= kSmallBelow || g_no_small_tiles);
+  const bool mid_ok = mt2 && kMergeMid && (kMergeMid == 2 || (long long)S * ((N + 31) / 32) <= cu_count());
   const bool merge = may_merge && fuse_attn && !g_generic_only && !g_no_merge_qkv &&
                      g_sync != nullptr && (size_t)S <= g_sync_words && (T <= 4 || mt2) && L % 16 == 0 && nks_fused <= (mt4 || mt2 ? 3 : 4) &&
                      2 * (long long)Cp * Mp * 2 < (1ll << 32) &&
@@ -492,10 +559,10 @@ int run_traj(const float* qsrc, const float* ksrc, const float* vsrc, const floa
       // (the V^T padding keys of frames that are not multiples of 32 keys are cleared by the kernel itself)
       const unsigned qtiles = (unsigned)((Mp + 63) / 64);
       // few tiles (cross-clip queries): one workgroup per (tile, q | k | v) -- a third of the weight stream each
-      hipLaunchKernelGGL((qkv_fused_kernel<BF>), dim3(qtiles, ((int)qtiles <= g_qkv_split_upto && !g_no_small_tiles) ? 3 : 1), dim3(512), kQkvLdsBytes, st, qsrc, qk_add, rm,
+      hipLaunchKernelGGL((qkv_fused_kernel<BF>), dim3(qtiles, ((int)qtiles <= kQkvSplitUpto && !g_no_small_tiles) ? 3 : 1), dim3(512), kQkvLdsBytes, st, qsrc, qk_add, rm,
                          p.wq, p.wk, p.wv, p.bq, p.bk, p.bv, w.q16, w.k16, w.v16, Mp, scale * kLog2e,
                          fuse_attn ? w.vt16 : (u16*)nullptr, N, L, T, nks_fused, posgen ? *posgen : PosGen{},
-                         (!g_no_wt_stores && 2 * (long long)Cp * Mp * 2 < (1ll << 32)) ? 1 : 0, g_status);
+                         2 * (long long)Cp * Mp * 2 < (1ll << 32) ? 1 : 0 /* write-through stores */, g_status);
       goto qkv_done;
     }
   }
@@ -695,16 +762,13 @@ int traj_attn_fwd_t(const float* query, const float* key, const float* value, fl
   Carver pc(const_cast<void*>(packed));
   TrajPacked p = carve_traj(pc, C, heads);
   Carver wc(ws);
-  TrajWs w = carve_traj_ws(wc, (long long)S * T * L, T, heads, false, padded_rows((long long)S * T * L, L));
+  const TrajAttnWs w = carve_traj_attn_ws(wc, S, T, L, C, heads);
   // the fused kernels always add a residual: feed zeros here (TrajectoryAttention.forward itself has none)
-  float* zeros = wc.take<float>((size_t)S * T * L * C);
-  if (hipMemsetAsync(zeros, 0, (size_t)S * T * L * C * sizeof(float), st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "memset failed");
+  if (hipMemsetAsync(w.zeros, 0, (size_t)S * T * L * C * sizeof(float), st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "memset failed");
   RowMap rm{T * L, L, 1, (long long)T * L, L, 1, 0};
-  int rc = run_traj<BF>(query, key, value, nullptr, zeros, out, attn, p, w, rm, S, T, L, C, heads, st);
+  int rc = run_traj<BF>(query, key, value, nullptr, w.zeros, out, attn, p, w.tw, rm, S, T, L, C, heads, st);
   return rc != AXVS_OK ? rc : last_launch_status();
 }
-
-bool sine_in_kernel(int C, int heads) { return !g_generic_only && C == 256 && heads == 8; }
 
 PosGen make_posgen(const AxvsSinePos3D& sp, int T, int H, int W, int C, int l_is_h) {
   PosGen pg{};
@@ -734,15 +798,9 @@ int axial_layer_fwd_t(const float* src, const float* pos, float* out, const void
   if (g_out_dtype && (fs != 0 || which == 1))
     return fail(AXVS_ERR_ARG, "layer_out_dtype: a 16-bit output map exists for the whole layer / its width pass on contiguous frames only");
   Carver wc(ws);
-  const LayerPlan plan = plan_layer(B, T, H, W, C, heads, F, h_attn != nullptr || w_attn != nullptr);
-  const long long Mq = std::max(padded_rows(M, H), padded_rows(M, W));      // q/k/v row space: frames padded to multiples of 16 rows
-  TrajWs tw = carve_traj_ws(wc, M, T, heads, plan.lean_traj, Mq);
-  float* buf1 = wc.take<float>((size_t)span * C);
+  const AxialWs w = carve_axial_ws(wc, plan_layer(B, T, H, W, C, heads, F, h_attn != nullptr || w_attn != nullptr), sine != nullptr, span, B, T, H, W, C, heads, F);
+  float* buf1 = w.buf1;
   float* const scratch1 = buf1;                // fp32 scratch of the generic FFN path (free once the width pass has read the rows)
-  float* buf2 = plan.need_buf2 ? wc.take<float>((size_t)span * C) : nullptr;
-  u16* y16 = plan.need_ffn_tmp ? wc.take<u16>((size_t)M * C) : nullptr;
-  u16* h16 = plan.need_ffn_tmp ? wc.take<u16>((size_t)M * F) : nullptr;
-  float* ffn_part = plan.need_ffn_part ? wc.take<float>((size_t)(F / 256) * M * C) : nullptr;
   const long long sB = fs ? (long long)T * fs : (long long)T * H * W, sT = fs ? fs : (long long)H * W;
 
   g_prof_next = 0;
@@ -758,7 +816,7 @@ int axial_layer_fwd_t(const float* src, const float* pos, float* out, const void
       ph = &pgh;
       pw = &pgw;
     } else {
-      float* pbuf = wc.take<float>((size_t)M * C);
+      float* pbuf = w.pos;
       const long long total = (long long)T * H * W * C;
       hipLaunchKernelGGL(pos3d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pbuf, B, T, H, W, C, sine->temperature,
                          sine->normalize, sine->scale);
@@ -773,7 +831,7 @@ int axial_layer_fwd_t(const float* src, const float* pos, float* out, const void
   RowMap rmh{T * H, H, W, sB, sT, W, 1};
   int rc = AXVS_OK;
   if (which != 2) {
-    rc = run_traj<BF>(src, src, src, pos, src, which == 1 ? out : buf1, h_attn, p.th, tw, rmh, B * W, T, H, C, heads, st, 1, nullptr, nullptr, nullptr, ph, true);
+    rc = run_traj<BF>(src, src, src, pos, src, which == 1 ? out : buf1, h_attn, p.th, w.tw, rmh, B * W, T, H, C, heads, st, 1, nullptr, nullptr, nullptr, ph, true);
     if (rc != AXVS_OK) return rc;
     if (which == 1) return last_launch_status();
   } else {
@@ -783,12 +841,12 @@ int axial_layer_fwd_t(const float* src, const float* pos, float* out, const void
   RowMap rmw{T * W, W, H, sB, sT, 1, W};
   const FfnArgs fa{p.w1, p.w2, p.b1, p.b2, p.g1, p.be1, p.g2, p.be2, F};
   bool ffn_done = false;
-  rc = run_traj<BF>(buf1, buf1, buf1, pos, buf1, buf2, w_attn, p.tw, tw, rmw, B * H, T, W, C, heads, st, 2, &fa, out, &ffn_done, pw, true);
+  rc = run_traj<BF>(buf1, buf1, buf1, pos, buf1, w.buf2, w_attn, p.tw, w.tw, rmw, B * H, T, W, C, heads, st, 2, &fa, out, &ffn_done, pw, true);
   if (rc != AXVS_OK) return rc;
   if (ffn_done) return last_launch_status();   // the width-pass kernel ran norm1 -> FFN -> norm2 too and wrote `out`
 
   // norm1 -> FFN -> norm2                               :181-185, :217-218
-  int rc2 = run_ffn<BF>(buf2, out, p, M, C, heads, F, scratch1, y16, h16, st, ffn_part, fs ? RowStride{H * W, fs - (long long)H * W} : RowStride{0, 0});
+  int rc2 = run_ffn<BF>(w.buf2, out, p, M, C, heads, F, scratch1, w.y16, w.h16, st, w.ffn_part, fs ? RowStride{H * W, fs - (long long)H * W} : RowStride{0, 0});
   if (rc2 != AXVS_OK) return rc2;
   return last_launch_status();
 }
@@ -803,18 +861,14 @@ int traj_layer_fwd_t(const float* src, const float* pos, float* out, const void*
   LayerPacked pf = carve_ffn(pc, C, F);
   const long long M = (long long)B * T * HW;
   Carver wc(ws);
-  TrajWs tw = carve_traj_ws(wc, M, T, heads, false, padded_rows(M, HW));
-  float* x = wc.take<float>((size_t)M * C);
-  float* tmp = wc.take<float>((size_t)M * C);
-  u16* y16 = wc.take<u16>((size_t)M * C);
-  u16* h16 = wc.take<u16>((size_t)M * F);
+  const TrajLayerWs w = carve_traj_layer_ws(wc, B, T, HW, C, heads, F);
   g_prof_next = 0;
   mark(st, "begin");
   // src [(B T), HW, C] is already the sequence order 'B (T HW) C': identity row map, T frames of HW keys
   RowMap rm{T * HW, HW, 1, (long long)T * HW, HW, 1, 0};
-  int rc = run_traj<BF>(src, src, src, pos, src, x, nullptr, pt, tw, rm, B, T, HW, C, heads, st, 0);
+  int rc = run_traj<BF>(src, src, src, pos, src, w.f.x, nullptr, pt, w.tw, rm, B, T, HW, C, heads, st, 0);
   if (rc != AXVS_OK) return rc;
-  rc = run_ffn<BF>(x, out, pf, M, C, heads, F, tmp, y16, h16, st);
+  rc = run_ffn<BF>(w.f.x, out, pf, M, C, heads, F, w.f.tmp, w.f.y16, w.f.h16, st);
   return rc != AXVS_OK ? rc : last_launch_status();
 }
 
@@ -848,6 +902,16 @@ CCHeadsPacked carve_cc_heads(Carver& c, int K1) {
   h.wa = c.take<float>(256); h.ba = c.take<float>(4);
   h.pix = c.take<float>(4);
   return h;
+}
+struct CCHeadsWs {
+  float* emb;        // [R][512] class | mask embeddings
+  u16* kern16;       // blocked [4][R][32] mask kernels
+};
+CCHeadsWs carve_cc_heads_ws(Carver& c, long long R) {
+  CCHeadsWs w;
+  w.emb = c.take<float>((size_t)R * 512);
+  w.kern16 = c.take<u16>((size_t)R * 128);
+  return w;
 }
 struct CCLayerWs {
   TrajWs tw;
@@ -962,12 +1026,11 @@ int cc_heads_fwd_t(const float* x, const float* pf, float* logits, float* masks,
                    int W, int K1, void* ws, hipStream_t st) {
   const long long R = (long long)B * Q * Tc;
   Carver wc(ws);
-  float* emb = wc.take<float>((size_t)R * 512);
-  u16* kern16 = wc.take<u16>((size_t)R * 128);
+  const CCHeadsWs w = carve_cc_heads_ws(wc, R);
   g_prof_next = 0;
   mark(st, "begin");
-  cc_heads_small_t<BF>(x, logits, kern16, packed, B, Q, Tc, K1, emb, st);
-  cc_masks_t<BF>(pf, kern16, masks, packed, B, Q, Tc, V, H, W, K1, 1, 0, 0, st);
+  cc_heads_small_t<BF>(x, logits, w.kern16, packed, B, Q, Tc, K1, w.emb, st);
+  cc_masks_t<BF>(pf, w.kern16, masks, packed, B, Q, Tc, V, H, W, K1, 1, 0, 0, st);
   return last_launch_status();
 }
 
@@ -996,6 +1059,16 @@ TLHeadsWs carve_tl_heads_ws(Carver& c, long long R) {
   w.xn16 = c.take<u16>((size_t)R * 256);
   w.h1 = c.take<u16>((size_t)R * 256);
   w.h2 = c.take<u16>((size_t)R * 256);
+  return w;
+}
+struct TLHeadsFwdWs {      // the stand-alone heads call: + the mask kernels (the modules keep theirs in ModuleWs::kern)
+  TLHeadsWs hw;
+  u16* kern16;
+};
+TLHeadsFwdWs carve_tl_heads_fwd_ws(Carver& c, long long R, int Cm) {
+  TLHeadsFwdWs w;
+  w.hw = carve_tl_heads_ws(c, R);
+  w.kern16 = c.take<u16>((size_t)R * Cm);
   return w;
 }
 
@@ -1046,12 +1119,11 @@ int tl_heads_fwd_t(const float* x, const float* mf, float* logits, float* masks,
                    int h, int w, int K1, int Cm, void* ws, hipStream_t st) {
   const long long R = (long long)B * Q * Tc;
   Carver wc(ws);
-  const TLHeadsWs hw = carve_tl_heads_ws(wc, R);
-  u16* kern16 = wc.take<u16>((size_t)R * Cm);
+  const TLHeadsFwdWs s = carve_tl_heads_fwd_ws(wc, R, Cm);
   g_prof_next = 0;
   mark(st, "begin");
-  tl_heads_small_t<BF>(x, logits, kern16, packed, B, Q, Tc, K1, Cm, hw, st);
-  tl_masks_t<BF>(mf, kern16, masks, B, Q, Tc, fpc, h, w, Cm, 1, 0, 0, st);
+  tl_heads_small_t<BF>(x, logits, s.kern16, packed, B, Q, Tc, K1, Cm, s.hw, st);
+  tl_masks_t<BF>(mf, s.kern16, masks, B, Q, Tc, fpc, h, w, Cm, 1, 0, 0, st);
   return last_launch_status();
 }
 
@@ -1077,6 +1149,54 @@ MsdaPacked carve_msda(Carver& c, int C, int heads, int L, int P) {
   return m;
 }
 
+template <bool BF>
+void pack_msda(const AxvsMsdaParams& p, const MsdaPacked& m, int C, int heads, int L, int P, hipStream_t st) {
+  const int d = C / heads, Cp = heads * 32, mlp = heads * L * P;
+  PackDim plainC{C, C, 0, 0, 0}, headC{C, Cp, heads, d, 0}, off{2 * mlp, 2 * mlp, 0, 0, 0}, lg{mlp, mlp, 0, 0, 0};
+  pack_w3<BF>(p.value_proj_w, m.wv, headC, plainC, st);
+  pack_w3<BF>(p.sampling_offsets_w, m.wq, off, plainC, st, 0, 3 * mlp);
+  pack_w3<BF>(p.attention_weights_w, m.wq, lg, plainC, st, 2 * mlp, 3 * mlp);
+  pack_w3<BF>(p.output_proj_w, m.wo, plainC, headC, st);
+  pack_b(p.value_proj_b, m.bv, headC, st);
+  copy_f32(p.sampling_offsets_b, m.bq, 2 * mlp, st);
+  copy_f32(p.attention_weights_b, m.bq + 2 * mlp, mlp, st);
+  copy_f32(p.output_proj_b, m.bo, C, st);
+  copy_f32(p.sampling_offsets_w, m.wq32, (size_t)2 * mlp * C, st);
+  copy_f32(p.attention_weights_w, m.wq32 + (size_t)2 * mlp * C, (size_t)mlp * C, st);
+  copy_f32(p.value_proj_w, m.wv32, (size_t)C * C, st);
+  copy_f32(p.output_proj_w, m.wo32, (size_t)C * C, st);
+}
+int check_msda_pack(int L, int P) {
+  if (L <= 0 || L > kMsdaMaxLevels || P <= 0 || L * P > 64) return fail(AXVS_ERR_ARG, "unsupported n_levels=%d / n_points=%d", L, P);
+  return AXVS_OK;
+}
+
+struct MsdaWs {
+  u16* value16;      // value_proj output, blocked 16-bit [N S][Cp]
+  float* qproj;      // sampling offsets | attention logits [N Lq][3 heads L P]
+  u16* o16;          // sampled rows: two 16-bit pieces / the same bytes as fp32 rows
+};
+MsdaWs carve_msda_ws(Carver& c, int N, int Lq, int S, int heads, int L, int P) {
+  const size_t Cp = (size_t)heads * 32;
+  MsdaWs w;
+  w.value16 = c.take<u16>((size_t)N * S * Cp);
+  w.qproj = c.take<float>((size_t)N * Lq * 3 * heads * L * P);
+  w.o16 = c.take<u16>(2 * (size_t)N * Lq * Cp);
+  return w;
+}
+struct MsdaLayerWs {
+  void* mws;         // the self-attention's MsdaWs (msda_fwd_t carves it)
+  FfnWs f;           // f.x = src + attention
+};
+MsdaLayerWs carve_msda_layer_ws(Carver& c, int N, int S, int C, int heads, int L, int P, int F) {
+  Carver m(nullptr);
+  carve_msda_ws(m, N, S, S, heads, L, P);
+  MsdaLayerWs w;
+  w.mws = c.take<char>(m.off);
+  w.f = carve_ffn_ws(c, (long long)N * S, C, F);
+  return w;
+}
+
 int msda_levels(const int* shapes, int L, int S, MsdaLevels* lv) {
   if (L <= 0 || L > kMsdaMaxLevels) return fail(AXVS_ERR_ARG, "n_levels=%d must be in 1..%d", L, kMsdaMaxLevels);
   long long start = 0;
@@ -1091,6 +1211,16 @@ int msda_levels(const int* shapes, int L, int S, MsdaLevels* lv) {
   if (start != S) return fail(AXVS_ERR_ARG, "spatial shapes cover %lld tokens, input has %d", start, S);   // modules/ms_deform_attn.py:96
   return AXVS_OK;
 }
+// the deformable attention's argument checks, in two halves (axvs_msda_layer_fwd has a check of its own between them)
+int check_msda_points(int ref_dim, int L, int P) {
+  if (ref_dim != 2 && ref_dim != 4) return fail(AXVS_ERR_ARG, "Last dim of reference_points must be 2 or 4, but get %d instead.", ref_dim);
+  if (L * P > 64) return fail(AXVS_ERR_ARG, "n_levels * n_points > 64 is not supported");
+  return AXVS_OK;
+}
+int check_msda_shapes(int N, int Lq, int S, const int* spatial_shapes, int L, MsdaLevels* lv) {
+  if ((long long)N * S > 2147483647LL / 64 || (long long)N * Lq > 2147483647LL / 64) return fail(AXVS_ERR_ARG, "too many tokens for 32-bit row indices");
+  return msda_levels(spatial_shapes, L, S, lv);
+}
 
 // Y[M][N] = epilogue(X[M][K] (+ X2) . W[N][K]^T) on the 128 x 128 split-precision kernel (axvs_gemm_nt.h), option msda_gemm = pieces
 int launch_nt128(const float* X, const float* X2, const float* W, float* Y, long long M, int N, int K, const tr::GemmEpi& e, hipStream_t st,
@@ -1099,7 +1229,7 @@ int launch_nt128(const float* X, const float* X2, const float* W, float* Y, long
   tr::GemmLd ld{lda ? lda : K, K, N, 0, X2};
   if (zsplit > 1) ld.ksteps = ((K + tr::kGK - 1) / tr::kGK + zsplit - 1) / zsplit;
   const dim3 grid((unsigned)((M + tr::kGT - 1) / tr::kGT), (unsigned)((N + tr::kGT - 1) / tr::kGT), (unsigned)(zsplit > 1 ? zsplit : 1));
-  const bool exact = g_msda_gemm == 3 || (g_msda_gemm == 4 && feeds_residual), gen = tr::gemm_nt_general(ld, K), add = X2 != nullptr;
+  const bool exact = kMsdaGemm == 3 || (kMsdaGemm == 4 && feeds_residual), gen = tr::gemm_nt_general(ld, K), add = X2 != nullptr;
 #define AXVS_NT128(NS_, GEN_, ADD_)                                                                                                  \
   {                                                                                                                                   \
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr::tr_gemm_nt_kernel<NS_, 1, GEN_, ADD_>))) return rc;                \
@@ -1116,7 +1246,7 @@ int launch_nt128(const float* X, const float* X2, const float* W, float* Y, long
   return AXVS_OK;
 }
 // rows from which the 128 x 128 kernel beats the 64 x 64 one (fewer rows: too few workgroups)
-inline bool use_nt128(long long rows, int C, int heads) { return g_msda_gemm && rows >= 2048 && C % 4 == 0 && C / heads == 32; }
+inline bool use_nt128(long long rows, int C, int heads) { return kMsdaGemm && rows >= 2048 && C % 4 == 0 && C / heads == 32; }
 
 // what: 0 = whole module (value_proj, offsets | logits, gather, output_proj), 1 = up to the gather with fp32 rows out
 // (`out` = sampled [N*Lq][C], no output_proj)
@@ -1127,21 +1257,19 @@ int msda_fwd_t(const float* query, const float* refp, int ref_dim, const float* 
   const int L = lv.L, Cp = heads * 32, nq = 3 * heads * L * P;
   const long long Rv = (long long)N * S, Rq = (long long)N * Lq;
   Carver wc(ws);
-  u16* value16 = wc.take<u16>((size_t)Rv * Cp);
-  float* qproj = wc.take<float>((size_t)Rq * nq);
-  u16* o16 = wc.take<u16>(2 * (size_t)Rq * Cp);
+  const MsdaWs w = carve_msda_ws(wc, N, Lq, S, heads, L, P);
   g_prof_next = 0;
   mark(st, "begin");
   // value_proj and output_proj feed the module output directly (no residual / norm inside the module): split precision
   const tr::Drop nodrop{0u, 0u, 0u, 1.f};
   if (use_nt128(Rv, C, heads)) {          // fp32 rows in, one 16-bit piece out in the blocked layout the gather reads
     tr::GemmEpi e{p.bv, 1.f, 0, nodrop, 0.f};
-    e.out16 = value16;
+    e.out16 = w.value16;
     e.kind16 = BF ? 2 : 1;
     e.zero_rows = mask;
     if (int rc = launch_nt128(input, nullptr, p.wv32, nullptr, Rv, Cp, C, e, st)) return rc;
   } else {
-    EpiBlocked16<BF> ev{value16, Rv, p.bv, 1.f, 0, 0};
+    EpiBlocked16<BF> ev{w.value16, Rv, p.bv, 1.f, 0, 0};
     ev.zero_rows = mask;
     launch_gemm<BF>(ALoadRowsF32Split3<BF>{input, (int)Rv, C}, p.wv, ev, (int)Rv, Cp, 3 * C, st);
   }
@@ -1149,11 +1277,11 @@ int msda_fwd_t(const float* query, const float* refp, int ref_dim, const float* 
   // sampling offsets | attention logits: fp32 rows in, fp32 rows out, [N Lq] x [3 heads L P] x C -- at a few thousand rows and more
   // the 128 x 128 split-precision kernel of the training tier (axvs_gemm_nt.h: fp32 operands split into bf16 pieces in its
   // loader) beats the 64 x 64 one (config 3, 21504 rows: the three projections of a deformable layer 27 + 59 + 30 us -> ~65 us)
-  if (g_msda_gemm && Rq >= 2048 && C % 4 == 0 && nq % 4 == 0) {
+  if (kMsdaGemm && Rq >= 2048 && C % 4 == 0 && nq % 4 == 0) {
     const tr::GemmEpi e{p.bq, 1.f, 0, nodrop, 0.f};
-    if (int rc = launch_nt128(query, qadd, p.wq32, qproj, Rq, nq, C, e, st)) return rc;
+    if (int rc = launch_nt128(query, qadd, p.wq32, w.qproj, Rq, nq, C, e, st)) return rc;
   } else {
-    launch_gemm<BF>(ALoadRowsF32Split3<BF>{query, (int)Rq, C, qadd}, p.wq, EpiRowsF32{qproj, nullptr, p.bq, identity_map(Rq), nq, 1.f}, (int)Rq,
+    launch_gemm<BF>(ALoadRowsF32Split3<BF>{query, (int)Rq, C, qadd}, p.wq, EpiRowsF32{w.qproj, nullptr, p.bq, identity_map(Rq), nq, 1.f}, (int)Rq,
                     nq, 3 * C, st);
   }
   mark(st, "msda.offsets+weights");
@@ -1161,9 +1289,9 @@ int msda_fwd_t(const float* query, const float* refp, int ref_dim, const float* 
   const dim3 ggrid((unsigned)((groups + 63) / 64));
   // the output projection on the 128 x 128 kernel reads the sampled rows as fp32 [N Lq][C] (same bytes as the two 16-bit pieces)
   const bool out128 = what != 1 && use_nt128(Rq, C, heads);
-  float* of32 = what == 1 ? out : (out128 ? reinterpret_cast<float*>(o16) : nullptr);
-  if (P == 4) hipLaunchKernelGGL((msda_gather_kernel<BF, 4>), ggrid, dim3(256), 0, st, value16, qproj, refp, ref_dim, lv, o16, N, S, Lq, heads, P, of32, C / heads);
-  else hipLaunchKernelGGL((msda_gather_kernel<BF, 0>), ggrid, dim3(256), 0, st, value16, qproj, refp, ref_dim, lv, o16, N, S, Lq, heads, P, of32, C / heads);
+  float* of32 = what == 1 ? out : (out128 ? reinterpret_cast<float*>(w.o16) : nullptr);
+  if (P == 4) hipLaunchKernelGGL((msda_gather_kernel<BF, 4>), ggrid, dim3(256), 0, st, w.value16, w.qproj, refp, ref_dim, lv, w.o16, N, S, Lq, heads, P, of32, C / heads);
+  else hipLaunchKernelGGL((msda_gather_kernel<BF, 0>), ggrid, dim3(256), 0, st, w.value16, w.qproj, refp, ref_dim, lv, w.o16, N, S, Lq, heads, P, of32, C / heads);
   mark(st, "msda.gather");
   if (what == 1) return last_launch_status();
   if (out128) {
@@ -1171,16 +1299,14 @@ int msda_fwd_t(const float* query, const float* refp, int ref_dim, const float* 
     e.res = residual;
     if (int rc = launch_nt128(of32, nullptr, p.wo32, out, Rq, C, C, e, st, true)) return rc;
   } else {
-    launch_gemm<BF>(ALoadBlockedSplit3<BF>{o16, Rq, (int)Rq, Cp}, p.wo, EpiRowsF32{out, residual, p.bo, identity_map(Rq), C, 1.f}, (int)Rq,
+    launch_gemm<BF>(ALoadBlockedSplit3<BF>{w.o16, Rq, (int)Rq, Cp}, p.wo, EpiRowsF32{out, residual, p.bo, identity_map(Rq), C, 1.f}, (int)Rq,
                     C, 3 * Cp, st);
   }
   mark(st, "msda.output_proj");
   return last_launch_status();
 }
 
-}  // namespace
 
-namespace {
 struct ModuleWs {
   void *chain, *heads;
   float* q;            // [layers][R][256] clip queries after every layer: the predictor heads run on all of them at once
@@ -1208,8 +1334,7 @@ int run_cc_module(const float* clip_query, const void* const* packed_layers, int
   for (int i = 0; i < layers; ++i) {
     float* nxt = w.q + (size_t)i * R * 256;
     float* also = i == layers - 1 ? last_query : nullptr;      // the caller's copy of the last layer's queries
-    int rc = dtype == AXVS_BF16 ? cc_layer_fwd_t<kBF>(cur, nxt, packed_layers[i], B, Q, Tc, rates, w.chain, st, also)
-                                : cc_layer_fwd_t<false>(cur, nxt, packed_layers[i], B, Q, Tc, rates, w.chain, st, also);
+    int rc = by_dtype(dtype, [&](auto bf) { return cc_layer_fwd_t<bf()>(cur, nxt, packed_layers[i], B, Q, Tc, rates, w.chain, st, also); });
     if (rc != AXVS_OK) return rc;
     cur = nxt;
   }
@@ -1317,9 +1442,7 @@ int axvs_traj_pack(const AxvsTrajParams* p, void* packed, int C, int heads, int 
   Carver c(packed);
   TrajPacked t = carve_traj(c, C, heads);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) pack_traj<kBF>(*p, t, C, heads, st);
-  else if (dtype == AXVS_F16) pack_traj<false>(*p, t, C, heads, st);
-  else return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  by_dtype(dtype, [&](auto bf) { pack_traj<bf()>(*p, t, C, heads, st); });
   return last_launch_status();
 }
 
@@ -1333,36 +1456,21 @@ int axvs_axial_layer_pack(const AxvsAxialLayerParams* p, void* packed, int C, in
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
-  if (int rcd = check_dtype(dtype)) return rcd;
+  if (int rc = check_ffn(d_ffn)) return rc;
   Carver c(packed);
   LayerPacked l = carve_layer(c, C, heads, d_ffn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  PackDim plainC{C, C, 0, 0, 0}, plainF{d_ffn, d_ffn, 0, 0, 0};
-  if (dtype == AXVS_BF16) {
-    pack_traj<kBF>(p->height_attn, l.th, C, heads, st);
-    pack_traj<kBF>(p->width_attn, l.tw, C, heads, st);
-    pack_w<kBF>(p->linear1_w, l.w1, plainF, plainC, st);
-    pack_w<kBF>(p->linear2_w, l.w2, plainC, plainF, st);
-  } else {
-    pack_traj<false>(p->height_attn, l.th, C, heads, st);
-    pack_traj<false>(p->width_attn, l.tw, C, heads, st);
-    pack_w<false>(p->linear1_w, l.w1, plainF, plainC, st);
-    pack_w<false>(p->linear2_w, l.w2, plainC, plainF, st);
-  }
-  pack_b(p->linear1_b, l.b1, plainF, st);
-  pack_b(p->linear2_b, l.b2, plainC, st);
-  pack_b(p->norm1_w, l.g1, plainC, st);
-  pack_b(p->norm1_b, l.be1, plainC, st);
-  pack_b(p->norm2_w, l.g2, plainC, st);
-  pack_b(p->norm2_b, l.be2, plainC, st);
+  by_dtype(dtype, [&](auto bf) {
+    pack_traj<bf()>(p->height_attn, l.th, C, heads, st);
+    pack_traj<bf()>(p->width_attn, l.tw, C, heads, st);
+    pack_ffn<bf()>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
+  });
   return last_launch_status();
 }
 
 size_t axvs_traj_attn_workspace_bytes(int S, int T, int L, int C, int heads) {
   Carver c(nullptr);
-  carve_traj_ws(c, (long long)S * T * L, T, heads, false, padded_rows((long long)S * T * L, L));
-  c.take<float>((size_t)S * T * L * C);
+  carve_traj_attn_ws(c, S, T, L, C, heads);
   return c.off;
 }
 
@@ -1373,29 +1481,14 @@ int axvs_traj_attn_fwd(const float* query, const float* key, const float* value,
   if (!query || !key || !value || !out || !packed || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (S <= 0 || T <= 0 || L <= 0) return fail(AXVS_ERR_ARG, "empty shape S=%d T=%d L=%d", S, T, L);
   if (int rc = check_cfg(C, heads)) return rc;
-  if (workspace_bytes < axvs_traj_attn_workspace_bytes(S, T, L, C, heads))
-    return fail(AXVS_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes,
-                axvs_traj_attn_workspace_bytes(S, T, L, C, heads));
+  if (int rc = check_ws(workspace_bytes, axvs_traj_attn_workspace_bytes(S, T, L, C, heads))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) return traj_attn_fwd_t<kBF>(query, key, value, out, space_attn, packed, S, T, L, C, heads, workspace, st);
-  if (dtype == AXVS_F16) return traj_attn_fwd_t<false>(query, key, value, out, space_attn, packed, S, T, L, C, heads, workspace, st);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) { return traj_attn_fwd_t<bf()>(query, key, value, out, space_attn, packed, S, T, L, C, heads, workspace, st); });
 }
 
-// span: rows spanned by a row-addressed temporary (= M unless the frames are strided)
 static size_t layer_ws_bytes(int B, int T, int H, int W, int C, int heads, int d_ffn, int want_attn_maps, int sine_pos, long long span) {
-  const long long M = (long long)B * T * H * W;
   Carver c(nullptr);
-  const LayerPlan plan = plan_layer(B, T, H, W, C, heads, d_ffn, want_attn_maps != 0);
-  carve_traj_ws(c, M, T, heads, plan.lean_traj, std::max(padded_rows(M, H), padded_rows(M, W)));
-  c.take<float>((size_t)span * C);
-  if (plan.need_buf2) c.take<float>((size_t)span * C);
-  if (plan.need_ffn_tmp) {
-    c.take<u16>((size_t)M * C);
-    c.take<u16>((size_t)M * d_ffn);
-  }
-  if (plan.need_ffn_part) c.take<float>((size_t)(d_ffn / 256) * M * C);
-  if (sine_pos && !sine_in_kernel(C, heads)) c.take<float>((size_t)M * C);     // materialised positions (tiers without in-kernel evaluation)
+  carve_axial_ws(c, plan_layer(B, T, H, W, C, heads, d_ffn, want_attn_maps != 0), sine_pos != 0, span, B, T, H, W, C, heads, d_ffn);
   return c.off;
 }
 size_t axvs_axial_layer_workspace_bytes_ex(int B, int T, int H, int W, int C, int heads, int d_ffn, int want_attn_maps, int sine_pos) {
@@ -1419,19 +1512,15 @@ int axvs_axial_layer_fwd_sine3d_strided(const float* src, const AxvsSinePos3D* p
   if (!src || !pos || !out || !packed || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0) return fail(AXVS_ERR_ARG, "empty shape B=%d T=%d H=%d W=%d", B, T, H, W);
   if (int rc = check_cfg(C, heads)) return rc;
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
+  if (int rc = check_ffn(d_ffn)) return rc;
   if (!axvs_axial_layer_strided_ok(C, heads, d_ffn)) return fail(AXVS_ERR_ARG, "strided frames need the fused tier (C = 256, 8 heads, d_ffn a multiple of 256)");
   if (frame_stride_rows < (long long)H * W) return fail(AXVS_ERR_ARG, "frame stride %lld < H W = %d rows", frame_stride_rows, H * W);
   if (T > 255 || H > 4095 || W > 4095) return fail(AXVS_ERR_ARG, "grid too large for generated positions");
   const long long span = ((long long)B * T - 1) * frame_stride_rows + (long long)H * W;
   if (span > 2147483647LL / 64) return fail(AXVS_ERR_ARG, "too many rows for 32-bit row indices");
-  if (int rcd = check_dtype(dtype)) return rcd;
-  const size_t need = axvs_axial_layer_workspace_bytes_strided(B, T, H, W, C, heads, d_ffn, frame_stride_rows);
-  if (workspace_bytes < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  if (int rc = check_ws(workspace_bytes, axvs_axial_layer_workspace_bytes_strided(B, T, H, W, C, heads, d_ffn, frame_stride_rows))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16)
-    return axial_layer_fwd_t<kBF>(src, nullptr, out, packed, B, T, H, W, C, heads, d_ffn, workspace, nullptr, nullptr, st, pos, 0, frame_stride_rows);
-  return axial_layer_fwd_t<false>(src, nullptr, out, packed, B, T, H, W, C, heads, d_ffn, workspace, nullptr, nullptr, st, pos, 0, frame_stride_rows);
+  return by_dtype(dtype, [&](auto bf) { return axial_layer_fwd_t<bf()>(src, nullptr, out, packed, B, T, H, W, C, heads, d_ffn, workspace, nullptr, nullptr, st, pos, 0, frame_stride_rows); });
 }
 
 size_t axvs_axial_layer_workspace_bytes(int B, int T, int H, int W, int C, int heads, int d_ffn) {
@@ -1445,16 +1534,11 @@ static int axial_layer_entry(const float* src, const float* pos, const AxvsSineP
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0) return fail(AXVS_ERR_ARG, "empty shape B=%d T=%d H=%d W=%d", B, T, H, W);
   if (src == out) return fail(AXVS_ERR_ARG, "out may not alias src");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
+  if (int rc = check_ffn(d_ffn)) return rc;
   if (sine && (T > 255 || H > 4095 || W > 4095)) return fail(AXVS_ERR_ARG, "grid too large for generated positions");
-  const size_t need = axvs_axial_layer_workspace_bytes_ex(B, T, H, W, C, heads, d_ffn, h_attn != nullptr || w_attn != nullptr, sine != nullptr);
-  if (workspace_bytes < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  if (int rc = check_ws(workspace_bytes, axvs_axial_layer_workspace_bytes_ex(B, T, H, W, C, heads, d_ffn, h_attn != nullptr || w_attn != nullptr, sine != nullptr))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16)
-    return axial_layer_fwd_t<kBF>(src, pos, out, packed, B, T, H, W, C, heads, d_ffn, workspace, h_attn, w_attn, st, sine);
-  if (dtype == AXVS_F16)
-    return axial_layer_fwd_t<false>(src, pos, out, packed, B, T, H, W, C, heads, d_ffn, workspace, h_attn, w_attn, st, sine);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) { return axial_layer_fwd_t<bf()>(src, pos, out, packed, B, T, H, W, C, heads, d_ffn, workspace, h_attn, w_attn, st, sine); });
 }
 
 int axvs_axial_layer_fwd(const float* src, const float* pos, float* out, const void* packed, int B, int T, int H, int W,
@@ -1473,12 +1557,10 @@ int axvs_axial_pass_fwd(const float* src, const float* pos, float* out, const vo
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0) return fail(AXVS_ERR_ARG, "empty shape B=%d T=%d H=%d W=%d", B, T, H, W);
   if (src == out) return fail(AXVS_ERR_ARG, "out may not alias src");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
-  if (workspace_bytes < axvs_axial_layer_workspace_bytes_ex(B, T, H, W, C, heads, d_ffn, 0, 0)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ffn(d_ffn)) return rc;
+  if (int rc = check_ws(workspace_bytes, axvs_axial_layer_workspace_bytes_ex(B, T, H, W, C, heads, d_ffn, 0, 0))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) return axial_layer_fwd_t<kBF>(src, pos, out, packed, B, T, H, W, C, heads, d_ffn, workspace, nullptr, nullptr, st, nullptr, pass + 1);
-  if (dtype == AXVS_F16) return axial_layer_fwd_t<false>(src, pos, out, packed, B, T, H, W, C, heads, d_ffn, workspace, nullptr, nullptr, st, nullptr, pass + 1);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) { return axial_layer_fwd_t<bf()>(src, pos, out, packed, B, T, H, W, C, heads, d_ffn, workspace, nullptr, nullptr, st, nullptr, pass + 1); });
 }
 
 size_t axvs_axial_layer_sine3d_workspace_bytes(int B, int T, int H, int W, int C, int heads, int d_ffn) {
@@ -1505,30 +1587,21 @@ int axvs_traj_layer_pack(const AxvsTrajLayerParams* p, void* packed, int C, int 
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
-  if (int rcd = check_dtype(dtype)) return rcd;
+  if (int rc = check_ffn(d_ffn)) return rc;
   Carver c(packed);
   TrajPacked t = carve_traj(c, C, heads);
   LayerPacked l = carve_ffn(c, C, d_ffn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) {
-    pack_traj<kBF>(p->temporal_attn, t, C, heads, st);
-    pack_ffn<kBF>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
-  } else {
-    pack_traj<false>(p->temporal_attn, t, C, heads, st);
-    pack_ffn<false>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
-  }
+  by_dtype(dtype, [&](auto bf) {
+    pack_traj<bf()>(p->temporal_attn, t, C, heads, st);
+    pack_ffn<bf()>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
+  });
   return last_launch_status();
 }
 
 size_t axvs_traj_layer_workspace_bytes(int B, int T, int HW, int C, int heads, int d_ffn) {
-  const long long M = (long long)B * T * HW;
   Carver c(nullptr);
-  carve_traj_ws(c, M, T, heads, false, padded_rows(M, HW));
-  c.take<float>((size_t)M * C);
-  c.take<float>((size_t)M * C);
-  c.take<u16>((size_t)M * C);
-  c.take<u16>((size_t)M * d_ffn);
+  carve_traj_layer_ws(c, B, T, HW, C, heads, d_ffn);
   return c.off;
 }
 
@@ -1539,21 +1612,28 @@ int axvs_traj_layer_fwd(const float* src, const float* pos, float* out, const vo
   if (B <= 0 || T <= 0 || HW <= 0) return fail(AXVS_ERR_ARG, "empty shape B=%d T=%d HW=%d", B, T, HW);
   if (src == out) return fail(AXVS_ERR_ARG, "out may not alias src");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
-  if (workspace_bytes < axvs_traj_layer_workspace_bytes(B, T, HW, C, heads, d_ffn)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ffn(d_ffn)) return rc;
+  if (int rc = check_ws(workspace_bytes, axvs_traj_layer_workspace_bytes(B, T, HW, C, heads, d_ffn))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) return traj_layer_fwd_t<kBF>(src, pos, out, packed, B, T, HW, C, heads, d_ffn, workspace, st);
-  if (dtype == AXVS_F16) return traj_layer_fwd_t<false>(src, pos, out, packed, B, T, HW, C, heads, d_ffn, workspace, st);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) { return traj_layer_fwd_t<bf()>(src, pos, out, packed, B, T, HW, C, heads, d_ffn, workspace, st); });
 }
 
 size_t axvs_ffn_workspace_bytes(long long M, int C, int d_ffn) {
   Carver c(nullptr);
-  c.take<float>((size_t)M * C);
-  c.take<float>((size_t)M * C);
-  c.take<u16>((size_t)M * C);
-  c.take<u16>((size_t)M * d_ffn);
+  carve_ffn_ws(c, M, C, d_ffn);
   return c.off;
+}
+
+// the stand-alone FFN on a copy of x (the generic path clobbers its input rows); p: the FFN part of a packed layer / a packed FFN
+static int ffn_fwd_checked(const float* x, float* out, const LayerPacked& p, long long M, int C, int heads, int d_ffn, int dtype, void* workspace,
+                           hipStream_t st) {
+  Carver wc(workspace);
+  const FfnWs w = carve_ffn_ws(wc, M, C, d_ffn);
+  if (hipMemcpyAsync(w.x, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return fail(AXVS_ERR_LAUNCH, "copy failed");
+  g_prof_next = 0;
+  int rc = by_dtype(dtype, [&](auto bf) { return run_ffn<bf()>(w.x, out, p, M, C, heads, d_ffn, w.tmp, w.y16, w.h16, st); });
+  return rc != AXVS_OK ? rc : last_launch_status();
 }
 
 int axvs_ffn_fwd(const float* x, float* out, const void* packed_layer, long long M, int C, int heads, int d_ffn, int dtype,
@@ -1562,21 +1642,9 @@ int axvs_ffn_fwd(const float* x, float* out, const void* packed_layer, long long
   if (!x || !out || !packed_layer || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (M <= 0) return fail(AXVS_ERR_ARG, "empty input");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (workspace_bytes < axvs_ffn_workspace_bytes(M, C, d_ffn)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = check_ws(workspace_bytes, axvs_ffn_workspace_bytes(M, C, d_ffn))) return rc;
   Carver pc(const_cast<void*>(packed_layer));
-  LayerPacked p = carve_layer(pc, C, heads, d_ffn);
-  Carver wc(workspace);
-  float* xin = wc.take<float>((size_t)M * C);
-  float* tmp = wc.take<float>((size_t)M * C);
-  u16* y16 = wc.take<u16>((size_t)M * C);
-  u16* h16 = wc.take<u16>((size_t)M * d_ffn);
-  if (hipMemcpyAsync(xin, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return fail(AXVS_ERR_LAUNCH, "copy failed");
-  g_prof_next = 0;
-  int rc = dtype == AXVS_BF16 ? run_ffn<kBF>(xin, out, p, M, C, heads, d_ffn, tmp, y16, h16, st)
-                              : run_ffn<false>(xin, out, p, M, C, heads, d_ffn, tmp, y16, h16, st);
-  return rc != AXVS_OK ? rc : last_launch_status();
+  return ffn_fwd_checked(x, out, carve_layer(pc, C, heads, d_ffn), M, C, heads, d_ffn, dtype, workspace, static_cast<hipStream_t>(stream));
 }
 
 size_t axvs_cc_layer_packed_bytes(void) {
@@ -1588,18 +1656,14 @@ size_t axvs_cc_layer_packed_bytes(void) {
 int axvs_cc_layer_pack(const AxvsCCLayerParams* p, void* packed, int dtype, void* stream) {
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
-  if (int rcd = check_dtype(dtype)) return rcd;
   Carver c(packed);
   CCLayerPacked l = carve_cc_layer(c);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned cb = (7 * 256 * 256 + 255) / 256;
-  if (dtype == AXVS_BF16) {
-    pack_traj<kBF>(p->attn, l.t, 256, 8, st);
-    hipLaunchKernelGGL((pack_aspp_taps_kernel<kBF>), dim3(cb), dim3(256), 0, st, p->aspp_w[0], p->aspp_w[1], p->aspp_w[2], p->aspp_proj_w, l.aspp_taps);
-  } else {
-    pack_traj<false>(p->attn, l.t, 256, 8, st);
-    hipLaunchKernelGGL((pack_aspp_taps_kernel<false>), dim3(cb), dim3(256), 0, st, p->aspp_w[0], p->aspp_w[1], p->aspp_w[2], p->aspp_proj_w, l.aspp_taps);
-  }
+  by_dtype(dtype, [&](auto bf) {
+    pack_traj<bf()>(p->attn, l.t, 256, 8, st);
+    hipLaunchKernelGGL((pack_aspp_taps_kernel<bf()>), dim3(cb), dim3(256), 0, st, p->aspp_w[0], p->aspp_w[1], p->aspp_w[2], p->aspp_proj_w, l.aspp_taps);
+  });
   hipLaunchKernelGGL(pack_aspp_bias_kernel, dim3(1), dim3(256), 0, st, p->aspp_b[0], p->aspp_b[1], p->aspp_b[2], p->aspp_proj_w, l.aspp_bias);
   copy_f32(p->norm_w, l.norm_w, 256, st); copy_f32(p->norm_b, l.norm_b, 256, st);
   copy_f32(p->aspp_norm_w, l.an_w, 256, st); copy_f32(p->aspp_norm_b, l.an_b, 256, st);
@@ -1619,11 +1683,9 @@ int axvs_cc_layer_fwd(const float* clip_query, float* out, const void* packed, i
   if (!clip_query || !out || !packed || !rates || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (B <= 0 || Q <= 0 || Tc <= 0) return fail(AXVS_ERR_ARG, "empty shape");
   if (clip_query == out) return fail(AXVS_ERR_ARG, "out may not alias clip_query");
-  if (workspace_bytes < axvs_cc_layer_workspace_bytes(B, Q, Tc)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ws(workspace_bytes, axvs_cc_layer_workspace_bytes(B, Q, Tc))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) return cc_layer_fwd_t<kBF>(clip_query, out, packed, B, Q, Tc, rates, workspace, st);
-  if (dtype == AXVS_F16) return cc_layer_fwd_t<false>(clip_query, out, packed, B, Q, Tc, rates, workspace, st);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) { return cc_layer_fwd_t<bf()>(clip_query, out, packed, B, Q, Tc, rates, workspace, st); });
 }
 
 size_t axvs_cc_heads_packed_bytes(int K1) {
@@ -1635,20 +1697,15 @@ size_t axvs_cc_heads_packed_bytes(int K1) {
 int axvs_cc_heads_pack(const AxvsCCHeadParams* p, void* packed, int K1, int dtype, void* stream) {
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed || K1 <= 0) return fail(AXVS_ERR_ARG, "bad argument");
-  if (int rcd = check_dtype(dtype)) return rcd;
   Carver c(packed);
   CCHeadsPacked h = carve_cc_heads(c, K1);
   hipStream_t st = static_cast<hipStream_t>(stream);
   PackDim n256{256, 256, 0, 0, 0}, n128{128, 128, 0, 0, 0};
-  if (dtype == AXVS_BF16) {
-    pack_w<kBF>(p->class_proj_w, h.wemb, n256, n256, st, 0, 512);
-    pack_w<kBF>(p->mask_proj_w, h.wemb, n256, n256, st, 256, 512);
-    pack_w<kBF>(p->mask_head_w, h.wmh, n128, n256, st);
-  } else {
-    pack_w<false>(p->class_proj_w, h.wemb, n256, n256, st, 0, 512);
-    pack_w<false>(p->mask_proj_w, h.wemb, n256, n256, st, 256, 512);
-    pack_w<false>(p->mask_head_w, h.wmh, n128, n256, st);
-  }
+  by_dtype(dtype, [&](auto bf) {
+    pack_w<bf()>(p->class_proj_w, h.wemb, n256, n256, st, 0, 512);
+    pack_w<bf()>(p->mask_proj_w, h.wemb, n256, n256, st, 256, 512);
+    pack_w<bf()>(p->mask_head_w, h.wmh, n128, n256, st);
+  });
   fold_bn(p->class_proj_bn, h.emb_mul, h.emb_add, 256, st);
   fold_bn(p->mask_proj_bn, h.emb_mul + 256, h.emb_add + 256, 256, st);
   fold_bn(p->mask_head_bn, h.mh_mul, h.mh_add, 128, st);
@@ -1662,9 +1719,7 @@ int axvs_cc_heads_pack(const AxvsCCHeadParams* p, void* packed, int K1, int dtyp
 
 size_t axvs_cc_heads_workspace_bytes(int B, int Q, int Tc) {
   Carver c(nullptr);
-  const long long R = (long long)B * Q * Tc;
-  c.take<float>((size_t)R * 512);
-  c.take<u16>((size_t)R * 128);
+  carve_cc_heads_ws(c, (long long)B * Q * Tc);
   return c.off;
 }
 
@@ -1675,11 +1730,9 @@ int axvs_cc_heads_fwd(const float* clip_query, const float* panoptic_features, f
   if (!clip_query || !panoptic_features || !pred_logits || !pred_masks || !packed || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (B <= 0 || Q <= 0 || Tc <= 0 || V <= 0 || H <= 0 || W <= 0 || K1 <= 0) return fail(AXVS_ERR_ARG, "empty shape");
   if (B * Tc > 1024) return fail(AXVS_ERR_ARG, "B*Tc > 1024 is not supported by the class head");
-  if (workspace_bytes < axvs_cc_heads_workspace_bytes(B, Q, Tc)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ws(workspace_bytes, axvs_cc_heads_workspace_bytes(B, Q, Tc))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) return cc_heads_fwd_t<kBF>(clip_query, panoptic_features, pred_logits, pred_masks, packed, B, Q, Tc, V, H, W, K1, workspace, st);
-  if (dtype == AXVS_F16) return cc_heads_fwd_t<false>(clip_query, panoptic_features, pred_logits, pred_masks, packed, B, Q, Tc, V, H, W, K1, workspace, st);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) { return cc_heads_fwd_t<bf()>(clip_query, panoptic_features, pred_logits, pred_masks, packed, B, Q, Tc, V, H, W, K1, workspace, st); });
 }
 
 // ---- the whole layer loop of the cross-clip modules in ONE call (CC/...:283-318, TLCC:925-950): the Python host of round 1 made
@@ -1701,8 +1754,7 @@ int axvs_cc_module_fwd(const float* clip_query, const float* panoptic_features, 
     return fail(AXVS_ERR_ARG, "null pointer");
   if (B <= 0 || Q <= 0 || Tc <= 0 || V <= 0 || H <= 0 || W <= 0 || K1 <= 0 || num_layers <= 0) return fail(AXVS_ERR_ARG, "empty shape");
   if (B * Tc > 1024) return fail(AXVS_ERR_ARG, "B*Tc > 1024 is not supported by the class head");
-  if (int rcd = check_dtype(dtype)) return rcd;
-  if (workspace_bytes < axvs_cc_module_workspace_bytes(B, Q, Tc, num_layers)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ws(workspace_bytes, axvs_cc_module_workspace_bytes(B, Q, Tc, num_layers))) return rc;
   const long long R = (long long)B * Q * Tc;
   Carver wc(workspace);
   const ModuleWs w = carve_module_ws(wc, axvs_cc_layer_workspace_bytes(B, Q, Tc), (size_t)num_layers * R * 512 * sizeof(float), R, num_layers, 128);
@@ -1713,12 +1765,10 @@ int axvs_cc_module_fwd(const float* clip_query, const float* panoptic_features, 
   const float* hq = w.q + (size_t)(num_layers - hl) * R * 256;
   auto heads = [&](hipStream_t hs) {
     float* emb = static_cast<float*>(w.heads);
-    if (dtype == AXVS_BF16) {
-      cc_heads_small_t<kBF>(hq, pred_logits, w.kern, packed_heads, B, Q, Tc, K1, emb, hs, hl);
-      return cc_masks_t<kBF>(panoptic_features, w.kern, pred_masks, packed_heads, B, Q, Tc, V, H, W, K1, hl, R * 32, mstride, hs);
-    }
-    cc_heads_small_t<false>(hq, pred_logits, w.kern, packed_heads, B, Q, Tc, K1, emb, hs, hl);
-    return cc_masks_t<false>(panoptic_features, w.kern, pred_masks, packed_heads, B, Q, Tc, V, H, W, K1, hl, R * 32, mstride, hs);
+    return by_dtype(dtype, [&](auto bf) {
+      cc_heads_small_t<bf()>(hq, pred_logits, w.kern, packed_heads, B, Q, Tc, K1, emb, hs, hl);
+      return cc_masks_t<bf()>(panoptic_features, w.kern, pred_masks, packed_heads, B, Q, Tc, V, H, W, K1, hl, R * 32, mstride, hs);
+    });
   };
   return run_cc_module(clip_query, packed_layers, num_layers, last_query, B, Q, Tc, rates, dtype, w, static_cast<hipStream_t>(stream), heads);
 }
@@ -1740,8 +1790,7 @@ int axvs_tl_cc_module_fwd(const float* clip_query, const float* mask_feature, fl
   if (B <= 0 || Q <= 0 || Tc <= 0 || frames_per_clip <= 0 || h <= 0 || w_ <= 0 || K1 <= 0 || num_layers <= 0) return fail(AXVS_ERR_ARG, "empty shape");
   if (Cm != 128 && Cm != 256) return fail(AXVS_ERR_ARG, "mask feature channels must be 128 or 256 (got %d)", Cm);
   if (Tc > 1024) return fail(AXVS_ERR_ARG, "more than 1024 clips are not supported by the class head");
-  if (int rcd = check_dtype(dtype)) return rcd;
-  if (workspace_bytes < axvs_tl_cc_module_workspace_bytes(B, Q, Tc, Cm, num_layers)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ws(workspace_bytes, axvs_tl_cc_module_workspace_bytes(B, Q, Tc, Cm, num_layers))) return rc;
   const long long R = (long long)B * Q * Tc;
   Carver hsz(nullptr);
   carve_tl_heads_ws(hsz, (long long)num_layers * R);
@@ -1752,12 +1801,10 @@ int axvs_tl_cc_module_fwd(const float* clip_query, const float* mask_feature, fl
   auto heads = [&](hipStream_t hs) {
     Carver hc(w.heads);
     const TLHeadsWs hw = carve_tl_heads_ws(hc, (long long)num_layers * R);
-    if (dtype == AXVS_BF16) {
-      tl_heads_small_t<kBF>(w.q, cls_logits, w.kern, packed_heads, B, Q, Tc, K1, Cm, hw, hs, num_layers);
-      return tl_masks_t<kBF>(mask_feature, w.kern, mask_logits, B, Q, Tc, frames_per_clip, h, w_, Cm, num_layers, R * 32, mstride, hs);
-    }
-    tl_heads_small_t<false>(w.q, cls_logits, w.kern, packed_heads, B, Q, Tc, K1, Cm, hw, hs, num_layers);
-    return tl_masks_t<false>(mask_feature, w.kern, mask_logits, B, Q, Tc, frames_per_clip, h, w_, Cm, num_layers, R * 32, mstride, hs);
+    return by_dtype(dtype, [&](auto bf) {
+      tl_heads_small_t<bf()>(w.q, cls_logits, w.kern, packed_heads, B, Q, Tc, K1, Cm, hw, hs, num_layers);
+      return tl_masks_t<bf()>(mask_feature, w.kern, mask_logits, B, Q, Tc, frames_per_clip, h, w_, Cm, num_layers, R * 32, mstride, hs);
+    });
   };
   return run_cc_module(clip_query, packed_layers, num_layers, last_query, B, Q, Tc, rates, dtype, w, static_cast<hipStream_t>(stream), heads);
 }
@@ -1772,20 +1819,15 @@ int axvs_tl_heads_pack(const AxvsTLHeadParams* p, void* packed, int K1, int Cm, 
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
   if (K1 <= 0 || (Cm != 128 && Cm != 256)) return fail(AXVS_ERR_ARG, "mask feature channels must be 128 or 256 (got %d)", Cm);
-  if (int rcd = check_dtype(dtype)) return rcd;
   Carver c(packed);
   TLHeadsPacked h = carve_tl_heads(c, K1, Cm);
   hipStream_t st = static_cast<hipStream_t>(stream);
   PackDim n256{256, 256, 0, 0, 0}, ncm{Cm, Cm, 0, 0, 0};
-  if (dtype == AXVS_BF16) {
-    pack_w<kBF>(p->mask_embed_w[0], h.w0, n256, n256, st);
-    pack_w<kBF>(p->mask_embed_w[1], h.w1, n256, n256, st);
-    pack_w<kBF>(p->mask_embed_w[2], h.w2, ncm, n256, st);
-  } else {
-    pack_w<false>(p->mask_embed_w[0], h.w0, n256, n256, st);
-    pack_w<false>(p->mask_embed_w[1], h.w1, n256, n256, st);
-    pack_w<false>(p->mask_embed_w[2], h.w2, ncm, n256, st);
-  }
+  by_dtype(dtype, [&](auto bf) {
+    pack_w<bf()>(p->mask_embed_w[0], h.w0, n256, n256, st);
+    pack_w<bf()>(p->mask_embed_w[1], h.w1, n256, n256, st);
+    pack_w<bf()>(p->mask_embed_w[2], h.w2, ncm, n256, st);
+  });
   copy_f32(p->mask_embed_b[0], h.b0, 256, st);
   copy_f32(p->mask_embed_b[1], h.b1, 256, st);
   copy_f32(p->mask_embed_b[2], h.b2, Cm, st);
@@ -1800,12 +1842,7 @@ int axvs_tl_heads_pack(const AxvsTLHeadParams* p, void* packed, int K1, int Cm, 
 
 size_t axvs_tl_heads_workspace_bytes(int B, int Q, int Tc, int Cm) {
   Carver c(nullptr);
-  const long long R = (long long)B * Q * Tc;
-  c.take<float>((size_t)R * 256);
-  c.take<u16>((size_t)R * 256);
-  c.take<u16>((size_t)R * 256);
-  c.take<u16>((size_t)R * 256);
-  c.take<u16>((size_t)R * Cm);
+  carve_tl_heads_fwd_ws(c, (long long)B * Q * Tc, Cm);
   return c.off;
 }
 
@@ -1817,11 +1854,9 @@ int axvs_tl_heads_fwd(const float* clip_query, const float* mask_feature, float*
   if (B <= 0 || Q <= 0 || Tc <= 0 || frames_per_clip <= 0 || h <= 0 || w <= 0 || K1 <= 0) return fail(AXVS_ERR_ARG, "empty shape");
   if (Cm != 128 && Cm != 256) return fail(AXVS_ERR_ARG, "mask feature channels must be 128 or 256 (got %d)", Cm);
   if (Tc > 1024) return fail(AXVS_ERR_ARG, "more than 1024 clips are not supported by the class head");
-  if (workspace_bytes < axvs_tl_heads_workspace_bytes(B, Q, Tc, Cm)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ws(workspace_bytes, axvs_tl_heads_workspace_bytes(B, Q, Tc, Cm))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) return tl_heads_fwd_t<kBF>(clip_query, mask_feature, cls_logits, mask_logits, packed, B, Q, Tc, frames_per_clip, h, w, K1, Cm, workspace, st);
-  if (dtype == AXVS_F16) return tl_heads_fwd_t<false>(clip_query, mask_feature, cls_logits, mask_logits, packed, B, Q, Tc, frames_per_clip, h, w, K1, Cm, workspace, st);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) { return tl_heads_fwd_t<bf()>(clip_query, mask_feature, cls_logits, mask_logits, packed, B, Q, Tc, frames_per_clip, h, w, K1, Cm, workspace, st); });
 }
 
 size_t axvs_msda_packed_bytes(int C, int heads, int L, int P) {
@@ -1834,41 +1869,16 @@ int axvs_msda_pack(const AxvsMsdaParams* p, void* packed, int C, int heads, int 
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (L <= 0 || L > kMsdaMaxLevels || P <= 0 || L * P > 64) return fail(AXVS_ERR_ARG, "unsupported n_levels=%d / n_points=%d", L, P);
-  if (int rcd = check_dtype(dtype)) return rcd;
+  if (int rc = check_msda_pack(L, P)) return rc;
   Carver c(packed);
-  MsdaPacked m = carve_msda(c, C, heads, L, P);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int d = C / heads, Cp = heads * 32, mlp = heads * L * P;
-  PackDim plainC{C, C, 0, 0, 0}, headC{C, Cp, heads, d, 0}, off{2 * mlp, 2 * mlp, 0, 0, 0}, lg{mlp, mlp, 0, 0, 0};
-  if (dtype == AXVS_BF16) {
-    pack_w3<kBF>(p->value_proj_w, m.wv, headC, plainC, st);
-    pack_w3<kBF>(p->sampling_offsets_w, m.wq, off, plainC, st, 0, 3 * mlp);
-    pack_w3<kBF>(p->attention_weights_w, m.wq, lg, plainC, st, 2 * mlp, 3 * mlp);
-    pack_w3<kBF>(p->output_proj_w, m.wo, plainC, headC, st);
-  } else {
-    pack_w3<false>(p->value_proj_w, m.wv, headC, plainC, st);
-    pack_w3<false>(p->sampling_offsets_w, m.wq, off, plainC, st, 0, 3 * mlp);
-    pack_w3<false>(p->attention_weights_w, m.wq, lg, plainC, st, 2 * mlp, 3 * mlp);
-    pack_w3<false>(p->output_proj_w, m.wo, plainC, headC, st);
-  }
-  pack_b(p->value_proj_b, m.bv, headC, st);
-  copy_f32(p->sampling_offsets_b, m.bq, 2 * mlp, st);
-  copy_f32(p->attention_weights_b, m.bq + 2 * mlp, mlp, st);
-  copy_f32(p->output_proj_b, m.bo, C, st);
-  copy_f32(p->sampling_offsets_w, m.wq32, (size_t)2 * mlp * C, st);
-  copy_f32(p->attention_weights_w, m.wq32 + (size_t)2 * mlp * C, (size_t)mlp * C, st);
-  copy_f32(p->value_proj_w, m.wv32, (size_t)C * C, st);
-  copy_f32(p->output_proj_w, m.wo32, (size_t)C * C, st);
+  const MsdaPacked m = carve_msda(c, C, heads, L, P);
+  by_dtype(dtype, [&](auto bf) { pack_msda<bf()>(*p, m, C, heads, L, P, static_cast<hipStream_t>(stream)); });
   return last_launch_status();
 }
 
 size_t axvs_msda_workspace_bytes(int N, int Lq, int S, int C, int heads, int L, int P) {
   Carver c(nullptr);
-  const size_t Cp = (size_t)heads * 32;
-  c.take<u16>((size_t)N * S * Cp);
-  c.take<float>((size_t)N * Lq * 3 * heads * L * P);
-  c.take<u16>(2 * (size_t)N * Lq * Cp);
+  carve_msda_ws(c, N, Lq, S, heads, L, P);
   (void)C;
   return c.off;
 }
@@ -1880,18 +1890,14 @@ int axvs_msda_fwd(const float* query, const float* reference_points, int ref_dim
   if (!query || !reference_points || !input_flatten || !spatial_shapes || !out || !packed || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (N <= 0 || Lq <= 0 || S <= 0 || P <= 0) return fail(AXVS_ERR_ARG, "empty shape");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (ref_dim != 2 && ref_dim != 4) return fail(AXVS_ERR_ARG, "Last dim of reference_points must be 2 or 4, but get %d instead.", ref_dim);
-  if (L * P > 64) return fail(AXVS_ERR_ARG, "n_levels * n_points > 64 is not supported");
-  if ((long long)N * S > 2147483647LL / 64 || (long long)N * Lq > 2147483647LL / 64) return fail(AXVS_ERR_ARG, "too many tokens for 32-bit row indices");
+  if (int rc = check_msda_points(ref_dim, L, P)) return rc;
   MsdaLevels lv;
-  if (int rc = msda_levels(spatial_shapes, L, S, &lv)) return rc;
-  if (workspace_bytes < axvs_msda_workspace_bytes(N, Lq, S, C, heads, L, P)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_msda_shapes(N, Lq, S, spatial_shapes, L, &lv)) return rc;
+  if (int rc = check_ws(workspace_bytes, axvs_msda_workspace_bytes(N, Lq, S, C, heads, L, P))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Carver pc(const_cast<void*>(packed));
   const MsdaPacked mp = carve_msda(pc, C, heads, L, P);
-  if (dtype == AXVS_BF16) return msda_fwd_t<kBF>(query, reference_points, ref_dim, input_flatten, padding_mask, lv, out, mp, N, Lq, S, C, heads, P, workspace, st);
-  if (dtype == AXVS_F16) return msda_fwd_t<false>(query, reference_points, ref_dim, input_flatten, padding_mask, lv, out, mp, N, Lq, S, C, heads, P, workspace, st);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) { return msda_fwd_t<bf()>(query, reference_points, ref_dim, input_flatten, padding_mask, lv, out, mp, N, Lq, S, C, heads, P, workspace, st); });
 }
 
 // ---- the two halves of the module for callers that work on the sampled rows before output_proj (Tube-Link plugin) ----
@@ -1903,18 +1909,16 @@ int axvs_msda_sample_fwd(const float* query, const float* query_pos, const float
   if (N <= 0 || Lq <= 0 || S <= 0 || P <= 0) return fail(AXVS_ERR_ARG, "empty shape");
   if (int rc = check_cfg(C, heads)) return rc;
   if ((C / heads) % 8) return fail(AXVS_ERR_ARG, "head_dim=%d must be a multiple of 8", C / heads);
-  if (ref_dim != 2 && ref_dim != 4) return fail(AXVS_ERR_ARG, "Last dim of reference_points must be 2 or 4, but get %d instead.", ref_dim);
-  if (L * P > 64) return fail(AXVS_ERR_ARG, "n_levels * n_points > 64 is not supported");
-  if ((long long)N * S > 2147483647LL / 64 || (long long)N * Lq > 2147483647LL / 64) return fail(AXVS_ERR_ARG, "too many tokens for 32-bit row indices");
+  if (int rc = check_msda_points(ref_dim, L, P)) return rc;
   MsdaLevels lv;
-  if (int rc = msda_levels(spatial_shapes, L, S, &lv)) return rc;
-  if (workspace_bytes < axvs_msda_workspace_bytes(N, Lq, S, C, heads, L, P)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_msda_shapes(N, Lq, S, spatial_shapes, L, &lv)) return rc;
+  if (int rc = check_ws(workspace_bytes, axvs_msda_workspace_bytes(N, Lq, S, C, heads, L, P))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Carver pc(const_cast<void*>(packed));
   const MsdaPacked mp = carve_msda(pc, C, heads, L, P);
-  if (dtype == AXVS_BF16) return msda_fwd_t<kBF>(query, reference_points, ref_dim, value, padding_mask, lv, sampled, mp, N, Lq, S, C, heads, P, workspace, st, query_pos, nullptr, 1);
-  if (dtype == AXVS_F16) return msda_fwd_t<false>(query, reference_points, ref_dim, value, padding_mask, lv, sampled, mp, N, Lq, S, C, heads, P, workspace, st, query_pos, nullptr, 1);
-  return fail(AXVS_ERR_ARG, "unknown dtype %d", dtype);
+  return by_dtype(dtype, [&](auto bf) {
+    return msda_fwd_t<bf()>(query, reference_points, ref_dim, value, padding_mask, lv, sampled, mp, N, Lq, S, C, heads, P, workspace, st, query_pos, nullptr, 1);
+  });
 }
 
 int axvs_msda_output_proj_fwd(const float* x, const float* identity, float* out, const void* packed, long long rows, int C, int heads,
@@ -1924,7 +1928,6 @@ int axvs_msda_output_proj_fwd(const float* x, const float* identity, float* out,
   if (rows <= 0 || rows > 2147483647LL / 64) return fail(AXVS_ERR_ARG, "bad row count");
   if (int rc = check_cfg(C, heads)) return rc;
   if (C / heads != 32) return fail(AXVS_ERR_ARG, "axvs_msda_output_proj_fwd needs head_dim 32 (got %d)", C / heads);
-  if (int rcd = check_dtype(dtype)) return rcd;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Carver pc(const_cast<void*>(packed));
   const MsdaPacked mp = carve_msda(pc, C, heads, L, P);
@@ -1936,8 +1939,7 @@ int axvs_msda_output_proj_fwd(const float* x, const float* identity, float* out,
     if (int rc = launch_nt128(x, nullptr, mp.wo32, out, rows, C, C, e128, st, true)) return rc;
     return last_launch_status();
   }
-  if (dtype == AXVS_BF16) launch_gemm<kBF>(ALoadRowsF32Split3<kBF>{x, (int)rows, C}, mp.wo, e, (int)rows, C, 3 * C, st);
-  else launch_gemm<false>(ALoadRowsF32Split3<false>{x, (int)rows, C}, mp.wo, e, (int)rows, C, 3 * C, st);
+  by_dtype(dtype, [&](auto bf) { launch_gemm<bf()>(ALoadRowsF32Split3<bf()>{x, (int)rows, C}, mp.wo, e, (int)rows, C, 3 * C, st); });
   return last_launch_status();
 }
 
@@ -1952,25 +1954,23 @@ size_t axvs_msda_layer_packed_bytes(int C, int heads, int L, int P, int d_ffn) {
 int axvs_msda_layer_pack(const AxvsMsdaLayerParams* p, void* packed, int C, int heads, int L, int P, int d_ffn, int dtype, void* stream) {
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
-  if (int rc = axvs_msda_pack(&p->self_attn, packed, C, heads, L, P, dtype, stream)) return rc;
+  if (int rc = check_ffn(d_ffn)) return rc;
+  if (int rc = check_cfg(C, heads)) return rc;
+  if (int rc = check_msda_pack(L, P)) return rc;
   Carver c(packed);
-  carve_msda(c, C, heads, L, P);
-  LayerPacked l = carve_ffn(c, C, d_ffn);
+  const MsdaPacked m = carve_msda(c, C, heads, L, P);
+  const LayerPacked l = carve_ffn(c, C, d_ffn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) pack_ffn<kBF>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
-  else pack_ffn<false>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
+  by_dtype(dtype, [&](auto bf) {
+    pack_msda<bf()>(p->self_attn, m, C, heads, L, P, st);
+    pack_ffn<bf()>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
+  });
   return last_launch_status();
 }
 
 size_t axvs_msda_layer_workspace_bytes(int N, int S, int C, int heads, int L, int P, int d_ffn) {
   Carver c(nullptr);
-  c.take<char>(axvs_msda_workspace_bytes(N, S, S, C, heads, L, P));
-  const size_t M = (size_t)N * S;
-  c.take<float>(M * C);            // x = src + attention
-  c.take<float>(M * C);            // generic FFN path scratch
-  c.take<u16>(M * C);
-  c.take<u16>(M * d_ffn);
+  carve_msda_layer_ws(c, N, S, C, heads, L, P, d_ffn);
   return c.off;
 }
 
@@ -1981,32 +1981,23 @@ int axvs_msda_layer_fwd(const float* src, const float* pos, const float* referen
   if (!src || !reference_points || !spatial_shapes || !out || !packed || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (N <= 0 || S <= 0 || P <= 0) return fail(AXVS_ERR_ARG, "empty shape");
   if (int rc = check_cfg(C, heads)) return rc;
-  if (ref_dim != 2 && ref_dim != 4) return fail(AXVS_ERR_ARG, "Last dim of reference_points must be 2 or 4, but get %d instead.", ref_dim);
-  if (L * P > 64) return fail(AXVS_ERR_ARG, "n_levels * n_points > 64 is not supported");
+  if (int rc = check_msda_points(ref_dim, L, P)) return rc;
   if (out == src) return fail(AXVS_ERR_ARG, "out must not alias src");
-  if ((long long)N * S > 2147483647LL / 64) return fail(AXVS_ERR_ARG, "too many tokens for 32-bit row indices");
   MsdaLevels lv;
-  if (int rc = msda_levels(spatial_shapes, L, S, &lv)) return rc;
-  if (workspace_bytes < axvs_msda_layer_workspace_bytes(N, S, C, heads, L, P, d_ffn)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
-  if (int rcd = check_dtype(dtype)) return rcd;
+  if (int rc = check_msda_shapes(N, S, S, spatial_shapes, L, &lv)) return rc;
+  if (int rc = check_ws(workspace_bytes, axvs_msda_layer_workspace_bytes(N, S, C, heads, L, P, d_ffn))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Carver pc(const_cast<void*>(packed));
   const MsdaPacked mp = carve_msda(pc, C, heads, L, P);
   const LayerPacked lp = carve_ffn(pc, C, d_ffn);
   Carver wc(workspace);
-  void* mws = wc.take<char>(axvs_msda_workspace_bytes(N, S, S, C, heads, L, P));
+  const MsdaLayerWs w = carve_msda_layer_ws(wc, N, S, C, heads, L, P, d_ffn);
   const long long M = (long long)N * S;
-  float* x = wc.take<float>((size_t)M * C);
-  float* tmp = wc.take<float>((size_t)M * C);
-  u16* y16 = wc.take<u16>((size_t)M * C);
-  u16* h16 = wc.take<u16>((size_t)M * d_ffn);
-  int rc = dtype == AXVS_BF16
-               ? msda_fwd_t<kBF>(src, reference_points, ref_dim, src, padding_mask, lv, x, mp, N, S, S, C, heads, P, mws, st, pos, src)
-               : msda_fwd_t<false>(src, reference_points, ref_dim, src, padding_mask, lv, x, mp, N, S, S, C, heads, P, mws, st, pos, src);
-  if (rc != AXVS_OK) return rc;
-  rc = dtype == AXVS_BF16 ? run_ffn<kBF>(x, out, lp, M, C, heads, d_ffn, tmp, y16, h16, st)
-                          : run_ffn<false>(x, out, lp, M, C, heads, d_ffn, tmp, y16, h16, st);
-  return rc != AXVS_OK ? rc : last_launch_status();
+  return by_dtype(dtype, [&](auto bf) {
+    if (int rc = msda_fwd_t<bf()>(src, reference_points, ref_dim, src, padding_mask, lv, w.f.x, mp, N, S, S, C, heads, P, w.mws, st, pos, src)) return rc;
+    int rc = run_ffn<bf()>(w.f.x, out, lp, M, C, heads, d_ffn, w.f.tmp, w.f.y16, w.f.h16, st);
+    return rc != AXVS_OK ? rc : last_launch_status();
+  });
 }
 
 int axvs_msda_core_fwd(const float* value, const int* spatial_shapes, const float* sampling_loc, const float* attn_weight, float* out,
@@ -2048,11 +2039,44 @@ int axvs_msda_core_bwd(const float* value, const int* spatial_shapes, const floa
 }
 
 // ---- pixel-decoder glue ----
+namespace {
+struct ConvGnPacked {
+  u16* w;                // split precision (hi | lo | hi) along K, rows in groups of 16
+  float *b, *g, *be;     // conv bias, GroupNorm weight / bias
+  float* wf;             // the fp32 weight as it is: the 128 x 128 split-precision GEMM splits its operands itself (token rows in, many rows)
+};
+ConvGnPacked carve_conv_gn(Carver& c, int Cin, int Cout) {
+  ConvGnPacked p;
+  p.w = c.take<u16>(3 * (size_t)Cin * ((Cout + 15) & ~15));
+  p.b = c.take<float>(Cout);
+  p.g = c.take<float>(Cout);
+  p.be = c.take<float>(Cout);
+  p.wf = c.take<float>((size_t)Cout * Cin);
+  return p;
+}
+struct ConvGnWs {
+  float *y, *stats, *partial, *tok;
+};
+// Callers size this workspace with max(Cin, Cout) in the Cout slot; the forward carves it with the real Cout.  The size is that of
+// y | tok | stats | partial with an [M][Cout] block each for y and tok, so that the token-row copy of an NCHW input ([M][Cin]) fits a
+// workspace sized that way (without the room the NCHW loader runs).  tok is the LAST block and ends where the workspace ends: it
+// starts M Cout floats before the end, NOT on a 256-byte boundary.  Whatever the caller's buffer holds behind tok's [M][Cin] rows
+// takes the split-K partials (axvs_conv1x1_gn_fwd).  stats is unused (the apply kernel sums the partials itself) and kept for the size.
+ConvGnWs carve_conv_gn_ws(Carver& c, int N, int HW, int Cout, int groups) {
+  const size_t ybytes = (size_t)N * HW * Cout * sizeof(float);
+  ConvGnWs w;
+  w.y = c.take<float>((size_t)N * HW * Cout);
+  w.stats = c.take<float>((size_t)N * groups * 2);
+  w.partial = c.take<float>((size_t)N * ((HW + 63) / 64) * groups * 2);
+  c.off += align_up(ybytes) - ybytes;
+  w.tok = c.take<float>((size_t)N * HW * Cout);
+  return w;
+}
+}  // namespace
+
 size_t axvs_conv1x1_gn_packed_bytes(int Cin, int Cout) {
   Carver c(nullptr);
-  c.take<u16>(3 * (size_t)Cin * ((Cout + 15) & ~15));
-  c.take<float>(Cout); c.take<float>(Cout); c.take<float>(Cout);
-  c.take<float>((size_t)Cout * Cin);      // the fp32 weight as it is: the 128 x 128 split-precision GEMM splits its operands itself (token rows in, many rows)
+  carve_conv_gn(c, Cin, Cout);
   return c.off;
 }
 
@@ -2060,28 +2084,21 @@ int axvs_conv1x1_gn_pack(const AxvsConvGnParams* p, void* packed, int Cin, int C
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
   if (Cin <= 0 || Cin % 32 || Cout <= 0 || Cout % 4) return fail(AXVS_ERR_ARG, "Cin=%d must be a multiple of 32, Cout=%d of 4", Cin, Cout);
-  if (int rcd = check_dtype(dtype)) return rcd;
   Carver c(packed);
-  u16* w = c.take<u16>(3 * (size_t)Cin * ((Cout + 15) & ~15));
-  float* b = c.take<float>(Cout); float* g = c.take<float>(Cout); float* be = c.take<float>(Cout);
+  const ConvGnPacked k = carve_conv_gn(c, Cin, Cout);
   hipStream_t st = static_cast<hipStream_t>(stream);
   PackDim nd{Cout, Cout, 0, 0, 0}, kd{Cin, Cin, 0, 0, 0};
-  if (dtype == AXVS_BF16) pack_w3<kBF>(p->conv_w, w, nd, kd, st);
-  else pack_w3<false>(p->conv_w, w, nd, kd, st);
-  copy_f32(p->conv_b, b, Cout, st);
-  copy_f32(p->gn_w, g, Cout, st);
-  copy_f32(p->gn_b, be, Cout, st);
-  float* wf = c.take<float>((size_t)Cout * Cin);
-  if (hipMemcpyAsync(wf, p->conv_w, (size_t)Cout * Cin * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "copy failed");
+  by_dtype(dtype, [&](auto bf) { pack_w3<bf()>(p->conv_w, k.w, nd, kd, st); });
+  copy_f32(p->conv_b, k.b, Cout, st);
+  copy_f32(p->gn_w, k.g, Cout, st);
+  copy_f32(p->gn_b, k.be, Cout, st);
+  if (hipMemcpyAsync(k.wf, p->conv_w, (size_t)Cout * Cin * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "copy failed");
   return last_launch_status();
 }
 
 size_t axvs_conv1x1_gn_workspace_bytes(int N, int HW, int Cout, int groups) {
   Carver c(nullptr);
-  c.take<float>((size_t)N * HW * Cout);
-  c.take<float>((size_t)N * HW * Cout);      // token-row copy of an NCHW input (callers size with max(Cin, Cout); without the room the NCHW loader runs)
-  c.take<float>((size_t)N * groups * 2);
-  c.take<float>((size_t)N * ((HW + 63) / 64) * groups * 2);
+  carve_conv_gn_ws(c, N, HW, Cout, groups);
   return c.off;
 }
 
@@ -2094,23 +2111,21 @@ int axvs_conv1x1_gn_fwd(const float* x, int in_layout, long long in_batch_stride
   if (Cin % 32 || Cout % 4 || groups <= 0 || Cout % groups || groups > 256) return fail(AXVS_ERR_ARG, "unsupported channels/groups %d/%d/%d", Cin, Cout, groups);
   if ((in_layout != 0 && in_layout != 1) || (out_layout != 0 && out_layout != 1)) return fail(AXVS_ERR_ARG, "layout must be 0 (NCHW) or 1 (token rows)");
   if ((long long)N * HW > 2147483647LL / 64) return fail(AXVS_ERR_ARG, "too many tokens for 32-bit row indices");
-  if (workspace_bytes < axvs_conv1x1_gn_workspace_bytes(N, HW, Cout, groups)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
-  if (int rcd = check_dtype(dtype)) return rcd;
+  if (int rc = check_ws(workspace_bytes, axvs_conv1x1_gn_workspace_bytes(N, HW, Cout, groups))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Carver pc(const_cast<void*>(packed));
-  const u16* w = pc.take<u16>(3 * (size_t)Cin * ((Cout + 15) & ~15));
-  const float* b = pc.take<float>(Cout); const float* g = pc.take<float>(Cout); const float* be = pc.take<float>(Cout);
-  const float* wf = pc.take<float>((size_t)Cout * Cin);
+  const ConvGnPacked k = carve_conv_gn(pc, Cin, Cout);
   Carver wc(workspace);
   const long long M = (long long)N * HW;
-  float* y = wc.take<float>((size_t)M * Cout);
-  float* stats = wc.take<float>((size_t)N * groups * 2);
+  const ConvGnWs cw = carve_conv_gn_ws(wc, N, HW, Cout, groups);
+  float *const y = cw.y, *const tok = cw.tok;
+  // bytes the token-row copy of an NCHW input needs from the start of the workspace (its [M][Cin] rows may reach past the size query's end)
+  const size_t tok_end = (size_t)(reinterpret_cast<char*>(tok) - static_cast<char*>(workspace)) + (size_t)M * Cin * sizeof(float);
   const int nblk = (HW + 63) / 64;
-  float* partial = wc.take<float>((size_t)N * nblk * groups * 2);
   if (Cout > 8192) return fail(AXVS_ERR_ARG, "Cout=%d too large for the GroupNorm statistics kernel", Cout);
   g_prof_next = 0;
   mark(st, "begin");
-  const EpiRowsF32 ey{y, nullptr, b, identity_map(M), Cout, 1.f};
+  const EpiRowsF32 ey{y, nullptr, k.b, identity_map(M), Cout, 1.f};
   // token rows in, many of them (the output projections of the large pyramid levels: [32786 x 512 x 256] at the shipped VIPSeg setting): the 128 x 128
   // three-piece kernel of the deformable attention's projections (fp32-grade like the split3 GEMM below; 143 against 60 - 115 TFLOP/s), one launch per
   // frame when the frames are rows of a larger buffer
@@ -2118,58 +2133,52 @@ int axvs_conv1x1_gn_fwd(const float* x, int in_layout, long long in_batch_stride
   const bool one = in_batch_stride == (long long)HW * in_ld;
   // split-K factor of the NCHW path: few 128 x 128 tiles and a long reduction -> enough workgroups for one round of the chip (at most 8, at least 4 k-steps each)
   int zs = 1;
-  if (in_layout == 0 && g_conv_nt128_splitk && Cin >= g_conv_nt128_splitk) {
+  if (in_layout == 0 && kConvNt128SplitK && Cin >= kConvNt128SplitK) {
     const long long tiles = ((M + 127) / 128) * ((Cout + 127) / 128);
-    if (tiles < g_conv_nt128_nchw && tiles >= 8) {
+    if (tiles < kConvNt128Nchw && tiles >= 8) {
       zs = (int)std::min<long long>(8, std::max<long long>(1, 256 / tiles));
       zs = std::min(zs, Cin / 32 / 4);
       // the partials live behind the token-row copy: as many as the caller's workspace has room for
-      const size_t off_tok = axvs_conv1x1_gn_workspace_bytes(N, HW, Cout, groups) - (size_t)M * Cout * sizeof(float), tok_end = off_tok + (size_t)M * Cin * sizeof(float);
       const long long room = workspace_bytes > tok_end ? (long long)((workspace_bytes - tok_end) / ((size_t)M * Cout * sizeof(float))) : 0;
       zs = (int)std::min<long long>(zs, room);
       if (zs < 2) zs = 1;
     }
   }
-  if (in_layout == 1 && g_msda_gemm && g_conv_nt128 && Cin % 4 == 0 && Cout % 4 == 0 && in_ld % 4 == 0 && in_batch_stride % 4 == 0 &&
-      (((one ? M : (long long)HW) + 127) / 128) * ((Cout + 127) / 128) >= g_conv_nt128 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-    const tr::GemmEpi e{b, 1.f, 0, tr::Drop{0, 0, 0, 1.f}, 0.f};
+  if (in_layout == 1 && kMsdaGemm && kConvNt128 && Cin % 4 == 0 && Cout % 4 == 0 && in_ld % 4 == 0 && in_batch_stride % 4 == 0 &&
+      (((one ? M : (long long)HW) + 127) / 128) * ((Cout + 127) / 128) >= kConvNt128 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+    const tr::GemmEpi e{k.b, 1.f, 0, tr::Drop{0, 0, 0, 1.f}, 0.f};
     for (int n = 0; n < (one ? 1 : N); ++n)
-      if (int rc = launch_nt128(x + (size_t)n * in_batch_stride, nullptr, wf, y + (size_t)n * HW * Cout, one ? M : HW, Cout, Cin, e, st, g_conv_nt128_exact != 0, in_ld)) return rc;
-  } else if (in_layout == 0 && g_msda_gemm && g_conv_nt128 && Cin % 4 == 0 && Cout % 4 == 0 &&
-             (((M + 127) / 128) * ((Cout + 127) / 128) >= g_conv_nt128_nchw || zs > 1) && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-
-             workspace_bytes >= axvs_conv1x1_gn_workspace_bytes(N, HW, Cout, groups) - (size_t)M * Cout * sizeof(float) + (size_t)M * Cin * sizeof(float)) {
+      if (int rc = launch_nt128(x + (size_t)n * in_batch_stride, nullptr, k.wf, y + (size_t)n * HW * Cout, one ? M : HW, Cout, Cin, e, st, kConvNt128Exact != 0, in_ld)) return rc;
+  } else if (in_layout == 0 && kMsdaGemm && kConvNt128 && Cin % 4 == 0 && Cout % 4 == 0 &&
+             (((M + 127) / 128) * ((Cout + 127) / 128) >= kConvNt128Nchw || zs > 1) && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
+             workspace_bytes >= tok_end) {
     // NCHW in, many rows: transposed to token rows once (64 x 64 tiles through LDS), then the same 128 x 128 kernel in ONE launch over all frames
-    float* tok = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + axvs_conv1x1_gn_workspace_bytes(N, HW, Cout, groups) - (size_t)M * Cout * sizeof(float));
     hipLaunchKernelGGL(nchw_to_tokens_kernel, dim3((unsigned)((HW + 63) / 64), (unsigned)((Cin + 63) / 64), N), dim3(256), 0, st, x, tok, Cin, HW);
     if (zs > 1) {      // few row tiles, long reduction (the coarsest level: [2150 x 256 x 2048]): split-K partials behind the token rows, added in z order + bias
       float* part = tok + (size_t)M * Cin;
       const tr::GemmEpi e{nullptr, 1.f, 0, tr::Drop{0, 0, 0, 1.f}, 0.f};
-      if (int rc = launch_nt128(tok, nullptr, wf, part, M, Cout, Cin, e, st, g_conv_nt128_exact != 0, 0, zs)) return rc;
+      if (int rc = launch_nt128(tok, nullptr, k.wf, part, M, Cout, Cin, e, st, kConvNt128Exact != 0, 0, zs)) return rc;
       const long long tot4 = M * Cout / 4;
-      hipLaunchKernelGGL(splitk_sum_bias_kernel, dim3((unsigned)((tot4 + 255) / 256)), dim3(256), 0, st, (const float*)part, y, zs, M * Cout, b, Cout, tot4);
+      hipLaunchKernelGGL(splitk_sum_bias_kernel, dim3((unsigned)((tot4 + 255) / 256)), dim3(256), 0, st, (const float*)part, y, zs, M * Cout, k.b, Cout, tot4);
     } else {
-      const tr::GemmEpi e{b, 1.f, 0, tr::Drop{0, 0, 0, 1.f}, 0.f};
-      if (int rc = launch_nt128(tok, nullptr, wf, y, M, Cout, Cin, e, st, g_conv_nt128_exact != 0)) return rc;
+      const tr::GemmEpi e{k.b, 1.f, 0, tr::Drop{0, 0, 0, 1.f}, 0.f};
+      if (int rc = launch_nt128(tok, nullptr, k.wf, y, M, Cout, Cin, e, st, kConvNt128Exact != 0)) return rc;
     }
-  } else
-  if (dtype == AXVS_BF16) {
-    if (in_layout == 0) launch_gemm<kBF>(ALoadNCHWSplit3<kBF>{x, (int)M, Cin, HW}, w, ey, (int)M, Cout, 3 * Cin, st);
-    else launch_gemm<kBF>(ALoadTokensSplit3<kBF>{x, (int)M, Cin, HW, in_batch_stride, in_ld}, w, ey, (int)M, Cout, 3 * Cin, st);
   } else {
-    if (in_layout == 0) launch_gemm<false>(ALoadNCHWSplit3<false>{x, (int)M, Cin, HW}, w, ey, (int)M, Cout, 3 * Cin, st);
-    else launch_gemm<false>(ALoadTokensSplit3<false>{x, (int)M, Cin, HW, in_batch_stride, in_ld}, w, ey, (int)M, Cout, 3 * Cin, st);
+    by_dtype(dtype, [&](auto bf) {
+      if (in_layout == 0) launch_gemm<bf()>(ALoadNCHWSplit3<bf()>{x, (int)M, Cin, HW}, k.w, ey, (int)M, Cout, 3 * Cin, st);
+      else launch_gemm<bf()>(ALoadTokensSplit3<bf()>{x, (int)M, Cin, HW, in_batch_stride, in_ld}, k.w, ey, (int)M, Cout, 3 * Cin, st);
+    });
   }
   mark(st, "glue.conv1x1");
   {
     const int n4 = Cout / 4, lanes = n4 < 256 ? n4 : 256, rg = 256 / lanes;
-    hipLaunchKernelGGL(gn_stats_kernel, dim3((unsigned)nblk, N), dim3(256), 2 * (size_t)rg * Cout * sizeof(float), st, y, partial, HW, Cout, groups);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3((unsigned)nblk, N), dim3(256), 2 * (size_t)rg * Cout * sizeof(float), st, y, cw.partial, HW, Cout, groups);
   }
   // (the per-group sums of the blocks' partials are formed by the apply kernel itself: no launch of their own)
-  (void)stats;
   const dim3 ag((unsigned)((HW + 63) / 64), (unsigned)((Cout + 63) / 64), N);
-  if (out_layout == 0) hipLaunchKernelGGL((gn_apply_kernel<true>), ag, dim3(256), 0, st, y, (const float*)partial, nblk, g, be, out, HW, Cout, groups, eps, (long long)0, (long long)Cout * HW);
-  else hipLaunchKernelGGL((gn_apply_kernel<false>), ag, dim3(256), 0, st, y, (const float*)partial, nblk, g, be, out, HW, Cout, groups, eps, out_ld, out_batch_stride);
+  if (out_layout == 0) hipLaunchKernelGGL((gn_apply_kernel<true>), ag, dim3(256), 0, st, y, (const float*)cw.partial, nblk, k.g, k.be, out, HW, Cout, groups, eps, (long long)0, (long long)Cout * HW);
+  else hipLaunchKernelGGL((gn_apply_kernel<false>), ag, dim3(256), 0, st, y, (const float*)cw.partial, nblk, k.g, k.be, out, HW, Cout, groups, eps, out_ld, out_batch_stride);
   mark(st, "glue.group_norm");
   return last_launch_status();
 }
@@ -2223,7 +2232,7 @@ int axvs_match_embds(const float* tgt_embds, const float* cur_embds, long long* 
                      size_t workspace_bytes, void* stream) {
   if (!tgt_embds || !cur_embds || !indices || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (Q <= 0 || Q > kLsapMax || C <= 0) return fail(AXVS_ERR_ARG, "Q=%d must be in 1..%d", Q, kLsapMax);
-  if (workspace_bytes < axvs_match_embds_workspace_bytes(Q, C)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ws(workspace_bytes, axvs_match_embds_workspace_bytes(Q, C))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* cost = static_cast<float*>(workspace);
   float* nrm = cost + (size_t)Q * Q;
@@ -2243,7 +2252,7 @@ int axvs_match_clips(const float* mask_embeddings, long long* indices, int V, in
                      size_t workspace_bytes, void* stream) {
   if (!mask_embeddings || !indices || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (V <= 0 || Tc <= 1 || C <= 0 || Q <= 0 || Q > kLsapMax) return fail(AXVS_ERR_ARG, "need V >= 1, Tc >= 2, Q in 1..%d", kLsapMax);
-  if (workspace_bytes < axvs_match_clips_workspace_bytes(V, Tc, Q, C)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ws(workspace_bytes, axvs_match_clips_workspace_bytes(V, Tc, Q, C))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* nrm = static_cast<float*>(workspace);
   float* cost = nrm + (size_t)V * Tc * Q * C;
@@ -2298,12 +2307,11 @@ int axvs_ffn_pack(const AxvsFfnParams* p, void* packed, int C, int d_ffn, int dt
   if (int rcd = check_dtype(dtype)) return rcd;
   if (!p || !packed) return fail(AXVS_ERR_ARG, "null pointer");
   if (int rc = check_cfg(C, C / 32 > 0 ? C / 32 : 1)) return rc;
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
+  if (int rc = check_ffn(d_ffn)) return rc;
   Carver c(packed);
   LayerPacked l = carve_ffn(c, C, d_ffn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == AXVS_BF16) pack_ffn<kBF>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
-  else pack_ffn<false>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st);
+  by_dtype(dtype, [&](auto bf) { pack_ffn<bf()>(p->norm1_w, p->norm1_b, p->linear1_w, p->linear1_b, p->linear2_w, p->linear2_b, p->norm2_w, p->norm2_b, l, C, d_ffn, st); });
   return last_launch_status();
 }
 
@@ -2314,22 +2322,10 @@ int axvs_ffn_packed_fwd(const float* x, float* out, const void* packed_ffn, long
   if (M <= 0) return fail(AXVS_ERR_ARG, "empty input");
   const int heads = C / 32 > 0 ? C / 32 : 1;      // head_dim 32: the fused FFN tier's configuration at C = 256 (heads only select the tier here)
   if (int rc = check_cfg(C, heads)) return rc;
-  if (d_ffn <= 0 || d_ffn % 32 != 0) return fail(AXVS_ERR_ARG, "d_ffn=%d must be a positive multiple of 32", d_ffn);
-  if (workspace_bytes < axvs_ffn_workspace_bytes(M, C, d_ffn)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = check_ffn(d_ffn)) return rc;
+  if (int rc = check_ws(workspace_bytes, axvs_ffn_workspace_bytes(M, C, d_ffn))) return rc;
   Carver pc(const_cast<void*>(packed_ffn));
-  LayerPacked p = carve_ffn(pc, C, d_ffn);
-  Carver wc(workspace);
-  float* xin = wc.take<float>((size_t)M * C);
-  float* tmp = wc.take<float>((size_t)M * C);
-  u16* y16 = wc.take<u16>((size_t)M * C);
-  u16* h16 = wc.take<u16>((size_t)M * d_ffn);
-  if (hipMemcpyAsync(xin, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return fail(AXVS_ERR_LAUNCH, "copy failed");
-  g_prof_next = 0;
-  int rc = dtype == AXVS_BF16 ? run_ffn<kBF>(xin, out, p, M, C, heads, d_ffn, tmp, y16, h16, st)
-                              : run_ffn<false>(xin, out, p, M, C, heads, d_ffn, tmp, y16, h16, st);
-  return rc != AXVS_OK ? rc : last_launch_status();
+  return ffn_fwd_checked(x, out, carve_ffn(pc, C, d_ffn), M, C, heads, d_ffn, dtype, workspace, static_cast<hipStream_t>(stream));
 }
 
 namespace {
@@ -2393,15 +2389,11 @@ int axvs_fpn_level_pack(const AxvsFpnLevelParams* p, void* packed, int Cin, int 
   hipStream_t st = static_cast<hipStream_t>(stream);
   PackDim nd{C, C, 0, 0, 0}, kd{Cin, Cin, 0, 0, 0}, md{Cm, Cm, 0, 0, 0}, cd{C, C, 0, 0, 0};
   const long long w3 = 9LL * C * C;
-  if (dtype == AXVS_BF16) {
-    pack_w3<kBF>(p->lateral_w, f.lat_w3, nd, kd, st);
-    hipLaunchKernelGGL((fpn_pack3x3_kernel<kBF>), dim3((unsigned)((w3 + 255) / 256)), dim3(256), 0, st, p->output_w, f.out_w, C, C);
-    if (Cm > 0) pack_w<kBF>(p->mask_w, f.mask_w, md, cd, st);
-  } else {
-    pack_w3<false>(p->lateral_w, f.lat_w3, nd, kd, st);
-    hipLaunchKernelGGL((fpn_pack3x3_kernel<false>), dim3((unsigned)((w3 + 255) / 256)), dim3(256), 0, st, p->output_w, f.out_w, C, C);
-    if (Cm > 0) pack_w<false>(p->mask_w, f.mask_w, md, cd, st);
-  }
+  by_dtype(dtype, [&](auto bf) {
+    pack_w3<bf()>(p->lateral_w, f.lat_w3, nd, kd, st);
+    hipLaunchKernelGGL((fpn_pack3x3_kernel<bf()>), dim3((unsigned)((w3 + 255) / 256)), dim3(256), 0, st, p->output_w, f.out_w, C, C);
+    if (Cm > 0) pack_w<bf()>(p->mask_w, f.mask_w, md, cd, st);
+  });
   if (hipMemcpyAsync(f.lat_wf, p->lateral_w, (size_t)C * Cin * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     return fail(AXVS_ERR_LAUNCH, "copy failed");
   copy_f32(p->lateral_gn_w, f.lat_g, C, st);
@@ -2434,7 +2426,7 @@ int axvs_fpn_level_fwd(const float* x, const float* up, long long up_batch_strid
       (reinterpret_cast<uintptr_t>(up) & 15))
     return fail(AXVS_ERR_ARG, "up: row stride %lld / batch stride %lld must be multiples of 4 floats covering [Hu*Wu, C] rows, pointer 16-byte aligned",
                 up_ld, up_batch_stride);
-  if (workspace_bytes < axvs_fpn_level_workspace_bytes(N, H, W, Cin, C, groups)) return fail(AXVS_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_ws(workspace_bytes, axvs_fpn_level_workspace_bytes(N, H, W, Cin, C, groups))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Carver pc(const_cast<void*>(packed));
   const FpnPacked f = carve_fpn(pc, Cin, C, Cm);
@@ -2443,18 +2435,16 @@ int axvs_fpn_level_fwd(const float* x, const float* up, long long up_batch_strid
   const int HW = H * W;
   const long long M = (long long)N * HW;
   const int nblk = (HW + 63) / 64, ntx = (W + kFpnTW - 1) / kFpnTW, tiles = ntx * ((H + kFpnTH - 1) / kFpnTH);
-  const bool bf = dtype == AXVS_BF16;
   g_prof_next = 0;
   mark(st, "begin");
   // 1. lateral 1x1 conv (no bias: use_bias = norm_cfg is None, TL:136) -> raw fp32 rows; the GEMMs of axvs_conv1x1_gn_fwd
-  if (g_msda_gemm && g_conv_nt128 && ((M + 127) / 128) * ((C + 127) / 128) >= g_conv_nt128_nchw) {
+  if (kMsdaGemm && kConvNt128 && ((M + 127) / 128) * ((C + 127) / 128) >= kConvNt128Nchw) {
     hipLaunchKernelGGL(nchw_to_tokens_kernel, dim3((unsigned)((HW + 63) / 64), (unsigned)((Cin + 63) / 64), N), dim3(256), 0, st, x, w.tok, Cin, HW);
     const tr::GemmEpi e{nullptr, 1.f, 0, tr::Drop{0, 0, 0, 1.f}, 0.f};
-    if (int rc = launch_nt128(w.tok, nullptr, f.lat_wf, w.lat, M, C, Cin, e, st, g_conv_nt128_exact != 0)) return rc;
+    if (int rc = launch_nt128(w.tok, nullptr, f.lat_wf, w.lat, M, C, Cin, e, st, kConvNt128Exact != 0)) return rc;
   } else {
     const EpiRowsF32 ey{w.lat, nullptr, nullptr, identity_map(M), C, 1.f};
-    if (bf) launch_gemm<kBF>(ALoadNCHWSplit3<kBF>{x, (int)M, Cin, HW}, f.lat_w3, ey, (int)M, C, 3 * Cin, st);
-    else launch_gemm<false>(ALoadNCHWSplit3<false>{x, (int)M, Cin, HW}, f.lat_w3, ey, (int)M, C, 3 * Cin, st);
+    by_dtype(dtype, [&](auto bf) { launch_gemm<bf()>(ALoadNCHWSplit3<bf()>{x, (int)M, Cin, HW}, f.lat_w3, ey, (int)M, C, 3 * Cin, st); });
   }
   mark(st, "fpn.lateral");
   {
@@ -2466,17 +2456,16 @@ int axvs_fpn_level_fwd(const float* x, const float* up, long long up_batch_strid
   // 2. GroupNorm apply + bilinear(up) -> merged f16 rows (TL:314-318)
   {
     const long long tot = M * (C / 4);
-    if (bf) hipLaunchKernelGGL((fpn_merge_kernel<kBF>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)w.lat, (const float*)w.stats1, (const float*)f.lat_g,
-                               (const float*)f.lat_b, up, up_batch_stride, up_ld, Hu, Wu, w.m16, N, H, W, C, groups);
-    else hipLaunchKernelGGL((fpn_merge_kernel<false>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)w.lat, (const float*)w.stats1, (const float*)f.lat_g,
-                            (const float*)f.lat_b, up, up_batch_stride, up_ld, Hu, Wu, w.m16, N, H, W, C, groups);
+    by_dtype(dtype, [&](auto bf) {
+      hipLaunchKernelGGL((fpn_merge_kernel<bf()>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)w.lat, (const float*)w.stats1, (const float*)f.lat_g,
+                         (const float*)f.lat_b, up, up_batch_stride, up_ld, Hu, Wu, w.m16, N, H, W, C, groups);
+    });
   }
   mark(st, "fpn.merge");
   // 3. 3x3 conv (implicit GEMM) + per-tile partial sums -> GroupNorm statistics (TL:319)
   {
     const dim3 grid((unsigned)tiles, (unsigned)((C + 255) / 256), (unsigned)N);
-    if (bf) hipLaunchKernelGGL((fpn_conv3x3_kernel<kBF>), grid, dim3(256), 0, st, (const u16*)w.m16, (const u16*)f.out_w, w.lat, w.cpart, H, W, C, C, ntx);
-    else hipLaunchKernelGGL((fpn_conv3x3_kernel<false>), grid, dim3(256), 0, st, (const u16*)w.m16, (const u16*)f.out_w, w.lat, w.cpart, H, W, C, C, ntx);
+    by_dtype(dtype, [&](auto bf) { hipLaunchKernelGGL((fpn_conv3x3_kernel<bf()>), grid, dim3(256), 0, st, (const u16*)w.m16, (const u16*)f.out_w, w.lat, w.cpart, H, W, C, C, ntx); });
     mark(st, "fpn.conv3x3");
     hipLaunchKernelGGL(fpn_gn_finalize_kernel, dim3(groups, N), dim3(256), 0, st, (const float*)w.cpart, tiles, C, C / groups, groups,
                        (double)HW * (C / groups), eps, w.stats2);
@@ -2491,8 +2480,7 @@ int axvs_fpn_level_fwd(const float* x, const float* up, long long up_batch_strid
   // 5. mask_feature = conv1x1(ReLU(GN(c))) + bias (TL:324), GroupNorm + ReLU in the A loader, NCHW fp32 out
   if (mask_feature) {
     const EpiNCHWBias em{mask_feature, f.mask_b, HW, Cm};
-    if (bf) launch_gemm<kBF>(ALoadGnRelu<kBF>{w.lat, w.stats2, f.out_g, f.out_b, (int)M, C, HW, groups}, f.mask_w, em, (int)M, Cm, C, st);
-    else launch_gemm<false>(ALoadGnRelu<false>{w.lat, w.stats2, f.out_g, f.out_b, (int)M, C, HW, groups}, f.mask_w, em, (int)M, Cm, C, st);
+    by_dtype(dtype, [&](auto bf) { launch_gemm<bf()>(ALoadGnRelu<bf()>{w.lat, w.stats2, f.out_g, f.out_b, (int)M, C, HW, groups}, f.mask_w, em, (int)M, Cm, C, st); });
     mark(st, "fpn.mask_feature");
   }
   return last_launch_status();

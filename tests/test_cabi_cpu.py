@@ -398,3 +398,79 @@ def test_in_place_levels_fall_back_when_the_strided_workspace_explodes():
     pos_many = modules.tag_sine3d(torch.zeros(8, 4, 32, 32, 256), 10000.0, True, 6.283185307179586)
     assert not layer.can_run_in_place(pos_many, frame_stride_rows=21504)
     assert not layer.can_run_in_place(pos_many, frame_stride_rows=2 ** 22)      # row indices beyond 32 bits / 64
+
+
+def _short_workspace_calls():
+    """(entry point, its size query's value, call with `ws` workspace bytes) for every eval-tier *_fwd that takes workspace_bytes.
+    Pointers are made up (distinct, 16-byte aligned, never dereferenced: the workspace check comes before any device work);
+    arguments the host reads before that check (spatial_shapes, rates, the sine specification) are real host objects."""
+    from axial_vs_amd import _lib
+    L = _lib.lib()
+    p = [ctypes.c_void_p(0x10000 * (i + 1)) for i in range(8)]
+    B, T, H, W, C, h, F = 1, 2, 16, 12, 256, 8, 1024
+    sine = ctypes.pointer(_lib.AxvsSinePos3D(10000.0, 1, 6.283, None))
+    rates = (ctypes.c_int * 3)(1, 2, 3)
+    shapes = (ctypes.c_int * 4)(8, 8, 4, 4)          # two levels, S = 80
+    layers = (ctypes.c_void_p * 2)(0x90000, 0xa0000)
+    N, S, Lq, nl, P = 2, 80, 80, 2, 4
+    Q, Tc, V, K1, Cm, fpc = 16, 3, 2, 25, 256, 2
+    stride = H * W + 40
+    return [
+        ("axvs_traj_attn_fwd", L.axvs_traj_attn_workspace_bytes(4, T, 16, C, h),
+         lambda ws: L.axvs_traj_attn_fwd(p[0], p[0], p[0], p[1], None, p[2], 4, T, 16, C, h, 0, p[3], ws, None)),
+        ("axvs_axial_layer_fwd", L.axvs_axial_layer_workspace_bytes_ex(B, T, H, W, C, h, F, 0, 0),
+         lambda ws: L.axvs_axial_layer_fwd(p[0], p[1], p[2], p[3], B, T, H, W, C, h, F, 0, p[4], ws, None, None, None)),
+        ("axvs_axial_layer_fwd[attention maps]", L.axvs_axial_layer_workspace_bytes_ex(B, T, H, W, C, h, F, 1, 0),
+         lambda ws: L.axvs_axial_layer_fwd(p[0], p[1], p[2], p[3], B, T, H, W, C, h, F, 0, p[4], ws, p[5], p[6], None)),
+        ("axvs_axial_layer_fwd_sine3d", L.axvs_axial_layer_workspace_bytes_ex(B, T, H, W, 128, h, F, 0, 1),
+         lambda ws: L.axvs_axial_layer_fwd_sine3d(p[0], sine, p[2], p[3], B, T, H, W, 128, h, F, 0, p[4], ws, None, None, None)),
+        ("axvs_axial_layer_fwd_sine3d_strided", L.axvs_axial_layer_workspace_bytes_strided(B, T, H, W, C, h, F, stride),
+         lambda ws: L.axvs_axial_layer_fwd_sine3d_strided(p[0], sine, p[2], p[3], B, T, H, W, C, h, F, 0, stride, p[4], ws, None)),
+        ("axvs_axial_pass_fwd", L.axvs_axial_layer_workspace_bytes_ex(B, T, H, W, C, h, F, 0, 0),
+         lambda ws: L.axvs_axial_pass_fwd(p[0], p[1], p[2], p[3], 1, B, T, H, W, C, h, F, 0, p[4], ws, None)),
+        ("axvs_traj_layer_fwd", L.axvs_traj_layer_workspace_bytes(B, T, H * W, C, h, F),
+         lambda ws: L.axvs_traj_layer_fwd(p[0], p[1], p[2], p[3], B, T, H * W, C, h, F, 0, p[4], ws, None)),
+        ("axvs_ffn_fwd", L.axvs_ffn_workspace_bytes(300, C, F),
+         lambda ws: L.axvs_ffn_fwd(p[0], p[1], p[2], 300, C, h, F, 0, p[3], ws, None)),
+        ("axvs_ffn_packed_fwd", L.axvs_ffn_workspace_bytes(300, C, F),
+         lambda ws: L.axvs_ffn_packed_fwd(p[0], p[1], p[2], 300, C, F, 0, p[3], ws, None)),
+        ("axvs_cc_layer_fwd", L.axvs_cc_layer_workspace_bytes(B, Q, Tc),
+         lambda ws: L.axvs_cc_layer_fwd(p[0], p[1], p[2], B, Q, Tc, rates, 0, p[3], ws, None)),
+        ("axvs_cc_heads_fwd", L.axvs_cc_heads_workspace_bytes(B, Q, Tc),
+         lambda ws: L.axvs_cc_heads_fwd(p[0], p[1], p[2], p[3], p[4], B, Q, Tc, V, 8, 8, K1, 0, p[5], ws, None)),
+        ("axvs_cc_module_fwd", L.axvs_cc_module_workspace_bytes(B, Q, Tc, nl),
+         lambda ws: L.axvs_cc_module_fwd(p[0], p[1], p[2], p[3], p[4], layers, p[5], nl, B, Q, Tc, V, 8, 8, K1, rates, 0, p[6], ws, None)),
+        ("axvs_tl_cc_module_fwd", L.axvs_tl_cc_module_workspace_bytes(B, Q, Tc, Cm, nl),
+         lambda ws: L.axvs_tl_cc_module_fwd(p[0], p[1], p[2], p[3], p[4], layers, p[5], nl, B, Q, Tc, fpc, 8, 8, K1, Cm, rates, 0, p[6], ws, None)),
+        ("axvs_tl_heads_fwd", L.axvs_tl_heads_workspace_bytes(B, Q, Tc, Cm),
+         lambda ws: L.axvs_tl_heads_fwd(p[0], p[1], p[2], p[3], p[4], B, Q, Tc, fpc, 8, 8, K1, Cm, 0, p[5], ws, None)),
+        ("axvs_msda_fwd", L.axvs_msda_workspace_bytes(N, Lq, S, C, h, 2, P),
+         lambda ws: L.axvs_msda_fwd(p[0], p[1], 2, p[2], None, shapes, p[3], p[4], N, Lq, S, C, h, 2, P, 0, p[5], ws, None)),
+        ("axvs_msda_sample_fwd", L.axvs_msda_workspace_bytes(N, Lq, S, C, h, 2, P),
+         lambda ws: L.axvs_msda_sample_fwd(p[0], None, p[1], 2, p[2], None, shapes, p[3], p[4], N, Lq, S, C, h, 2, P, 0, p[5], ws, None)),
+        ("axvs_msda_layer_fwd", L.axvs_msda_layer_workspace_bytes(N, S, C, h, 2, P, F),
+         lambda ws: L.axvs_msda_layer_fwd(p[0], p[1], p[2], 2, None, shapes, p[3], p[4], N, S, C, h, 2, P, F, 0, p[5], ws, None)),
+        ("axvs_conv1x1_gn_fwd", L.axvs_conv1x1_gn_workspace_bytes(N, 99, 256, 32),
+         lambda ws: L.axvs_conv1x1_gn_fwd(p[0], 0, 512 * 99, 99, p[1], 1, 99 * 256, 256, p[2], N, 99, 512, 256, 32, 1e-5, 0, p[3], ws, None)),
+        ("axvs_fpn_level_fwd", L.axvs_fpn_level_workspace_bytes(N, 10, 14, 512, 256, 32),
+         lambda ws: L.axvs_fpn_level_fwd(p[0], p[1], 5 * 7 * 256, 256, 5, 7, p[2], None, p[3], N, 10, 14, 512, 256, 0, 32, 1e-5, 0, p[4], ws, None)),
+    ]
+
+
+def test_every_forward_refuses_a_workspace_one_byte_short():
+    """The workspace contract of include/axvs.h: a *_fwd entry point called with fewer bytes than its size query asks for returns
+    AXVS_ERR_WORKSPACE (-2) before any device work, and the error text holds both sizes.  (Every eval-tier entry point makes its
+    workspace check before it touches the device, so none is left out.)"""
+    from axial_vs_amd import _lib
+    L = _lib.lib()
+    calls = _short_workspace_calls()
+    names = {n.split("[")[0] for n, _, _ in calls}
+    eval_fwd = {n for n, (_, args) in _lib.SIGNATURES.items() if n.endswith("_fwd") or "_fwd_" in n
+                if "_train_" not in n and ctypes.c_size_t in args}
+    assert names == eval_fwd, sorted(names ^ eval_fwd)
+    for name, need, call in calls:
+        assert need > 0, name
+        rc = call(need - 1)
+        err = L.axvs_last_error().decode()
+        assert rc == -2, (name, rc, err)
+        assert str(need - 1) in err and str(need) in err and "workspace too small" in err, (name, err)
