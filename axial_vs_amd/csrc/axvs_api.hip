@@ -1173,14 +1173,17 @@ int check_msda_pack(int L, int P) {
 
 struct MsdaWs {
   u16* value16;      // value_proj output, blocked 16-bit [N S][Cp]
-  float* qproj;      // sampling offsets | attention logits [N Lq][3 heads L P]
+  float* qproj;      // sampling offsets | attention logits [N Lq][msda_qld(heads, L, P)]
   u16* o16;          // sampled rows: two 16-bit pieces / the same bytes as fp32 rows
 };
+// row stride of qproj: 3 heads L P rounded up to the float4 groups the GEMM epilogue stores (a group that crossed the end of a row
+// overwrote the first offsets of the next one when 3 heads L P was no multiple of 4)
+inline int msda_qld(int heads, int L, int P) { return (3 * heads * L * P + 3) & ~3; }
 MsdaWs carve_msda_ws(Carver& c, int N, int Lq, int S, int heads, int L, int P) {
   const size_t Cp = (size_t)heads * 32;
   MsdaWs w;
   w.value16 = c.take<u16>((size_t)N * S * Cp);
-  w.qproj = c.take<float>((size_t)N * Lq * 3 * heads * L * P);
+  w.qproj = c.take<float>((size_t)N * Lq * msda_qld(heads, L, P));
   w.o16 = c.take<u16>(2 * (size_t)N * Lq * Cp);
   return w;
 }
@@ -1254,7 +1257,7 @@ template <bool BF>
 int msda_fwd_t(const float* query, const float* refp, int ref_dim, const float* input, const unsigned char* mask, const MsdaLevels& lv,
                float* out, const MsdaPacked& p, int N, int Lq, int S, int C, int heads, int P, void* ws, hipStream_t st,
                const float* qadd = nullptr, const float* residual = nullptr, int what = 0) {
-  const int L = lv.L, Cp = heads * 32, nq = 3 * heads * L * P;
+  const int L = lv.L, Cp = heads * 32, nq = 3 * heads * L * P, qld = msda_qld(heads, L, P);
   const long long Rv = (long long)N * S, Rq = (long long)N * Lq;
   Carver wc(ws);
   const MsdaWs w = carve_msda_ws(wc, N, Lq, S, heads, L, P);
@@ -1281,7 +1284,7 @@ int msda_fwd_t(const float* query, const float* refp, int ref_dim, const float* 
     const tr::GemmEpi e{p.bq, 1.f, 0, nodrop, 0.f};
     if (int rc = launch_nt128(query, qadd, p.wq32, w.qproj, Rq, nq, C, e, st)) return rc;
   } else {
-    launch_gemm<BF>(ALoadRowsF32Split3<BF>{query, (int)Rq, C, qadd}, p.wq, EpiRowsF32{w.qproj, nullptr, p.bq, identity_map(Rq), nq, 1.f}, (int)Rq,
+    launch_gemm<BF>(ALoadRowsF32Split3<BF>{query, (int)Rq, C, qadd}, p.wq, EpiRowsF32{w.qproj, nullptr, p.bq, identity_map(Rq), qld, 1.f}, (int)Rq,
                     nq, 3 * C, st);
   }
   mark(st, "msda.offsets+weights");
@@ -1290,8 +1293,8 @@ int msda_fwd_t(const float* query, const float* refp, int ref_dim, const float* 
   // the output projection on the 128 x 128 kernel reads the sampled rows as fp32 [N Lq][C] (same bytes as the two 16-bit pieces)
   const bool out128 = what != 1 && use_nt128(Rq, C, heads);
   float* of32 = what == 1 ? out : (out128 ? reinterpret_cast<float*>(w.o16) : nullptr);
-  if (P == 4) hipLaunchKernelGGL((msda_gather_kernel<BF, 4>), ggrid, dim3(256), 0, st, w.value16, w.qproj, refp, ref_dim, lv, w.o16, N, S, Lq, heads, P, of32, C / heads);
-  else hipLaunchKernelGGL((msda_gather_kernel<BF, 0>), ggrid, dim3(256), 0, st, w.value16, w.qproj, refp, ref_dim, lv, w.o16, N, S, Lq, heads, P, of32, C / heads);
+  if (P == 4) hipLaunchKernelGGL((msda_gather_kernel<BF, 4>), ggrid, dim3(256), 0, st, w.value16, w.qproj, refp, ref_dim, lv, w.o16, N, S, Lq, heads, P, qld, of32, C / heads);
+  else hipLaunchKernelGGL((msda_gather_kernel<BF, 0>), ggrid, dim3(256), 0, st, w.value16, w.qproj, refp, ref_dim, lv, w.o16, N, S, Lq, heads, P, qld, of32, C / heads);
   mark(st, "msda.gather");
   if (what == 1) return last_launch_status();
   if (out128) {

@@ -141,13 +141,14 @@ __global__ __launch_bounds__(256) void msda_core_bwd_kernel(const float* __restr
 
 // ---- module path: softmax over the L*P logits, sampling locations from the reference points, bilinear gather, weighted
 //      sum.  value16: blocked 16-bit [M][N*S][32] (head blocks, written by the value_proj GEMM epilogue);
-//      qproj: fp32 [N*Lq][3*M*L*P] = sampling offsets (M,L,P,2) | attention logits (M,L,P) (one GEMM on the query);
+//      qproj: fp32 [N*Lq][qld >= 3*M*L*P] = sampling offsets (M,L,P,2) | attention logits (M,L,P) (one GEMM on the query; qld is a
+//      multiple of 4: the GEMM epilogue stores float4 groups, which must not run over the end of a row);
 //      o16: blocked 16-bit [2M][N*Lq][32] for the output_proj GEMM: hi blocks then lo blocks (o = hi + lo, split precision).
 //      4 lanes per (query, head): lane j owns channels 8j..8j+7 (16-byte loads), a sample corner is one 64-byte segment. ----
 template <bool BF, int PT>   // PT > 0: n_points known at compile time (all 4*PT corner loads of a level in flight together)
 __global__ __launch_bounds__(256) void msda_gather_kernel(const u16* __restrict__ value16, const float* __restrict__ qproj,
                                                           const float* __restrict__ refp, int ref_dim, MsdaLevels lv,
-                                                          u16* __restrict__ o16, int N, int S, int Lq, int M, int Prt,
+                                                          u16* __restrict__ o16, int N, int S, int Lq, int M, int Prt, int qld,
                                                           float* __restrict__ of32 = nullptr, int d = 32) {
   // of32 != nullptr: the sampled rows go out as fp32 [N*Lq][M*d] (natural channel order) instead of the split 16-bit blocks
   // -- the Tube-Link plugin runs its temporal encoder on them before output_proj (TL ...pixel_decoder.py:613-633).
@@ -161,8 +162,8 @@ __global__ __launch_bounds__(256) void msda_gather_kernel(const u16* __restrict_
   const long long row = g / M;
   const int n = (int)(row / Lq);
   const int L = lv.L, LP = L * P, MLP = M * LP;
-  const float* offs = qproj + row * 3 * MLP + (long long)m * LP * 2;
-  const float* logit = qproj + row * 3 * MLP + 2 * MLP + (long long)m * LP;
+  const float* offs = qproj + row * qld + (long long)m * LP * 2;
+  const float* logit = qproj + row * qld + 2 * MLP + (long long)m * LP;
   float mx = -INFINITY;
   for (int i = 0; i < LP; ++i) mx = fmaxf(mx, logit[i]);
   float den = 0.f;

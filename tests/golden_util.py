@@ -105,7 +105,8 @@ MSDA_MODULE = ["g7_msda_module_N2_C256_L3_S252", "g7_msda_module_N1_C64_L2_S39",
 
 
 def msda_core_inputs(m):
-    """The reference test's input recipe (ops/test.py:36-41), seeded; `spread` pushes locations outside [0,1]."""
+    """The reference test's input recipe (ops/test.py:36-41), seeded; `spread` pushes locations outside [0,1].  Locations are (x, y),
+    normalised to [0, 1] over each level's map: the convention stated once in msda_cases.py."""
     g = torch.Generator().manual_seed(m["seed"])
     shapes, N, M, D, Lq, P, spread = m["shapes"], m["N"], m["M"], m["D"], m["Lq"], m["P"], m["spread"]
     L, S = len(shapes), sum(h * w for h, w in shapes)
