@@ -128,7 +128,7 @@ def _fill(cls, ptrs, i):
         elif issubclass(t, C.Array):
             v, i = t(*ptrs[i:i + t._length_]), i + t._length_
         else:
-            v, i = ptrs[i], i + 1
+            v, i = (ptrs[i] if i < len(ptrs) else None), i + 1      # (too few pointers: counted to the end, refused by fill)
         setattr(s, name, v)
     return s, i
 

@@ -28,68 +28,23 @@ from torch import Tensor
 
 from . import _lib
 from ._autograd import apply, cast, draw_seed, f32c, grad_buffer, nbytes, place, require_gpu
+from ._params import CC_PER_LAYER as _PER_LAYER, cc_bn_modules, cc_chain_params, cc_head_with_running, cc_layer_struct, cc_module_params, tl_head_params
 
 
-def _bn_modules(mod):
-    return [mod._class_embedding_projection.norm, mod._mask_embedding_projection.norm, mod._predictor._transformer_mask_head.norm,
-            mod._predictor._pixel_space_mask_batch_norm]
-
-
-def chain_parameters(mod, num_layers: int) -> List[Tensor]:
-    ps: List[Tensor] = []
-    for i in range(num_layers):
-        lay, asp, cn = mod.transformer_trajectory_self_attention_layers[i], mod.conv_short_aggregate_layers[i], mod.conv_norms[i]
-        at = lay.self_attn
-        ps += [at.qkv.weight, at.qkv.bias, at.proj_q.weight, at.proj_q.bias, at.proj_kv.weight, at.proj_kv.bias, at.proj.weight, at.proj.bias,
-               lay.norm.weight, lay.norm.bias]
-        for k in range(3):
-            conv = getattr(asp, f"_aspp_conv{k}")
-            ps += [conv.weight, conv.bias]
-        ps += [asp._proj_conv_bn_act.conv.weight, asp._proj_conv_bn_act.norm.weight, asp._proj_conv_bn_act.norm.bias, cn.weight, cn.bias]
-    return ps
-
-
-def module_parameters(mod) -> List[Tensor]:
-    """Every trainable tensor of the module, in the order the autograd Function returns gradients."""
-    ps = chain_parameters(mod, mod.num_layers)
-    pr = mod._predictor
-    ps += [mod._class_embedding_projection.conv.weight, mod._class_embedding_projection.norm.weight, mod._class_embedding_projection.norm.bias,
-           mod._mask_embedding_projection.conv.weight, mod._mask_embedding_projection.norm.weight, mod._mask_embedding_projection.norm.bias,
-           pr._transformer_mask_head.conv.weight, pr._transformer_mask_head.norm.weight, pr._transformer_mask_head.norm.bias,
-           pr._transformer_class_head.conv.weight, pr._transformer_class_head.conv.bias,
-           pr._transformer_class_activation_head.conv.weight, pr._transformer_class_activation_head.conv.bias,
-           pr._pixel_space_mask_batch_norm.weight, pr._pixel_space_mask_batch_norm.bias]
-    return ps
-
-
-_PER_LAYER = 21
-
-
-def _layer_struct(ptrs: List[int], Cc: int = 256):
-    """AxvsCCLayerParams (or, with gradient buffers, AxvsCCLayerGrads: same layout) from one layer's 21 tensors."""
-    s = _lib.AxvsCCLayerParams()
-    qkv_w, qkv_b = ptrs[0], ptrs[1]
-    s.attn = _lib.AxvsTrajParams(qkv_w, qkv_b, qkv_w + 4 * Cc * Cc, qkv_b + 4 * Cc, qkv_w + 8 * Cc * Cc, qkv_b + 8 * Cc, *ptrs[2:8])
-    s.norm_w, s.norm_b = ptrs[8], ptrs[9]
-    for k in range(3):
-        s.aspp_w[k], s.aspp_b[k] = ptrs[10 + 2 * k], ptrs[11 + 2 * k]
-    s.aspp_proj_w, s.aspp_norm_w, s.aspp_norm_b, s.conv_norm_w, s.conv_norm_b = ptrs[16:21]
-    return s
+# the parameter lists handed to autograd (their names here are part of the tested surface): the chain's 21 tensors per layer, then the
+# 15 of the heads; the Tube-Link head's 12 in AxvsTLHeadParams field order
+chain_parameters = cc_chain_params
+module_parameters = cc_module_params
+tl_heads_parameters = tl_head_params
 
 
 def _layers(ptrs: List[int], nl: int):
     """The AxvsCCLayerParams (or AxvsCCLayerGrads) array of `nl` layers from the chain's tensors."""
-    return (_lib.AxvsCCLayerParams * nl)(*[_layer_struct(ptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
+    return (_lib.AxvsCCLayerParams * nl)(*[cc_layer_struct(ptrs[i * _PER_LAYER:(i + 1) * _PER_LAYER]) for i in range(nl)])
 
 
 def _head_struct(ptrs: List[int], running) -> _lib.AxvsCCHeadParams:
-    h = _lib.AxvsCCHeadParams()
-    h.class_proj_w, h.class_proj_bn = ptrs[0], _lib.AxvsBN(ptrs[1], ptrs[2], running[0][0], running[0][1])
-    h.mask_proj_w, h.mask_proj_bn = ptrs[3], _lib.AxvsBN(ptrs[4], ptrs[5], running[1][0], running[1][1])
-    h.mask_head_w, h.mask_head_bn = ptrs[6], _lib.AxvsBN(ptrs[7], ptrs[8], running[2][0], running[2][1])
-    h.class_head_w, h.class_head_b, h.act_head_w, h.act_head_b = ptrs[9:13]
-    h.pixel_bn = _lib.AxvsBN(ptrs[13], ptrs[14], running[3][0], running[3][1])
-    return h
+    return _lib.fill(_lib.AxvsCCHeadParams, cc_head_with_running(ptrs, running))
 
 
 class _AllReduce:
@@ -220,7 +175,7 @@ def cc_module_train(mod, clip_query: Tensor, panoptic_features: Tensor):
     for lay in mod.transformer_trajectory_self_attention_layers:
         if lay.normalize_before or lay.dropout.p != 0.0:
             raise NotImplementedError("axial_vs_amd: the cross-clip layer is post-norm with dropout 0 (CC:249-255)")
-    bns = _bn_modules(mod)
+    bns = cc_bn_modules(mod)
     K1 = mod._predictor._transformer_class_head.conv.weight.shape[0]
     nl = mod.num_layers
     p_attn, p_aspp = float(mod.attn_drop), float(mod.aspp_drop)
@@ -320,14 +275,6 @@ def cc_layers_train(mod, clip_query: Tensor, num_layers: int, rates, p_attn: flo
 
 
 # ---- the Tube-Link head's prediction heads, all layers at once (axvs_tl_heads_train_*) ------------------------------------------------
-def tl_heads_parameters(mod) -> List[Tensor]:
-    """The head's trainable tensors in AxvsTLHeadParams field order: post_norm, activation_proj, cls_embed, the three mask_embed weights,
-    the three mask_embed biases."""
-    pn, me = mod.transformer_decoder.post_norm, mod.mask_embed
-    return [pn.weight, pn.bias, mod.activation_proj.weight, mod.activation_proj.bias, mod.cls_embed.weight, mod.cls_embed.bias,
-            me[0].weight, me[2].weight, me[4].weight, me[0].bias, me[2].bias, me[4].bias]
-
-
 def tl_heads_cfg(nl: int, B: int, Q: int, Tc: int, fpc: int, h: int, w: int, K1: int, Cm: int) -> _lib.AxvsTLHeadTrainCfg:
     return _lib.AxvsTLHeadTrainCfg(int(B), int(Q), int(Tc), int(fpc), int(h), int(w), int(K1), int(Cm), int(nl))
 

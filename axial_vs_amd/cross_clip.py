@@ -18,7 +18,8 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from . import _lib
-from .modules import _dev_f32, _param_key, _require_eval, _select_sync_words, _stream, _traj_struct, _workspace, _guarded
+from ._params import cc_bn_modules, cc_head_params, cc_head_with_running, cc_layer_params, cc_layer_struct, tl_head_params
+from .modules import _cached_pack, _dev_f32, _operand_dtype, _pack_weights, _require_eval, _select_sync_words, _workspace, _guarded
 
 
 class _LayerNormCF(nn.Module):
@@ -101,34 +102,17 @@ class MaXTronCCPredictor(nn.Module):         # CC:30-43
         nn.init.constant_(self._pixel_space_mask_batch_norm.weight, 0.1)
 
 
-def _bn(m) -> _lib.AxvsBN:
-    return m.weight, m.bias, m.running_mean, m.running_var
-
-
-def _pack_cc_layers(mod, num_layers, f, keep, dt, dev):
+def _pack_cc_layers(mod, num_layers: int, dt: str) -> List[Tensor]:
     """axvs_cc_layer_pack for every (trajectory layer, ASPP, LayerNorm) triple of `mod` -> list of packed device buffers."""
-    L = _lib.lib()
     layers = []
     for i in range(num_layers):
-        lay, asp, cn = mod.transformer_trajectory_self_attention_layers[i], mod.conv_short_aggregate_layers[i], mod.conv_norms[i]
-        ps = _lib.AxvsCCLayerParams()
-        ps.attn = _traj_struct(lay.self_attn, keep)
-        ps.norm_w, ps.norm_b = f(lay.norm.weight), f(lay.norm.bias)
-        for k in range(3):
-            conv = getattr(asp, f"_aspp_conv{k}")
-            ps.aspp_w[k], ps.aspp_b[k] = f(conv.weight), f(conv.bias)
-        ps.aspp_proj_w = f(asp._proj_conv_bn_act.conv.weight)
-        nrm = asp._proj_conv_bn_act.norm
+        ts = cc_layer_params(mod, i)
+        nrm = mod.conv_short_aggregate_layers[i]._proj_conv_bn_act.norm
         if isinstance(nrm, nn.BatchNorm1d):      # 'syncbn', eval mode: y * scale + shift with the running statistics (eps 1e-3)
             scale = (nrm.weight.detach().float() * torch.rsqrt(nrm.running_var.float() + nrm.eps)).contiguous()
             shift = (nrm.bias.detach().float() - nrm.running_mean.float() * scale).contiguous()
-            ps.aspp_norm_w, ps.aspp_norm_b = f(scale), f(shift)
-        else:
-            ps.aspp_norm_w, ps.aspp_norm_b = f(nrm.weight), f(nrm.bias)
-        ps.conv_norm_w, ps.conv_norm_b = f(cn.weight), f(cn.bias)
-        buf = torch.empty(L.axvs_cc_layer_packed_bytes(), dtype=torch.uint8, device=dev)
-        _lib.check(L.axvs_cc_layer_pack(C.byref(ps), buf.data_ptr(), _lib.DTYPES[dt], _stream(dev)), "axvs_cc_layer_pack")
-        layers.append(buf)
+            ts[17:19] = [scale, shift]           # in the places of aspp_norm_w / aspp_norm_b
+        layers.append(_pack_weights("axvs_cc_layer", cc_layer_struct, ts, (), dt))
     return layers
 
 
@@ -161,47 +145,16 @@ class CrossClipTrackingModule(nn.Module):
         # (CC:283-322); False = only the last layer's predictor heads run and 'aux_outputs' is [] -- what the reference's own inference
         # path keeps (maxtron_cc_model.py reads aux_outputs under self.training only): 3/4 of the mask einsum's HBM writes less
         self.eval_aux_outputs = True
-        self._packed = None
-        self._packed_key = None
 
     # ---- packing -------------------------------------------------------------------------------------------------
-    def _dtype(self) -> str:
-        from . import modules
-        return self.mfma_dtype or modules.default_operand_dtype()
+    _dtype = _operand_dtype
 
     def _pack(self):
-        dt = self._dtype()
-        key = _param_key(self, dt) + tuple((b.data_ptr(), b._version) for b in self.buffers())
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
-        L = _lib.lib()
-        dev = self.conv_norms[0].weight.device
-        keep: list = []
-
-        def f(t):
-            tt = _dev_f32(t.detach(), "parameter")
-            keep.append(tt)
-            return tt.data_ptr()
-
-        layers = _pack_cc_layers(self, self.num_layers, f, keep, dt, dev)
-        pr = self._predictor
-        K1 = pr._transformer_class_head.conv.weight.shape[0]
-        hp = _lib.AxvsCCHeadParams()
-        hp.class_proj_w = f(self._class_embedding_projection.conv.weight)
-        hp.class_proj_bn = _lib.AxvsBN(*[f(t) for t in _bn(self._class_embedding_projection.norm)])
-        hp.mask_proj_w = f(self._mask_embedding_projection.conv.weight)
-        hp.mask_proj_bn = _lib.AxvsBN(*[f(t) for t in _bn(self._mask_embedding_projection.norm)])
-        hp.mask_head_w = f(pr._transformer_mask_head.conv.weight)
-        hp.mask_head_bn = _lib.AxvsBN(*[f(t) for t in _bn(pr._transformer_mask_head.norm)])
-        hp.class_head_w, hp.class_head_b = f(pr._transformer_class_head.conv.weight), f(pr._transformer_class_head.conv.bias)
-        hp.act_head_w = f(pr._transformer_class_activation_head.conv.weight)
-        hp.act_head_b = f(pr._transformer_class_activation_head.conv.bias)
-        hp.pixel_bn = _lib.AxvsBN(*[f(t) for t in _bn(pr._pixel_space_mask_batch_norm)])
-        hbuf = torch.empty(L.axvs_cc_heads_packed_bytes(K1), dtype=torch.uint8, device=dev)
-        _lib.check(L.axvs_cc_heads_pack(C.byref(hp), hbuf.data_ptr(), K1, _lib.DTYPES[dt], _stream(dev)), "axvs_cc_heads_pack")
-        torch.cuda.current_stream(dev).synchronize()      # `keep` (fp32 staging copies) may be released after this
-        self._packed, self._packed_key = (layers, hbuf, K1), key
-        return self._packed
+        def build(dt):
+            K1 = self._predictor._transformer_class_head.conv.weight.shape[0]
+            heads = cc_head_with_running(cc_head_params(self), [(bn.running_mean, bn.running_var) for bn in cc_bn_modules(self)])
+            return _pack_cc_layers(self, self.num_layers, dt), _pack_weights("axvs_cc_heads", _lib.AxvsCCHeadParams, heads, (K1,), dt), K1
+        return _cached_pack(self, "module", self._dtype(), (self,), build, buffers=True)      # (buffers: the running statistics)
 
     # ---- forward (CC:275-322) ------------------------------------------------------------------------------------
     def _forward_train(self, clip_query: Tensor, panoptic_features: Tensor):
@@ -314,41 +267,15 @@ class TubeLinkCrossClipHead(nn.Module):
             self.conv_norms.append(nn.LayerNorm(256))
         self.activation_proj = nn.Linear(256, 1)
         self.mfma_dtype = mfma_dtype
-        self._packed = None
-        self._packed_key = None
 
-    def _dtype(self) -> str:
-        from . import modules
-        return self.mfma_dtype or modules.default_operand_dtype()
+    _dtype = _operand_dtype
 
     def _pack(self):
-        dt = self._dtype()
-        key = _param_key(self, dt) + tuple((b.data_ptr(), b._version) for b in self.buffers())     # (running statistics of aspp_norm_fn = 'syncbn')
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
-        L = _lib.lib()
-        dev = self.activation_proj.weight.device
-        keep: list = []
-
-        def f(t):
-            tt = _dev_f32(t.detach(), "parameter")
-            keep.append(tt)
-            return tt.data_ptr()
-
-        layers = _pack_cc_layers(self, self.num_cc_layers, f, keep, dt, dev)
-        K1, Cm = self.cls_embed.weight.shape[0], self.mask_embed[4].weight.shape[0]
-        hp = _lib.AxvsTLHeadParams()
-        pn = self.transformer_decoder.post_norm
-        hp.post_norm_w, hp.post_norm_b = f(pn.weight), f(pn.bias)
-        hp.activation_proj_w, hp.activation_proj_b = f(self.activation_proj.weight), f(self.activation_proj.bias)
-        hp.cls_embed_w, hp.cls_embed_b = f(self.cls_embed.weight), f(self.cls_embed.bias)
-        for k, idx in enumerate((0, 2, 4)):
-            hp.mask_embed_w[k], hp.mask_embed_b[k] = f(self.mask_embed[idx].weight), f(self.mask_embed[idx].bias)
-        hbuf = torch.empty(L.axvs_tl_heads_packed_bytes(K1, Cm), dtype=torch.uint8, device=dev)
-        _lib.check(L.axvs_tl_heads_pack(C.byref(hp), hbuf.data_ptr(), K1, Cm, _lib.DTYPES[dt], _stream(dev)), "axvs_tl_heads_pack")
-        torch.cuda.current_stream(dev).synchronize()
-        self._packed, self._packed_key = (layers, hbuf, K1, Cm), key
-        return self._packed
+        def build(dt):
+            K1, Cm = self.cls_embed.weight.shape[0], self.mask_embed[4].weight.shape[0]
+            return (_pack_cc_layers(self, self.num_cc_layers, dt),
+                    _pack_weights("axvs_tl_heads", _lib.AxvsTLHeadParams, tl_head_params(self), (K1, Cm), dt), K1, Cm)
+        return _cached_pack(self, "head", self._dtype(), (self,), build, buffers=True)      # (buffers: running statistics of aspp_norm_fn = 'syncbn')
 
     def _forward_train(self, clip_query: Tensor, mask_features: Tensor):
         """train() mode (TLCC:925-947 with forward_head_clips :761-781 and pred_class :783-797 under autograd): the layer chain on the

@@ -15,6 +15,7 @@ from torch import Tensor
 
 from . import _lib
 from ._autograd import cast, f32c, place, require_gpu
+from ._params import conv_gn_params
 
 
 class _ConvGnTrain(torch.autograd.Function):
@@ -77,5 +78,5 @@ def conv_gn_train(x: Tensor, conv: torch.nn.Conv2d, gn: torch.nn.GroupNorm, out_
         N = x.shape[0]
         H, W = hw if hw is not None else (x.shape[1], 1)
         in_layout = "tokens"
-    return _ConvGnTrain.apply(x, conv.weight.reshape(Cout, Cin), conv.bias, gn.weight, gn.bias, in_layout, out_layout, N, H * W, Cin, Cout, gn.num_groups,
+    return _ConvGnTrain.apply(x, *conv_gn_params(conv, gn), in_layout, out_layout, N, H * W, Cin, Cout, gn.num_groups,
                               float(gn.eps), (H, W))

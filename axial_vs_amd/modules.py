@@ -27,6 +27,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import _lib
+from ._params import axial_layer_params, traj_layer_params, traj_params
 
 _DEFAULT_DTYPE = "f16"
 
@@ -44,6 +45,11 @@ def default_operand_dtype() -> str:
     """16-bit operand type of the modules that have no fp32 tier (everything but the axial layer / TemporalEncoder): the default,
     or 'f16' when the default is 'f32'."""
     return "f16" if _DEFAULT_DTYPE == "f32" else _DEFAULT_DTYPE
+
+
+def _operand_dtype(mod) -> str:
+    """`_dtype` of every module without an fp32 tier: its own `mfma_dtype`, else the default 16-bit operand type."""
+    return mod.mfma_dtype or default_operand_dtype()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -176,12 +182,50 @@ def _has_hooks(mod: nn.Module) -> bool:
     return bool(mod._forward_hooks or mod._forward_pre_hooks or _m._global_forward_hooks or _m._global_forward_pre_hooks)
 
 
+_PACKS = "_axvs_packs"      # where an owner's packed weights live: owner.__dict__[_PACKS] = {slot: (key, blob)} -- no buffer, not in the state dict
+_NO_PACKS: dict = {}
+
+
 def invalidate_pack(mod: nn.Module) -> None:
     """Forget cached parameter references / packed weights of `mod` and its children."""
     for m in mod.modules():
         m.__dict__.pop("_axvs_refs", None)
-        if "_packed" in m.__dict__:
-            m.__dict__["_packed"] = None
+        m.__dict__.pop(_PACKS, None)
+
+
+def _cached_pack(owner: nn.Module, slot: str, dt: str, mods, build, buffers: bool = False, sync: bool = True):
+    """The packed weights `build(dt)` of `owner`, rebuilt when a parameter of `mods` (or, with `buffers`, a buffer of `owner`: the
+    running statistics folded into the blob) or the operand type `dt` changes.  This is on every eval forward: a hit costs the keys
+    and one comparison.
+    `sync`: wait for the pack kernels before the blob is stored, as most sites always have.  TrajectoryAttention and the axial layer
+    pass False: their pack is reached from TemporalEncoder.prepack and from forwards under a caller's graph capture or on a forked
+    stream, where a stream synchronisation is not allowed; the pack kernels are ordered before the forward on the same stream."""
+    key = [_param_key(m, dt) for m in mods]
+    if buffers:
+        key.append(tuple((b.data_ptr(), b._version) for b in owner.buffers()))
+    ent = owner.__dict__.get(_PACKS, _NO_PACKS).get(slot)
+    if ent is not None and ent[0] == key:
+        return ent[1]
+    blob = build(dt)
+    if sync:
+        torch.cuda.current_stream(next(mods[0].parameters()).device).synchronize()
+    owner.__dict__.setdefault(_PACKS, {})[slot] = (key, blob)
+    return blob
+
+
+def _pack_weights(name: str, struct, tensors, dims, dt: str) -> Tensor:
+    """One `<name>_pack` call: `tensors` (a parameter struct's order, _params.py) cast to fp32 on the device once, their pointers
+    filled into `struct` (a _lib Structure, or a callable from the pointers to one), a buffer of `<name>_packed_bytes(*dims)`."""
+    L = _lib.lib()
+    ts = [None if t is None else _dev_f32(t.detach(), "parameter") for t in tensors]        # (alive until the pack is enqueued)
+    ptrs = [_ptr(t) for t in ts]
+    ps = _lib.fill(struct, ptrs) if isinstance(struct, type) else struct(ptrs)
+    dev = ts[0].device
+    # (zeroed: the pack kernels leave the slots of forms their configuration does not use unwritten -- the reassociated temporal forms at a
+    #  head_dim other than 32 -- and a blob's bytes are a function of the weights alone)
+    buf = torch.zeros(getattr(L, name + "_packed_bytes")(*dims), dtype=torch.uint8, device=dev)
+    _lib.check(getattr(L, name + "_pack")(C.byref(ps), buf.data_ptr(), *dims, _lib.DTYPES[dt], _stream(dev)), name + "_pack")
+    return buf
 
 
 class _on:
@@ -400,22 +444,6 @@ def disable_range_check() -> None:
         w[0] = int(w[0]) & ~1
 
 
-def _traj_struct(m: "TrajectoryAttention", keep: list) -> _lib.AxvsTrajParams:
-    C_ = m.proj.weight.shape[0]
-    if hasattr(m, "qkv"):  # cross-clip flavour: slices of the fused projection
-        w, b = _dev_f32(m.qkv.weight.detach(), "qkv.weight"), _dev_f32(m.qkv.bias.detach(), "qkv.bias")
-        qw, kw, vw = w[:C_], w[C_:2 * C_], w[2 * C_:]
-        qb, kb, vb = b[:C_], b[C_:2 * C_], b[2 * C_:]
-    else:
-        qw, qb = m.q.weight, m.q.bias
-        kw, kb = m.k.weight, m.k.bias
-        vw, vb = m.v.weight, m.v.bias
-    ts = [_dev_f32(t.detach(), "parameter") for t in (qw, qb, kw, kb, vw, vb, m.proj_q.weight, m.proj_q.bias,
-                                                      m.proj_kv.weight, m.proj_kv.bias, m.proj.weight, m.proj.bias)]
-    keep.extend(ts)
-    return _lib.AxvsTrajParams(*[t.data_ptr() for t in ts])
-
-
 # ---------------------------------------------------------------------------------------------
 # TrajectoryAttention   (WC/temporal_attention.py:20-76, TL:652-708)
 # ---------------------------------------------------------------------------------------------
@@ -436,25 +464,12 @@ class TrajectoryAttention(nn.Module):
 
         self.mfma_dtype = mfma_dtype
         self.return_attn = False     # the [(S h), N, T, L] map is opt-in: materialising it defeats the fusion
-        self._packed: Optional[Tensor] = None
-        self._packed_key = None
 
-    def _dtype(self) -> str:
-        return self.mfma_dtype or default_operand_dtype()
+    _dtype = _operand_dtype
 
     def _pack(self) -> Tensor:
-        dt = self._dtype()
-        key = _param_key(self, dt)
-        if self._packed is None or key != self._packed_key:
-            L = _lib.lib()
-            C_, dev = self.proj.weight.shape[0], self.proj.weight.device
-            keep: list = []
-            ps = _traj_struct(self, keep)
-            buf = torch.empty(L.axvs_traj_packed_bytes(C_, self.num_heads), dtype=torch.uint8, device=dev)
-            _lib.check(L.axvs_traj_pack(C.byref(ps), buf.data_ptr(), C_, self.num_heads, _lib.DTYPES[dt], _stream(dev)),
-                       "axvs_traj_pack")
-            self._packed, self._packed_key = buf, key
-        return self._packed
+        return _cached_pack(self, "traj", self._dtype(), (self,), lambda dt: _pack_weights(
+            "axvs_traj", _lib.AxvsTrajParams, traj_params(self), (self.proj.weight.shape[0], self.num_heads), dt), sync=False)
 
     @_guarded
     def forward(self, query, key, value, num_frames=2):
@@ -536,8 +551,6 @@ class TemporalAxialTrajectoryAttentionLayer(nn.Module):
         # from (src, pos, seed) first (+1 forward, nothing kept)
         self.recompute = False
         self.dropout_seed: Optional[int] = None   # train() mode: fixed dropout seed (tests); None = drawn from torch's CPU generator
-        self._packed: Optional[Tensor] = None
-        self._packed_key = None
 
     def _dtype(self) -> str:
         if self.linear1.in_features // self.n_heads > 32:
@@ -549,28 +562,13 @@ class TemporalAxialTrajectoryAttentionLayer(nn.Module):
         if dt == "f32":
             raise NotImplementedError("axial_vs_amd: the fp32 tier (mfma_dtype='f32', head_dim 64) has no packed weights and no "
                                       "per-pass entry point (forward_pass / dist.offaxis_forward run on the 16-bit tier)")
-        key = _param_key(self, dt)
-        if self._packed is None or key != self._packed_key:
-            if abs(self.norm1.eps - 1e-5) > 0 or abs(self.norm2.eps - 1e-5) > 0:
-                raise NotImplementedError("axial_vs_amd: LayerNorm eps must be 1e-5")
-            L = _lib.lib()
-            C_, F, dev = self.linear1.in_features, self.linear1.out_features, self.linear1.weight.device
-            keep: list = []
-            ps = _lib.AxvsAxialLayerParams()
-            ps.height_attn = _traj_struct(self.height_attn, keep)
-            ps.width_attn = _traj_struct(self.width_attn, keep)
-            for name, t in (("norm1_w", self.norm1.weight), ("norm1_b", self.norm1.bias),
-                            ("linear1_w", self.linear1.weight), ("linear1_b", self.linear1.bias),
-                            ("linear2_w", self.linear2.weight), ("linear2_b", self.linear2.bias),
-                            ("norm2_w", self.norm2.weight), ("norm2_b", self.norm2.bias)):
-                tt = _dev_f32(t.detach(), name)
-                keep.append(tt)
-                setattr(ps, name, tt.data_ptr())
-            buf = torch.empty(L.axvs_axial_layer_packed_bytes(C_, self.n_heads, F), dtype=torch.uint8, device=dev)
-            _lib.check(L.axvs_axial_layer_pack(C.byref(ps), buf.data_ptr(), C_, self.n_heads, F, _lib.DTYPES[dt],
-                                               _stream(dev)), "axvs_axial_layer_pack")
-            self._packed, self._packed_key = buf, key
-        return self._packed
+        return _cached_pack(self, "layer", dt, (self,), self._build_pack, sync=False)
+
+    def _build_pack(self, dt: str) -> Tensor:
+        if abs(self.norm1.eps - 1e-5) > 0 or abs(self.norm2.eps - 1e-5) > 0:
+            raise NotImplementedError("axial_vs_amd: LayerNorm eps must be 1e-5")
+        return _pack_weights("axvs_axial_layer", _lib.AxvsAxialLayerParams, axial_layer_params(self),
+                             (self.linear1.in_features, self.n_heads, self.linear1.out_features), dt)
 
     @_guarded
     def forward(self, src: Tensor, pos: Tensor):
@@ -749,8 +747,6 @@ class TemporalTrajectoryAttentionLayer(nn.Module):
         # fixed dropout seed (tests) or None = drawn from torch's CPU generator
         self.recompute = False
         self.dropout_seed: Optional[int] = None
-        self._packed: Optional[Tensor] = None
-        self._packed_key = None
 
     def _dtype(self) -> str:
         if self.mfma_dtype == "f32" or self.linear1.in_features // self.n_heads > 32:
@@ -758,27 +754,9 @@ class TemporalTrajectoryAttentionLayer(nn.Module):
         return self.mfma_dtype or default_operand_dtype()
 
     def _pack(self) -> Tensor:
-        dt = self._dtype()
-        key = _param_key(self, dt)
-        if self._packed is None or key != self._packed_key:
-            L = _lib.lib()
-            C_, F, dev = self.linear1.in_features, self.linear1.out_features, self.linear1.weight.device
-            keep: list = []
-            ps = _lib.AxvsTrajLayerParams()
-            ps.temporal_attn = _traj_struct(self.temporal_attn, keep)
-            for name, t in (("norm1_w", self.norm1.weight), ("norm1_b", self.norm1.bias),
-                            ("linear1_w", self.linear1.weight), ("linear1_b", self.linear1.bias),
-                            ("linear2_w", self.linear2.weight), ("linear2_b", self.linear2.bias),
-                            ("norm2_w", self.norm2.weight), ("norm2_b", self.norm2.bias)):
-                tt = _dev_f32(t.detach(), name)
-                keep.append(tt)
-                setattr(ps, name, tt.data_ptr())
-            buf = torch.empty(L.axvs_traj_layer_packed_bytes(C_, self.n_heads, F), dtype=torch.uint8, device=dev)
-            _lib.check(L.axvs_traj_layer_pack(C.byref(ps), buf.data_ptr(), C_, self.n_heads, F, _lib.DTYPES[dt], _stream(dev)),
-                       "axvs_traj_layer_pack")
-            torch.cuda.current_stream(dev).synchronize()
-            self._packed, self._packed_key = buf, key
-        return self._packed
+        return _cached_pack(self, "layer", self._dtype(), (self,), lambda dt: _pack_weights(
+            "axvs_traj_layer", _lib.AxvsTrajLayerParams, traj_layer_params(self),
+            (self.linear1.in_features, self.n_heads, self.linear1.out_features), dt))
 
     @_guarded
     def forward(self, src: Tensor, pos: Tensor):

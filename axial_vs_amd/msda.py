@@ -23,7 +23,8 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from . import _lib
-from .modules import _dev_f32, _param_key, _require_eval, _stream, _workspace, _guarded
+from ._params import msda_layer_params, msda_params
+from .modules import _cached_pack, _dev_f32, _operand_dtype, _pack_weights, _require_eval, _stream, _workspace, _guarded
 
 
 def _shapes_host(spatial_shapes) -> list:
@@ -110,8 +111,6 @@ class MSDeformAttn(nn.Module):
         self.value_proj = nn.Linear(d_model, d_model)
         self.output_proj = nn.Linear(d_model, d_model)
         self.mfma_dtype = mfma_dtype
-        self._packed = None
-        self._packed_key = None
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -132,35 +131,11 @@ class MSDeformAttn(nn.Module):
         nn.init.xavier_uniform_(self.output_proj.weight.data)
         nn.init.constant_(self.output_proj.bias.data, 0.)
 
-    def _dtype(self) -> str:
-        from . import modules
-        return self.mfma_dtype or modules.default_operand_dtype()
+    _dtype = _operand_dtype
 
     def _pack(self):
-        dt = self._dtype()
-        key = _param_key(self, dt)
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
-        L = _lib.lib()
-        dev = self.value_proj.weight.device
-        keep = []
-
-        def f(t):
-            tt = _dev_f32(t.detach(), "parameter")
-            keep.append(tt)
-            return tt.data_ptr()
-
-        ps = _lib.AxvsMsdaParams()
-        for name in ("value_proj", "sampling_offsets", "attention_weights", "output_proj"):
-            lin = getattr(self, name)
-            setattr(ps, name + "_w", f(lin.weight))
-            setattr(ps, name + "_b", f(lin.bias))
-        buf = torch.empty(L.axvs_msda_packed_bytes(self.d_model, self.n_heads, self.n_levels, self.n_points), dtype=torch.uint8, device=dev)
-        _lib.check(L.axvs_msda_pack(C.byref(ps), buf.data_ptr(), self.d_model, self.n_heads, self.n_levels, self.n_points,
-                                    _lib.DTYPES[dt], _stream(dev)), "axvs_msda_pack")
-        torch.cuda.current_stream(dev).synchronize()
-        self._packed, self._packed_key = buf, key
-        return buf
+        return _cached_pack(self, "msda", self._dtype(), (self,), lambda dt: _pack_weights(
+            "axvs_msda", _lib.AxvsMsdaParams, msda_params(self), (self.d_model, self.n_heads, self.n_levels, self.n_points), dt))
 
     @_guarded
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index=None,
@@ -267,48 +242,17 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
         self.recompute = False
         self.dropout_seed: Optional[int] = None
         self.amp_compute = True
-        self._packed = None
-        self._packed_key = None
 
     @staticmethod
     def with_pos_embed(tensor, pos):
         return tensor if pos is None else tensor + pos
 
-    def _dtype(self) -> str:
-        from . import modules
-        return self.mfma_dtype or modules.default_operand_dtype()
+    _dtype = _operand_dtype
 
     def _pack(self):
-        dt = self._dtype()
-        key = _param_key(self, dt)
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
-        L = _lib.lib()
         a = self.self_attn
-        dev = self.norm1.weight.device
-        keep = []
-
-        def f(t):
-            tt = _dev_f32(t.detach(), "parameter")
-            keep.append(tt)
-            return tt.data_ptr()
-
-        ps = _lib.AxvsMsdaLayerParams()
-        for name in ("value_proj", "sampling_offsets", "attention_weights", "output_proj"):
-            lin = getattr(a, name)
-            setattr(ps.self_attn, name + "_w", f(lin.weight))
-            setattr(ps.self_attn, name + "_b", f(lin.bias))
-        for name in ("norm1", "linear1", "linear2", "norm2"):
-            mod = getattr(self, name)
-            setattr(ps, name + "_w", f(mod.weight))
-            setattr(ps, name + "_b", f(mod.bias))
-        buf = torch.empty(L.axvs_msda_layer_packed_bytes(self.d_model, a.n_heads, a.n_levels, a.n_points, self.d_ffn), dtype=torch.uint8,
-                          device=dev)
-        _lib.check(L.axvs_msda_layer_pack(C.byref(ps), buf.data_ptr(), self.d_model, a.n_heads, a.n_levels, a.n_points, self.d_ffn,
-                                          _lib.DTYPES[dt], _stream(dev)), "axvs_msda_layer_pack")
-        torch.cuda.current_stream(dev).synchronize()
-        self._packed, self._packed_key = buf, key
-        return buf
+        return _cached_pack(self, "layer", self._dtype(), (self,), lambda dt: _pack_weights(
+            "axvs_msda_layer", _lib.AxvsMsdaLayerParams, msda_layer_params(self), (self.d_model, a.n_heads, a.n_levels, a.n_points, self.d_ffn), dt))
 
     def _train_tier_takes(self, src, pos, reference_points, spatial_shapes, padding_mask) -> bool:
         """Whether the training tier (axvs_msda_layer_train_*) runs this call: the dimensions within the bounds its size function

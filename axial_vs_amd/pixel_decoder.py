@@ -12,7 +12,6 @@ token buffers.  Eval only; configurations with spatial layers (with or without t
 from __future__ import annotations
 
 import copy
-import ctypes as C
 import math
 from typing import Dict, List, Optional
 
@@ -21,7 +20,9 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import _lib
-from .modules import PositionEmbeddingSine3D, TemporalEncoder, _dev_f32, _has_hooks, _param_key, _require_eval, _stream, _workspace, _guarded
+from ._params import conv_gn_params
+from .modules import (PositionEmbeddingSine3D, TemporalEncoder, _cached_pack, _dev_f32, _has_hooks, _operand_dtype, _pack_weights, _require_eval, _stream,
+                      _workspace, _guarded)
 from .msda import MSDeformAttn, MSDeformAttnTransformerEncoderLayer
 
 
@@ -298,40 +299,18 @@ class MSDeformAttnPixelDecoder(nn.Module):
         self.cross_clip_training = cross_clip_training
         self.conv_dims = conv_dims
         self.mfma_dtype = mfma_dtype
-        self._packed = None
-        self._packed_key = None
         self._pos_cache = None          # (key, pos 2-D tokens, [pos 3-D per temporal level]) of the last shapes seen
 
-    def _dtype(self) -> str:
-        from . import modules
-        return self.mfma_dtype or modules.default_operand_dtype()
+    _dtype = _operand_dtype
 
     def _pack_projs(self):
-        dt = self._dtype()
-        from .modules import _param_key
-        key = (_param_key(self.input_proj, dt), _param_key(self.output_proj, dt))     # (the cached walk: `.parameters()` costs ~10 us per projection)
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
-        projs = list(self.input_proj) + list(self.output_proj)
-        L = _lib.lib()
-        dev = self.input_proj[0][0].weight.device
-        keep, bufs = [], []
-
-        def f(t):
-            tt = _dev_f32(t.detach(), "parameter")
-            keep.append(tt)
-            return tt.data_ptr()
-
-        for m in projs:
-            cout, cin = m[0].weight.shape[:2]
-            ps = _lib.AxvsConvGnParams(f(m[0].weight), f(m[0].bias), f(m[1].weight), f(m[1].bias))
-            buf = torch.empty(L.axvs_conv1x1_gn_packed_bytes(cin, cout), dtype=torch.uint8, device=dev)
-            _lib.check(L.axvs_conv1x1_gn_pack(C.byref(ps), buf.data_ptr(), cin, cout, _lib.DTYPES[dt], _stream(dev)), "axvs_conv1x1_gn_pack")
-            bufs.append(buf)
-        torch.cuda.current_stream(dev).synchronize()
-        n = len(self.input_proj)
-        self._packed, self._packed_key = (bufs[:n], bufs[n:]), key
-        return self._packed
+        """(packed input projections, packed output projections), one axvs_conv1x1_gn_pack each."""
+        def build(dt):
+            bufs = [_pack_weights("axvs_conv1x1_gn", _lib.AxvsConvGnParams, conv_gn_params(m[0], m[1]), (m[0].in_channels, m[0].out_channels), dt)
+                    for m in list(self.input_proj) + list(self.output_proj)]
+            n = len(self.input_proj)
+            return bufs[:n], bufs[n:]
+        return _cached_pack(self, "projs", self._dtype(), (self.input_proj, self.output_proj), build)
 
     def forward_features(self, features):
         from .modules import _on
@@ -339,10 +318,10 @@ class MSDeformAttnPixelDecoder(nn.Module):
             return self._forward_features(features)
 
     def _forward_features_train(self, features):
-        from .glue_training import conv_gn_train
         """train() mode (WC/msdeformattn.py:404-437, :91-174 under autograd): the 1x1 convolutions + GroupNorm run the library's training tier
         (round 6: axial_vs_amd.glue_training, forward and backward in HIP; rounds 3 - 5 used torch's kernels here), the level embeddings are torch parameters added by torch; the sine embeddings come from the library's kernels (constants); the encoder's layers run
         their training tiers (deformable layers: axvs_msda_layer_train_*; axial-trajectory layers: axvs_axial_layer_train_*)."""
+        from .glue_training import conv_gn_train
         order = self.transformer_spatial_in_features[::-1]
         xs = [features[f] for f in order]
         BT = xs[0].shape[0]

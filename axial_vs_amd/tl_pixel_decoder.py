@@ -15,7 +15,6 @@ LayerNorm / Linear around the plugin's own training path) -- not yet the library
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import List, Optional
 
@@ -25,7 +24,8 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from . import _lib
-from .modules import PositionEmbeddingSine3D, _dev_f32, _param_key, _stream, _workspace, _guarded
+from ._params import conv_gn_params, ffn_params, fpn_level_params
+from .modules import PositionEmbeddingSine3D, _cached_pack, _dev_f32, _operand_dtype, _pack_weights, _param_key, _stream, _workspace, _guarded
 from .tube_link import MultiScaleDeformableAxialTrajectoryAttention
 
 _ATTN = "MultiScaleDeformableAxialTrajectoryAttention"
@@ -175,7 +175,6 @@ class TubeLinkPixelDecoder(nn.Module):
         self.mask_feature = nn.Conv2d(feat_channels, out_channels, kernel_size=1, stride=1, padding=0)  # TL:155-156
         self.num_outs = num_outs
         self.mfma_dtype = mfma_dtype
-        self._packs = {}
         self._pos_cache = None
         self._record_layers = None      # a list: eval forwards append each encoder layer's output rows [BT, S, C] (tests)
         self.init_weights()
@@ -198,67 +197,24 @@ class TubeLinkPixelDecoder(nn.Module):
         # so it keeps the xavier_normal_ sweep above (the reference's behaviour, restated as is)
 
     # ------------------------------------------------------------------ packs
-    def _dtype(self) -> str:
-        from . import modules
-        return self.mfma_dtype or modules.default_operand_dtype()
-
-    def _pack(self, name: str, mods, build):
-        dt = self._dtype()
-        key = tuple(_param_key(m, dt) for m in mods)
-        ent = self._packs.get(name)
-        if ent is not None and ent[0] == key:
-            return ent[1]
-        buf = build(dt)
-        torch.cuda.current_stream(buf.device).synchronize()
-        self._packs[name] = (key, buf)
-        return buf
+    _dtype = _operand_dtype
 
     def _pack_input(self, i: int) -> Tensor:
         m = self.input_convs[i]
-
-        def build(dt):
-            L = _lib.lib()
-            cin, cout = m.conv.in_channels, m.conv.out_channels
-            w = [_dev_f32(t.detach(), "input_convs") for t in (m.conv.weight, m.conv.bias, m.gn.weight, m.gn.bias)]
-            ps = _lib.AxvsConvGnParams(*[t.data_ptr() for t in w])
-            buf = torch.empty(L.axvs_conv1x1_gn_packed_bytes(cin, cout), dtype=torch.uint8, device=w[0].device)
-            _lib.check(L.axvs_conv1x1_gn_pack(C.byref(ps), buf.data_ptr(), cin, cout, _lib.DTYPES[dt], _stream(buf.device)), "axvs_conv1x1_gn_pack")
-            torch.cuda.current_stream(buf.device).synchronize()
-            return buf
-        return self._pack(f"in{i}", [m], build)
+        return _cached_pack(self, f"in{i}", self._dtype(), (m,), lambda dt: _pack_weights(
+            "axvs_conv1x1_gn", _lib.AxvsConvGnParams, conv_gn_params(m.conv, m.gn), (m.conv.in_channels, m.conv.out_channels), dt))
 
     def _pack_ffn(self, k: int) -> Tensor:
         layer = self.encoder.layers[k]
-        fc1, fc2 = layer.ffns[0].layers[0][0], layer.ffns[0].layers[1]
-        n1, n2 = layer.norms[0], layer.norms[1]
-
-        def build(dt):
-            L = _lib.lib()
-            w = [_dev_f32(t.detach(), "ffn") for t in (n1.weight, n1.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, n2.weight, n2.bias)]
-            ps = _lib.AxvsFfnParams(*[t.data_ptr() for t in w])
-            buf = torch.empty(L.axvs_ffn_packed_bytes(self.feat_channels, self.d_ffn), dtype=torch.uint8, device=w[0].device)
-            _lib.check(L.axvs_ffn_pack(C.byref(ps), buf.data_ptr(), self.feat_channels, self.d_ffn, _lib.DTYPES[dt], _stream(buf.device)), "axvs_ffn_pack")
-            torch.cuda.current_stream(buf.device).synchronize()
-            return buf
-        return self._pack(f"ffn{k}", [layer.ffns[0], layer.norms], build)
+        return _cached_pack(self, f"ffn{k}", self._dtype(), (layer.ffns[0], layer.norms), lambda dt: _pack_weights(
+            "axvs_ffn", _lib.AxvsFfnParams, ffn_params(layer), (self.feat_channels, self.d_ffn), dt))
 
     def _pack_fpn(self, i: int) -> Tensor:
         lat, out = self.lateral_convs[i], self.output_convs[i]
-        with_mask = i == 0
-        mods = [lat, out] + ([self.mask_feature] if with_mask else [])
-
-        def build(dt):
-            L = _lib.lib()
-            cin, Cc, Cm = lat.conv.in_channels, self.feat_channels, self.out_channels if with_mask else 0
-            w = [_dev_f32(t.detach(), "fpn") for t in (lat.conv.weight, lat.gn.weight, lat.gn.bias, out.conv.weight, out.gn.weight, out.gn.bias)]
-            if with_mask:
-                w += [_dev_f32(self.mask_feature.weight.detach(), "mask_feature"), _dev_f32(self.mask_feature.bias.detach(), "mask_feature")]
-            ps = _lib.AxvsFpnLevelParams(*([t.data_ptr() for t in w] + [None] * (8 - len(w))))
-            buf = torch.empty(L.axvs_fpn_level_packed_bytes(cin, Cc, Cm), dtype=torch.uint8, device=w[0].device)
-            _lib.check(L.axvs_fpn_level_pack(C.byref(ps), buf.data_ptr(), cin, Cc, Cm, _lib.DTYPES[dt], _stream(buf.device)), "axvs_fpn_level_pack")
-            torch.cuda.current_stream(buf.device).synchronize()
-            return buf
-        return self._pack(f"fpn{i}", mods, build)
+        mask = self.mask_feature if i == 0 else None          # the finest level carries the mask head
+        return _cached_pack(self, f"fpn{i}", self._dtype(), (lat, out) + ((mask,) if i == 0 else ()), lambda dt: _pack_weights(
+            "axvs_fpn_level", _lib.AxvsFpnLevelParams, fpn_level_params(lat, out, mask),
+            (lat.conv.in_channels, self.feat_channels, self.out_channels if i == 0 else 0), dt))
 
     # ------------------------------------------------------------------ forward (TL:187-325)
     def _check_inputs(self, feats) -> None:

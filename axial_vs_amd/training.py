@@ -32,34 +32,12 @@ from torch import Tensor
 
 from . import _lib
 from ._autograd import apply, cast, draw_seed, f32c, grad_buffer, nbytes, place, require_gpu
+from ._params import axial_layer_params, msda_layer_params, traj_layer_params
 
-_TRAJ = ("q", "k", "v", "proj_q", "proj_kv", "proj")
-_TAIL = ("norm1", "linear1", "linear2", "norm2")
-
-
-def layer_parameters(layer) -> List[Tensor]:
-    """The layer's parameters in AxvsAxialLayerParams field order (include/axvs.h)."""
-    ps: List[Tensor] = []
-    for attn in (layer.height_attn, layer.width_attn):
-        for n in _TRAJ:
-            m = getattr(attn, n)
-            ps += [m.weight, m.bias]
-    for n in _TAIL:
-        m = getattr(layer, n)
-        ps += [m.weight, m.bias]
-    return ps
-
-
-def traj_layer_parameters(layer) -> List[Tensor]:
-    """A TemporalTrajectoryAttentionLayer's parameters in AxvsTrajLayerParams field order (include/axvs.h)."""
-    ps: List[Tensor] = []
-    for n in _TRAJ:
-        m = getattr(layer.temporal_attn, n)
-        ps += [m.weight, m.bias]
-    for n in _TAIL:
-        m = getattr(layer, n)
-        ps += [m.weight, m.bias]
-    return ps
+# the parameter lists handed to autograd, in their struct's field order (their names here are part of the tested surface)
+layer_parameters = axial_layer_params
+traj_layer_parameters = traj_layer_params
+msda_layer_parameters = msda_layer_params
 
 
 # the two layers' entry points: (library symbol prefix, parameter struct); `dims` is the size argument list of each
@@ -166,21 +144,6 @@ def traj_layer_train(layer, src: Tensor, pos: Tensor, dropout: bool = True, reco
 
 
 # ---- MSDeformAttnTransformerEncoderLayer (WC/msdeformattn.py:177-216): axvs_msda_layer_train_fwd / _bwd ----------------------------------
-_MSDA = ("value_proj", "sampling_offsets", "attention_weights", "output_proj")
-
-
-def msda_layer_parameters(layer) -> List[Tensor]:
-    """An MSDeformAttnTransformerEncoderLayer's parameters in AxvsMsdaLayerParams field order (include/axvs.h)."""
-    ps: List[Tensor] = []
-    for n in _MSDA:
-        m = getattr(layer.self_attn, n)
-        ps += [m.weight, m.bias]
-    for n in _TAIL:
-        m = getattr(layer, n)
-        ps += [m.weight, m.bias]
-    return ps
-
-
 class _MsdaLayerTrain(torch.autograd.Function):
     """forward / backward of one deformable encoder layer through the library's training tier.  reference_points, the padding
     mask and the spatial shapes are constants (no gradient)."""

@@ -22,7 +22,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import _lib
-from .modules import TubeLinkTemporalEncoder, _dev_f32, _guarded, _param_key, _require_eval, _stream, _workspace
+from ._params import msda_params
+from .modules import TubeLinkTemporalEncoder, _cached_pack, _dev_f32, _guarded, _operand_dtype, _pack_weights, _require_eval, _stream, _workspace
 from .msda import _shapes_host
 
 
@@ -59,8 +60,6 @@ class MultiScaleDeformableAxialTrajectoryAttention(nn.Module):
         if self.skip_connect:
             self.gamma = nn.Parameter(1e-6 * torch.ones(embed_dims), requires_grad=True)
         self.mfma_dtype = mfma_dtype
-        self._packed = None
-        self._packed_key = None
         self.init_weights()
 
     def init_weights(self) -> None:
@@ -81,32 +80,13 @@ class MultiScaleDeformableAxialTrajectoryAttention(nn.Module):
         nn.init.xavier_uniform_(self.output_proj.weight)
         nn.init.constant_(self.output_proj.bias, 0.)
 
-    def _dtype(self) -> str:
-        from . import modules
-        return self.mfma_dtype or modules.default_operand_dtype()
+    _dtype = _operand_dtype
 
     def _pack(self) -> Tensor:
-        dt = self._dtype()
-        key = tuple(_param_key(getattr(self, n), dt) for n in ("value_proj", "sampling_offsets", "attention_weights", "output_proj"))
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
-        L = _lib.lib()
-        dev = self.value_proj.weight.device
-        keep = []
-        ps = _lib.AxvsMsdaParams()
-        for name in ("value_proj", "sampling_offsets", "attention_weights", "output_proj"):
-            lin = getattr(self, name)
-            for suffix, t in (("_w", lin.weight), ("_b", lin.bias)):
-                tt = _dev_f32(t.detach(), name)
-                keep.append(tt)
-                setattr(ps, name + suffix, tt.data_ptr())
-        buf = torch.empty(L.axvs_msda_packed_bytes(self.embed_dims, self.num_heads, self.num_levels, self.num_points), dtype=torch.uint8,
-                          device=dev)
-        _lib.check(L.axvs_msda_pack(C.byref(ps), buf.data_ptr(), self.embed_dims, self.num_heads, self.num_levels, self.num_points,
-                                    _lib.DTYPES[dt], _stream(dev)), "axvs_msda_pack")
-        torch.cuda.current_stream(dev).synchronize()
-        self._packed, self._packed_key = buf, key
-        return buf
+        # (keyed by the four projections alone: the temporal encoder below packs its own layers)
+        return _cached_pack(self, "msda", self._dtype(), (self.value_proj, self.sampling_offsets, self.attention_weights, self.output_proj),
+                            lambda dt: _pack_weights("axvs_msda", _lib.AxvsMsdaParams, msda_params(self),
+                                                     (self.embed_dims, self.num_heads, self.num_levels, self.num_points), dt))
 
     @_guarded
     def forward(self, query: Tensor, key: Optional[Tensor] = None, value: Optional[Tensor] = None, identity: Optional[Tensor] = None,

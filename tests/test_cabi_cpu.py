@@ -269,6 +269,225 @@ def test_cross_clip_module_parameters_are_the_chain_then_the_heads():
     assert len({id(p) for p in ps}) == len(ps)
 
 
+def _field_paths(cls, prefix=""):
+    """dotted paths of a parameter struct's pointer slots in declaration order (nested structs recursively, arrays by element)"""
+    out = []
+    for name, t in cls._fields_:
+        if issubclass(t, ctypes.Structure):
+            out += _field_paths(t, prefix + name + ".")
+        elif issubclass(t, ctypes.Array):
+            out += [f"{prefix}{name}.{k}" for k in range(t._length_)]
+        else:
+            out.append(prefix + name)
+    return out
+
+
+def _by_path(mod, path):
+    """the tensor a field path names on a module whose attributes the struct's fields follow: `a.b_w` -> mod.a.b.weight"""
+    *owners, leaf = path.split(".")
+    for o in owners:
+        mod = getattr(mod, o)
+    attr, kind = leaf.rsplit("_", 1)
+    return getattr(getattr(mod, attr), {"w": "weight", "b": "bias"}[kind])
+
+
+def _tl_decoder(num_layers=1):
+    import axial_vs_amd as ax
+    attn = dict(type="MultiScaleDeformableAxialTrajectoryAttention", embed_dims=256, num_heads=8, num_levels=2, num_temporal_levels=1,
+                num_temporal_layers=1, num_temporal_dim=128, num_points=4)
+    return ax.TubeLinkPixelDecoder(in_channels=[64, 64, 64, 64], encoder=dict(num_layers=num_layers, transformerlayers=dict(
+        attn_cfgs=attn, ffn_cfgs=dict(feedforward_channels=128, num_fcs=2), operation_order=("self_attn", "norm", "ffn", "norm"))))
+
+
+def _cc_module(nl=1, norm_fn="ln"):
+    import axial_vs_amd as ax
+    return ax.CrossClipTrackingModule(num_layers=nl, num_classes=3, attn_drop=0.0, aspp_drop=0.0, kernel_sizes=[3, 3, 3], atrous_rates=[1, 2, 3],
+                                      norm_fn=norm_fn, num_clip_frames=1)
+
+
+def _same(got, want):
+    assert len(got) == len(want), (len(got), len(want))
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a is b, i
+
+
+def _fill_takes_exactly(cls, n):
+    from axial_vs_amd import _lib
+    _lib.fill(cls, range(1, n + 1))
+    for wrong in (n - 1, n + 1):
+        with pytest.raises(ValueError):
+            _lib.fill(cls, range(1, wrong + 1))
+
+
+def test_order_functions_name_each_struct_field_in_declaration_order():
+    """Every function of axial_vs_amd._params returns, slot by slot, the very Parameter its struct's field names -- and as many as
+    _lib.fill takes for that struct."""
+    import axial_vs_amd as ax
+    from axial_vs_amd import _lib, _params as P
+    from axial_vs_amd.pixel_decoder import _conv_gn
+    # structs whose fields follow the module's attribute names: the expected tensor comes from the field path
+    attn = ax.TrajectoryAttention(64, 8)
+    msda = ax.MSDeformAttn(64, 2, 8, 4)
+    plugin = ax.MultiScaleDeformableAxialTrajectoryAttention(embed_dims=64, num_levels=2, num_temporal_dim=128)
+    for cls, fn, mod in ((_lib.AxvsTrajParams, P.traj_params, attn),
+                         (_lib.AxvsAxialLayerParams, P.axial_layer_params, ax.TemporalAxialTrajectoryAttentionLayer(64, 128, n_heads=8)),
+                         (_lib.AxvsTrajLayerParams, P.traj_layer_params, ax.TemporalTrajectoryAttentionLayer(64, 128, n_heads=8)),
+                         (_lib.AxvsMsdaParams, P.msda_params, msda), (_lib.AxvsMsdaParams, P.msda_params, plugin),
+                         (_lib.AxvsMsdaLayerParams, P.msda_layer_params, ax.MSDeformAttnTransformerEncoderLayer(64, 128, n_levels=2, n_heads=8, n_points=4))):
+        paths = _field_paths(cls)
+        _same(fn(mod), [_by_path(mod, p) for p in paths])
+        _fill_takes_exactly(cls, len(paths))
+    # the others: the expected attributes, spelled out here
+    pair = _conv_gn(32, 64)
+    _same(P.conv_gn_params(pair[0], pair[1]), [pair[0].weight, pair[0].bias, pair[1].weight, pair[1].bias])
+    dec = _tl_decoder()
+    cm = dec.input_convs[0]
+    _same(P.conv_gn_params(cm.conv, cm.gn), [cm.conv.weight, cm.conv.bias, cm.gn.weight, cm.gn.bias])
+    _fill_takes_exactly(_lib.AxvsConvGnParams, 4)
+    lay = dec.encoder.layers[0]
+    _same(P.ffn_params(lay), [lay.norms[0].weight, lay.norms[0].bias, lay.ffns[0].layers[0][0].weight, lay.ffns[0].layers[0][0].bias,
+                              lay.ffns[0].layers[1].weight, lay.ffns[0].layers[1].bias, lay.norms[1].weight, lay.norms[1].bias])
+    assert _field_paths(_lib.AxvsFfnParams) == ["norm1_w", "norm1_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b", "norm2_w", "norm2_b"]
+    _fill_takes_exactly(_lib.AxvsFfnParams, 8)
+    assert len(dec.lateral_convs) == 2
+    for i, mask in ((0, dec.mask_feature), (1, None)):
+        lat, out = dec.lateral_convs[i], dec.output_convs[i]
+        _same(P.fpn_level_params(lat, out, mask), [lat.conv.weight, lat.gn.weight, lat.gn.bias, out.conv.weight, out.gn.weight, out.gn.bias,
+                                                   None if mask is None else mask.weight, None if mask is None else mask.bias])
+    assert _field_paths(_lib.AxvsFpnLevelParams) == ["lateral_w", "lateral_gn_w", "lateral_gn_b", "output_w", "output_gn_w", "output_gn_b", "mask_w", "mask_b"]
+    _fill_takes_exactly(_lib.AxvsFpnLevelParams, 8)
+    s = _lib.fill(_lib.AxvsFpnLevelParams, [1, 2, 3, 4, 5, 6, None, None])
+    assert s.mask_w is None and s.mask_b is None and s.output_gn_b == 6
+
+    # cross-clip layer: 21 tensors (fused qkv) for 25 slots; cc_layer_struct places the q / k / v row blocks of the fused projection
+    mod = _cc_module(nl=2)
+    for i in range(2):
+        lay, asp, cn = mod.transformer_trajectory_self_attention_layers[i], mod.conv_short_aggregate_layers[i], mod.conv_norms[i]
+        at, pj = lay.self_attn, asp._proj_conv_bn_act
+        want = {"attn.q_w": (at.qkv.weight, 0), "attn.q_b": (at.qkv.bias, 0), "attn.k_w": (at.qkv.weight, 4 * 256 * 256), "attn.k_b": (at.qkv.bias, 4 * 256),
+                "attn.v_w": (at.qkv.weight, 8 * 256 * 256), "attn.v_b": (at.qkv.bias, 8 * 256), "attn.proj_q_w": (at.proj_q.weight, 0),
+                "attn.proj_q_b": (at.proj_q.bias, 0), "attn.proj_kv_w": (at.proj_kv.weight, 0), "attn.proj_kv_b": (at.proj_kv.bias, 0),
+                "attn.proj_w": (at.proj.weight, 0), "attn.proj_b": (at.proj.bias, 0), "norm_w": (lay.norm.weight, 0), "norm_b": (lay.norm.bias, 0),
+                "aspp_w.0": (asp._aspp_conv0.weight, 0), "aspp_w.1": (asp._aspp_conv1.weight, 0), "aspp_w.2": (asp._aspp_conv2.weight, 0),
+                "aspp_b.0": (asp._aspp_conv0.bias, 0), "aspp_b.1": (asp._aspp_conv1.bias, 0), "aspp_b.2": (asp._aspp_conv2.bias, 0),
+                "aspp_proj_w": (pj.conv.weight, 0), "aspp_norm_w": (pj.norm.weight, 0), "aspp_norm_b": (pj.norm.bias, 0),
+                "conv_norm_w": (cn.weight, 0), "conv_norm_b": (cn.bias, 0)}
+        ps = P.cc_layer_params(mod, i)
+        assert len(ps) == P.CC_PER_LAYER == 21 and len({id(t) for t in ps}) == 21
+        st = P.cc_layer_struct([(k + 1) << 32 for k in range(21)])          # (entry k as a fake address with room for the offsets)
+        paths = _field_paths(_lib.AxvsCCLayerParams)
+        assert sorted(paths) == sorted(want)
+        for path in paths:
+            v = st
+            for part in path.split("."):
+                v = v[int(part)] if part.isdigit() else getattr(v, part)
+            assert ps[(v >> 32) - 1] is want[path][0] and v & 0xffffffff == want[path][1], path
+        _same(P.cc_chain_params(mod, 2)[21 * i:21 * (i + 1)], ps)
+    for wrong in (20, 22):
+        with pytest.raises(ValueError):
+            P.cc_layer_struct(list(range(1, wrong + 1)))
+    # cross-clip heads: the trainable tensors in AxvsCCHeadGrads order; with the running statistics, AxvsCCHeadParams order
+    pr, cp, mp = mod._predictor, mod._class_embedding_projection, mod._mask_embedding_projection
+    want = {"class_proj_w": cp.conv.weight, "class_proj_bn": cp.norm, "mask_proj_w": mp.conv.weight, "mask_proj_bn": mp.norm,
+            "mask_head_w": pr._transformer_mask_head.conv.weight, "mask_head_bn": pr._transformer_mask_head.norm,
+            "class_head_w": pr._transformer_class_head.conv.weight, "class_head_b": pr._transformer_class_head.conv.bias,
+            "act_head_w": pr._transformer_class_activation_head.conv.weight, "act_head_b": pr._transformer_class_activation_head.conv.bias,
+            "pixel_bn": pr._pixel_space_mask_batch_norm}
+    bn_attr = {"w": "weight", "b": "bias", "mean": "running_mean", "var": "running_var"}
+
+    def head_tensor(path):
+        name, _, sub = path.partition(".")
+        return getattr(want[name], bn_attr[sub]) if sub else want[name]
+    heads = P.cc_head_params(mod)
+    _same(heads, [head_tensor(p) for p in _field_paths(_lib.AxvsCCHeadGrads)])
+    _fill_takes_exactly(_lib.AxvsCCHeadGrads, 15)
+    running = [(bn.running_mean, bn.running_var) for bn in P.cc_bn_modules(mod)]
+    _same(P.cc_head_with_running(heads, running), [head_tensor(p) for p in _field_paths(_lib.AxvsCCHeadParams)])
+    _fill_takes_exactly(_lib.AxvsCCHeadParams, 23)
+    _same(P.cc_module_params(mod), P.cc_chain_params(mod, 2) + heads)
+    # Tube-Link head
+    hd = ax.TubeLinkCrossClipHead(num_classes=3, out_channels=128, num_cc_layers=1)
+    pn, me = hd.transformer_decoder.post_norm, hd.mask_embed
+    _same(P.tl_head_params(hd), [pn.weight, pn.bias, hd.activation_proj.weight, hd.activation_proj.bias, hd.cls_embed.weight, hd.cls_embed.bias,
+                                 me[0].weight, me[2].weight, me[4].weight, me[0].bias, me[2].bias, me[4].bias])
+    assert _field_paths(_lib.AxvsTLHeadParams) == ["post_norm_w", "post_norm_b", "activation_proj_w", "activation_proj_b", "cls_embed_w", "cls_embed_b",
+                                                   "mask_embed_w.0", "mask_embed_w.1", "mask_embed_w.2", "mask_embed_b.0", "mask_embed_b.1", "mask_embed_b.2"]
+    _fill_takes_exactly(_lib.AxvsTLHeadParams, 12)
+
+
+def test_training_tier_hands_autograd_the_order_functions_tensors(monkeypatch):
+    """What each training entry point passes to its autograd Function as parameters is, element for element, what the struct's order
+    function returns (the Parameters themselves: autograd accumulates into their .grad)."""
+    import axial_vs_amd as ax
+    from axial_vs_amd import _params as P, cc_training, glue_training, training
+    from axial_vs_amd.pixel_decoder import _conv_gn
+
+    class Handed(Exception):
+        pass
+
+    def record(owner, fn, *args):
+        raise Handed(args)
+
+    def handed(call, *args, **kw):
+        with pytest.raises(Handed) as e:
+            call(*args, **kw)
+        return e.value.args[0]
+
+    monkeypatch.setattr(training, "apply", record)
+    monkeypatch.setattr(cc_training, "apply", record)
+    monkeypatch.setattr(glue_training._ConvGnTrain, "apply", staticmethod(lambda *args: record(None, None, *args)))
+    src, pos = torch.zeros(2, 12, 64), torch.zeros(1, 2, 3, 4, 64)
+    layer = ax.TemporalAxialTrajectoryAttentionLayer(64, 128, n_heads=8)
+    want = P.axial_layer_params(layer)
+    assert len(want) == 32
+    _same(handed(training.axial_layer_train, layer, src, pos)[-32:], want)
+    _same(training.layer_parameters(layer), want)
+    layer = ax.TemporalTrajectoryAttentionLayer(64, 128, n_heads=8)
+    _same(handed(training.traj_layer_train, layer, src, pos)[-20:], P.traj_layer_params(layer))
+    _same(training.traj_layer_parameters(layer), P.traj_layer_params(layer))
+    layer = ax.MSDeformAttnTransformerEncoderLayer(64, 128, n_levels=1, n_heads=8, n_points=4)
+    _same(handed(training.msda_layer_train, layer, torch.zeros(1, 12, 64), None, torch.zeros(1, 12, 1, 2), [(3, 4)])[-16:], P.msda_layer_params(layer))
+    nl = 2
+    mod = _cc_module(nl)
+    want = P.cc_module_params(mod)
+    assert len(want) == nl * 21 + 15
+    _same(handed(cc_training.cc_module_train, mod, torch.zeros(1, 16, 2, 256), torch.zeros(1, 128, 2, 4, 8))[-len(want):], want)
+    _same(cc_training.module_parameters(mod), want)
+    _same(cc_training.chain_parameters(mod, nl), want[:nl * 21])
+    _same(handed(cc_training.cc_layers_train, mod, torch.zeros(1, 16, 2, 256), nl, [1, 2, 3], 0.0, 0.0)[-nl * 21:], P.cc_chain_params(mod, nl))
+    hd = ax.TubeLinkCrossClipHead(num_classes=3, out_channels=128, num_cc_layers=1)
+    cfg = cc_training.tl_heads_cfg(1, 1, 16, 2, 1, 4, 8, 4, 128)
+    _same(handed(cc_training.tl_heads_train, hd, torch.zeros(1, 1, 16, 2, 256), torch.zeros(1, 2, 128, 4, 8), cfg)[-12:], P.tl_head_params(hd))
+    _same(cc_training.tl_heads_parameters(hd), P.tl_head_params(hd))
+    pair = _conv_gn(32, 64)
+    _same(handed(glue_training.conv_gn_train, torch.zeros(1, 32, 3, 4), pair[0], pair[1])[1:5], P.conv_gn_params(pair[0], pair[1]))
+
+
+def test_invalidate_pack_clears_every_stored_blob():
+    """Every pack site keeps its blobs in the same slot of its owner's __dict__ (not a buffer: state dicts do not see it);
+    invalidate_pack empties that slot on a module and on all its children -- both pixel decoders included."""
+    import axial_vs_amd as ax
+    from axial_vs_amd import modules
+    z, m = load("g8_pixel_decoder_T2_S2")
+    wc = _decoder_from_meta(m)
+    owners = [ax.TrajectoryAttention(64, 8), ax.TemporalAxialTrajectoryAttentionLayer(64, 128, n_heads=8),
+              ax.TemporalTrajectoryAttentionLayer(64, 128, n_heads=8), ax.MSDeformAttn(64, 2, 8, 4),
+              ax.MSDeformAttnTransformerEncoderLayer(64, 128, n_levels=2, n_heads=8, n_points=4),
+              ax.MultiScaleDeformableAxialTrajectoryAttention(embed_dims=64, num_levels=2, num_temporal_dim=128), _cc_module(),
+              ax.TubeLinkCrossClipHead(num_classes=3, out_channels=128, num_cc_layers=1), wc.within_clip_tracking_module, _tl_decoder()]
+    sentinel = object()
+    keys_before = [set(o.state_dict()) for o in owners]
+    for o in owners:
+        o.__dict__[modules._PACKS] = {"slot": ("key", sentinel), "other": ("key", sentinel)}
+    assert [set(o.state_dict()) for o in owners] == keys_before
+    parent = torch.nn.ModuleList([torch.nn.ModuleList(owners[:5]), *owners[5:-1], wc])       # (the within-clip decoder as a grandchild)
+    ax.invalidate_pack(parent)
+    ax.invalidate_pack(owners[-1])
+    for o in owners:
+        assert modules._PACKS not in o.__dict__, type(o).__name__
+        assert not any(v is sentinel for v in o.__dict__.values())
+
+
 def test_reference_extension_stand_in_exposes_the_two_entry_points():
     """`import MultiScaleDeformableAttention as MSDA` (OPS/functions/ms_deform_attn_func.py:22) resolves to the stand-in module and
     finds ms_deform_attn_forward / ms_deform_attn_backward with the extension's argument lists (OPS/src/ms_deform_attn.h:24-67)."""
