@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("AXVS_LIB_PATH") or os.path.join(_HERE, "libaxvs.so")
 
 AXVS_F16 = 0
 AXVS_BF16 = 1
+AXVS_F32 = 2      # fp32 / uint8 inputs: only where an entry point says so (axvs_video_matcher)
+AXVS_U8 = 3
 DTYPES = {"f16": AXVS_F16, "fp16": AXVS_F16, "float16": AXVS_F16, "bf16": AXVS_BF16, "bfloat16": AXVS_BF16}
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -233,6 +235,10 @@ SIGNATURES = {
     "axvs_match_embds": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp, C.c_size_t, _fp]),
     "axvs_match_clips_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "axvs_match_clips": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [_fp, C.c_size_t, _fp]),
+    "axvs_linear_sum_assignment_rect": (C.c_int, [_fp, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp, C.c_int, _fp]),
+    "axvs_video_matcher_workspace_bytes": (C.c_size_t, [C.c_int] * 4 + [C.c_longlong]),
+    "axvs_video_matcher": (C.c_int, [C.POINTER(_fp), C.c_int, C.POINTER(_fp), _fp, C.c_int, _fp, C.POINTER(C.c_int)] + [C.c_int] * 4 +
+                           [C.c_longlong, C.c_int, C.c_int] + [_fp] * 5 + [_fp, C.c_size_t, _fp]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

@@ -266,6 +266,147 @@ __global__ __launch_bounds__(64) void lsap_kernel(const float* __restrict__ cost
   }
 }
 
+// Rectangular problems (prediction-to-ground-truth matching: nr queries x nc objects, nc != nr almost always): the same
+// restatement, one wave per problem, on the `R x n` WORKING problem with R = min(nr, nc) rows and n = max(nr, nc) columns -- SciPy
+// solves a tall matrix on its transpose, so there are R augmentations over n columns either way.  The scan order through
+// `remaining`, the tie rule and the dual updates are those of lsap_kernel above (its `n` is the working column count here).
+// Problems of one launch share nr and the leading dimension; the column count of problem z is counts.nc[z] (kernel argument:
+// the caller knows the object counts on the host, so they need neither a copy nor a device buffer) or nc_max for all.
+// Output like scipy.optimize.linear_sum_assignment: (row_ind, col_ind) sorted by row, min(nr, nc) pairs, the rest of the kmax
+// slots -1.  LDS_COST: the working matrix is staged in LDS in working orientation (row stride n), read from global in memory order.
+constexpr int kLsapCountsPerLaunch = 256;
+struct LsapCounts {
+  unsigned short nc[kLsapCountsPerLaunch];
+};
+template <int CPL, bool LDS_COST>
+__global__ __launch_bounds__(64) void lsap_rect_kernel(const float* __restrict__ cost_all, long long ld, int nr0, int nc_max, LsapCounts counts,
+                                                       int use_counts, long long* __restrict__ rows_all, long long* __restrict__ cols_all, int kmax) {
+  extern __shared__ float scost[];
+  __shared__ double u[kLsapMax];
+  __shared__ int path[kLsapMax], row4col_m[kLsapMax], col4row[kLsapMax];
+  const int lane = threadIdx.x;
+  const double INF = __builtin_huge_val();
+  const int nc0 = use_counts ? (int)counts.nc[blockIdx.x] : nc_max;
+  const float* gcost = cost_all + (long long)blockIdx.x * nr0 * ld;
+  long long* rows = rows_all + (long long)blockIdx.x * kmax;
+  long long* cols = cols_all + (long long)blockIdx.x * kmax;
+  const bool tr = nc0 < nr0;
+  const int R = tr ? nc0 : nr0, n = tr ? nr0 : nc0;
+  for (int k = R + lane; k < kmax; k += 64) { rows[k] = -1; cols[k] = -1; }
+  if (R == 0) return;
+  if (LDS_COST) {
+    for (int idx = lane; idx < nr0 * nc0; idx += 64) {
+      const int a = idx / nc0, b = idx - a * nc0;
+      scost[tr ? b * n + a : idx] = gcost[(long long)a * ld + b];
+    }
+  }
+  const float* cost = LDS_COST ? scost : gcost;
+  const long long rs = LDS_COST ? n : (tr ? 1 : ld), cs = LDS_COST ? 1 : (tr ? ld : 1);   // working (i, j) -> cost[i * rs + j * cs]
+  for (int i = lane; i < n; i += 64) { row4col_m[i] = -1; path[i] = -1; }
+  for (int i = lane; i < R; i += 64) { u[i] = 0.0; col4row[i] = -1; }
+  double v[CPL], spc[CPL];
+  int row4col[CPL], pos[CPL];
+  bool removed[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) { v[c] = 0.0; row4col[c] = -1; }
+  __syncthreads();
+  for (int curRow = 0; curRow < R; ++curRow) {
+    // ---- augmenting_path ----
+    double minVal = 0.0;
+    int num_remaining = n;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int j = lane + 64 * c;
+      pos[c] = n - 1 - j;                              // remaining[it] = n - it - 1
+      removed[c] = j >= n;
+      spc[c] = INF;
+    }
+    int sink = -1, i = curRow;
+    while (sink == -1) {
+      const double ui = u[i];
+      const float* crow = cost + (long long)i * rs;
+      LsapCand best{INF, 0x7fffffff};
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const int j = lane + 64 * c;
+        if (!removed[c]) {
+          const double r = minVal + (double)crow[j * cs] - ui - v[c];
+          if (r < spc[c]) { path[j] = i; spc[c] = r; }
+          const LsapCand cand{spc[c], lsap_key(row4col[c] == -1, pos[c])};
+          if (lsap_better(cand, best)) best = cand;
+        }
+      }
+      minVal = lsap_wave_min_f64(best.v);
+      if (minVal == INF) { sink = -2; break; }         // infeasible (cannot happen with finite costs)
+      const int k2 = lsap_wave_min_i32(best.v == minVal ? best.k2 : 0x7fffffff);
+      const int index = k2 < 0 ? -1 - k2 : k2;
+      int wj = -1, wr = -1;
+      const int last = num_remaining - 1;
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        if (!removed[c]) {
+          if (pos[c] == index) { wj = lane + 64 * c; wr = row4col[c]; removed[c] = true; }
+          else if (pos[c] == last) pos[c] = index;
+        }
+      }
+      const unsigned long long m = __ballot(wj >= 0);
+      const int wl = __builtin_ctzll(m);
+      const int j = __builtin_amdgcn_readlane(wj, wl);
+      const int r4c = __builtin_amdgcn_readlane(wr, wl);
+      if (r4c == -1) sink = j; else i = r4c;
+      --num_remaining;
+    }
+    if (sink < 0) break;
+    // ---- update the dual variables ----
+    if (lane == 0) u[curRow] += minVal;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int j = lane + 64 * c;
+      if (removed[c] && j < n) {
+        if (j != sink) u[row4col[c]] += minVal - spc[c];
+        v[c] -= minVal - spc[c];
+      }
+    }
+    __syncthreads();
+    // ---- augment the previous solution ----
+    if (lane == 0) {
+      int j = sink;
+      while (true) {
+        const int r = path[j];
+        row4col_m[j] = r;
+        const int t = col4row[r];
+        col4row[r] = j;
+        j = t;
+        if (r == curRow) break;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int j = lane + 64 * c;
+      if (j < n) row4col[c] = row4col_m[j];
+    }
+  }
+  __syncthreads();
+  if (!tr) {
+    for (int r = lane; r < R; r += 64) { rows[r] = r; cols[r] = col4row[r]; }
+  } else {
+    // working columns are the caller's rows: the assigned ones in increasing order (SciPy: argsort of the transposed col4row)
+    int base = 0;
+    for (int j0 = 0; j0 < n; j0 += 64) {
+      const int j = j0 + lane;
+      const int r = j < n ? row4col_m[j] : -1;
+      const unsigned long long m = __ballot(r != -1);
+      if (r != -1) {
+        const int k = base + __popcll(m & ((1ull << lane) - 1ull));
+        rows[k] = j;
+        cols[k] = r;
+      }
+      base += __popcll(m);
+    }
+  }
+}
+
 // rows of x [R][C] divided by their norm (`x / x.norm(dim=1)[:, None]`), one wave per row
 __global__ __launch_bounds__(256) void normalize_rows1_kernel(const float* __restrict__ x_all, float* __restrict__ out, long long R, int C) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);

@@ -28,6 +28,8 @@ extern "C" {
 
 #define AXVS_F16 0
 #define AXVS_BF16 1
+#define AXVS_F32 2  /* fp32 / uint8 (bool) inputs: only where an entry point says so (axvs_video_matcher) */
+#define AXVS_U8 3
 
 #define AXVS_OK 0
 #define AXVS_ERR_ARG (-1)       /* bad shape / null pointer / unsupported configuration */
@@ -489,6 +491,33 @@ int axvs_match_embds(const float* tgt_embds, const float* cur_embds, long long* 
 size_t axvs_match_clips_workspace_bytes(int V, int Tc, int Q, int C);
 int axvs_match_clips(const float* mask_embeddings, long long* indices, int V, int Tc, int Q, int C, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* ---- Prediction-to-ground-truth matching (VideoHungarianMatcher, maxtron_deeplab/modeling/matcher.py:48-124) on the device.
+ *      axvs_linear_sum_assignment_rect: `batch` problems of nr rows; problem z is cost + z*nr*ld (fp32, row stride ld >= nc_max) and has
+ *      nc_per_problem[z] columns (a HOST array; NULL: nc_max for all).  (rows_out, cols_out) int64 [batch][min(nr, nc_max)] =
+ *      scipy.optimize.linear_sum_assignment(cost_z): min(nr, nc_z) pairs sorted by row, the unused tail -1.  nr in 1..512, nc in 0..512
+ *      (nc_max == 0: nothing is written); otherwise AXVS_ERR_ARG.  Costs must be finite (SciPy raises on NaN / -inf; the kernel
+ *      does not look).
+ *      axvs_video_matcher: all (layer, video) problems of a training step in one call, no host synchronisation.
+ *        pred_masks / pred_logits  HOST arrays of L device pointers: layer l's masks [B][Q][P] (mask_dtype AXVS_F16 / AXVS_BF16 / AXVS_F32,
+ *                                  P = T*H*W) and logits fp32 [B][Q][K1] (K1 = K + 1: the void class last)
+ *        targets, labels           the videos' ground truth concatenated along M: masks [sum M_b][P] (target_dtype AXVS_U8 for bool / uint8,
+ *                                  or AXVS_F32) and int64 labels [sum M_b] (a label outside 0..K-1 is clamped; the reference raises)
+ *        m_per_video               HOST array of B object counts (0 allowed), M_max their maximum
+ *        sims                      fp32 [3][L*B][Q][M_max]: mask similarity, class similarity, cost = -mask_sim * class_sim (columns >= M_b zero)
+ *        rows_out, cols_out        int64 [L*B][min(Q, M_max)], problem (l, b) at l*B + b: min(Q, M_b) pairs, the tail -1
+ *        matched_dice, matched_cls fp32 [L*B][min(Q, M_max)]: mask / class similarity at the matched pairs (tail 0)
+ *      L <= 16, B <= 64, Q and M_max <= 512 with ceil32(Q) + ceil32(M_max) <= 576, otherwise AXVS_ERR_ARG.  pred_masks is read ONCE
+ *      while ceil(Q/32) * ceil(M_max/32) <= 16 (the 32 x 32 output blocks one workgroup accumulates: Q = 128 with M <= 128, Q = 256
+ *      with M <= 64); beyond that the blocks are split into chunks of 16 over the grid and every chunk reads the logits and
+ *      redoes the softmax of its pixels (2 chunks: two passes). */
+int axvs_linear_sum_assignment_rect(const float* cost, long long ld, int nr, int nc_max, const int* nc_per_problem, long long* rows_out,
+                                    long long* cols_out, int batch, void* stream);
+size_t axvs_video_matcher_workspace_bytes(int L, int B, int Q, int M_max, long long P);
+int axvs_video_matcher(const void* const* pred_masks, int mask_dtype, const float* const* pred_logits, const void* targets, int target_dtype,
+                       const long long* labels, const int* m_per_video, int L, int B, int Q, int K1, long long P, int M_max, int masking_void_pixel,
+                       float* sims, long long* rows_out, long long* cols_out, float* matched_dice, float* matched_cls, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- PositionEmbeddingSine3D.forward(x, mask=None) in channels-last form
  *      WC/pos_embeddings.py:86-130: pos fp32 [B,T,H,W,C], C = 2*num_pos_feats. */
