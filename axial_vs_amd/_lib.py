@@ -239,6 +239,12 @@ SIGNATURES = {
     "axvs_video_matcher_workspace_bytes": (C.c_size_t, [C.c_int] * 4 + [C.c_longlong]),
     "axvs_video_matcher": (C.c_int, [C.POINTER(_fp), C.c_int, C.POINTER(_fp), _fp, C.c_int, _fp, C.POINTER(C.c_int)] + [C.c_int] * 4 +
                            [C.c_longlong, C.c_int, C.c_int] + [_fp] * 5 + [_fp, C.c_size_t, _fp]),
+    "axvs_set_criterion_saved_bytes": (C.c_size_t, [C.c_int] * 3),
+    "axvs_set_criterion_workspace_bytes": (C.c_size_t, [C.c_int] * 4 + [C.c_longlong]),
+    "axvs_set_criterion_fwd": (C.c_int, [C.POINTER(_fp), C.POINTER(_fp), _fp, C.c_int, _fp, C.POINTER(C.c_int)] + [_fp] * 4 + [C.c_int] * 5 +
+                               [C.c_longlong, C.c_int, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
+    "axvs_set_criterion_bwd": (C.c_int, [_fp, C.POINTER(_fp), C.POINTER(_fp), _fp, C.c_int, C.POINTER(C.c_int)] + [C.c_int] * 4 +
+                               [C.c_longlong, C.c_int, C.c_int, _fp, C.POINTER(_fp), C.POINTER(_fp), _fp]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

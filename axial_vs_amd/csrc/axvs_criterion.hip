@@ -1,0 +1,150 @@
+// C-ABI entry points of the set criterion (include/axvs.h: axvs_set_criterion_*) and the launch sequences behind them.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include "axvs_host.h"
+#include "axvs_criterion.h"
+
+using namespace axvs;
+
+namespace {
+
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+int last_launch_status() {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(AXVS_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
+  return AXVS_OK;
+}
+
+// workgroups per problem of the pixel kernels: two per CU over all problems, at least 4 pixel tiles each (a workgroup ends with one
+// cross-lane reduction per query, about a tile's worth of work), and at most 2^22 pixels each (the nonzero count of a workgroup is
+// kept in fp32)
+struct CritPlan { int npb, tiles_per_wg; };
+CritPlan crit_plan(int nprob, long long P) {
+  const long long ntiles = (P + kCritTP - 1) / kCritTP;
+  long long npb = std::min<long long>((512 + nprob - 1) / nprob, (ntiles + 3) / 4);
+  npb = std::max<long long>(npb, (ntiles + 65535) / 65536);
+  npb = std::max<long long>(npb, 1);
+  const long long per = (ntiles + npb - 1) / npb;
+  return {(int)((ntiles + per - 1) / per), (int)per};
+}
+
+int crit_check_shape(int L, int B, int N, int K1, long long P) {
+  if (L <= 0 || L > kCritMaxLayers || B <= 0 || B > kCritMaxVideos)
+    return fail(AXVS_ERR_ARG, "L=%d must be in 1..%d and B=%d in 1..%d", L, kCritMaxLayers, B, kCritMaxVideos);
+  if (N <= 0 || N > kCritMaxN) return fail(AXVS_ERR_ARG, "N=%d queries must be in 1..%d (the assignment kernel's bound)", N, kCritMaxN);
+  if (K1 < 2 || P <= 0 || P > (1ll << 40)) return fail(AXVS_ERR_ARG, "need K + 1 = %d >= 2 logits and P = %lld >= 1 pixels", K1, P);
+  return AXVS_OK;
+}
+
+int fill_args(CritArgs& a, const float* const* pred_masks, const float* const* pred_logits, const int* m_per_video, int L, int B, int* total) {
+  memset(&a, 0, sizeof(a));
+  if (!pred_masks || !pred_logits || !m_per_video) return fail(AXVS_ERR_ARG, "null pointer");
+  int off = 0;
+  for (int b = 0; b < B; ++b) {
+    if (m_per_video[b] < 0 || m_per_video[b] > kCritMaxM) return fail(AXVS_ERR_ARG, "m_per_video[%d]=%d is outside 0..%d", b, m_per_video[b], kCritMaxM);
+    a.m[b] = m_per_video[b];
+    a.off[b] = off;
+    off += m_per_video[b];
+  }
+  for (int l = 0; l < L; ++l) {
+    if (!pred_masks[l] || !pred_logits[l]) return fail(AXVS_ERR_ARG, "null pointer (layer %d)", l);
+    a.masks[l] = pred_masks[l];
+    a.logits[l] = pred_logits[l];
+  }
+  *total = off;
+  return AXVS_OK;
+}
+
+}  // namespace
+
+size_t axvs_set_criterion_saved_bytes(int L, int B, int N) {
+  if (L <= 0 || L > kCritMaxLayers || B <= 0 || B > kCritMaxVideos || N <= 0 || N > kCritMaxN) {
+    fail(AXVS_ERR_ARG, "L=%d must be in 1..%d, B=%d in 1..%d and N=%d in 1..%d", L, kCritMaxLayers, B, kCritMaxVideos, N, kCritMaxN);
+    return 0;
+  }
+  return align_up((size_t)crit_saved_words(L, B, N) * 4);
+}
+
+size_t axvs_set_criterion_workspace_bytes(int L, int B, int N, int K1, long long P) {
+  if (crit_check_shape(L, B, N, K1, P)) return 0;
+  const CritPlan pl = crit_plan(L * B, P);
+  return align_up((size_t)L * B * pl.npb * crit_part_stride(N) * sizeof(float));
+}
+
+int axvs_set_criterion_fwd(const float* const* pred_masks, const float* const* pred_logits, const void* targets, int target_dtype,
+                           const long long* labels, const int* m_per_video, const long long* rows, const long long* cols,
+                           const float* matched_dice, const float* matched_cls, int kmax, int L, int B, int N, int K1, long long P,
+                           int masking_void_pixel, int share_final_matching, float* losses, void* saved, void* workspace,
+                           long long workspace_bytes, void* stream) {
+  if (int rc = crit_check_shape(L, B, N, K1, P)) return rc;
+  if (target_dtype != AXVS_F32 && target_dtype != AXVS_U8) return fail(AXVS_ERR_ARG, "target dtype %d is not AXVS_F32 / AXVS_U8", target_dtype);
+  CritArgs a;
+  int total = 0;
+  if (int rc = fill_args(a, pred_masks, pred_logits, m_per_video, L, B, &total)) return rc;
+  if (kmax < 0 || kmax > N) return fail(AXVS_ERR_ARG, "kmax=%d pairs per problem must be in 0..N=%d", kmax, N);
+  if (!losses || !saved || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
+  if (kmax > 0 && (!targets || !labels || !rows || !cols || !matched_dice || !matched_cls)) return fail(AXVS_ERR_ARG, "null pointer");
+  const size_t need = axvs_set_criterion_workspace_bytes(L, B, N, K1, P);
+  if (workspace_bytes < 0 || (size_t)workspace_bytes < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, need);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nprob = L * B, share = share_final_matching != 0, masking = masking_void_pixel != 0;
+  const CritPlan pl = crit_plan(nprob, P);
+  const CritSaved s = crit_saved_views(saved, L, B, N);
+  float* part = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(criterion_index_kernel, dim3((share ? 1 : L) * B), dim3(256), 0, st, a, rows, cols, matched_dice, matched_cls, labels, B, N, K1, kmax, s);
+  const dim3 grid(pl.npb, nprob);
+#define AXVS_CRIT_FWD(KERNEL)                                                                                                              \
+  do {                                                                                                                                     \
+    if (target_dtype == AXVS_U8) hipLaunchKernelGGL(KERNEL<kCritU8>, grid, dim3(256), 0, st, a, targets, (const int*)s.inv, B, N, P,    \
+                                                    pl.tiles_per_wg, masking, share, part);                                                \
+    else hipLaunchKernelGGL(KERNEL<kCritF32>, grid, dim3(256), 0, st, a, targets, (const int*)s.inv, B, N, P, pl.tiles_per_wg, masking, \
+                            share, part);                                                                                                  \
+  } while (0)
+  if (N <= 4 * kCritNPW) AXVS_CRIT_FWD(criterion_fwd_kernel);
+  else AXVS_CRIT_FWD(criterion_fwd_any_kernel);
+#undef AXVS_CRIT_FWD
+  hipLaunchKernelGGL(criterion_finish_kernel, dim3(L), dim3(256), 0, st, a, (const float*)part, pl.npb, B, N, K1, masking, share, s, losses);
+  return last_launch_status();
+}
+
+int axvs_set_criterion_bwd(const float* grad_losses, const float* const* pred_masks, const float* const* pred_logits, const void* targets,
+                           int target_dtype, const int* m_per_video, int L, int B, int N, int K1, long long P, int masking_void_pixel,
+                           int share_final_matching, const void* saved, float* const* d_pred_masks, float* const* d_pred_logits, void* stream) {
+  if (int rc = crit_check_shape(L, B, N, K1, P)) return rc;
+  if (target_dtype != AXVS_F32 && target_dtype != AXVS_U8) return fail(AXVS_ERR_ARG, "target dtype %d is not AXVS_F32 / AXVS_U8", target_dtype);
+  CritArgs a;
+  int total = 0;
+  if (int rc = fill_args(a, pred_masks, pred_logits, m_per_video, L, B, &total)) return rc;
+  if (!grad_losses || !saved || !d_pred_masks || !d_pred_logits) return fail(AXVS_ERR_ARG, "null pointer");
+  if (total > 0 && !targets) return fail(AXVS_ERR_ARG, "null pointer");
+  bool any_masks = false, any_logits = false;
+  for (int l = 0; l < L; ++l) {
+    a.dmasks[l] = d_pred_masks[l];
+    a.dlogits[l] = d_pred_logits[l];
+    any_masks |= d_pred_masks[l] != nullptr;
+    any_logits |= d_pred_logits[l] != nullptr;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nprob = L * B, share = share_final_matching != 0, masking = masking_void_pixel != 0;
+  const CritPlan pl = crit_plan(nprob, P);
+  const CritSaved s = crit_saved_views(const_cast<void*>(saved), L, B, N);
+  const dim3 grid(pl.npb, nprob);
+#define AXVS_CRIT_BWD(KERNEL)                                                                                                              \
+  do {                                                                                                                                     \
+    if (target_dtype == AXVS_U8) hipLaunchKernelGGL(KERNEL<kCritU8>, grid, dim3(256), 0, st, a, targets, grad_losses, B, N, P,          \
+                                                    pl.tiles_per_wg, masking, share, s);                                                   \
+    else hipLaunchKernelGGL(KERNEL<kCritF32>, grid, dim3(256), 0, st, a, targets, grad_losses, B, N, P, pl.tiles_per_wg, masking, share, s); \
+  } while (0)
+  if (any_masks) {
+    if (N <= 4 * kCritNPW) AXVS_CRIT_BWD(criterion_bwd_kernel);
+    else AXVS_CRIT_BWD(criterion_bwd_any_kernel);
+  }
+#undef AXVS_CRIT_BWD
+  const int nrows = nprob * N;
+  if (any_logits) hipLaunchKernelGGL(criterion_logits_bwd_kernel, dim3((nrows + 3) / 4), dim3(256), 0, st, a, grad_losses, B, N, K1, s, nrows);
+  return last_launch_status();
+}

@@ -59,8 +59,31 @@ def _mask_dtype(t: Tensor) -> int:
     return {torch.float32: _lib.AXVS_F32, torch.float16: _lib.AXVS_F16, torch.bfloat16: _lib.AXVS_BF16}[t.dtype]
 
 
-def _run_matcher(layers: List[Dict[str, Tensor]], targets: List[Dict[str, Tensor]], masking_void_pixel: bool):
-    """All (layer, video) problems in one library call.  Returns (m, Q, sims [3, L*B, Q, M_max], rows, cols, dice, cls [L*B, min(Q, M_max)])."""
+def _cat_targets(targets: List[Dict[str, Tensor]], m: List[int], P: int, mdt: torch.dtype) -> Tuple[Tensor, Tensor]:
+    """The videos' ground truth concatenated along M, as the library takes it: masks [sum M_b, P] (uint8 for bool / uint8 targets,
+    else fp32 through `mdt`) and int64 labels [sum M_b].  Videos without objects contribute nothing."""
+    tm, tl = [], []
+    for t, mb in zip(targets, m):
+        gm, gl = t["masks"], t["labels"]
+        if mb == 0:
+            continue
+        if gm.shape[0] != mb or gm[0].numel() != P:
+            raise RuntimeError(f"target masks {tuple(gm.shape)} do not match {mb} labels and {P} predicted pixels")
+        if gm.dtype == torch.bool:
+            gm = gm.view(torch.uint8) if gm.is_contiguous() else gm.to(torch.uint8)
+        elif gm.dtype != torch.uint8:
+            gm = gm.to(mdt).float()            # matcher.py:81,83: `.to(out_mask)` then `.float()`
+        tm.append(gm.flatten(1))
+        tl.append(gl.to(torch.int64))
+    if len({x.dtype for x in tm}) > 1:
+        tm = [x.float() for x in tm]
+    tcat = (tm[0] if len(tm) == 1 else torch.cat(tm)).contiguous()
+    lcat = (tl[0] if len(tl) == 1 else torch.cat(tl)).contiguous()
+    return tcat, lcat
+
+
+def _run_matcher(layers: List[Dict[str, Tensor]], targets: List[Dict[str, Tensor]], masking_void_pixel: bool, cat=None):
+    """All (layer, video) problems in one library call (`cat`: the caller's `_cat_targets` result, when it has one).  Returns (m, Q, sims [3, L*B, Q, M_max], rows, cols, dice, cls [L*B, min(Q, M_max)])."""
     masks, logits = [], []
     for o in layers:
         pm, pl = o["pred_masks"], o["pred_logits"]
@@ -93,23 +116,7 @@ def _run_matcher(layers: List[Dict[str, Tensor]], targets: List[Dict[str, Tensor
     sims = torch.empty(3, nprob, Q, M_max, dtype=torch.float32, device=dev)
     if M_max == 0:
         return m, Q, sims, rows, cols, dice, cls
-    tm, tl = [], []
-    for t, mb in zip(targets, m):
-        gm, gl = t["masks"], t["labels"]
-        if mb == 0:
-            continue
-        if gm.shape[0] != mb or gm[0].numel() != P:
-            raise RuntimeError(f"target masks {tuple(gm.shape)} do not match {mb} labels and {P} predicted pixels")
-        if gm.dtype == torch.bool:
-            gm = gm.view(torch.uint8) if gm.is_contiguous() else gm.to(torch.uint8)
-        elif gm.dtype != torch.uint8:
-            gm = gm.to(mdt).float()            # matcher.py:81,83: `.to(out_mask)` then `.float()`
-        tm.append(gm.flatten(1))
-        tl.append(gl.to(torch.int64))
-    if len({x.dtype for x in tm}) > 1:
-        tm = [x.float() for x in tm]
-    tcat = (tm[0] if len(tm) == 1 else torch.cat(tm)).contiguous()
-    lcat = (tl[0] if len(tl) == 1 else torch.cat(tl)).contiguous()
+    tcat, lcat = cat if cat is not None else _cat_targets(targets, m, P, mdt)
     Lb = _lib.lib()
     st = _stream(dev)
     ws = _workspace(dev, Lb.axvs_video_matcher_workspace_bytes(L, B, Q, M_max, P), st)

@@ -519,6 +519,33 @@ int axvs_video_matcher(const void* const* pred_masks, int mask_dtype, const floa
                        float* sims, long long* rows_out, long long* cols_out, float* matched_dice, float* matched_cls, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- The set criterion's `labels` and `masks` losses and their gradients (MaXTronCCSetCriterion / MaXTronWCSetCriterion,
+ *      maxtron_deeplab/modeling/cc_criterion.py:144-200, :237-266, :338-412) on top of axvs_video_matcher's device indices: all
+ *      (layer, video) problems of a step per call, no host synchronisation, no atomics (results are run-to-run identical), and no
+ *      [B][N][P] temporary besides the gradient itself.  Layer 0 is the final prediction, layer 1 + i is aux_outputs[i].
+ *        pred_masks / pred_logits  HOST arrays of L device pointers: fp32 [B][N][P] and fp32 [B][N][K1], as axvs_video_matcher takes them
+ *        targets, labels, m_per_video   as axvs_video_matcher takes them (target_dtype AXVS_U8 or AXVS_F32; a label outside 0..K-1 is clamped)
+ *        rows, cols, matched_dice, matched_cls   axvs_video_matcher's outputs, [LM*B][kmax] with LM = 1 when share_final_matching
+ *                                  (one matching serves every layer, and the void IoU of an unmatched query is taken on layer 0's
+ *                                  masks), else LM = L (matching l*B + b serves layer l); kmax = 0: no object in any video
+ *        losses                    fp32 [L][3]: loss_ce, loss_mask, loss_dice of every layer
+ *        saved                     axvs_set_criterion_saved_bytes(L, B, N) bytes the forward writes and the backward reads: O(L*B*N)
+ *        grad_losses               DEVICE fp32 [L][3]: the upstream gradients of `losses`
+ *        d_pred_masks / d_pred_logits   HOST arrays of L device pointers shaped like the inputs; a NULL entry skips that gradient
+ *      workspace_bytes travels as long long.  L <= 16, B <= 64, N <= 512, M_b <= 512, any P <= 2^40; otherwise AXVS_ERR_ARG (the size
+ *      functions return 0 and axvs_last_error() names the bound).  pred_masks is read once by the forward and once by the backward
+ *      while N <= 128; beyond that a pixel tile is read three times per pass, the second and third time from L2. */
+size_t axvs_set_criterion_saved_bytes(int L, int B, int N);
+size_t axvs_set_criterion_workspace_bytes(int L, int B, int N, int K1, long long P);
+int axvs_set_criterion_fwd(const float* const* pred_masks, const float* const* pred_logits, const void* targets, int target_dtype,
+                           const long long* labels, const int* m_per_video, const long long* rows, const long long* cols,
+                           const float* matched_dice, const float* matched_cls, int kmax, int L, int B, int N, int K1, long long P,
+                           int masking_void_pixel, int share_final_matching, float* losses, void* saved, void* workspace,
+                           long long workspace_bytes, void* stream);
+int axvs_set_criterion_bwd(const float* grad_losses, const float* const* pred_masks, const float* const* pred_logits, const void* targets,
+                           int target_dtype, const int* m_per_video, int L, int B, int N, int K1, long long P, int masking_void_pixel,
+                           int share_final_matching, const void* saved, float* const* d_pred_masks, float* const* d_pred_logits, void* stream);
+
 /* ---- PositionEmbeddingSine3D.forward(x, mask=None) in channels-last form
  *      WC/pos_embeddings.py:86-130: pos fp32 [B,T,H,W,C], C = 2*num_pos_feats. */
 int axvs_pos3d(float* pos, int B, int T, int H, int W, int C, float temperature, int normalize, float scale,
