@@ -1,5 +1,5 @@
-// Host side of the cross-clip tracking module's training tier (included by axvs_train.hip inside namespace axvs::{anonymous}: it
-// shares Ctx / pass_fwd / pass_bwd / the GEMM wrappers with the within-clip layer).  Kernels: axvs_cc_train.h.
+// Host side of the cross-clip tracking module's training tier (part of axvs_train.hip's translation unit: it shares Ctx / pass_fwd /
+// pass_bwd / the GEMM wrappers of axvs_train_host.h with the within-clip layer).  Kernels: axvs_cc_train.h.
 //
 // Forward  = CrossClipTrackingModule.forward in train() mode (CC:275-322): per layer the trajectory attention layer (CC:133-173, post-norm,
 //            no positional term, dropout 0, attention-map dropout p_attn_drop), the ASPP (CC:176-201) + residual + LayerNorm (CC:293-295), then
@@ -8,6 +8,12 @@
 // Backward = the same chain in reverse; shared head weights accumulate over the layers inside one weight-gradient GEMM.
 // Rows of every activation: (b, q, t) -- the reference's clip_query layout [B,Q,Tc,C]; the trajectory attention reads its
 // 'b (t q) c' order through the RowMap.
+#pragma once
+#include "axvs_cc_train.h"
+#include "axvs_train_host.h"
+
+namespace axvs {
+namespace {
 
 constexpr int kCcC = 256, kCcCm = 128, kCcHeads = 8, kCcMaxLayers = 16;
 
@@ -32,8 +38,7 @@ int make_cc_shape(CCShape& s, const AxvsCCTrainCfg* cfg) {
   if ((long long)cfg->B * cfg->Tc > 1024) return fail(AXVS_ERR_ARG, "cross-clip training: B*Tc > 1024");
   for (int k = 0; k < 3; ++k)
     if (cfg->rates[k] <= 0) return fail(AXVS_ERR_ARG, "cross-clip training: atrous rate %d", cfg->rates[k]);
-  if (!(cfg->p_attn_drop >= 0.f && cfg->p_attn_drop < 1.f) || !(cfg->p_aspp_drop >= 0.f && cfg->p_aspp_drop < 1.f))
-    return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  if (int rc = check_drop(cfg->p_attn_drop, cfg->p_aspp_drop)) return rc;
   s.B = cfg->B; s.Q = cfg->Q; s.Tc = cfg->Tc; s.V = chain ? 1 : cfg->V; s.H = chain ? 1 : cfg->H; s.W = chain ? 4 : cfg->W;
   s.K1 = chain ? 4 : cfg->K1; s.nl = cfg->num_layers;
   for (int k = 0; k < 3; ++k) s.rates[k] = cfg->rates[k];
@@ -57,7 +62,7 @@ struct CCSaved {
   float *mean[4], *rstd[4];   // BatchNorm sites: 0 class projection, 1 mask projection, 2 mask head, 3 pixel space
 };
 
-CCSaved carve_cc_saved(Bump& b, const CCShape& s) {
+CCSaved carve_cc_saved(Carver& b, const CCShape& s) {
   CCSaved v{};
   const size_t MC = (size_t)s.M * kCcC, G = (size_t)s.nl;
   for (int i = 0; i < s.nl; ++i) {
@@ -106,7 +111,7 @@ void dk_plan(const CCShape& s, int* ksteps, int* z) {
   *z = (nk + ks - 1) / ks;
 }
 
-CCScratch carve_cc_scratch(Bump& b, const CCShape& s, bool backward) {
+CCScratch carve_cc_scratch(Carver& b, const CCShape& s, bool backward) {
   CCScratch c{};
   const size_t MC = (size_t)s.M * kCcC, G = (size_t)s.nl;
   c.xcol = b.f(3 * MC);
@@ -149,7 +154,7 @@ inline unsigned eblocks(size_t n) { return blocks(n, 256); }
 
 int cc_sync(const CCCtx& k, float* buf, size_t n) {
   if (!k.cfg->allreduce) return AXVS_OK;
-  if (int rc = status()) return rc;
+  if (int rc = last_launch_status()) return rc;
   if (k.cfg->allreduce(k.cfg->allreduce_user, buf, n, k.st) != 0) return fail(AXVS_ERR_LAUNCH, "the caller's all-reduce reported an error");
   return AXVS_OK;
 }
@@ -221,7 +226,7 @@ int cc_chain_forward(const CCCtx& k, const float* cq, const AxvsCCLayerParams* l
     hipLaunchKernelGGL(tr_ln_fwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, k.st, (const float*)L.u, p.conv_norm_w, p.conv_norm_b, sv.x2 + (size_t)l * MC,
                        L.meanu, L.rstdu, M, C, 1e-5f);
   }
-  return status();
+  return last_launch_status();
 }
 
 int cc_forward(const CCCtx& k, const float* cq, const float* pf, float* logits_out, float* masks_out, float* bn_stats_out,
@@ -303,7 +308,7 @@ int cc_forward(const CCCtx& k, const float* cq, const float* pf, float* logits_o
                      1e-3f, sv.mean[3], sv.rstd[3], so, 1);
   hipLaunchKernelGGL(cct_scalar_bn_apply_kernel, dim3(eblocks(s.E / 4), G), dim3(256), 0, k.st, (const float*)sv.logits_pre, (const float*)sv.mean[3],
                      (const float*)sv.rstd[3], hp.pixel_bn.w, hp.pixel_bn.b, masks_out, s.E / 4);
-  return status();
+  return last_launch_status();
 }
 
 int cc_chain_backward(const CCCtx& k, const float* cq, const AxvsCCLayerParams* layers, const AxvsCCLayerGrads* lg, float* d_cq, const CCSaved& sv);
@@ -450,14 +455,7 @@ int cc_chain_backward(const CCCtx& k, const float* cq, const AxvsCCLayerParams* 
                        false)) != AXVS_OK)
       return rc;
   }
-  return status();
-}
-
-int cc_check_ptrs(const void* p, size_t bytes, const char* what) {
-  const void* const* f = static_cast<const void* const*>(p);
-  for (size_t i = 0; i < bytes / sizeof(void*); ++i)
-    if (!f[i]) return fail(AXVS_ERR_ARG, "null pointer (field %zu of %s)", i, what);
-  return AXVS_OK;
+  return last_launch_status();
 }
 
 int cc_setup(CCCtx& k, const AxvsCCTrainCfg* cfg, void* scratch, size_t scratch_bytes, void* saved, size_t saved_bytes, CCSaved& sv, bool backward,
@@ -465,18 +463,16 @@ int cc_setup(CCCtx& k, const AxvsCCTrainCfg* cfg, void* scratch, size_t scratch_
   int rc;
   if ((rc = make_cc_shape(k.s, cfg)) != AXVS_OK) return rc;
   k.cfg = cfg;
-  Bump sb(saved), cb(scratch);
+  Carver sb(saved), cb(scratch);
   sv = carve_cc_saved(sb, k.s);
   k.c.d = k.s.d;
   k.c.sc = carve_scratch(cb, k.s.d, backward);
   k.x = carve_cc_scratch(cb, k.s, backward);
-  if (sb.off > saved_bytes || cb.off > scratch_bytes)
-    return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
-  k.st = k.c.st = static_cast<hipStream_t>(stream);
   k.c.scale = 1.f / sqrtf((float)k.s.d.D);
   // tokens of a sequence in the reference's 'b (t q) c' order (CC:284) over natural rows (b, q, t)
   k.rm = RowMap{k.s.Tc * k.s.Q, k.s.Q, 1, (long long)k.s.Q * k.s.Tc, 1, k.s.Tc, 0};
-  return k.c.g.init(k.st);
+  k.st = static_cast<hipStream_t>(stream);
+  return train_begin(k.c, sb, saved_bytes, cb, scratch_bytes, stream);
 }
 
 // ---- Tube-Link cross-clip head: the prediction heads of ALL layers, train() mode ------------------------------------------------------
@@ -517,7 +513,7 @@ int make_tlh_shape(TLHShape& s, const AxvsTLHeadTrainCfg* cfg) {
 struct TLHSaved {
   float *mean, *rstd, *xn, *p, *pooled, *h1, *h2, *me;   // LayerNorm statistics / output, pooling weights, pooled rows, MLP activations
 };
-TLHSaved carve_tlh_saved(Bump& b, const TLHShape& s) {
+TLHSaved carve_tlh_saved(Carver& b, const TLHShape& s) {
   TLHSaved v{};
   const size_t RC = (size_t)s.R * kCcC;
   v.mean = b.f(s.R); v.rstd = b.f(s.R);
@@ -547,7 +543,7 @@ void tlh_plan(const TLHShape& s, int* ks, int* z) {
   *z = (nk + k - 1) / k;
 }
 
-TLHScratch carve_tlh_scratch(Bump& b, const TLHShape& s, bool backward, Scratch* sc) {
+TLHScratch carve_tlh_scratch(Carver& b, const TLHShape& s, bool backward, Scratch* sc) {
   TLHScratch x{};
   const size_t RC = (size_t)s.R * kCcC, RM = (size_t)s.R * s.Cm;
   x.kt = b.f(RM);
@@ -573,13 +569,10 @@ int tlh_setup(Ctx& c, TLHShape& s, TLHSaved& sv, TLHScratch& x, const AxvsTLHead
               size_t scratch_bytes, bool backward, void* stream) {
   int rc;
   if ((rc = make_tlh_shape(s, cfg)) != AXVS_OK) return rc;
-  Bump sb(saved), cb(scratch);
+  Carver sb(saved), cb(scratch);
   sv = carve_tlh_saved(sb, s);
   x = carve_tlh_scratch(cb, s, backward, &c.sc);
-  if (sb.off > saved_bytes || cb.off > scratch_bytes)
-    return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
-  c.st = static_cast<hipStream_t>(stream);
-  return c.g.init(c.st);
+  return train_begin(c, sb, saved_bytes, cb, scratch_bytes, stream);
 }
 
 int tlh_forward(const Ctx& c, const TLHShape& s, const float* X, const float* mf, float* cls, float* masks, const AxvsTLHeadParams& p,
@@ -614,7 +607,7 @@ int tlh_forward(const Ctx& c, const TLHShape& s, const float* X, const float* mf
                               (int)HW, GQ, HW, HW, al_mf, al_o, nullptr, s.Q, grp_ld)) != AXVS_OK)
         return rc;
     }
-  return status();
+  return last_launch_status();
 }
 
 int tlh_backward(const Ctx& c, const TLHShape& s, const float* d_cls, const float* d_masks, const float* X, const float* mf, const AxvsTLHeadParams& p,
@@ -682,5 +675,8 @@ int tlh_backward(const Ctx& c, const TLHShape& s, const float* d_cls, const floa
   c.colsum(x.dxn, R, C, g.post_norm_b, X, sv.mean, sv.rstd, g.post_norm_w);
   hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(blocks(R, 4)), dim3(256), 0, c.st, (const float*)x.dxn, X, p.post_norm_w, (const float*)sv.mean,
                      (const float*)sv.rstd, d_q, R, C);
-  return status();
+  return last_launch_status();
 }
+
+}  // namespace
+}  // namespace axvs

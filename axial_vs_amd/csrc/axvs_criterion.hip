@@ -11,14 +11,6 @@ using namespace axvs;
 
 namespace {
 
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-int last_launch_status() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(AXVS_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return AXVS_OK;
-}
-
 // workgroups per problem of the pixel kernels: two per CU over all problems, at least 4 pixel tiles each (a workgroup ends with one
 // cross-lane reduction per query, about a tile's worth of work), and at most 2^22 pixels each (the nonzero count of a workgroup is
 // kept in fp32)

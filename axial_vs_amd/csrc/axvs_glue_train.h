@@ -9,8 +9,12 @@
 //             d_beta = sum_n A,  d_gamma = sum_n B,  S1[n,g] = sum_{c in g} gamma_c A[n,c],  S2[n,g] = sum_{c in g} gamma_c B[n,c]
 //             d_y = rstd (gamma d_out - (S1 + xhat S2) / cnt)
 //             d_W = d_y^T x,  d_b = column sums of d_y,  d_x = d_y W
-// Included by axvs_train.hip only, INSIDE its `namespace axvs { namespace {` (like axvs_cc_train_host.h): the kernels have internal linkage.
+// Part of axvs_train.hip's translation unit only: the kernels have internal linkage.
 #pragma once
+#include "axvs_common.h"
+
+namespace axvs {
+namespace {
 
 // t [N][HW][C] token rows -> x [N][C][HW] (the inverse of nchw_to_tokens_kernel); 64 x 64 tiles through LDS, any HW, C a multiple of 4
 __global__ __launch_bounds__(256) void gt_tokens_to_nchw_kernel(const float* __restrict__ t, float* __restrict__ x, int C, int HW, long long t_batch_stride, long long t_ld) {
@@ -194,3 +198,5 @@ __global__ __launch_bounds__(256) void gt_gn_bwd_apply_kernel(float* __restrict_
   *reinterpret_cast<float4*>(d + r * C + c) = float4{dd[0], dd[1], dd[2], dd[3]};
 }
 
+}  // namespace
+}  // namespace axvs

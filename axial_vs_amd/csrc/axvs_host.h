@@ -1,4 +1,5 @@
-// Host-side plumbing shared by the translation units of libaxvs.so: error string, per-device kernel attributes, the
+// Host-side plumbing shared by the translation units of libaxvs.so: error string, launch status, the bump allocator over
+// caller-owned buffers and its workspace check, per-device kernel attributes, the
 // packed-weight / workspace views of one trajectory attention, and the launcher of the fused trajectory kernels (whose
 // instantiations are compiled one (operand type, frame count) pair per translation unit: axvs_temporal_inst.hip).
 #pragma once
@@ -36,6 +37,32 @@ inline int fail(int code, const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
+}
+
+inline int last_launch_status() {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(AXVS_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
+  return AXVS_OK;
+}
+
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+struct Carver {  // bump allocator over a caller-owned buffer (nullptr: size only)
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* p) : base(static_cast<char*>(p)) {}
+  template <class T>
+  T* take(size_t n) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off = align_up(off + n * sizeof(T));
+    return p;
+  }
+  float* f(size_t n) { return take<float>(n); }
+};
+
+inline int check_ws(size_t have, size_t need) {
+  if (have < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %zu < %zu", have, need);
+  return AXVS_OK;
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: remember (device, kernel) pairs that have

@@ -1,547 +1,12 @@
 // Training tier of TemporalAxialTrajectoryAttentionLayer behind the C ABI: forward that keeps the activations,
 // and the backward pass.  Kernels: axvs_train.h; the Linear layers (forward, input gradient, weight gradient) run on the
 // split-precision bf16 MFMA GEMM kernels of axvs_train_gemm.h (round 3: no vendor BLAS on this path any more).
-#include "axvs_host.h"
-#include "axvs_train.h"
-#include "axvs_train_gemm.h"
-#include "axvs_cc_train.h"
+#include "axvs_train_host.h"
+#include "axvs_cc_train_host.h"
+#include "axvs_glue_train.h"
 
 namespace axvs {
 namespace {
-
-using namespace tr;
-
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-
-struct Bump {   // bump allocator over a caller-owned buffer (nullptr: size only)
-  char* base;
-  size_t off = 0;
-  explicit Bump(void* p) : base(static_cast<char*>(p)) {}
-  float* f(size_t n) {
-    float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off = align256(off + n * sizeof(float));
-    return p;
-  }
-};
-
-// ---- the Linear layers' GEMMs: split-precision bf16 MFMA kernels (axvs_train_gemm.h) ------------------------------------------------
-// The instantiation the last Gemm launch of this thread ran (include/axvs.h, AxvsTestGemm::variant, has the encoding): set in
-// launch_nt / launch_tn, the only places that launch the GEMM kernels, and reported by axvs_test_train_gemm.
-thread_local int t_gemm_variant = 0;
-
-struct Gemm {
-  hipStream_t st = nullptr;
-  int init(hipStream_t s) {
-    st = s;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<2>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<3>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<2, 0, false, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<3, 0, false, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<2, 0, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<3, 0, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<2, 0, true, false, false, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<2, 0, false, false, false, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<1>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<1, 0, false, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<1, 0, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<1, 0, false, false, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<1, 0, false, true, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<1, 0, true, false, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false, 0, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<true, 0, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false, 1>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false, 2>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false, 0, false, true>))) return rc;
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<true, 0, false, true>))) return rc;
-    return ensure_max_lds(reinterpret_cast<const void*>(tr_gemm_tn_kernel<false>));
-  }
-  // The argument checks of nt(), wgrad_partials() and tn_direct(): they run before anything touches the device (axvs_test_train_gemm
-  // calls them ahead of init(), so a refused call needs no GPU).
-  static int check_nt(int N, int K, const GemmLd& ld) {
-    if (N % 4 || ld.c % 4 || (ld.al_a == 4 && ld.a % 4) || (ld.al_b == 4 && ld.b % 4))
-      return fail(AXVS_ERR_ARG, "training GEMM: N=%d and the row strides must be multiples of 4 (K=%d)", N, K);
-    if (ld.aff && !ld.a2) return fail(AXVS_ERR_ARG, "training GEMM: the affine loader needs its second operand");
-    return AXVS_OK;
-  }
-  // (the weight-gradient kernel always runs its 16-byte loader: both row strides must keep every row 16-byte aligned)
-  static int check_wgrad(int N, int K, long long ldy, long long ldx) {
-    if (N % 8 || K % 8 || ldy % 4 || ldx % 4)
-      return fail(AXVS_ERR_ARG, "training GEMM: N=%d and K=%d must be multiples of 8, the row strides ldy=%lld and ldx=%lld multiples of 4", N, K,
-                  ldy, ldx);
-    return AXVS_OK;
-  }
-  static int check_tn(int N, long long lda, bool stat, int grp_rows) {
-    if (N % 4 || lda % 4) return fail(AXVS_ERR_ARG, "einsum GEMM: N=%d must be a multiple of 4", N);
-    if (grp_rows > 0 && stat) return fail(AXVS_ERR_ARG, "einsum GEMM: grouped output rows take no statistics");
-    return AXVS_OK;
-  }
-  template <int NS, bool GEN = false, bool ADD = false, bool F16 = false, bool AFF = false>
-  void launch_nt(dim3 grid, const float* X, const float* W, float* Y, long long M, int N, int K, const GemmLd& ld, const GemmEpi& e) const {
-    t_gemm_variant = 0x100 | NS | GEN << 2 | ADD << 3 | F16 << 4 | AFF << 5;
-    hipLaunchKernelGGL((tr_gemm_nt_kernel<NS, 0, GEN, ADD, F16, AFF>), grid, dim3(512), gemm_nt_lds<NS>(), st, X, W, Y, M, N, K, ld, e);
-  }
-  template <bool GEN, int AMP = 0, bool STATS = false, bool GRP = false>
-  void launch_tn(dim3 grid, const float* dY, const float* X, float* part, long long M, int N, int K, long long chunk, float* part_b,
-                 const GemmLd& ld) const {
-    t_gemm_variant = 0x200 | GEN | AMP << 1 | STATS << 3 | GRP << 4;
-    hipLaunchKernelGGL((tr_gemm_tn_kernel<GEN, AMP, STATS, GRP>), grid, dim3(512), kGemmLds, st, dY, X, part, M, N, K, chunk, part_b, ld);
-  }
-  // row-major:  Y[M,N] = beta Y + epilogue(X[M,K] W[N,K]^T); epilogue (optional): + bias, * mul, ReLU, dropout by element index
-  // exact: three bf16 pieces per operand (fp32 accuracy) -- for the GEMM in front of the ReLU (see tr_gemm_nt_kernel)
-  // ld (optional): row strides of X, W, Y (sub-matrices of wider buffers); ld.ksteps > 0 with zsplits: split-K partials [z][M][ld.c]
-  int nt(const float* X, const float* W, float* Y, long long M, int N, int K, GemmLd ld, const GemmEpi& e, bool exact, int zsplits = 1) const {
-    if (int rc = check_nt(N, K, ld)) return rc;
-    if (M <= 0) return AXVS_OK;
-    const dim3 grid((unsigned)((M + kGT - 1) / kGT), (unsigned)((N + kGT - 1) / kGT), (unsigned)zsplits);
-    // (a deeper register prefetch for grids of a few workgroups was measured and does not pay: these launches are bound by their
-    //  fixed cost -- ~11 us whatever K -- not by the load round trips of the k-loop)
-    const bool gen = gemm_nt_general(ld, K), add = ld.a2 != nullptr;   // (the general loader takes the addend at run time)
-    if (ld.aff) {                     // affine A operand (two-piece products: an input-gradient GEMM)
-      if (gen) launch_nt<2, true, false, false, true>(grid, X, W, Y, M, N, K, ld, e);
-      else launch_nt<2, false, false, false, true>(grid, X, W, Y, M, N, K, ld, e);
-      return AXVS_OK;
-    }
-    if (g_train_amp) {                // torch.autocast: one 16-bit piece per operand (1: bf16, 2: fp16), whatever the caller's `exact`
-      if (g_train_amp == 2) {
-        if (gen) launch_nt<1, true, false, true>(grid, X, W, Y, M, N, K, ld, e);
-        else if (add) launch_nt<1, false, true, true>(grid, X, W, Y, M, N, K, ld, e);
-        else launch_nt<1, false, false, true>(grid, X, W, Y, M, N, K, ld, e);
-      } else {
-        if (gen) launch_nt<1, true>(grid, X, W, Y, M, N, K, ld, e);
-        else if (add) launch_nt<1, false, true>(grid, X, W, Y, M, N, K, ld, e);
-        else launch_nt<1>(grid, X, W, Y, M, N, K, ld, e);
-      }
-      return AXVS_OK;
-    }
-    if (exact && gen) launch_nt<3, true>(grid, X, W, Y, M, N, K, ld, e);
-    else if (exact && add) launch_nt<3, false, true>(grid, X, W, Y, M, N, K, ld, e);
-    else if (exact) launch_nt<3>(grid, X, W, Y, M, N, K, ld, e);
-    else if (gen) launch_nt<2, true>(grid, X, W, Y, M, N, K, ld, e);
-    else if (add) launch_nt<2, false, true>(grid, X, W, Y, M, N, K, ld, e);
-    else launch_nt<2>(grid, X, W, Y, M, N, K, ld, e);
-    return AXVS_OK;
-  }
-  // X2 (nullable): added to X element-wise in the loader (q = k = Linear(x + pos) without an x + pos buffer)
-  int fwd(const float* X, const float* W, float* Y, long long M, int N, int K, float beta = 0.f, const GemmEpi* ep = nullptr,
-          bool exact = false, const float* X2 = nullptr) const {
-    GemmEpi e = ep ? *ep : GemmEpi{nullptr, 1.f, 0, Drop{0u, 0u, 0u, 1.f}, 0.f};
-    e.beta = beta;
-    return nt(X, W, Y, M, N, K, GemmLd{K, K, N, 0, X2}, e, exact);
-  }
-  // dW[N,K] = dY[M,N]^T X[M,K]: the reduction runs over the M rows and the output is small, so the rows are split kSplit ways
-  // into `part` ([kSplit + 1][N*K]); the caller sums the partials (deterministic).  ldy / ldx: row strides of dY / X (0: N / K).
-  static constexpr int kSplit = 64;
-  int wgrad_partials(const float* dY, const float* X, float* part, long long M, int N, int K, int* nparts, float* part_b = nullptr,
-                     long long ldy = 0, long long ldx = 0) const {
-    const GemmLd ld{ldy ? ldy : N, ldx ? ldx : K, K, 0};
-    if (int rc = check_wgrad(N, K, ld.a, ld.b)) return rc;
-    long long chunk = (M + kSplit - 1) / kSplit;
-    chunk = (chunk + kGK - 1) / kGK * kGK;                 // whole k-steps per split
-    const int np = (int)((M + chunk - 1) / chunk);
-    const dim3 grid((unsigned)(((N + kGT - 1) / kGT) * ((K + kGT - 1) / kGT)), (unsigned)np);
-    if (g_train_amp == 1) launch_tn<false, 1>(grid, dY, X, part, M, N, K, chunk, part_b, ld);
-    else if (g_train_amp == 2) launch_tn<false, 2>(grid, dY, X, part, M, N, K, chunk, part_b, ld);
-    else launch_tn<false>(grid, dY, X, part, M, N, K, chunk, part_b, ld);
-    *nparts = np;
-    return AXVS_OK;
-  }
-  // P[N][K] (row stride ldo) = A[Mc][N]^T X[Mc][K]: the contraction over a FEW rows Mc (the 128 channels of the mask einsum,
-  // CC:55) in one split, straight into the caller's tensor
-  // al_x / al_o: alignment (floats) of the rows of X and P -- K is a pixel count and need not be a multiple of anything
-  // stat (nullable): GemmLd with the stat_* fields set -- the tile sums of P for the BatchNorm behind the einsum (STATS instantiation)
-  // grp_rows > 0: output row n at P + (n / grp_rows) grp_ld + (n % grp_rows) ldo (GemmLd::c_grp_rows)
-  int tn_direct(const float* A, const float* X, float* P, int Mc, int N, int K, long long lda, long long ldx, long long ldo, int al_x, int al_o,
-                const GemmLd* stat = nullptr, int grp_rows = 0, long long grp_ld = 0) const {
-    if (int rc = check_tn(N, lda, stat != nullptr, grp_rows)) return rc;
-    const dim3 grid((unsigned)(((N + kGT - 1) / kGT) * ((K + kGT - 1) / kGT)), 1u);
-    const long long chunk = (Mc + kGK - 1) / kGK * kGK;
-    GemmLd ld{lda, ldx, ldo, 0};
-    ld.al_b = al_x;
-    ld.al_c = al_o;
-    ld.c_grp_rows = grp_rows;
-    ld.c_grp_ld = grp_ld;
-    const bool gen = !(al_x == 4 && al_o == 4 && K % 4 == 0);
-    if (grp_rows > 0) {
-      if (gen) launch_tn<true, 0, false, true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
-      else launch_tn<false, 0, false, true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
-      return AXVS_OK;
-    }
-    if (stat) {
-      ld.stat_part = stat->stat_part; ld.stat_shift = stat->stat_shift; ld.stat_nblk = stat->stat_nblk; ld.stat_blk0 = stat->stat_blk0;
-      ld.stat_rows = stat->stat_rows;
-      if (gen) launch_tn<true, 0, true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
-      else launch_tn<false, 0, true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
-      return AXVS_OK;
-    }
-    if (gen) launch_tn<true>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
-    else launch_tn<false>(grid, A, X, P, Mc, N, K, chunk, nullptr, ld);
-    return AXVS_OK;
-  }
-};
-
-// ---- shapes and buffers ----------------------------------------------------------------------------------------------------
-struct Dims {
-  int B, T, H, W, C, heads, F, D;
-  long long M, HW;
-};
-
-int make_dims_any(Dims& d, int B, int T, int H, int W, int C, int heads, int F) {
-  if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0 || F <= 0) return fail(AXVS_ERR_ARG, "non-positive dimension");
-  if (C % heads) return fail(AXVS_ERR_ARG, "C=%d must be a multiple of heads=%d", C, heads);
-  const int D = C / heads;
-  if (D != 8 && D != 16 && D != 32 && D != 64) return fail(AXVS_ERR_ARG, "training tier: head_dim=%d not built (8, 16, 32, 64)", D);
-  if (F % 8) return fail(AXVS_ERR_ARG, "training tier: d_ffn=%d must be a multiple of 8", F);
-  if (T > 16) return fail(AXVS_ERR_ARG, "training tier: T=%d > 16 frames per clip not built", T);
-  const long long M = (long long)B * T * H * W;
-  if (M * (long long)(T > 1 ? T : 1) > INT32_MAX) return fail(AXVS_ERR_ARG, "training tier: B*T*H*W*T exceeds 2^31 rows");
-  d = Dims{B, T, H, W, C, heads, F, D, M, (long long)H * W};
-  return AXVS_OK;
-}
-
-// the axial layer: frames are axis lengths (H or W keys)
-int make_dims(Dims& d, int B, int T, int H, int W, int C, int heads, int F) {
-  if (int rc = make_dims_any(d, B, T, H, W, C, heads, F)) return rc;
-  if ((size_t)2 * (H > W ? H : W) * d.D * sizeof(float) > 160 * 1024) return fail(AXVS_ERR_ARG, "training tier: axis length too long for LDS");
-  return AXVS_OK;
-}
-
-// Frame length the spatial half's kernels take: the fp32 MFMA kernels (head_dim 32) any (keys chunked through LDS beyond ~550);
-// the VALU kernels (head_dim 8 / 16 / 64, or option train_valu) hold a whole frame's K and V in LDS.
-int check_frame(int D, long long L) {
-  if (D == 32 && !g_train_valu) return AXVS_OK;
-  const long long maxL = 160 * 1024 / (2 * D * (long long)sizeof(float));
-  if (L > maxL)
-    return fail(AXVS_ERR_ARG, "training tier: head_dim=%d with frames of %lld keys: the VALU attention kernel holds a frame in LDS, at most %lld keys "
-                "(frames of any length need head_dim 32)", D, L, maxL);
-  return AXVS_OK;
-}
-
-// the full T*H*W layer: one frame is all HW tokens of an image
-int make_traj_dims(Dims& d, int B, int T, int HW, int C, int heads, int F) {
-  if (int rc = make_dims_any(d, B, T, 1, HW, C, heads, F)) return rc;
-  return check_frame(d.D, HW);
-}
-
-struct PassSaved {
-  float *q, *k, *v, *x, *xd, *q2, *kv2, *o;
-  float* st;   // softmax statistics of the spatial half [(s heads + h), N, T, 3]: max, 1 / sum (forward), D (backward part 1)
-};
-struct Saved {
-  PassSaved p[2];
-  float *buf1, *buf2, *mean1, *rstd1, *z, *r, *u, *mean2, *rstd2;
-};
-
-PassSaved carve_pass(Bump& b, const Dims& d) {
-  PassSaved p{};
-  const size_t MC = (size_t)d.M * d.C;
-  p.q = b.f(MC);
-  p.k = b.f(MC);
-  p.v = b.f(MC);
-  p.x = b.f(MC * d.T);
-  p.xd = b.f(MC);
-  p.q2 = b.f(MC);
-  p.kv2 = b.f(MC * d.T * 2);
-  p.o = b.f(MC);
-  p.st = b.f((size_t)d.M * d.heads * d.T * 3);
-  return p;
-}
-
-// npass: 2 (axial layer: height and width pass, buf1 between them) or 1 (full layer: its pass writes buf2)
-Saved carve_saved(Bump& b, const Dims& d, int npass = 2) {
-  Saved s{};
-  const size_t MC = (size_t)d.M * d.C;
-  for (int i = 0; i < npass; ++i) s.p[i] = carve_pass(b, d);
-  if (npass == 2) s.buf1 = b.f(MC);
-  s.buf2 = b.f(MC);
-  s.mean1 = b.f(d.M);
-  s.rstd1 = b.f(d.M);
-  s.z = b.f(MC);
-  s.r = b.f((size_t)d.M * d.F);
-  s.u = b.f(MC);
-  s.mean2 = b.f(d.M);
-  s.rstd2 = b.f(d.M);
-  return s;
-}
-
-constexpr int kColsumBlocks = 512;
-
-struct Scratch {
-  float *a, *t0, *d_o, *dq2, *dkv2, *dx, *dxd, *dq, *dk, *dv, *da, *g0, *g1, *dr, *part_a, *part_b, *wpart, *wt;
-};
-
-Scratch carve_scratch(Bump& b, const Dims& d, bool backward) {
-  Scratch s{};
-  const size_t MC = (size_t)d.M * d.C;
-  s.a = b.f(MC);
-  s.t0 = b.f(MC);
-  if (!backward) return s;
-  s.d_o = b.f(MC);
-  s.dq2 = b.f(MC);
-  s.dkv2 = b.f(MC * d.T * 2);
-  s.dx = b.f(MC * d.T);
-  s.dxd = b.f(MC);
-  s.dq = b.f(MC);
-  s.dk = b.f(MC);
-  s.dv = b.f(MC);
-  s.da = b.f(MC);
-  s.g0 = b.f(MC);
-  s.g1 = b.f(MC);
-  s.dr = b.f((size_t)d.M * d.F);
-  const size_t wide = (size_t)(2 * d.C > d.F ? 2 * d.C : d.F);
-  s.part_a = b.f(kColsumBlocks * wide);
-  s.part_b = b.f(kColsumBlocks * wide);
-  const size_t wmax = (size_t)d.C * (2 * d.C > d.F ? 2 * d.C : d.F);     // largest weight: proj_kv [2C, C] or linear1/2 [F, C]
-  s.wpart = b.f((Gemm::kSplit + 1) * wmax);
-  s.wt = b.f(wmax);
-  return s;
-}
-
-Drop make_drop(float p, unsigned seed, unsigned site) {
-  Drop d{seed, site, 0u, 1.f};
-  if (p > 0.f) {
-    d.thr = (unsigned)((double)p * 16777216.0);
-    d.scale = 1.f / (1.f - p);
-  }
-  return d;
-}
-
-inline unsigned blocks(size_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
-
-#define AXVS_D_SWITCH(D_, ...)                       \
-  switch (D_) {                                      \
-    case 8: { constexpr int kD = 8; __VA_ARGS__; } break;   \
-    case 16: { constexpr int kD = 16; __VA_ARGS__; } break; \
-    case 64: { constexpr int kD = 64; __VA_ARGS__; } break; \
-    default: { constexpr int kD = 32; __VA_ARGS__; } break; \
-  }
-
-struct Ctx {
-  Dims d;
-  Gemm g;
-  hipStream_t st;
-  float scale;
-  Scratch sc;
-
-  void add(const float* a, const float* b, float* y, size_t n) const {
-    hipLaunchKernelGGL(tr_add_kernel, dim3(blocks(n / 4)), dim3(256), 0, st, a, b, y, n / 4);
-  }
-  void bias_act(float* y, const float* bias, long long rows, int N, float mul, int relu, Drop dr) const {
-    hipLaunchKernelGGL(tr_bias_act_kernel, dim3(blocks((size_t)rows * N / 4)), dim3(256), 0, st, y, bias, rows, N, mul, relu, dr);
-  }
-  // bias / LayerNorm parameter gradients: out_a[c] = sum_r dy[r][c]; with x: out_b[c] = sum_r dy[r][c] xhat[r][c]
-  void colsum(const float* dy, long long rows, int N, float* out_a, const float* x = nullptr, const float* mean = nullptr,
-              const float* rstd = nullptr, float* out_b = nullptr) const {
-    long long rpb = (rows + kColsumBlocks - 1) / kColsumBlocks;
-    if (rpb < 64) rpb = 64;
-    const int nblk = (int)((rows + rpb - 1) / rpb);
-    hipLaunchKernelGGL(tr_colsum_kernel, dim3(nblk), dim3(256), 0, st, dy, x, mean, rstd, sc.part_a, sc.part_b, rows, N, (int)rpb);
-    hipLaunchKernelGGL(tr_colsum_final_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, (const float*)sc.part_a, nblk, (size_t)N, out_a);
-    if (x) hipLaunchKernelGGL(tr_colsum_final_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, (const float*)sc.part_b, nblk, (size_t)N, out_b);
-  }
-  // dW[N,K] = dY[M,N]^T X[M,K]; db (nullable) [N] = column sums of dY -- the bias gradient rides in the same GEMM launch
-  // mul: the gradients are those of mul * dY (a scale that sits between the Linear layer and the tensor dY belongs to)
-  int wgrad(const float* dY, const float* X, float* dW, long long M, int N, int K, float* db = nullptr, long long ldy = 0,
-            long long ldx = 0, float mul = 1.f) const {
-    int np = 0;
-    int rc = g.wgrad_partials(dY, X, sc.wpart, M, N, K, &np, db ? sc.part_a : nullptr, ldy, ldx);
-    if (rc != AXVS_OK) return rc;
-    const size_t n = (size_t)N * K;
-    if (db) {      // one launch adds the partials of the weight and of the bias gradient (same order of additions as the single kernel)
-      const unsigned ba = blocks(n, 256), bb = blocks(N, 256);
-      hipLaunchKernelGGL(tr_colsum_final_pair_kernel, dim3(ba + bb), dim3(256), 0, st, (const float*)sc.wpart, n, dW, (const float*)sc.part_a, (size_t)N, db,
-                         np, (int)ba, mul);
-    } else {
-      hipLaunchKernelGGL(tr_colsum_final_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, (const float*)sc.wpart, np, n, dW, mul);
-    }
-    return AXVS_OK;
-  }
-  // dX[M,K] = beta dX + dY[M,N] W[N,K]      (through W^T, in the forward GEMM's form)
-  // exact: three-piece operands (see axvs_train_gemm.h) -- where the result feeds a sum that cancels analytically
-  // mul: dX = mul * dY W; res / res2 (nullable, [M][K]): added in the epilogue
-  int dgrad(const float* dY, const float* W, float* dX, long long M, int N, int K, float beta, long long ldy = 0, bool exact = false,
-            float mul = 1.f, const float* res = nullptr, const float* res2 = nullptr) const {
-    const GemmLd ld{ldy ? ldy : N, N, K, 0};
-    if (int rc = Gemm::check_nt(K, N, ld)) return rc;      // (before the transpose: a refused call launches nothing)
-    hipLaunchKernelGGL(tr_transpose_kernel, dim3((K + 31) / 32, (N + 31) / 32), dim3(256), 0, st, W, sc.wt, N, K);
-    GemmEpi e{nullptr, mul, 0, Drop{0u, 0u, 0u, 1.f}, beta};
-    e.res = res;
-    e.res2 = res2;
-    return g.nt(dY, sc.wt, dX, M, K, N, ld, e, exact || g_train_exact >= 2);
-  }
-  int spatial_lds(const void* fn, size_t bytes) const { return bytes > 64 * 1024 ? ensure_max_lds(fn) : AXVS_OK; }
-};
-
-// The spatial half runs on the fp32 MFMA kernels (forward and both backward parts, or none of them: the backward reads the
-// statistics the forward leaves) when head_dim is 32 and a sequence's scaled q + dx rows fit in LDS.
-// queries the key-side backward kernel stages at a time: all of a sequence when they fit in LDS (the within-clip layer: <= 512),
-// else chunks of 512 (the cross-clip module over 12 clips of 128 queries)
-int spatial_kv_chunk(const RowMap& rm) {
-  const int Np = (rm.N + 15) / 16 * 16;
-  return Np <= 512 ? Np : 512;
-}
-bool mfma_spatial(const Dims& d, const RowMap& rm) {
-  const size_t lds_q = (size_t)2 * ((rm.L + 15) / 16 * 16) * kTrLd * sizeof(float);
-  return d.D == 32 && !g_train_valu && lds_q <= 160 * 1024;
-}
-// head_dim 32, frames too long for LDS: the chunked-key query-side kernels (the key side is tr_spatial_bwd_kv_mfma_kernel either way)
-bool chunk_spatial(const Dims& d, const RowMap& rm) { return d.D == 32 && !g_train_valu && !mfma_spatial(d, rm); }
-// grid of the chunked kernels: y counts blocks of 4 * kSpQT query tiles
-inline int chunk_tiles(const RowMap& rm) { return (((rm.N + 15) / 16 + 4 * kSpQT - 1) / (4 * kSpQT)) * 4; }
-
-// Launch grid of the fp32 MFMA spatial-attention kernels: x = (sequence, head); the 16-row tiles each wave walks (y) and the frames (z)
-// are spread over more workgroups until there are about g_spatial_wgs of them -- every (tile, frame) is computed by exactly one
-// wave with the same instructions whatever the split.
-dim3 spatial_grid(int sh, int tiles, int frames) {
-  const int target = g_spatial_wgs;                  // workgroups wanted (option "train_spatial_wgs")
-  if (sh >= target) return dim3(sh, 1, 1);
-  const int z = frames;
-  int y = (target + sh * z - 1) / (sh * z);
-  const int ymax = (tiles + 3) / 4;
-  y = y > ymax ? ymax : (y < 1 ? 1 : y);
-  return dim3(sh, y, z);
-}
-
-// one axial pass, forward: xout = xin + dropout1(TrajectoryAttention(q = k = xin + pos, v = xin))   WC/temporal_attention.py:35-76
-int pass_fwd(const Ctx& c, const float* xin, const float* pos, float* xout, const AxvsTrajParams& w, const PassSaved& s, RowMap rm, int S,
-             Drop attn_drop, Drop drop1) {
-  const Dims& d = c.d;
-  const long long M = d.M;
-  const int C = d.C;
-  const Drop none = make_drop(0.f, 0, 0);
-  int rc;
-  // q = k = Linear(x + pos): the sum is formed in the GEMM's A loader (the cross-clip layer has no positional term, CC:96)
-  // (the biases ride in the GEMM epilogues; `ex`: option train_exact -- forward products with fp32 accuracy)
-  const bool ex = g_train_exact != 0;
-  const GemmEpi eq{w.q_b, 1.f, 0, none, 0.f}, ek{w.k_b, 1.f, 0, none, 0.f}, ev{w.v_b, 1.f, 0, none, 0.f};
-  if ((rc = c.g.fwd(xin, w.q_w, s.q, M, C, C, 0.f, &eq, ex, pos)) != AXVS_OK) return rc;
-  if ((rc = c.g.fwd(xin, w.k_w, s.k, M, C, C, 0.f, &ek, ex, pos)) != AXVS_OK) return rc;
-  if ((rc = c.g.fwd(xin, w.v_w, s.v, M, C, C, 0.f, &ev, ex)) != AXVS_OK) return rc;
-  const size_t lds = (size_t)2 * rm.L * d.D * sizeof(float);
-  const size_t lds_mfma = (size_t)2 * ((rm.L + 15) / 16 * 16) * kTrLd * sizeof(float);
-  if (mfma_spatial(d, rm) && g_train_attn_split && rm.L <= 16 * kSpMaxTiles) {   // 16-bit matrix cores, three-piece operands, a frame's scores in registers
-    const size_t lds_split = spatial_split_lds(rm.L);
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_split_kernel), lds_split)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_fwd_split_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, d.T), dim3(256), lds_split, c.st, (const float*)s.q,
-                       (const float*)s.k, (const float*)s.v, s.x, s.st, rm, d.T, C, d.heads, c.scale, attn_drop);
-  } else if (mfma_spatial(d, rm)) {                                     // head_dim 32 (every shipped config): fp32 MFMA kernels
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_mfma_kernel), lds_mfma)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_fwd_mfma_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, d.T), dim3(256), lds_mfma, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, s.x, s.st, rm, d.T, C, d.heads, c.scale, attn_drop);
-  } else if (chunk_spatial(d, rm)) {                                    // head_dim 32, long frames: keys chunked through LDS
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_chunk_kernel), spatial_chunk_lds())) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_fwd_chunk_kernel, spatial_grid(S * d.heads, chunk_tiles(rm), d.T), dim3(256), spatial_chunk_lds(), c.st, (const float*)s.q,
-                       (const float*)s.k, (const float*)s.v, s.x, s.st, rm, d.T, C, d.heads, c.scale, attn_drop);
-  } else {
-  if ((rc = check_frame(d.D, rm.L)) != AXVS_OK) return rc;
-  AXVS_D_SWITCH(d.D, {
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_kernel<kD>), lds)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_fwd_kernel<kD>, dim3(S * d.heads), dim3(256), lds, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, s.x, rm, d.T, C, d.heads, c.scale, attn_drop);
-  })
-  }
-  hipLaunchKernelGGL(tr_diag_gather_kernel, dim3(blocks((size_t)M * C / 4)), dim3(256), 0, c.st, (const float*)s.x, s.xd, M, d.T, d.HW, C);
-  const GemmEpi epq{w.proj_q_b, c.scale, 0, none, 0.f}, epkv{w.proj_kv_b, 1.f, 0, none, 0.f};
-  if ((rc = c.g.fwd(s.xd, w.proj_q_w, s.q2, M, C, C, 0.f, &epq, ex)) != AXVS_OK) return rc;
-  if ((rc = c.g.fwd(s.x, w.proj_kv_w, s.kv2, M * d.T, 2 * C, C, 0.f, &epkv, ex)) != AXVS_OK) return rc;
-  AXVS_D_SWITCH(d.D, {
-    if (d.T <= 8) hipLaunchKernelGGL((tr_temporal_fwd_kernel<kD, 8>), dim3(blocks((size_t)M * d.heads)), dim3(256), 0, c.st, (const float*)s.q2,
-                                     (const float*)s.kv2, s.o, M, d.T, C, d.heads);
-    else hipLaunchKernelGGL((tr_temporal_fwd_kernel<kD, 16>), dim3(blocks((size_t)M * d.heads)), dim3(256), 0, c.st, (const float*)s.q2,
-                            (const float*)s.kv2, s.o, M, d.T, C, d.heads);
-  })
-  if ((rc = c.g.fwd(s.o, w.proj_w, c.sc.t0, M, C, C, 0.f, nullptr, ex)) != AXVS_OK) return rc;
-  hipLaunchKernelGGL(tr_bias_drop_res_kernel, dim3(blocks((size_t)M * C / 4)), dim3(256), 0, c.st, (const float*)c.sc.t0, w.proj_b, xin, xout, rm,
-                     M, C, drop1);
-  return AXVS_OK;
-}
-
-// backward of one axial pass.  d_out: gradient of the pass output; d_in: gradient of the pass input (written); d_pos: nullable,
-// written when `pos_first`, accumulated otherwise.
-int pass_bwd(const Ctx& c, const float* d_out, const float* xin, const float* pos, const AxvsTrajParams& w, const AxvsTrajGrads& gw,
-             const PassSaved& s, RowMap rm, int S, Drop attn_drop, Drop drop1, float* d_in, float* d_pos, bool pos_first) {
-  const Dims& d = c.d;
-  const long long M = d.M;
-  const int C = d.C, T = d.T;
-  const Scratch& sc = c.sc;
-  const size_t MC = (size_t)M * C;
-  int rc;
-  // proj and dropout1
-  hipLaunchKernelGGL(tr_drop_bwd_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, d_out, sc.t0, rm, M, C, drop1);
-  if ((rc = c.wgrad(sc.t0, s.o, gw.proj_w, M, C, C, gw.proj_b)) != AXVS_OK) return rc;
-  if ((rc = c.dgrad(sc.t0, w.proj_w, sc.d_o, M, C, C, 0.f)) != AXVS_OK) return rc;
-  // temporal half
-  AXVS_D_SWITCH(d.D, {
-    if (T <= 8) hipLaunchKernelGGL((tr_temporal_bwd_kernel<kD, 8>), dim3(blocks((size_t)M * d.heads)), dim3(256), 0, c.st, (const float*)s.q2,
-                                   (const float*)s.kv2, (const float*)sc.d_o, sc.dq2, sc.dkv2, M, T, C, d.heads);
-    else hipLaunchKernelGGL((tr_temporal_bwd_kernel<kD, 16>), dim3(blocks((size_t)M * d.heads)), dim3(256), 0, c.st, (const float*)s.q2,
-                            (const float*)s.kv2, (const float*)sc.d_o, sc.dq2, sc.dkv2, M, T, C, d.heads);
-  })
-  if ((rc = c.wgrad(sc.dkv2, s.x, gw.proj_kv_w, M * T, 2 * C, C, gw.proj_kv_b)) != AXVS_OK) return rc;
-  if ((rc = c.dgrad(sc.dkv2, w.proj_kv_w, sc.dx, M * T, 2 * C, C, 0.f)) != AXVS_OK) return rc;
-  // q2 = scale (proj_q(xd)): the scale rides in the two GEMMs' epilogues
-  if ((rc = c.wgrad(sc.dq2, s.xd, gw.proj_q_w, M, C, C, gw.proj_q_b, 0, 0, c.scale)) != AXVS_OK) return rc;
-  if ((rc = c.dgrad(sc.dq2, w.proj_q_w, sc.dxd, M, C, C, 0.f, 0, false, c.scale)) != AXVS_OK) return rc;
-  hipLaunchKernelGGL(tr_diag_scatter_add_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, sc.dx, (const float*)sc.dxd, M, T, d.HW, C);
-  // spatial half
-  const size_t lds = (size_t)2 * rm.L * d.D * sizeof(float);
-  constexpr int QC = 32;
-  const size_t lds2 = (size_t)(QC * d.D + QC * T * d.D + QC * T * 3) * sizeof(float);
-  const size_t lds_q = (size_t)2 * ((rm.L + 15) / 16 * 16) * kTrLd * sizeof(float);
-  const int kv_chunk = spatial_kv_chunk(rm);
-  const size_t lds_kv = (size_t)kv_chunk * (2 * kTrLd + 4) * sizeof(float);
-  if (mfma_spatial(d, rm) || chunk_spatial(d, rm)) {       // the forward was an MFMA kernel too: (max, 1 / sum) are in s.st
-    if (chunk_spatial(d, rm)) {
-      if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_chunk_kernel), spatial_chunk_lds())) != AXVS_OK) return rc;
-      hipLaunchKernelGGL(tr_spatial_bwd_q_chunk_kernel, spatial_grid(S * d.heads, chunk_tiles(rm), 1), dim3(256), spatial_chunk_lds(), c.st, (const float*)s.q,
-                         (const float*)s.k, (const float*)s.v, (const float*)s.x, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
-    } else {
-      if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_mfma_kernel), lds_q)) != AXVS_OK) return rc;
-      hipLaunchKernelGGL(tr_spatial_bwd_q_mfma_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, 1), dim3(256), lds_q, c.st, (const float*)s.q, (const float*)s.k,
-                         (const float*)s.v, (const float*)s.x, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
-    }
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_kv_mfma_kernel), lds_kv)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_bwd_kv_mfma_kernel, spatial_grid(S * d.heads, (rm.L + 15) / 16, T), dim3(256), lds_kv, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, (const float*)sc.dx, (const float*)s.st, sc.dk, sc.dv, rm, T, C, d.heads, c.scale, attn_drop, kv_chunk);
-  } else {
-  if ((rc = check_frame(d.D, rm.L)) != AXVS_OK) return rc;
-  AXVS_D_SWITCH(d.D, {
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_kernel<kD>), lds)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_bwd_q_kernel<kD>, dim3(S * d.heads), dim3(256), lds, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
-    hipLaunchKernelGGL(tr_spatial_bwd_kv_kernel<kD>, dim3(S * d.heads), dim3(256), lds2, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, (const float*)sc.dx, (const float*)s.st, sc.dk, sc.dv, rm, T, C, d.heads, c.scale, attn_drop, QC);
-  })
-  }
-  // q / k / v projections
-  const float* const xa = pos ? sc.a : xin;
-  if (pos) c.add(xin, pos, sc.a, MC);
-  if ((rc = c.wgrad(sc.dq, xa, gw.q_w, M, C, C, gw.q_b)) != AXVS_OK) return rc;
-  if ((rc = c.wgrad(sc.dk, xa, gw.k_w, M, C, C, gw.k_b)) != AXVS_OK) return rc;
-  if ((rc = c.wgrad(sc.dv, xin, gw.v_w, M, C, C, gw.v_b)) != AXVS_OK) return rc;
-  if ((rc = c.dgrad(sc.dq, w.q_w, sc.da, M, C, C, 0.f)) != AXVS_OK) return rc;
-  if ((rc = c.dgrad(sc.dk, w.k_w, sc.da, M, C, C, 1.f)) != AXVS_OK) return rc;
-  // d_in = d_out (residual) + dv Wv + da;   d_pos (+)= da
-  if ((rc = c.dgrad(sc.dv, w.v_w, d_in, M, C, C, 0.f, 0, false, 1.f, d_out, sc.da)) != AXVS_OK) return rc;
-  if (d_pos) {
-    if (pos_first) {
-      if (hipMemcpyAsync(d_pos, sc.da, MC * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
-    } else {
-      c.add(d_pos, sc.da, d_pos, MC);
-    }
-  }
-  return AXVS_OK;
-}
-
-// every field of a parameter / gradient struct (pointers only) is non-null
-template <class P>
-int check_ptrs(const P* p, const char* what = "AxvsAxialLayerParams") {
-  const float* const* f = reinterpret_cast<const float* const*>(p);
-  for (size_t i = 0; i < sizeof(P) / sizeof(float*); ++i)
-    if (!f[i]) return fail(AXVS_ERR_ARG, "null parameter pointer (field %zu of %s)", i, what);
-  return AXVS_OK;
-}
 
 // norm1 -> FFN -> norm2 behind the attention (WC/temporal_attention.py:181-185): the same in both layers, whose parameter / gradient
 // structs end in these eight fields
@@ -555,12 +20,6 @@ template <class P>
 TailParams tail_params(const P& p) { return TailParams{p.norm1_w, p.norm1_b, p.linear1_w, p.linear1_b, p.linear2_w, p.linear2_b, p.norm2_w, p.norm2_b}; }
 template <class G>
 TailGrads tail_grads(const G& g) { return TailGrads{g.norm1_w, g.norm1_b, g.linear1_w, g.linear1_b, g.linear2_w, g.linear2_b, g.norm2_w, g.norm2_b}; }
-
-int status() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(AXVS_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return AXVS_OK;
-}
 
 // site_h / site_o: dropout sites of the FFN hidden and output (5, 6 in the trajectory layers)
 int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, float p_drop, unsigned seed, unsigned site_h = 5, unsigned site_o = 6);
@@ -598,7 +57,7 @@ int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, floa
   hipLaunchKernelGGL(tr_bias_drop_res_kernel, dim3(blocks((size_t)M * C / 4)), dim3(256), 0, c.st, (const float*)c.sc.t0, p.linear2_b, (const float*)s.z,
                      s.u, id, M, C, make_drop(p_drop, seed, site_o));
   hipLaunchKernelGGL(tr_ln_fwd_kernel, dim3(blocks(M, 4)), dim3(256), 0, c.st, (const float*)s.u, p.norm2_w, p.norm2_b, out, s.mean2, s.rstd2, M, C, 1e-5f);
-  return status();
+  return last_launch_status();
 }
 
 // the full layer (WC/temporal_attention.py:133-155): one pass over all T*HW tokens of a clip (one sequence per clip, frames of HW keys;
@@ -641,19 +100,14 @@ int tail_bwd(const Ctx& c, const float* d_out, const TailParams& p, const TailGr
   return AXVS_OK;
 }
 
-// the shared prologue of the four entry points of each layer: checks, buffers, stream
+// the shared prologue of the four entry points of each trajectory layer: buffers, checks, stream
 int train_setup(Ctx& c, Saved& s, int npass, bool backward, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-  Bump sb(saved), cb(scratch);
+  Carver sb(saved), cb(scratch);
   s = carve_saved(sb, c.d, npass);
   c.sc = carve_scratch(cb, c.d, backward);
-  if (sb.off > saved_bytes || cb.off > scratch_bytes) return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
-  c.st = static_cast<hipStream_t>(stream);
   c.scale = 1.f / sqrtf((float)c.d.D);
-  return c.g.init(c.st);
+  return train_begin(c, sb, saved_bytes, cb, scratch_bytes, stream);
 }
-
-#include "axvs_cc_train_host.h"
-#include "axvs_glue_train.h"
 
 // ---- 1x1 convolution + GroupNorm in train() mode (axvs_glue_train.h) ----
 struct ConvGnBufs {
@@ -662,7 +116,7 @@ struct ConvGnBufs {
   float *part, *ab, *S, *dy, *dxt, *otok;      // scratch
   float *wpart, *part_a, *wt;      // scratch of the weight-gradient / input-gradient GEMMs
 };
-ConvGnBufs carve_convgn(Bump& sv, Bump& sc, long long N, long long HW, int Cin, int Cout, int G, bool copy_x, bool backward, bool out_nchw) {
+ConvGnBufs carve_convgn(Carver& sv, Carver& sc, long long N, long long HW, int Cin, int Cout, int G, bool copy_x, bool backward, bool out_nchw) {
   ConvGnBufs b{};
   const size_t M = (size_t)(N * HW);
   const int nblk = (int)((HW + 63) / 64);
@@ -744,7 +198,7 @@ struct MdScratch {
   float *dval, *dsamp, *gloc, *gaw, *doff;      // backward
 };
 
-MdSaved carve_md_saved(Bump& b, const MdShape& m) {
+MdSaved carve_md_saved(Carver& b, const MdShape& m) {
   MdSaved s{};
   const size_t MC = (size_t)m.d.M * m.d.C, MH = (size_t)m.d.M * m.d.heads * m.LP;
   s.t = carve_saved(b, m.d, 0);
@@ -756,7 +210,7 @@ MdSaved carve_md_saved(Bump& b, const MdShape& m) {
 }
 
 // the Scratch fields the shared code uses here: a, t0 (forward); g0, g1, dr, part_a / part_b, wpart, wt (backward)
-void carve_md_scratch(Bump& b, const MdShape& m, bool backward, Scratch& sc, MdScratch& x) {
+void carve_md_scratch(Carver& b, const MdShape& m, bool backward, Scratch& sc, MdScratch& x) {
   const Dims& d = m.d;
   const size_t MC = (size_t)d.M * d.C, MH = (size_t)d.M * d.heads * m.LP;
   sc = Scratch{};
@@ -786,14 +240,12 @@ void carve_md_scratch(Bump& b, const MdShape& m, bool backward, Scratch& sc, MdS
 
 int md_setup(Ctx& c, const MdShape& m, MdSaved& s, MdScratch& x, bool backward, void* saved, size_t saved_bytes, void* scratch,
              size_t scratch_bytes, void* stream) {
-  Bump sb(saved), cb(scratch);
+  Carver sb(saved), cb(scratch);
   c.d = m.d;
   s = carve_md_saved(sb, m);
   carve_md_scratch(cb, m, backward, c.sc, x);
-  if (sb.off > saved_bytes || cb.off > scratch_bytes) return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sb.off, scratch_bytes, cb.off);
-  c.st = static_cast<hipStream_t>(stream);
   c.scale = 1.f;
-  return c.g.init(c.st);
+  return train_begin(c, sb, saved_bytes, cb, scratch_bytes, stream);
 }
 
 // [sampling_offsets; attention_weights] weight and bias, so that the query path is one GEMM (and one input-gradient GEMM)
@@ -869,7 +321,7 @@ int md_backward(const Ctx& c, const MdShape& m, const MdScratch& x, const float*
   if ((rc = c.dgrad(x.dval, a.value_proj_w, d_src, M, C, C, 0.f, 0, false, 1.f, sc.g1, sc.t0)) != AXVS_OK) return rc;
   if (d_pos && hipMemcpyAsync(d_pos, sc.t0, MC * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
     return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
-  return status();
+  return last_launch_status();
 }
 
 }  // namespace
@@ -888,7 +340,7 @@ extern "C" {
 size_t axvs_axial_layer_train_saved_bytes(int B, int T, int H, int W, int C, int heads, int d_ffn) {
   Dims d;
   if (make_dims(d, B, T, H, W, C, heads, d_ffn) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   carve_saved(b, d);
   return b.off;
 }
@@ -896,7 +348,7 @@ size_t axvs_axial_layer_train_saved_bytes(int B, int T, int H, int W, int C, int
 size_t axvs_axial_layer_train_scratch_bytes(int B, int T, int H, int W, int C, int heads, int d_ffn, int backward) {
   Dims d;
   if (make_dims(d, B, T, H, W, C, heads, d_ffn) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   carve_scratch(b, d, backward != 0);
   return b.off;
 }
@@ -905,11 +357,11 @@ int axvs_axial_layer_train_fwd(const float* src, const float* pos, float* out, c
                                int W, int C, int heads, int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, void* saved,
                                size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
   if (!src || !pos || !out || !params || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
-  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  if (int rc = check_drop(p_dropout, p_attn_drop)) return rc;
   Ctx c{};
   Saved s;
   int rc;
-  if ((rc = make_dims(c.d, B, T, H, W, C, heads, d_ffn)) != AXVS_OK || (rc = check_ptrs(params)) != AXVS_OK) return rc;
+  if ((rc = make_dims(c.d, B, T, H, W, C, heads, d_ffn)) != AXVS_OK || (rc = check_ptrs(params, "AxvsAxialLayerParams")) != AXVS_OK) return rc;
   if ((rc = train_setup(c, s, 2, false, saved, saved_bytes, scratch, scratch_bytes, stream)) != AXVS_OK) return rc;
   return forward(c, src, pos, out, *params, s, p_dropout, p_attn_drop, seed);
 }
@@ -919,12 +371,12 @@ int axvs_axial_layer_train_bwd(const float* d_out, const float* src, const float
                                int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, int recompute, void* saved, size_t saved_bytes,
                                void* scratch, size_t scratch_bytes, void* stream) {
   if (!d_out || !src || !pos || !params || !grads || !d_src || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
-  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  if (int rc = check_drop(p_dropout, p_attn_drop)) return rc;
   Ctx c{};
   Saved s;
   int rc;
-  if ((rc = make_dims(c.d, B, T, H, W, C, heads, d_ffn)) != AXVS_OK || (rc = check_ptrs(params)) != AXVS_OK ||
-      (rc = check_ptrs(reinterpret_cast<const AxvsAxialLayerParams*>(grads))) != AXVS_OK)
+  if ((rc = make_dims(c.d, B, T, H, W, C, heads, d_ffn)) != AXVS_OK || (rc = check_ptrs(params, "AxvsAxialLayerParams")) != AXVS_OK ||
+      (rc = check_ptrs(grads, "AxvsAxialLayerGrads")) != AXVS_OK)
     return rc;
   if ((rc = train_setup(c, s, 2, true, saved, saved_bytes, scratch, scratch_bytes, stream)) != AXVS_OK) return rc;
   const Dims& d = c.d;
@@ -945,14 +397,14 @@ int axvs_axial_layer_train_bwd(const float* d_out, const float* src, const float
   if ((rc = pass_bwd(c, sc.g0, src, pos, p.height_attn, g.height_attn, s.p[0], rmh, d.B * d.W, make_drop(p_dropout, seed, 1),
                      make_drop(p_attn_drop, seed, 2), d_src, d_pos, false)) != AXVS_OK)
     return rc;
-  return status();
+  return last_launch_status();
 }
 
 // ---- the full T*H*W layer (TemporalTrajectoryAttentionLayer), training tier: the axial layer's pass and tail code -----------------------
 size_t axvs_traj_layer_train_saved_bytes(int B, int T, int HW, int C, int heads, int d_ffn) {
   Dims d;
   if (make_traj_dims(d, B, T, HW, C, heads, d_ffn) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   carve_saved(b, d, 1);
   return b.off;
 }
@@ -960,7 +412,7 @@ size_t axvs_traj_layer_train_saved_bytes(int B, int T, int HW, int C, int heads,
 size_t axvs_traj_layer_train_scratch_bytes(int B, int T, int HW, int C, int heads, int d_ffn, int backward) {
   Dims d;
   if (make_traj_dims(d, B, T, HW, C, heads, d_ffn) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   carve_scratch(b, d, backward != 0);
   return b.off;
 }
@@ -969,7 +421,7 @@ int axvs_traj_layer_train_fwd(const float* src, const float* pos, float* out, co
                               int heads, int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, void* saved, size_t saved_bytes, void* scratch,
                               size_t scratch_bytes, void* stream) {
   if (!src || !pos || !out || !params || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
-  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  if (int rc = check_drop(p_dropout, p_attn_drop)) return rc;
   Ctx c{};
   Saved s;
   int rc;
@@ -982,7 +434,7 @@ int axvs_traj_layer_train_bwd(const float* d_out, const float* src, const float*
                               float* d_src, float* d_pos, int B, int T, int HW, int C, int heads, int d_ffn, float p_dropout, float p_attn_drop,
                               unsigned seed, int recompute, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
   if (!d_out || !src || !pos || !params || !grads || !d_src || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
-  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  if (int rc = check_drop(p_dropout, p_attn_drop)) return rc;
   Ctx c{};
   Saved s;
   int rc;
@@ -997,21 +449,21 @@ int axvs_traj_layer_train_bwd(const float* d_out, const float* src, const float*
   if ((rc = pass_bwd(c, c.sc.g1, src, pos, params->temporal_attn, grads->temporal_attn, s.p[0], traj_rowmap(c.d), B, make_drop(p_dropout, seed, 1),
                      make_drop(p_attn_drop, seed, 2), d_src, d_pos, true)) != AXVS_OK)
     return rc;
-  return status();
+  return last_launch_status();
 }
 
 // ---- MSDeformAttnTransformerEncoderLayer, training tier ------------------------------------------------------------------------
 size_t axvs_msda_layer_train_saved_bytes(int N, int S, int C, int heads, int L, int P, int d_ffn) {
   MdShape m;
   if (make_md_shape(m, N, S, C, heads, L, P, d_ffn) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   carve_md_saved(b, m);
   return b.off;
 }
 size_t axvs_msda_layer_train_scratch_bytes(int N, int S, int C, int heads, int L, int P, int d_ffn, int backward) {
   MdShape m;
   if (make_md_shape(m, N, S, C, heads, L, P, d_ffn) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   Scratch sc;
   MdScratch x;
   carve_md_scratch(b, m, backward != 0, sc, x);
@@ -1022,7 +474,7 @@ int axvs_msda_layer_train_fwd(const float* src, const float* pos, const float* r
                               int d_ffn, float p_dropout, float p_attn_drop, unsigned seed, void* saved, size_t saved_bytes, void* scratch,
                               size_t scratch_bytes, void* stream) {
   if (!src || !reference_points || !spatial_shapes || !out || !params || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
-  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  if (int rc = check_drop(p_dropout, p_attn_drop)) return rc;
   MdShape m;
   Ctx c{};
   MdSaved s;
@@ -1041,7 +493,7 @@ int axvs_msda_layer_train_bwd(const float* d_out, const float* src, const float*
                               size_t scratch_bytes, void* stream) {
   if (!d_out || !src || !reference_points || !spatial_shapes || !params || !grads || !d_src || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
   if (d_pos && !pos) return fail(AXVS_ERR_ARG, "d_pos wanted without pos");
-  if (!(p_dropout >= 0.f && p_dropout < 1.f) || !(p_attn_drop >= 0.f && p_attn_drop < 1.f)) return fail(AXVS_ERR_ARG, "dropout probability outside [0, 1)");
+  if (int rc = check_drop(p_dropout, p_attn_drop)) return rc;
   MdShape m;
   Ctx c{};
   MdSaved s;
@@ -1060,7 +512,7 @@ int axvs_msda_layer_train_bwd(const float* d_out, const float* src, const float*
 size_t axvs_cc_module_train_saved_bytes(const AxvsCCTrainCfg* cfg) {
   CCShape s;
   if (make_cc_shape(s, cfg) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   carve_cc_saved(b, s);
   return b.off;
 }
@@ -1068,7 +520,7 @@ size_t axvs_cc_module_train_saved_bytes(const AxvsCCTrainCfg* cfg) {
 size_t axvs_cc_module_train_scratch_bytes(const AxvsCCTrainCfg* cfg, int backward) {
   CCShape s;
   if (make_cc_shape(s, cfg) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   carve_scratch(b, s.d, backward != 0);
   carve_cc_scratch(b, s, backward != 0);
   return b.off;
@@ -1090,8 +542,8 @@ int axvs_cc_module_train_fwd(const float* clip_query, const float* panoptic_feat
   int rc;
   if ((rc = cc_setup(k, cfg, scratch, scratch_bytes, saved, saved_bytes, sv, false, stream)) != AXVS_OK) return rc;
   for (int l = 0; l < k.s.nl; ++l)
-    if ((rc = cc_check_ptrs(&layers[l], sizeof(AxvsCCLayerParams), "AxvsCCLayerParams")) != AXVS_OK) return rc;
-  if ((rc = cc_check_ptrs(heads, sizeof(AxvsCCHeadParams), "AxvsCCHeadParams")) != AXVS_OK) return rc;
+    if ((rc = check_ptrs(&layers[l], "AxvsCCLayerParams")) != AXVS_OK) return rc;
+  if ((rc = check_ptrs(heads, "AxvsCCHeadParams")) != AXVS_OK) return rc;
   return cc_forward(k, clip_query, panoptic_features, pred_logits, pred_masks, bn_stats, layers, *heads, sv);
 }
 
@@ -1107,11 +559,11 @@ int axvs_cc_module_train_bwd(const float* d_logits, const float* d_masks, const 
   int rc;
   if ((rc = cc_setup(k, cfg, scratch, scratch_bytes, saved, saved_bytes, sv, true, stream)) != AXVS_OK) return rc;
   for (int l = 0; l < k.s.nl; ++l) {
-    if ((rc = cc_check_ptrs(&layers[l], sizeof(AxvsCCLayerParams), "AxvsCCLayerParams")) != AXVS_OK) return rc;
-    if ((rc = cc_check_ptrs(&layer_grads[l], sizeof(AxvsCCLayerGrads), "AxvsCCLayerGrads")) != AXVS_OK) return rc;
+    if ((rc = check_ptrs(&layers[l], "AxvsCCLayerParams")) != AXVS_OK) return rc;
+    if ((rc = check_ptrs(&layer_grads[l], "AxvsCCLayerGrads")) != AXVS_OK) return rc;
   }
-  if ((rc = cc_check_ptrs(heads, sizeof(AxvsCCHeadParams), "AxvsCCHeadParams")) != AXVS_OK) return rc;
-  if ((rc = cc_check_ptrs(head_grads, sizeof(AxvsCCHeadGrads), "AxvsCCHeadGrads")) != AXVS_OK) return rc;
+  if ((rc = check_ptrs(heads, "AxvsCCHeadParams")) != AXVS_OK) return rc;
+  if ((rc = check_ptrs(head_grads, "AxvsCCHeadGrads")) != AXVS_OK) return rc;
   return cc_backward(k, d_logits, d_masks, clip_query, panoptic_features, layers, *heads, layer_grads, *head_grads, d_clip_query, sv);
 }
 
@@ -1124,11 +576,11 @@ int axvs_cc_layers_train_fwd(const float* clip_query, float* out_queries, const 
   int rc;
   if ((rc = cc_setup(k, cfg, scratch, scratch_bytes, saved, saved_bytes, sv, false, stream)) != AXVS_OK) return rc;
   for (int l = 0; l < k.s.nl; ++l)
-    if ((rc = cc_check_ptrs(&layers[l], sizeof(AxvsCCLayerParams), "AxvsCCLayerParams")) != AXVS_OK) return rc;
+    if ((rc = check_ptrs(&layers[l], "AxvsCCLayerParams")) != AXVS_OK) return rc;
   if ((rc = cc_chain_forward(k, clip_query, layers, sv)) != AXVS_OK) return rc;
   const size_t n = (size_t)k.s.nl * k.s.M * kCcC;
   if (hipMemcpyAsync(out_queries, sv.x2, n * sizeof(float), hipMemcpyDeviceToDevice, k.st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
-  return status();
+  return last_launch_status();
 }
 
 int axvs_cc_layers_train_bwd(const float* d_queries, const float* clip_query, const AxvsCCLayerParams* layers, const AxvsCCLayerGrads* layer_grads,
@@ -1140,8 +592,8 @@ int axvs_cc_layers_train_bwd(const float* d_queries, const float* clip_query, co
   int rc;
   if ((rc = cc_setup(k, cfg, scratch, scratch_bytes, saved, saved_bytes, sv, true, stream)) != AXVS_OK) return rc;
   for (int l = 0; l < k.s.nl; ++l) {
-    if ((rc = cc_check_ptrs(&layers[l], sizeof(AxvsCCLayerParams), "AxvsCCLayerParams")) != AXVS_OK) return rc;
-    if ((rc = cc_check_ptrs(&layer_grads[l], sizeof(AxvsCCLayerGrads), "AxvsCCLayerGrads")) != AXVS_OK) return rc;
+    if ((rc = check_ptrs(&layers[l], "AxvsCCLayerParams")) != AXVS_OK) return rc;
+    if ((rc = check_ptrs(&layer_grads[l], "AxvsCCLayerGrads")) != AXVS_OK) return rc;
   }
   const size_t n = (size_t)k.s.nl * k.s.M * kCcC;            // the chain adds the next layer's input gradient into this buffer
   if (hipMemcpyAsync(k.x.dx2h, d_queries, n * sizeof(float), hipMemcpyDeviceToDevice, k.st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
@@ -1152,7 +604,7 @@ int axvs_cc_layers_train_bwd(const float* d_queries, const float* clip_query, co
 size_t axvs_tl_heads_train_saved_bytes(const AxvsTLHeadTrainCfg* cfg) {
   TLHShape s;
   if (make_tlh_shape(s, cfg) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   carve_tlh_saved(b, s);
   return b.off;
 }
@@ -1160,7 +612,7 @@ size_t axvs_tl_heads_train_saved_bytes(const AxvsTLHeadTrainCfg* cfg) {
 size_t axvs_tl_heads_train_scratch_bytes(const AxvsTLHeadTrainCfg* cfg, int backward) {
   TLHShape s;
   if (make_tlh_shape(s, cfg) != AXVS_OK) return 0;
-  Bump b(nullptr);
+  Carver b(nullptr);
   Scratch sc{};
   carve_tlh_scratch(b, s, backward != 0, &sc);
   return b.off;
@@ -1174,7 +626,7 @@ int axvs_tl_heads_train_fwd(const float* queries, const float* mask_feature, flo
   TLHSaved sv;
   TLHScratch x;
   int rc;
-  if ((rc = cc_check_ptrs(params, sizeof(AxvsTLHeadParams), "AxvsTLHeadParams")) != AXVS_OK) return rc;
+  if ((rc = check_ptrs(params, "AxvsTLHeadParams")) != AXVS_OK) return rc;
   if ((rc = tlh_setup(c, s, sv, x, cfg, saved, saved_bytes, scratch, scratch_bytes, false, stream)) != AXVS_OK) return rc;
   return tlh_forward(c, s, queries, mask_feature, cls_logits, mask_logits, *params, sv, x);
 }
@@ -1189,21 +641,21 @@ int axvs_tl_heads_train_bwd(const float* d_cls, const float* d_masks, const floa
   TLHSaved sv;
   TLHScratch x;
   int rc;
-  if ((rc = cc_check_ptrs(params, sizeof(AxvsTLHeadParams), "AxvsTLHeadParams")) != AXVS_OK) return rc;
-  if ((rc = cc_check_ptrs(grads, sizeof(AxvsTLHeadGrads), "AxvsTLHeadGrads")) != AXVS_OK) return rc;
+  if ((rc = check_ptrs(params, "AxvsTLHeadParams")) != AXVS_OK) return rc;
+  if ((rc = check_ptrs(grads, "AxvsTLHeadGrads")) != AXVS_OK) return rc;
   if ((rc = tlh_setup(c, s, sv, x, cfg, saved, saved_bytes, scratch, scratch_bytes, true, stream)) != AXVS_OK) return rc;
   return tlh_backward(c, s, d_cls, d_masks, queries, mask_feature, *params, *grads, d_queries, d_mask_feature, sv, x);
 }
 
 // ---- 1x1 convolution + GroupNorm, train() mode (WC/msdeformattn.py:349-375 under autograd) ----
 size_t axvs_conv1x1_gn_train_saved_bytes(int N, int HW, int Cin, int Cout, int groups, int in_layout, long long in_batch_stride, long long in_ld) {
-  Bump sv(nullptr), sc(nullptr);
+  Carver sv(nullptr), sc(nullptr);
   const bool copy_x = in_layout == 0 || !(in_ld == Cin && in_batch_stride == (long long)HW * Cin);
   carve_convgn(sv, sc, N, HW, Cin, Cout, groups, copy_x, false, false);
   return sv.off;
 }
 size_t axvs_conv1x1_gn_train_scratch_bytes(int N, int HW, int Cin, int Cout, int groups, int backward) {
-  Bump sv(nullptr), sc(nullptr);
+  Carver sv(nullptr), sc(nullptr);
   carve_convgn(sv, sc, N, HW, Cin, Cout, groups, true, backward != 0, true);
   return sc.off;
 }
@@ -1214,12 +666,11 @@ int axvs_conv1x1_gn_train_fwd(const float* x, int in_layout, long long in_batch_
   if (!x || !out || !p || !p->conv_w || !p->conv_b || !p->gn_w || !p->gn_b || !saved || !scratch) return fail(AXVS_ERR_ARG, "null pointer");
   if (int rc = convgn_check(N, HW, Cin, Cout, groups, in_layout, out_layout, in_batch_stride, in_ld, out_batch_stride, out_ld)) return rc;
   const bool copy_x = in_layout == 0 || !(in_ld == Cin && in_batch_stride == (long long)HW * Cin);
-  Bump sv(saved), sc(scratch);
+  Carver sv(saved), sc(scratch);
   const ConvGnBufs b = carve_convgn(sv, sc, N, HW, Cin, Cout, groups, copy_x, false, out_layout == 0);
-  if (sv.off > saved_bytes || sc.off > scratch_bytes) return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sv.off, scratch_bytes, sc.off);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Gemm g;
-  if (int rc = g.init(st)) return rc;
+  Ctx c{};
+  if (int rc = train_begin(c, sv, saved_bytes, sc, scratch_bytes, stream)) return rc;
+  hipStream_t st = c.st;
   const long long M = (long long)N * HW;
   const int nblk = (HW + 63) / 64;
   const float* xt = x;
@@ -1233,7 +684,7 @@ int axvs_conv1x1_gn_train_fwd(const float* x, int in_layout, long long in_batch_
   }
   // y = x W^T + b: three bf16 pieces per operand (fp32 accuracy: the GroupNorm statistics are formed on it)
   GemmEpi e{p->conv_b, 1.f, 0, Drop{0u, 0u, 0u, 1.f}, 0.f};
-  if (int rc = g.fwd(xt, p->conv_w, b.y, M, Cout, Cin, 0.f, &e, true)) return rc;
+  if (int rc = c.g.fwd(xt, p->conv_w, b.y, M, Cout, Cin, 0.f, &e, true)) return rc;
   hipLaunchKernelGGL((gt_block_colsums_kernel<0>), dim3((unsigned)nblk, (unsigned)N), dim3(256), 0, st, (const float*)b.y, (const float*)nullptr, (const float*)nullptr, b.part,
                      HW, Cout, groups);
   hipLaunchKernelGGL(gt_sum_blocks_kernel, dim3(blocks((size_t)N * Cout)), dim3(256), 0, st, (const float*)b.part, b.ab, nblk, Cout, (long long)N * Cout);
@@ -1249,7 +700,7 @@ int axvs_conv1x1_gn_train_fwd(const float* x, int in_layout, long long in_batch_
     hipLaunchKernelGGL(gt_tokens_to_nchw_kernel, dim3((unsigned)nblk, (unsigned)((Cout + 63) / 64), (unsigned)N), dim3(256), 0, st, (const float*)b.otok, out, Cout, HW,
                        (long long)HW * Cout, (long long)Cout);
   }
-  return status();
+  return last_launch_status();
 }
 
 /* d_out in the forward's out layout; x as in the forward (read only when it was contiguous token rows: otherwise the saved copy is used); grads: every
@@ -1261,12 +712,10 @@ int axvs_conv1x1_gn_train_bwd(const float* d_out, int out_layout, long long out_
     return fail(AXVS_ERR_ARG, "null pointer");
   if (int rc = convgn_check(N, HW, Cin, Cout, groups, in_layout, out_layout, in_batch_stride, in_ld, out_batch_stride, out_ld)) return rc;
   const bool copy_x = in_layout == 0 || !(in_ld == Cin && in_batch_stride == (long long)HW * Cin);
-  Bump sv(saved), sc(scratch);
+  Carver sv(saved), sc(scratch);
   const ConvGnBufs b = carve_convgn(sv, sc, N, HW, Cin, Cout, groups, copy_x, true, out_layout == 0);
-  if (sv.off > saved_bytes || sc.off > scratch_bytes) return fail(AXVS_ERR_WORKSPACE, "training buffers too small: saved %zu < %zu or scratch %zu < %zu", saved_bytes, sv.off, scratch_bytes, sc.off);
   Ctx c{};
-  c.st = static_cast<hipStream_t>(stream);
-  if (int rc = c.g.init(c.st)) return rc;
+  if (int rc = train_begin(c, sv, saved_bytes, sc, scratch_bytes, stream)) return rc;
   c.sc.wpart = b.wpart; c.sc.part_a = b.part_a; c.sc.wt = b.wt;
   hipStream_t st = c.st;
   const long long M = (long long)N * HW;
@@ -1301,19 +750,25 @@ int axvs_conv1x1_gn_train_bwd(const float* d_out, int out_layout, long long out_
       return fail(AXVS_ERR_ARG, "conv1x1 + GroupNorm backward: an input gradient in strided token rows is not built (pass contiguous rows or NCHW)");
     }
   }
-  return status();
+  return last_launch_status();
 }
 
-// ---- test hooks: one call of the GEMM dispatch above (include/axvs.h) --------------------------------------------------------------
+// the Ctx scratch one test call uses: wpart and the bias partials part_a (weight gradient), wt (input gradient)
+static void carve_test_gemm(Carver& b, const AxvsTestGemm& t, Scratch& sc) {
+  if (t.op == AXVS_TEST_GEMM_WGRAD) {
+    sc.wpart = b.f((size_t)(Gemm::kSplit + 1) * t.N * t.K);
+    sc.part_a = b.f((size_t)Gemm::kSplit * t.N);
+  } else if (t.op == AXVS_TEST_GEMM_DGRAD) {
+    sc.wt = b.f((size_t)t.N * t.K);
+  }
+}
+
+// ---- test hooks: one call of the GEMM dispatch (axvs_train_host.h, include/axvs.h) --------------------------------------------------------------
 size_t axvs_test_train_gemm_scratch_bytes(const AxvsTestGemm* t) {
   if (!t) return 0;
-  Bump b(nullptr);
-  if (t->op == AXVS_TEST_GEMM_WGRAD) {
-    b.f((size_t)(Gemm::kSplit + 1) * t->N * t->K);     // Ctx::sc.wpart
-    b.f((size_t)Gemm::kSplit * t->N);                 // Ctx::sc.part_a (the bias partials)
-  } else if (t->op == AXVS_TEST_GEMM_DGRAD) {
-    b.f((size_t)t->N * t->K);                         // Ctx::sc.wt
-  }
+  Carver b(nullptr);
+  Scratch sc{};
+  carve_test_gemm(b, *t, sc);
   return b.off;
 }
 
@@ -1348,13 +803,8 @@ int axvs_test_train_gemm(AxvsTestGemm* t, void* scratch, void* stream) {
   Ctx c{};
   c.st = static_cast<hipStream_t>(stream);
   if ((rc = c.g.init(c.st))) return rc;
-  Bump b(scratch);
-  if (t->op == AXVS_TEST_GEMM_WGRAD) {
-    c.sc.wpart = b.f((size_t)(Gemm::kSplit + 1) * t->N * t->K);
-    c.sc.part_a = b.f((size_t)Gemm::kSplit * t->N);
-  } else if (t->op == AXVS_TEST_GEMM_DGRAD) {
-    c.sc.wt = b.f((size_t)t->N * t->K);
-  }
+  Carver b(scratch);
+  carve_test_gemm(b, *t, c.sc);
   t_gemm_variant = 0;
   switch (t->op) {
     case AXVS_TEST_GEMM_NT: rc = c.g.nt(t->a, t->b, t->c, t->M, t->N, t->K, ld, e, t->exact != 0, t->zsplits > 0 ? t->zsplits : 1); break;
@@ -1370,7 +820,7 @@ int axvs_test_train_gemm(AxvsTestGemm* t, void* scratch, void* stream) {
   }
   t->variant = t_gemm_variant;
   if (rc) return rc;
-  return status();
+  return last_launch_status();
 }
 
 }  // extern "C"

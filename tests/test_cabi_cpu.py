@@ -693,3 +693,80 @@ def test_every_forward_refuses_a_workspace_one_byte_short():
         err = L.axvs_last_error().decode()
         assert rc == -2, (name, rc, err)
         assert str(need - 1) in err and str(need) in err and "workspace too small" in err, (name, err)
+
+
+def _short_training_calls():
+    """(entry point, saved bytes, scratch bytes, call with (saved_bytes, scratch_bytes)) for every *_train_fwd / *_train_bwd, at the
+    smallest shapes each family takes.  Pointers are made up as in _short_workspace_calls (the size check comes before any device
+    work); what the host reads before that check (configurations, spatial_shapes, the fields of the parameter structs) is real."""
+    from axial_vs_amd import _lib
+    L = _lib.lib()
+    p = [ctypes.c_void_p(0x10000 * (i + 1)) for i in range(10)]
+
+    def full(cls, n=1):      # n structs of `cls`, every field a made-up non-null pointer
+        k = ctypes.sizeof(cls) // ctypes.sizeof(ctypes.c_void_p)
+        one = [_lib.fill(cls, [ctypes.c_void_p(0x100000 + 64 * (j * k + i)) for i in range(k)]) for j in range(n)]
+        return (cls * n)(*one)
+    B, T, H, W, C, h, F = 1, 2, 4, 4, 64, 8, 64
+    ax, tj, md = full(_lib.AxvsAxialLayerParams), full(_lib.AxvsTrajLayerParams), full(_lib.AxvsMsdaLayerParams)
+    shapes = (ctypes.c_int * 4)(4, 4, 2, 2)          # two levels, S = 20
+    N, S, nlv, P = 1, 20, 2, 4
+    cc = _lib.AxvsCCTrainCfg(B=1, Q=8, Tc=2, V=1, H=4, W=4, K1=3, num_layers=2, rates=(ctypes.c_int * 3)(1, 2, 3))
+    chain = _lib.AxvsCCTrainCfg(B=1, Q=8, Tc=2, num_layers=2, rates=(ctypes.c_int * 3)(1, 2, 3), chain_only=1)
+    ccl, cch, cchg = full(_lib.AxvsCCLayerParams, 2), full(_lib.AxvsCCHeadParams), full(_lib.AxvsCCHeadGrads)
+    tl = _lib.AxvsTLHeadTrainCfg(B=1, Q=4, Tc=2, frames_per_clip=1, h=4, w=4, K1=3, Cm=128, num_layers=1)
+    tlp, tlg = full(_lib.AxvsTLHeadParams), full(_lib.AxvsTLHeadGrads)
+    gn = full(_lib.AxvsConvGnParams)
+    HW, Cin, Cout, G = 16, 8, 8, 2
+    cg = (HW * Cin, HW)                              # NCHW: batch stride, row stride
+    co = (HW * Cout, HW)
+    conv_saved = L.axvs_conv1x1_gn_train_saved_bytes(N, HW, Cin, Cout, G, 0, *cg)
+    return [
+        ("axvs_axial_layer_train_fwd", L.axvs_axial_layer_train_saved_bytes(B, T, H, W, C, h, F), L.axvs_axial_layer_train_scratch_bytes(B, T, H, W, C, h, F, 0),
+         lambda sv, sc: L.axvs_axial_layer_train_fwd(p[0], p[1], p[2], ax, B, T, H, W, C, h, F, 0.1, 0.1, 7, p[3], sv, p[4], sc, None)),
+        ("axvs_axial_layer_train_bwd", L.axvs_axial_layer_train_saved_bytes(B, T, H, W, C, h, F), L.axvs_axial_layer_train_scratch_bytes(B, T, H, W, C, h, F, 1),
+         lambda sv, sc: L.axvs_axial_layer_train_bwd(p[0], p[1], p[2], ax, ax, p[3], p[4], B, T, H, W, C, h, F, 0.1, 0.1, 7, 0, p[5], sv, p[6], sc, None)),
+        ("axvs_traj_layer_train_fwd", L.axvs_traj_layer_train_saved_bytes(B, T, H * W, C, h, F), L.axvs_traj_layer_train_scratch_bytes(B, T, H * W, C, h, F, 0),
+         lambda sv, sc: L.axvs_traj_layer_train_fwd(p[0], p[1], p[2], tj, B, T, H * W, C, h, F, 0.1, 0.1, 7, p[3], sv, p[4], sc, None)),
+        ("axvs_traj_layer_train_bwd", L.axvs_traj_layer_train_saved_bytes(B, T, H * W, C, h, F), L.axvs_traj_layer_train_scratch_bytes(B, T, H * W, C, h, F, 1),
+         lambda sv, sc: L.axvs_traj_layer_train_bwd(p[0], p[1], p[2], tj, tj, p[3], p[4], B, T, H * W, C, h, F, 0.1, 0.1, 7, 1, p[5], sv, p[6], sc, None)),
+        ("axvs_msda_layer_train_fwd", L.axvs_msda_layer_train_saved_bytes(N, S, C, h, nlv, P, F), L.axvs_msda_layer_train_scratch_bytes(N, S, C, h, nlv, P, F, 0),
+         lambda sv, sc: L.axvs_msda_layer_train_fwd(p[0], p[1], p[2], 2, None, shapes, p[3], md, N, S, C, h, nlv, P, F, 0.1, 0.1, 7, p[4], sv, p[5], sc, None)),
+        ("axvs_msda_layer_train_bwd", L.axvs_msda_layer_train_saved_bytes(N, S, C, h, nlv, P, F), L.axvs_msda_layer_train_scratch_bytes(N, S, C, h, nlv, P, F, 1),
+         lambda sv, sc: L.axvs_msda_layer_train_bwd(p[0], p[1], p[2], p[3], 2, None, shapes, md, md, p[4], p[5], N, S, C, h, nlv, P, F, 0.1, 0.1, 7, 0,
+                                                    p[6], sv, p[7], sc, None)),
+        ("axvs_cc_module_train_fwd", L.axvs_cc_module_train_saved_bytes(cc), L.axvs_cc_module_train_scratch_bytes(cc, 0),
+         lambda sv, sc: L.axvs_cc_module_train_fwd(p[0], p[1], p[2], p[3], p[4], ccl, cch, cc, p[5], sv, p[6], sc, None)),
+        ("axvs_cc_module_train_bwd", L.axvs_cc_module_train_saved_bytes(cc), L.axvs_cc_module_train_scratch_bytes(cc, 1),
+         lambda sv, sc: L.axvs_cc_module_train_bwd(p[0], p[1], p[2], p[3], ccl, cch, ccl, cchg, p[4], cc, p[5], sv, p[6], sc, None)),
+        ("axvs_cc_layers_train_fwd", L.axvs_cc_module_train_saved_bytes(chain), L.axvs_cc_module_train_scratch_bytes(chain, 0),
+         lambda sv, sc: L.axvs_cc_layers_train_fwd(p[0], p[1], ccl, chain, p[2], sv, p[3], sc, None)),
+        ("axvs_cc_layers_train_bwd", L.axvs_cc_module_train_saved_bytes(chain), L.axvs_cc_module_train_scratch_bytes(chain, 1),
+         lambda sv, sc: L.axvs_cc_layers_train_bwd(p[0], p[1], ccl, ccl, p[2], chain, p[3], sv, p[4], sc, None)),
+        ("axvs_tl_heads_train_fwd", L.axvs_tl_heads_train_saved_bytes(tl), L.axvs_tl_heads_train_scratch_bytes(tl, 0),
+         lambda sv, sc: L.axvs_tl_heads_train_fwd(p[0], p[1], p[2], p[3], tlp, tl, p[4], sv, p[5], sc, None)),
+        ("axvs_tl_heads_train_bwd", L.axvs_tl_heads_train_saved_bytes(tl), L.axvs_tl_heads_train_scratch_bytes(tl, 1),
+         lambda sv, sc: L.axvs_tl_heads_train_bwd(p[0], p[1], p[2], p[3], tlp, tlg, p[4], p[5], tl, p[6], sv, p[7], sc, None)),
+        ("axvs_conv1x1_gn_train_fwd", conv_saved, L.axvs_conv1x1_gn_train_scratch_bytes(N, HW, Cin, Cout, G, 0),
+         lambda sv, sc: L.axvs_conv1x1_gn_train_fwd(p[0], 0, *cg, p[1], 0, *co, gn, N, HW, Cin, Cout, G, 1e-5, p[2], sv, p[3], sc, None)),
+        ("axvs_conv1x1_gn_train_bwd", conv_saved, L.axvs_conv1x1_gn_train_scratch_bytes(N, HW, Cin, Cout, G, 1),
+         lambda sv, sc: L.axvs_conv1x1_gn_train_bwd(p[0], 0, *co, p[1], 0, *cg, gn, gn, p[2], N, HW, Cin, Cout, G, p[3], sv, p[4], sc, None)),
+    ]
+
+
+def test_every_training_entry_point_refuses_buffers_one_byte_short():
+    """The buffer contract of the training tier (include/axvs.h): a *_train_fwd / *_train_bwd called with one byte less than either of
+    its size queries asks for -- saved_bytes, then scratch_bytes -- returns AXVS_ERR_WORKSPACE (-2) before any device work, and the
+    error text holds the short size and the needed one.  Every training entry point is covered: the names come from SIGNATURES."""
+    from axial_vs_amd import _lib
+    L = _lib.lib()
+    calls = _short_training_calls()
+    train = {n for n in _lib.SIGNATURES if n.endswith("_train_fwd") or n.endswith("_train_bwd")}
+    assert {n for n, _, _, _ in calls} == train, sorted({n for n, _, _, _ in calls} ^ train)
+    for name, saved, scratch, call in calls:
+        assert saved > 0 and scratch > 0, (name, saved, scratch)
+        for sv, sc, short, need in ((saved - 1, scratch, saved - 1, saved), (saved, scratch - 1, scratch - 1, scratch)):
+            rc = call(sv, sc)
+            err = L.axvs_last_error().decode()
+            assert rc == -2, (name, rc, err)
+            assert f"{short} < {need}" in err and "training buffers too small" in err, (name, err)

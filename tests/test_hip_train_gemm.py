@@ -25,7 +25,6 @@ output groups, unwritten statistics slots): they must come back bit-identical, a
 operand's extent into a NaN in the result."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -82,19 +81,16 @@ def vclass(v):
 
 
 def registered():
-    """The instantiations Gemm::init registers (axvs_train.hip), as variant ids."""
-    src = open(os.path.join(ROOT, "axial_vs_amd", "csrc", "axvs_train.hip")).read()
-    body = re.search(r"int init\(hipStream_t s\) \{(.*?)\n  \}", src, re.S).group(1)
-    is_true = lambda s: s == "true"
+    """Every instantiation the dispatch rules of Gemm can reach (expect_nt, expect_wgrad and expect_tn below state the same rules per
+    call), as variant ids."""
     out = set()
-    for kind, args in re.findall(r"tr_gemm_(nt|tn)_kernel<([^>]*)>", body):
-        a = [x.strip() for x in args.split(",")]
-        if kind == "nt":
-            a += ["0", "false", "false", "false", "false"][len(a) - 1:]
-            out.add(nt_var(int(a[0]), is_true(a[2]), is_true(a[3]), is_true(a[4]), is_true(a[5])))
-        else:
-            a += ["false", "0", "false", "false"][len(a):]
-            out.add(tn_var(is_true(a[0]), int(a[1]), is_true(a[2]), is_true(a[3])))
+    for gen, add in ((False, False), (True, False), (False, True)):      # the general loader takes the addend at run time: no GEN + ADD
+        out |= {nt_var(ns, gen, add) for ns in (2, 3)}                   # split precision: two pieces, or three when exact
+        out |= {nt_var(1, gen, add, f16) for f16 in (False, True)}       # train_amp 1 (bf16) / 2 (fp16): one piece
+    out |= {nt_var(2, gen, aff=True) for gen in (False, True)}           # the affine loader: two pieces, no addend
+    out |= {tn_var(False, amp) for amp in (0, 1, 2)}                     # weight gradient: 16-byte loader, follows train_amp
+    for gen in (False, True):                                            # einsum: plain, with statistics, or grouped output rows
+        out |= {tn_var(gen), tn_var(gen, stats=True), tn_var(gen, grp=True)}
     return out
 
 
