@@ -320,13 +320,17 @@ __global__ __launch_bounds__(256) void criterion_finish_kernel(CritArgs a, const
       s.wcls[o] = wc;
       s.label[o] = lab;
       const float* x = a.logits[l] + ((long long)b * N + n) * K1;
-      float mx = -__builtin_huge_valf();
+      // CE = log(1 + sum of exp(x[c] - max) over the other classes) - (x[lab] - max): (max + log(sum)) - x[lab] cancels when the label's logit
+      // dominates (the whole loss of a one-query problem), and log(1 + s) of a rounded 1 + s loses s's low bits
+      float mx = x[0];
+      int am = 0;
 #pragma unroll 8
-      for (int c = 0; c < K1; ++c) mx = fmaxf(mx, x[c]);
+      for (int c = 1; c < K1; ++c)
+        if (x[c] > mx) { mx = x[c]; am = c; }
       float se = 0.f;
 #pragma unroll 8
-      for (int c = 0; c < K1; ++c) se += expf(x[c] - mx);
-      const float ce = (mx + logf(se)) - x[lab];
+      for (int c = 0; c < K1; ++c) se += c == am ? 0.f : expf(x[c] - mx);
+      const float ce = log1pf(se) - (x[lab] - mx);
       sf[n] = (lab == K1 - 1 ? 0.25f : 0.75f) * ce * wc;
     }
     __syncthreads();

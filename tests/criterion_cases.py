@@ -25,7 +25,29 @@ THE BOUND of the CPU test on the reference's fp32 values is derived from the num
 or log-softmax value carries (N + 4) u, a sum of P non-negative terms at most (P - 1) u more whatever the order, a ratio of two such sums
 twice that plus the division, and each loss is a product / mean of a few such ratios and of the matcher's similarities
 (fp32_bound_mask): fp32_bound = 4 (P + N + K + 8) u.  The same bound, relative to the largest entry, holds for a gradient element, which is
-a short sum of products of such quantities."""
+a short sum of products of such quantities.
+
+EDGE CASES.  CASES sits on the grid the kernels were written for: N a multiple of 4 (wave g of a workgroup holds the queries g, g + 4, ...)
+and P of 1 to 4 tiles of 64 pixels or an even split.  EDGE_CASES are fixtures of the same kind at the sizes where the guard code runs;
+a problem gets min(ceil(512 / (L B)), ceil(ntiles / 4)) workgroups of ceil(ntiles / that) tiles, the last one with what is left.
+    N = 1, P = 1, K + 1 = 2   three waves without a query, every ce exactly 0 (count = max(0, 1)), d pred_masks zero in exact arithmetic
+    N = 2, M = (1, 3)         N < 4; M = 3 > N is solved on the transpose; own matching per layer; P = 65: one full tile and one pixel
+    N = 3, M = (2, 0)         N < 4; P = 63: a single partial tile; the second video has no object; shared matching over 3 layers; float
+    N = 5, M = (0, 4)         wave 0 holds two queries, the others one; the FIRST video has no object (its offset into the concatenated
+                              targets is the next video's); P = 300: 5 tiles, two workgroups of 3 and 2 tiles (the second one's range is
+                              clamped, starts on an odd tile and ends on a 44-pixel tile); 5 tiles split evenly under no plan of >= 2 tiles
+    N = 7, M = (9, 2)         waves of 2, 2, 2 and 1 queries; M = 9 > N; no masking; the same split; the case of the input-form tests
+    N = 127                   the top register slot of wave 3 is empty (the unrolled `q < N` guard at 32 slots); the same split
+    N = 129, M = (4, 3)       the first N of the any-size kernels, wave 0's last query alone; two videos with their own matching per layer;
+                              the any-size kernels on two workgroups
+    N = 130, P = 581          10 tiles: three workgroups of 4, 4 and 2 tiles on the any-size kernels; float targets
+    N = 260, M = 40           the any-size kernels' LDS arrays beyond 256; in the matcher 9 x 2 = 18 output blocks, so two block chunks,
+                              on two pixel workgroups, with more than 48 KB of dynamic LDS
+    N = 512, P = 70           the bound on N
+    N = 6, M = (0, 0)         no video has an object: mask and dice losses exactly 0, the class loss comes from the void IoU alone
+UNSCREENED_CASES holds what the reference cannot give a screened fixture for: objects whose masks are all zero (target kind "blank";
+N = 6, P = 65).  Every similarity is 0, every assignment ties, and the stability screen fails by construction.  Under masking every
+pixel is void; the tests assert the exact zeros and compare the class loss with the restatement on the device's own pairs."""
 import json
 import os
 
@@ -49,6 +71,30 @@ CASES = {
     "g19_criterion_N100_M1_L1_share_mv1": (100, (1,), 40, 1, 8, 8, 1, 1, 1, "bool"),
 }
 BIG, RAGGED = "g19_criterion_N128_M23_L2_share_mv1", "g19_criterion_N20_M33-7_L3_own_mv1"
+
+# The edges of the kernels' guard code, in the same format (see EDGE CASES above)
+EDGE_CASES = {
+    "g19_criterion_N1_M1_L1_share_mv1": (1, (1,), 1, 1, 1, 1, 1, 1, 1, "bool"),
+    "g19_criterion_N2_M1-3_L2_own_mv1": (2, (1, 3), 3, 1, 5, 13, 2, 0, 1, "bool"),
+    "g19_criterion_N3_M2-0_L3_share_mv1_float": (3, (2, 0), 4, 1, 7, 9, 3, 1, 1, "float"),
+    "g19_criterion_N5_M0-4_L2_own_mv1": (5, (0, 4), 6, 1, 4, 75, 2, 0, 1, "bool"),
+    "g19_criterion_N7_M9-2_L2_share_mv0": (7, (9, 2), 5, 2, 5, 30, 2, 1, 0, "bool"),
+    "g19_criterion_N127_M6_L1_share_mv1": (127, (6,), 9, 1, 5, 60, 1, 1, 1, "bool"),
+    "g19_criterion_N129_M4-3_L2_own_mv1": (129, (4, 3), 9, 1, 4, 75, 2, 0, 1, "bool"),
+    "g19_criterion_N130_M5_L1_share_mv1_float": (130, (5,), 3, 1, 7, 83, 1, 1, 1, "float"),
+    "g19_criterion_N260_M40_L1_share_mv1": (260, (40,), 10, 1, 4, 75, 1, 1, 1, "bool"),
+    "g19_criterion_N512_M3_L1_share_mv1": (512, (3,), 5, 1, 2, 35, 1, 1, 1, "bool"),
+    "g19_criterion_N6_M0-0_L2_share_mv1": (6, (0, 0), 4, 1, 5, 13, 2, 1, 1, "bool"),
+}
+# the edge cases whose pixel range is split over workgroups (the GPU test asserts the split from the library's size query), and the two
+# of them that run the any-size kernels
+SPLIT = ["g19_criterion_N5_M0-4_L2_own_mv1", "g19_criterion_N7_M9-2_L2_share_mv0", "g19_criterion_N127_M6_L1_share_mv1",
+         "g19_criterion_N129_M4-3_L2_own_mv1", "g19_criterion_N130_M5_L1_share_mv1_float", "g19_criterion_N260_M40_L1_share_mv1"]
+ANY_SPLIT = ["g19_criterion_N129_M4-3_L2_own_mv1", "g19_criterion_N130_M5_L1_share_mv1_float"]
+# No fixture: every similarity of all-zero targets is 0, every assignment ties, and no matching passes the generator's stability screen
+UNSCREENED_CASES = {
+    "blank_N6_M3-2_L2_share_mv1": (6, (3, 2), 4, 1, 5, 13, 2, 1, 1, "blank"),
+}
 KEYS = ("loss_ce", "loss_mask", "loss_dice")
 
 
@@ -68,7 +114,8 @@ def make_case(case, seed):
     targets = []
     for b, M in enumerate(Ms):
         _, _, labels, tbool, tf = mc.make_inputs(N, M, K, T, H, W, 19500 + 10 * seed + b)
-        targets.append({"labels": labels, "masks": tbool if kind == "bool" else tf.float()})
+        masks = {"bool": tbool, "float": tf.float(), "blank": torch.zeros_like(tbool)}[kind]       # blank: objects whose masks are all zero
+        targets.append({"labels": labels, "masks": masks})
     layers = []
     for l in range(L):
         ins = [mc.make_inputs(N, 1, K, T, H, W, 19600 + 100 * seed + 10 * l + b)[:2] for b in range(len(Ms))]
@@ -140,6 +187,19 @@ def nonzero_counts64(layers, targets, pairs, K, masking, share):
             if masking:
                 ce = ce * (~void).double()
             res.append(int((ce != 0).sum()))
+    return res
+
+
+def void_pixels(fx):
+    """per matching j and video b: bool [P], the pixels the restatement calls void (no matched target has weight >= 1 there in sum)"""
+    res = []
+    for j, per_video in enumerate(fx.pairs):
+        out = []
+        for b, (rows, cols) in enumerate(per_video):
+            t = torch.zeros(fx.N, fx.P, dtype=torch.float64)
+            t[rows] = fx.targets[b]["masks"].double().flatten(1)[cols]
+            out.append(t.sum(0) < 1)
+        res.append(out)
     return res
 
 

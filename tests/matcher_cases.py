@@ -32,9 +32,27 @@ U32 = 2.0 ** -24
 # (Q, M, K, T, H, W): the per-element cases.  P = T*H*W is 120, 768, 64, 234, 1024 -- 234 and 120 are no multiple of the 64-pixel tile,
 # M = 33 > Q = 20 is solved on the transpose, M = 1 and M = 33 / 23 / 5 are no multiple of the 32-wide MFMA block, Q = 100 / 20 / 16 neither.
 # The sixth shape has 9 x 2 = 18 output blocks of 32 x 32: more than the 16 one workgroup holds, so the similarity kernel runs it in two
-# block chunks (each chunk repeats the softmax of its pixels).
+# block chunks (each chunk repeats the softmax of its pixels).  Every Q here is a multiple of 4 (wave g holds the queries g, g + 4, ...) and
+# every P at most 4 tiles or an even split over the pixel workgroups: what that leaves out is EDGE_SHAPES below.
 SHAPES = [(16, 5, 7, 2, 6, 10), (128, 23, 124, 2, 16, 24), (100, 1, 40, 1, 8, 8), (20, 33, 10, 2, 9, 13), (128, 64, 124, 4, 16, 16),
           (288, 40, 10, 2, 8, 13)]
+# (Q, M, K, T, H, W) without reference fixtures, checked against `restate` at the format-derived bounds: what the grid of SHAPES leaves out.
+#   (5, 3, P = 300)    Q = 5: wave 0 holds two queries, the others one.  5 tiles: two workgroups of 3 and 2 tiles, the second with a clamped
+#                      range, starting on an odd tile and ending on a 44-pixel one.
+#   (3, 40, P = 63)    Q = 3 < 4: a wave without a query.  One partial tile.  M > Q: solved on the transpose; 63 pixels over 40 objects leave
+#                      some targets empty (similarity exactly 0).
+#   (260, 40, P = 300) 9 x 2 = 18 output blocks, so two block chunks, which here meet two pixel workgroups; 352 LDS rows = 91.5 KB of
+#                      dynamic LDS (above the 48 KB a kernel gets without asking).
+EDGE_SHAPES = [(5, 3, 6, 1, 4, 75), (3, 40, 4, 1, 7, 9), (260, 40, 10, 1, 4, 75)]
+EDGE_SEED = 18500
+
+
+def edge_inputs(s):
+    """(pred, logits, labels, {"bool": , "float": } targets) of an EDGE_SHAPES entry"""
+    pred, logits, labels, tbool, tf = make_inputs(*s, EDGE_SEED + s[0])
+    return pred.float(), logits, labels, {"bool": tbool, "float": tf.float()}
+
+
 # (target kind, masking_void_pixel) combinations stored per shape: all four on the shapes with a small cost matrix, the two diagonal ones
 # on the others (their outputs are what makes a fixture big)
 ALL_COMBOS = [("bool", 1), ("bool", 0), ("float", 1), ("float", 0)]

@@ -118,6 +118,38 @@ def test_similarity_and_cost_per_element_against_float64(s, kind, mv, dtype):
     assert torch.equal(dice[0], ms[ind[0][0], ind[0][1]]) and torch.equal(cls[0], cs[ind[0][0], ind[0][1]])      # device indices index device tensors
 
 
+@pytest.mark.parametrize("s", mc.EDGE_SHAPES, ids=lambda v: "x".join(map(str, v)))
+@pytest.mark.parametrize("kind", ["bool", "float"])
+@pytest.mark.parametrize("mv", [1, 0])
+def test_similarity_at_ragged_query_counts_and_pixel_splits_against_float64(s, kind, mv):
+    """the shapes the fixtures' grid leaves out (matcher_cases.EDGE_SHAPES: Q = 5 and 3, a ragged split of 5 tiles, one partial tile,
+    two block chunks on two pixel workgroups), without reference fixtures: every element against the float64 restatement at the
+    format-derived bounds, fp32_bound_mask + fp32_bound_class for mask similarity and cost, fp32_bound_class for class similarity.
+    A plain fp32 evaluation stays under half of them (tests/test_matcher_cpu.py); they are there to catch a dropped tile, a skipped
+    partial or a wrong chunk (errors of 1 / ntiles or 1 / Q), not to measure rounding.  The assignment is SciPy's on the device's cost."""
+    import axial_vs_amd as ax
+    from axial_vs_amd import _lib
+    Q, M, K, T, H, W = s
+    P = T * H * W
+    pred, logits, labels, targets = mc.edge_inputs(s)
+    ms64, cs64, C64, _, _ = mc.restate(pred, logits, targets[kind], labels, mv)
+    out = {"pred_masks": pred.cuda()[None], "pred_logits": logits.cuda()[None]}
+    tg = [{"labels": labels.cuda(), "masks": targets[kind].cuda()}]
+    if P > 256:           # split over pixel workgroups (a workgroup's partial sums are Q M + Q + M floats); with Q = 260 on two block chunks
+        assert _lib.lib().axvs_video_matcher_workspace_bytes(1, 1, Q, M, P) >= 2 * (Q * M + Q + M) * 4
+    (ms, cs, C), = ax.matcher_costs(out, tg, masking_void_pixel=bool(mv))
+    assert ms.shape == cs.shape == C.shape == (Q, M)
+    bm, bc = mc.fp32_bound_mask(Q, P), mc.fp32_bound_class(K + 1)
+    errs = [mc.rel_err(ms, ms64), mc.rel_err(cs, cs64), mc.rel_err(C, C64)]
+    print(f"[matcher edge] Q{Q} M{M} P{P} {kind} masking={mv}: error / bound  mask_sim {errs[0] / (bm + bc):.4f} class_sim {errs[1] / bc:.4f} "
+          f"cost {errs[2] / (bm + bc):.4f}")
+    assert errs[0] <= bm + bc and errs[2] <= bm + bc and errs[1] <= bc, errs
+    ind, dice, cls = ax.VideoHungarianMatcher(masking_void_pixel=bool(mv))(out, tg)
+    r, k = _scipy_pairs(C.cpu().numpy())
+    assert np.array_equal(ind[0][0].cpu().numpy(), r) and np.array_equal(ind[0][1].cpu().numpy(), k)
+    assert torch.equal(dice[0], ms[ind[0][0], ind[0][1]]) and torch.equal(cls[0], cs[ind[0][0], ind[0][1]])
+
+
 def _e2e_restated(fx):
     """float64 matched values of every (layer, video) with objects, and the reference's own fp32 error on them pooled over the fixture:
     the yardstick of the end-to-end matched values (8x, like the per-element test)"""

@@ -62,6 +62,32 @@ def test_restatement_reproduces_the_end_to_end_fixtures(name):
             assert mc.rel_err(r["cls"], cs[rows, cols]) <= mc.fp32_bound_class(m["K"] + 1)
 
 
+@pytest.mark.parametrize("s", mc.EDGE_SHAPES, ids=lambda v: "x".join(map(str, v)))
+@pytest.mark.parametrize("kind", ["bool", "float"])
+@pytest.mark.parametrize("mv", [1, 0])
+def test_plain_fp32_evaluation_stays_under_half_the_format_bounds(s, kind, mv):
+    """the shapes the GPU test checks without reference fixtures (matcher_cases.EDGE_SHAPES): the restatement's formulas evaluated in
+    fp32 by torch on the CPU are within HALF of fp32_bound_mask + fp32_bound_class (mask similarity, cost) and of fp32_bound_class
+    (class similarity) of float64, so the bounds leave an honest fp32 kernel room and still sit far below an error of 1 / ntiles or 1 / Q"""
+    Q, M, K, T, H, W = s
+    P = T * H * W
+    pred, logits, labels, targets = mc.edge_inputs(s)
+    ms64, cs64, C64, _, _ = mc.restate(pred, logits, targets[kind], labels, mv)
+    p = torch.softmax(pred.flatten(1), 0)
+    t = targets[kind].float().flatten(1)
+    if mv:
+        p = p * (t.sum(0, keepdim=True) > 0).float()
+    ms = (p @ t.T) / ((p.sum(-1)[:, None] + t.sum(-1)[None, :]) / 2.0 + 1e-5)
+    cs = torch.softmax(logits, -1)[:, :-1][:, labels]
+    assert ms.dtype == cs.dtype == torch.float32
+    bm, bc = mc.fp32_bound_mask(Q, P), mc.fp32_bound_class(K + 1)
+    errs = mc.rel_err(ms, ms64), mc.rel_err(cs, cs64), mc.rel_err(-ms * cs, C64)
+    print(f"[matcher cpu] edge {s} {kind} masking={mv}: fp32 / bound  mask_sim {errs[0] / (bm + bc):.3f} class_sim {errs[1] / bc:.3f} cost {errs[2] / (bm + bc):.3f}")
+    assert errs[0] <= 0.5 * (bm + bc) and errs[2] <= 0.5 * (bm + bc) and errs[1] <= 0.5 * bc
+    assert bm + bc < 0.1 / max(Q, (P + 63) // 64)                 # a dropped tile or query changes a value by 1 / ntiles or 1 / Q: over 10 bounds
+    assert float(ms64.max()) > 0.0
+
+
 def _declared_arg_count(name):
     text = open(os.path.join(ROOT, "include", "axvs.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
