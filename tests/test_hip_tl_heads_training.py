@@ -41,7 +41,15 @@ def seeded_case(B, Tc, Q, fpc, h, w, layers, K, Cm, seed):
     return dict(w=wts, cq=cq, mf=mf, layers=layers, K=K, Cm=Cm, seed=seed)
 
 
-SEEDED = dict(B=2, Tc=3, Q=16, fpc=2, h=25, w=43, layers=2, K=12, Cm=256, seed=911)
+SEEDED = {
+    "seeded_B2_Tc3_25x43": dict(B=2, Tc=3, Q=16, fpc=2, h=25, w=43, layers=2, K=12, Cm=256, seed=911),
+    # Tc = 1: the class pooling's softmax over one clip, every ASPP tap on the row itself; Q = 4 the smallest; one pixel per frame
+    "seeded_Tc1_Q4_1x1": dict(B=1, Tc=1, Q=4, fpc=1, h=1, w=1, layers=1, K=3, Cm=128, seed=912),
+    # Tc = 16, the most the tier builds; three layers: with a mask-feature gradient tlt_sum_layers_kernel adds their shares; 15 pixels
+    "seeded_Tc16_Q4_3x5_L3": dict(B=1, Tc=16, Q=4, fpc=1, h=3, w=5, layers=3, K=7, Cm=256, seed=913),
+    # B = 3; Q = 132 = a whole 128-row tile plus 4 rows; 133 pixels per frame (odd, one tile plus 5); two frames per clip
+    "seeded_B3_Q132_7x19_f2": dict(B=3, Tc=2, Q=132, fpc=2, h=7, w=19, layers=2, K=12, Cm=256, seed=914),
+}
 
 
 def make_head(k, p_drop=0.0, seed=None):
@@ -89,19 +97,20 @@ def compare(k, mf_grad=False):
     return e
 
 
-@pytest.mark.parametrize("name", FIXTURES + ["seeded_B2_Tc3_25x43"])
+@pytest.mark.parametrize("name", FIXTURES + list(SEEDED))
 def test_heads_tier_matches_float64_autograd(name):
-    k = fixture_case(name) if name in FIXTURES else seeded_case(**SEEDED)
+    k = fixture_case(name) if name in FIXTURES else seeded_case(**SEEDED[name])
     e = compare(k)
     worst = max(e, key=e.get)
     print(f"{name}: worst {worst} {e[worst]:.2e}; d_clip_query {e['d_clip_query']:.2e}")
     assert max(e.values()) < TOL, {n: f"{v:.2e}" for n, v in e.items() if v >= TOL}
 
 
-@pytest.mark.parametrize("name", ["g6_tl_cc_head_Tc2_Q20_f1_L1", "seeded_B2_Tc3_25x43"])
+@pytest.mark.parametrize("name", ["g6_tl_cc_head_Tc2_Q20_f1_L1", "seeded_B2_Tc3_25x43", "seeded_Tc16_Q4_3x5_L3", "seeded_B3_Q132_7x19_f2"])
 def test_mask_feature_gradient(name):
-    """d_mask_features when the pixel features want a gradient: one layer (written directly) and two layers (shares added in order)."""
-    k = fixture_case(name) if name in FIXTURES else seeded_case(**SEEDED)
+    """d_mask_features when the pixel features want a gradient: one layer (written directly), two and three layers (shares added in
+    order)."""
+    k = fixture_case(name) if name in FIXTURES else seeded_case(**SEEDED[name])
     e = compare(k, mf_grad=True)
     print(f"{name}: d_mask_features {e['d_mask_features']:.2e}")
     assert max(e.values()) < TOL, {n: f"{v:.2e}" for n, v in e.items() if v >= TOL}
