@@ -25,9 +25,10 @@ inline int g_train_exact = 1;
 // axvs_set_option("train_amp", 1 | 2): the GEMMs of the training tier (forward, input gradients, weight gradients) take ONE 16-bit piece per
 // operand (1: bf16, 2: fp16) -- the products torch.autocast gives the reference's nn.Linear layers; 0 (default): split precision
 inline int g_train_amp = 0;
-// axvs_set_option("train_spatial_wgs", n): workgroups the spatial-attention kernels of the training tier are spread over
+// workgroups the spatial-attention kernels of the training tier are spread over (a constant: round 6 dropped the option key
+// "train_spatial_wgs" with the other thresholds)
 inline int g_spatial_wgs = 512;
-// axvs_set_option("train_attn_split", 0): the training tier's attention forward on the fp32 MFMA kernel (any axis length) instead of
+// 0 (a constant as well: no option key sets it): the training tier's attention forward on the fp32 MFMA kernel (any axis length) instead of
 // the split-precision 16-bit MFMA one (three bf16 pieces per operand, a frame's score tiles in registers; axis length <= 128)
 inline int g_train_attn_split = 1;
 

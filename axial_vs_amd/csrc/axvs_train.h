@@ -1,6 +1,7 @@
 // Training tier of the axial-trajectory attention layer: fp32 activations in natural [B,T,H,W] row order, the
 // attention / softmax / dropout / LayerNorm kernels here, the Linear layers' GEMMs (forward, dgrad, wgrad) in axvs_gemm_nt.h /
-// axvs_train_gemm.h (split-precision bf16 MFMA; host side: axvs_train.hip).  Nothing here is on the inference path; that stays on the fused 16-bit MFMA kernels (axvs_fused.h).
+// axvs_train_gemm.h (split-precision bf16 MFMA).  Host side: axvs_train_host.h (shapes, buffers, the tier choice and the launches of a
+// trajectory pass), entry points in axvs_train.hip.  Nothing here is on the inference path; that stays on the fused 16-bit MFMA kernels (axvs_fused.h).
 //
 // Reference semantics (WC/temporal_attention.py): TrajectoryAttention.forward :35-76 (dropout on the spatial attention map :55),
 // TemporalAxialTrajectoryAttentionLayer.forward :187-220 (dropout1 on each pass output :204, :213; dropout2 / dropout3 in the
@@ -20,6 +21,12 @@ __device__ __forceinline__ void load_row(float (&r)[D], const float* p) {
     const float4 v = *reinterpret_cast<const float4*>(p + i);
     r[i] = v.x; r[i + 1] = v.y; r[i + 2] = v.z; r[i + 3] = v.w;
   }
+}
+template <int D>
+__device__ __forceinline__ void load_row(float (&r)[D], const float* p, float scale) {
+  load_row<D>(r, p);
+#pragma unroll
+  for (int i = 0; i < D; ++i) r[i] *= scale;
 }
 template <int D>
 __device__ __forceinline__ void store_row(float* p, const float (&r)[D]) {
@@ -45,6 +52,18 @@ __device__ __forceinline__ void axpy_lds(float (&acc)[D], float a, const float* 
   }
 }
 
+// The two layouts every spatial kernel shares (the backward rebuilds P and the dropout masks from exactly these):
+// statistics (max, 1 / sum, D) of (sequence s, head h, query qn, frame f): stats is [(s heads + h), N, T, 3]
+template <class F>
+__device__ __forceinline__ F* stat_ptr(F* stats, int s, int h, int qn, int f, int heads, int N, int T) {
+  return stats + ((((size_t)s * heads + h) * N + qn) * T + f) * 3;
+}
+// dropout element index of P[(s h), qn, f, n = 0]: its offset in the reference's tensor; key n of the frame is + n
+// (qn is 64-bit so that a caller's sum of chunk, tile and lane offsets joins the 64-bit sum term by term)
+__device__ __forceinline__ unsigned long long drop_base(int s, int h, unsigned long long qn, int f, int heads, int N, int T, int L) {
+  return ((((unsigned long long)s * heads + h) * N + qn) * T + f) * L;
+}
+
 // the rows of frame f of sequence s, head h: global [.., C] -> LDS [L][D]
 template <int D>
 __device__ __forceinline__ void stage_frame(float* dst, const float* src, const RowMap& rm, int s, int f, int h, int C, int tid) {
@@ -58,7 +77,7 @@ __device__ __forceinline__ void stage_frame(float* dst, const float* src, const 
 
 // ---- spatial half, forward (WC/temporal_attention.py:47-58): x[q, f, :] = sum_n drop(softmax_n(scale q.k_{f,n})) v_{f,n}
 //      one workgroup per (sequence, head), one thread per query, K_f / V_f of the frame in LDS.  x: [M, T, C] by natural row.
-//      dropout index of P[(s h), q, f, n] is its offset in the reference's tensor: (((s heads + h) N + q) T + f) L + n.
+//      dropout index of P[(s h), q, f, n]: drop_base(..) + n.
 template <int D>
 __global__ __launch_bounds__(256) void tr_spatial_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                               const float* __restrict__ v, float* __restrict__ x, RowMap rm, int T, int C,
@@ -86,7 +105,7 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_kernel(const float* __rest
       float sum = 0.f, acc[D];
 #pragma unroll
       for (int i = 0; i < D; ++i) acc[i] = 0.f;
-      const unsigned long long base = ((((unsigned long long)s * heads + h) * N + qn) * T + f) * L;
+      const unsigned long long base = drop_base(s, h, qn, f, heads, N, T, L);
       for (int n = 0; n < L; ++n) {
         const float p = __expf(dot_lds<D>(qr, ks + n * D) - mx);
         sum += p;
@@ -118,14 +137,72 @@ __device__ __forceinline__ float xor_sum16_32(float v) {
   return v + __shfl_xor(v, 32, 64);
 }
 
-// rows of frame f of (sequence s, head h) -> LDS [ceil16(L)][kTrLd], rows past L zero
-__device__ __forceinline__ void stage_frame36(float* dst, const float* src, const RowMap& rm, int s, int f, int h, int C, int tid) {
-  const int Lp = (rm.L + 15) & ~15;
-  for (int i = tid; i < Lp * 8; i += 256) {
+__host__ __device__ inline int ceil16(int n) { return (n + 15) & ~15; }
+
+// `count` rows of (sequence s, head h) from sequence row `first` on -> LDS [ceil16(count)][kTrLd], rows past `count` zero.
+// A frame's keys: first = f L, count = L; a chunk of them: first = f L + c0.
+__device__ __forceinline__ void stage_rows36(float* dst, const float* src, const RowMap& rm, int s, int first, int count, int h, int C, int tid) {
+  const int np = ceil16(count);
+  for (int i = tid; i < np * 8; i += 256) {
     const int n = i >> 3, c4 = i & 7;
     float4 v = {0.f, 0.f, 0.f, 0.f};
-    if (n < rm.L) v = *reinterpret_cast<const float4*>(src + nat_row(rm, s * rm.N + f * rm.L + n) * C + h * 32 + c4 * 4);
+    if (n < count) v = *reinterpret_cast<const float4*>(src + nat_row(rm, s * rm.N + first + n) * C + h * 32 + c4 * 4);
     *reinterpret_cast<float4*>(dst + n * kTrLd + c4 * 4) = v;
+  }
+}
+// A operands of the 4 x 2 MFMAs that contract keys nl .. nl + 3: channels j and 16 + j of those rows of a staged tile
+__device__ __forceinline__ void load_cols(float (&a)[4][2], const float* tile, int nl, int j) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    a[r][0] = tile[(nl + r) * kTrLd + j];
+    a[r][1] = tile[(nl + r) * kTrLd + j + 16];
+  }
+}
+
+// dynamic LDS of the LDS-resident query-side kernels: K | V of a frame, [ceil16(L)][kTrLd] each (two equal halves)
+__host__ __device__ inline size_t spatial_frame_lds(int L) { return (size_t)2 * ceil16(L) * kTrLd * sizeof(float); }
+
+// One (16-query, 16-key) tile of the forward: kr / qr are this lane's 8 channels of key / scaled query j, va the V^T operands of
+// keys n0 .. n0 + 3 (this lane's 4 keys of the frame), base the query's dropout base; m / sum / acc are the query's running state.
+__device__ __forceinline__ void fwd_tile(const float (&kr)[8], const float (&qr)[8], const float (&va)[4][2], int n0, int L, const Drop& dr,
+                                         unsigned long long base, float& m, float& sum, f32x4 (&acc)[2]) {
+  f32x4 sc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 8; ++t) sc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[t], qr[t], sc, 0, 0, 0);
+  float tmax = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (n0 + r >= L) sc[r] = -INFINITY;
+    tmax = fmaxf(tmax, sc[r]);
+  }
+  const float mn = fmaxf(m, xor_max16_32(tmax));
+  const float alpha = __expf(m - mn);
+  float p[4], ps = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    p[r] = __expf(sc[r] - mn);
+    ps += p[r];
+    if (n0 + r < L) p[r] *= drop_keep(dr, base + n0 + r);
+  }
+  sum = sum * alpha + xor_sum16_32(ps);
+  m = mn;
+  acc[0] *= alpha;
+  acc[1] *= alpha;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[r][0], p[r], acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[r][1], p[r], acc[1], 0, 0, 0);
+  }
+}
+// x of (query, frame) = acc / sum and the softmax statistics the backward kernels rebuild P from.  xo: the lane's channels 4 g .. of
+// the x row (lane (query j, group g) holds channels dt * 16 + 4 g + r); st: the statistics triple, written by group 0.
+__device__ __forceinline__ void fwd_store(float* xo, float* st, const f32x4 (&acc)[2], float m, float sum, int g) {
+  const float inv = 1.f / sum;
+  *reinterpret_cast<float4*>(xo) = float4{acc[0][0] * inv, acc[0][1] * inv, acc[0][2] * inv, acc[0][3] * inv};
+  *reinterpret_cast<float4*>(xo + 16) = float4{acc[1][0] * inv, acc[1][1] * inv, acc[1][2] * inv, acc[1][3] * inv};
+  if (g == 0) {
+    st[0] = m;
+    st[1] = inv;
   }
 }
 
@@ -136,74 +213,33 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_mfma_kernel(const float* _
   extern __shared__ float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
   const int s = blockIdx.x / heads, h = blockIdx.x - s * heads, N = rm.N, L = rm.L;
-  const int Lp = (L + 15) & ~15, nkt = Lp >> 4, nqt = (N + 15) >> 4;
+  const int nkt = ceil16(L) >> 4, nqt = (N + 15) >> 4;
   float* ks = smem;
-  float* vs = smem + Lp * kTrLd;
+  float* vs = smem + spatial_frame_lds(L) / sizeof(float) / 2;
   // few sequences (the cross-clip module: B x heads workgroups): gridDim.y splits the query tiles, gridDim.z the frames -- every
   // (query tile, frame) is computed by exactly one wave whatever the split, with the same instructions
   const int fper = (T + (int)gridDim.z - 1) / (int)gridDim.z, f0 = (int)blockIdx.z * fper, f1 = min(T, f0 + fper);
   for (int f = f0; f < f1; ++f) {
     __syncthreads();
-    stage_frame36(ks, k, rm, s, f, h, C, tid);
-    stage_frame36(vs, v, rm, s, f, h, C, tid);
+    stage_rows36(ks, k, rm, s, f * L, L, h, C, tid);
+    stage_rows36(vs, v, rm, s, f * L, L, h, C, tid);
     __syncthreads();
     for (int qt = (int)blockIdx.y * 4 + wave; qt < nqt; qt += 4 * (int)gridDim.y) {
-      const int qn = qt * 16 + j;
-      const long long mq = nat_row(rm, s * N + min(qn, N - 1));
+      const int qn = qt * 16 + j, qc = min(qn, N - 1);
+      const long long mq = nat_row(rm, s * N + qc);
       float qr[8];
-      {
-        const float4 a = *reinterpret_cast<const float4*>(q + mq * C + h * 32 + 8 * g), b = *reinterpret_cast<const float4*>(q + mq * C + h * 32 + 8 * g + 4);
-        qr[0] = a.x * scale; qr[1] = a.y * scale; qr[2] = a.z * scale; qr[3] = a.w * scale;
-        qr[4] = b.x * scale; qr[5] = b.y * scale; qr[6] = b.z * scale; qr[7] = b.w * scale;
-      }
+      load_row(qr, q + mq * C + h * 32 + 8 * g, scale);
       float m = -INFINITY, sum = 0.f;
       f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      const unsigned long long base = ((((unsigned long long)s * heads + h) * N + min(qn, N - 1)) * T + f) * L;
+      const unsigned long long base = drop_base(s, h, qc, f, heads, N, T, L);
       for (int kt = 0; kt < nkt; ++kt) {
-        const float* kp = ks + (kt * 16 + j) * kTrLd + 8 * g;
-        const float4 ka = *reinterpret_cast<const float4*>(kp), kb = *reinterpret_cast<const float4*>(kp + 4);
-        const float kr[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
-        f32x4 sc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 8; ++t) sc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[t], qr[t], sc, 0, 0, 0);
+        float kr[8], va[4][2];
+        load_row(kr, ks + (kt * 16 + j) * kTrLd + 8 * g);
         const int n0 = kt * 16 + 4 * g;             // my 4 keys: n0 .. n0 + 3
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (n0 + r >= L) sc[r] = -INFINITY;
-          tmax = fmaxf(tmax, sc[r]);
-        }
-        const float mn = fmaxf(m, xor_max16_32(tmax));
-        const float alpha = __expf(m - mn);
-        float p[4], ps = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          p[r] = __expf(sc[r] - mn);
-          ps += p[r];
-          if (n0 + r < L) p[r] *= drop_keep(dr, base + n0 + r);
-        }
-        sum = sum * alpha + xor_sum16_32(ps);
-        m = mn;
-        acc[0] *= alpha;
-        acc[1] *= alpha;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float* vp = vs + (n0 + r) * kTrLd + j;
-          acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[0], p[r], acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[16], p[r], acc[1], 0, 0, 0);
-        }
+        load_cols(va, vs, n0, j);
+        fwd_tile(kr, qr, va, n0, L, dr, base, m, sum, acc);
       }
-      if (qn < N) {
-        const float inv = 1.f / sum;
-        float* xo = x + (mq * T + f) * C + h * 32 + 4 * g;        // lane (query j, group g): channels dt * 16 + 4 g + r
-        *reinterpret_cast<float4*>(xo) = float4{acc[0][0] * inv, acc[0][1] * inv, acc[0][2] * inv, acc[0][3] * inv};
-        *reinterpret_cast<float4*>(xo + 16) = float4{acc[1][0] * inv, acc[1][1] * inv, acc[1][2] * inv, acc[1][3] * inv};
-        if (g == 0) {                                 // softmax statistics of (query, frame): the backward kernels rebuild P from them
-          float* st = stats + ((((size_t)s * heads + h) * N + qn) * T + f) * 3;
-          st[0] = m;
-          st[1] = inv;
-        }
-      }
+      if (qn < N) fwd_store(x + (mq * T + f) * C + h * 32 + 4 * g, stat_ptr(stats, s, h, qn, f, heads, N, T), acc, m, sum, g);
     }
   }
 }
@@ -219,7 +255,7 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_mfma_kernel(const float* _
 //      accumulators, no running statistics.  Operand layouts: S^T = K Q^T is a 16x16x32 product (lane (j, g) holds channels
 //      8 g .. 8 g + 7 of key / query j, as in the fp32 kernel), X^T += V^T P^T a 16x16x16 one (lane (j, g) holds keys 4 g .. 4 g + 3:
 //      the probabilities stay where the score tile left them).  Statistics (max, 1 / sum), dropout indices and the output layout
-//      are those of tr_spatial_fwd_mfma_kernel, so the backward kernels do not care which one ran (saved activations of the two
+//      are those of tr_spatial_fwd_mfma_kernel (stat_ptr, drop_base, fwd_store), so the backward kernels do not care which one ran (saved activations of the two
 //      agree to 1e-6).  Measured at [1,4,256,64,64]: 107 -> 97 us per launch -- and the counters say why not more
 //      (profiles/r3_train_attention_pmc.json): the kernel is bound by VALU issue, 290 VALU instructions per 16-key tile and wave
 //      (dropout hash of four scores ~100, the three-piece split of four probabilities ~50, mask / max / exp / sum ~30, 64-bit
@@ -254,7 +290,7 @@ __device__ __forceinline__ f32x4 mfma6_16(const s16x4 (&a)[3], const s16x4 (&b)[
 }
 // LDS bytes: K pieces [3][Lp][32] + V^T pieces [3][32][Lp + 4] (16-bit)
 __host__ __device__ inline size_t spatial_split_lds(int L) {
-  const int Lp = (L + 15) & ~15;
+  const int Lp = ceil16(L);
   return (size_t)3 * ((size_t)Lp * 32 + (size_t)32 * (Lp + 4)) * sizeof(u16);
 }
 
@@ -266,7 +302,7 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_split_kernel(const float* 
   u16* const kp = reinterpret_cast<u16*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
   const int s = blockIdx.x / heads, h = blockIdx.x - s * heads, N = rm.N, L = rm.L;
-  const int Lp = (L + 15) & ~15, nkt = Lp >> 4, nqt = (N + 15) >> 4, LV = Lp + 4;
+  const int Lp = ceil16(L), nkt = Lp >> 4, nqt = (N + 15) >> 4, LV = Lp + 4;
   u16* const vt = kp + 3 * Lp * 32;
   const int fper = (T + (int)gridDim.z - 1) / (int)gridDim.z, f0 = (int)blockIdx.z * fper, f1 = min(T, f0 + fper);
   const int qstep = 4 * (int)gridDim.y;
@@ -277,10 +313,8 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_split_kernel(const float* 
       float kv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, vv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       if (n < L) {
         const long long row = nat_row(rm, s * N + f * L + n) * C + h * 32 + c8 * 8;
-        const float4 a = *reinterpret_cast<const float4*>(k + row), b = *reinterpret_cast<const float4*>(k + row + 4);
-        const float4 c = *reinterpret_cast<const float4*>(v + row), d = *reinterpret_cast<const float4*>(v + row + 4);
-        kv[0] = a.x; kv[1] = a.y; kv[2] = a.z; kv[3] = a.w; kv[4] = b.x; kv[5] = b.y; kv[6] = b.z; kv[7] = b.w;
-        vv[0] = c.x; vv[1] = c.y; vv[2] = c.z; vv[3] = c.w; vv[4] = d.x; vv[5] = d.y; vv[6] = d.z; vv[7] = d.w;
+        load_row(kv, k + row);
+        load_row(vv, v + row);
       }
       u16x8 ph, pm, pl;
 #pragma unroll
@@ -341,7 +375,7 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_split_kernel(const float* 
         }
       }
       m = xor_max16_32(m);
-      const unsigned long long base = ((((unsigned long long)s * heads + h) * N + min(qn, N - 1)) * T + f) * L;
+      const unsigned long long base = drop_base(s, h, min(qn, N - 1), f, heads, N, T, L);
       float sum = 0.f;
       f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
@@ -368,17 +402,7 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_split_kernel(const float* 
         }
       }
       sum = xor_sum16_32(sum);
-      if (qn < N) {
-        const float inv = 1.f / sum;
-        float* xo = x + (mq * T + f) * C + h * 32 + 4 * g;
-        *reinterpret_cast<float4*>(xo) = float4{acc[0][0] * inv, acc[0][1] * inv, acc[0][2] * inv, acc[0][3] * inv};
-        *reinterpret_cast<float4*>(xo + 16) = float4{acc[1][0] * inv, acc[1][1] * inv, acc[1][2] * inv, acc[1][3] * inv};
-        if (g == 0) {
-          float* st = stats + ((((size_t)s * heads + h) * N + qn) * T + f) * 3;
-          st[0] = m;
-          st[1] = inv;
-        }
-      }
+      if (qn < N) fwd_store(x + (mq * T + f) * C + h * 32 + 4 * g, stat_ptr(stats, s, h, qn, f, heads, N, T), acc, m, sum, g);
     }
   }
 }
@@ -387,6 +411,40 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_split_kernel(const float* 
 //      16-key tile  S^T = K Q^T,  dP^T = V dX^T  (8 + 8 MFMAs),  dS = P (keep dP - D) with P rebuilt from the forward's (max, 1/sum),
 //      dq^T += K^T dS^T (4 x 2 MFMAs, keys {4 g + r} per step as in the forward).  dq accumulates over the frames in global memory
 //      (first frame writes).  Writes D into stats[.., 2] for part 2.
+// dx of (query, frame) for the lane's 8 channels and D = dx . x summed over the query's 4 lane groups
+__device__ __forceinline__ float load_dx_D(float (&dxr)[8], const float* dxp, const float* xp) {
+  float xr[8];
+  load_row(dxr, dxp);
+  load_row(xr, xp);
+  return xor_sum16_32(dxr[0] * xr[0] + dxr[1] * xr[1] + dxr[2] * xr[2] + dxr[3] * xr[3] + dxr[4] * xr[4] + dxr[5] * xr[5] + dxr[6] * xr[6] +
+                      dxr[7] * xr[7]);
+}
+// One (16-query, 16-key) tile of the query-side backward: kr / vr are this lane's 8 channels of key j, qr / dxr those of query j,
+// ka the K^T operands of keys n0 .. n0 + 3; (m, inv) the forward's statistics, D = dx . x; acc is dq^T before the scale.
+__device__ __forceinline__ void bwd_q_tile(const float (&kr)[8], const float (&vr)[8], const float (&qr)[8], const float (&dxr)[8],
+                                           const float (&ka)[4][2], float m, float inv, float D, int n0, int L, const Drop& dr,
+                                           unsigned long long base, f32x4 (&acc)[2]) {
+  f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    sc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[t], qr[t], sc, 0, 0, 0);
+    dp = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[t], dxr[t], dp, 0, 0, 0);
+  }
+  float ds[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const bool valid = n0 + r < L;
+    const float P = valid ? __expf(sc[r] - m) * inv : 0.f;
+    const float keep = drop_keep(dr, base + n0 + r);      // (hashed for padding keys too: no branch; P = 0 there)
+    ds[r] = P * ((valid ? keep : 0.f) * dp[r] - D);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[r][0], ds[r], acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[r][1], ds[r], acc[1], 0, 0, 0);
+  }
+}
+
 __global__ __launch_bounds__(256) void tr_spatial_bwd_q_mfma_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                      const float* __restrict__ v, const float* __restrict__ x,
                                                                      const float* __restrict__ dx, float* __restrict__ dq,
@@ -395,63 +453,31 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_mfma_kernel(const float*
   extern __shared__ float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
   const int s = blockIdx.x / heads, h = blockIdx.x - s * heads, N = rm.N, L = rm.L;
-  const int Lp = (L + 15) & ~15, nkt = Lp >> 4, nqt = (N + 15) >> 4;
+  const int nkt = ceil16(L) >> 4, nqt = (N + 15) >> 4;
   float* ks = smem;
-  float* vs = smem + Lp * kTrLd;
+  float* vs = smem + spatial_frame_lds(L) / sizeof(float) / 2;
   for (int f = 0; f < T; ++f) {            // (dq accumulates over the frames: they stay in one workgroup; gridDim.y splits the query tiles)
     __syncthreads();
-    stage_frame36(ks, k, rm, s, f, h, C, tid);
-    stage_frame36(vs, v, rm, s, f, h, C, tid);
+    stage_rows36(ks, k, rm, s, f * L, L, h, C, tid);
+    stage_rows36(vs, v, rm, s, f * L, L, h, C, tid);
     __syncthreads();
     for (int qt = (int)blockIdx.y * 4 + wave; qt < nqt; qt += 4 * (int)gridDim.y) {
       const int qn = qt * 16 + j, qc = min(qn, N - 1);
       const long long mq = nat_row(rm, s * N + qc);
       float qr[8], dxr[8];
-      float dsum;
-      {
-        const float* qp = q + mq * C + h * 32 + 8 * g;
-        const float* gp = dx + (mq * T + f) * C + h * 32 + 8 * g;
-        const float* xp = x + (mq * T + f) * C + h * 32 + 8 * g;
-        const float4 a = *reinterpret_cast<const float4*>(qp), b = *reinterpret_cast<const float4*>(qp + 4);
-        const float4 c = *reinterpret_cast<const float4*>(gp), d = *reinterpret_cast<const float4*>(gp + 4);
-        const float4 e = *reinterpret_cast<const float4*>(xp), e2 = *reinterpret_cast<const float4*>(xp + 4);
-        qr[0] = a.x * scale; qr[1] = a.y * scale; qr[2] = a.z * scale; qr[3] = a.w * scale;
-        qr[4] = b.x * scale; qr[5] = b.y * scale; qr[6] = b.z * scale; qr[7] = b.w * scale;
-        dxr[0] = c.x; dxr[1] = c.y; dxr[2] = c.z; dxr[3] = c.w; dxr[4] = d.x; dxr[5] = d.y; dxr[6] = d.z; dxr[7] = d.w;
-        dsum = xor_sum16_32(c.x * e.x + c.y * e.y + c.z * e.z + c.w * e.w + d.x * e2.x + d.y * e2.y + d.z * e2.z + d.w * e2.w);
-      }
-      float* st = stats + ((((size_t)s * heads + h) * N + qc) * T + f) * 3;
+      load_row(qr, q + mq * C + h * 32 + 8 * g, scale);
+      const float dsum = load_dx_D(dxr, dx + (mq * T + f) * C + h * 32 + 8 * g, x + (mq * T + f) * C + h * 32 + 8 * g);
+      float* st = stat_ptr(stats, s, h, qc, f, heads, N, T);
       const float m = st[0], inv = st[1];
       f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      const unsigned long long base = ((((unsigned long long)s * heads + h) * N + qc) * T + f) * L;
+      const unsigned long long base = drop_base(s, h, qc, f, heads, N, T, L);
       for (int kt = 0; kt < nkt; ++kt) {
-        const float* kp = ks + (kt * 16 + j) * kTrLd + 8 * g;
-        const float* vp = vs + (kt * 16 + j) * kTrLd + 8 * g;
-        const float4 ka = *reinterpret_cast<const float4*>(kp), kb = *reinterpret_cast<const float4*>(kp + 4);
-        const float4 va = *reinterpret_cast<const float4*>(vp), vb = *reinterpret_cast<const float4*>(vp + 4);
-        const float kr[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
-        const float vr[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
-        f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          sc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[t], qr[t], sc, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[t], dxr[t], dp, 0, 0, 0);
-        }
+        float kr[8], vr[8], ka[4][2];
+        load_row(kr, ks + (kt * 16 + j) * kTrLd + 8 * g);
+        load_row(vr, vs + (kt * 16 + j) * kTrLd + 8 * g);
         const int n0 = kt * 16 + 4 * g;
-        float ds[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool valid = n0 + r < L;
-          const float P = valid ? __expf(sc[r] - m) * inv : 0.f;
-          const float kp_ = valid ? drop_keep(dr, base + n0 + r) : 0.f;
-          ds[r] = P * (kp_ * dp[r] - dsum);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float* kt_ = ks + (n0 + r) * kTrLd + j;
-          acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(kt_[0], ds[r], acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(kt_[16], ds[r], acc[1], 0, 0, 0);
-        }
+        load_cols(ka, ks, n0, j);
+        bwd_q_tile(kr, vr, qr, dxr, ka, m, inv, dsum, n0, L, dr, base, acc);
       }
       if (qn < N) {
         float* o = dq + mq * C + h * 32 + 4 * g;
@@ -473,6 +499,9 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_mfma_kernel(const float*
 // ---- backward on the matrix cores, part 2 (keys): per frame the queries' scaled q, dx and statistics sit in LDS; a wave owns a
 //      16-key tile and walks all query tiles:  S = Q K^T, dP = dX V^T (queries on the D rows: lane (key j, group g) holds queries
 //      4 g + r),  dv^T += dX^T (P keep),  dk^T += (scale Q)^T dS  (4 x 2 MFMAs each, queries {4 g + r} per step).
+// dynamic LDS for Nc staged queries: scale * q [Nc][kTrLd] | dx of the frame [Nc][kTrLd] | (max, 1 / sum, D, -) [Nc][4]
+__host__ __device__ inline size_t spatial_kv_lds(int Nc) { return (size_t)Nc * (2 * kTrLd + 4) * sizeof(float); }
+
 __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                       const float* __restrict__ v, const float* __restrict__ dx,
                                                                       const float* __restrict__ stats, float* __restrict__ dk,
@@ -481,11 +510,15 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float
   extern __shared__ float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
   const int s = blockIdx.x / heads, h = blockIdx.x - s * heads, N = rm.N, L = rm.L;
-  const int Np = (N + 15) & ~15, nkt = (L + 15) >> 4;
+  const int Np = ceil16(N), nkt = (L + 15) >> 4;
   const int nchunks = (Np + Nc - 1) / Nc;          // 1: the whole sequence's queries fit (the within-clip layer); more: 12+ clips of 128 queries
-  float* qs = smem;                      // [Nc][kTrLd] scale * q
-  float* gs = qs + Nc * kTrLd;           // [Nc][kTrLd] dx of the frame
-  float* ss = gs + Nc * kTrLd;           // [Nc][4]     max, 1/sum, D of (query, frame)
+  float* qs = smem;                      // the three parts of spatial_kv_lds(Nc)
+  float* gs = qs + Nc * kTrLd;
+  float* ss = gs + Nc * kTrLd;
+  // (the two staging loops are stage_rows36 with a scale, a T-strided source and all Nc rows filled.  They stay written out, and the
+  //  dropout index below sums its query offsets in 64 bits: with stage_rows36 here and an int query index the kernel's code changed
+  //  throughout and measured 4 - 6 % slower; as written its assembly is the parent's but for the order of two loads --
+  //  profiles/train_attn_refactor.md)
   auto stage_q = [&](int c0) {           // scaled q rows c0 .. c0 + Nc
     for (int i = tid; i < Nc * 8; i += 256) {
       const int n = i >> 3, c4 = i & 7;
@@ -505,7 +538,7 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float
       *reinterpret_cast<float4*>(gs + n * kTrLd + c4 * 4) = t;
     }
     for (int n = tid; n < Nc; n += 256) {
-      const float* st = stats + ((((size_t)s * heads + h) * N + min(c0 + n, N - 1)) * T + f) * 3;
+      const float* st = stat_ptr(stats, s, h, min(c0 + n, N - 1), f, heads, N, T);
       // padding queries: 1/sum = 0 makes their probabilities vanish
       *reinterpret_cast<float4*>(ss + n * 4) = float4{st[0], c0 + n < N ? st[1] : 0.f, st[2], 0.f};
     }
@@ -525,14 +558,8 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float
       const int kn = kt * 16 + j, kc = min(kn, L - 1);                  // key index within the frame
       const long long mk = nat_row(rm, s * N + f * L + (have ? kc : 0));
       float kr[8], vr[8];
-      {
-        const float* kp = k + mk * C + h * 32 + 8 * g;
-        const float* vp = v + mk * C + h * 32 + 8 * g;
-        const float4 a = *reinterpret_cast<const float4*>(kp), b = *reinterpret_cast<const float4*>(kp + 4);
-        const float4 c = *reinterpret_cast<const float4*>(vp), d = *reinterpret_cast<const float4*>(vp + 4);
-        kr[0] = a.x; kr[1] = a.y; kr[2] = a.z; kr[3] = a.w; kr[4] = b.x; kr[5] = b.y; kr[6] = b.z; kr[7] = b.w;
-        vr[0] = c.x; vr[1] = c.y; vr[2] = c.z; vr[3] = c.w; vr[4] = d.x; vr[5] = d.y; vr[6] = d.z; vr[7] = d.w;
-      }
+      load_row(kr, k + mk * C + h * 32 + 8 * g);
+      load_row(vr, v + mk * C + h * 32 + 8 * g);
       f32x4 dka[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, dva[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
       for (int ch = 0; ch < nchunks; ++ch) {
         const int c0 = ch * Nc;
@@ -545,12 +572,9 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float
         const int nq_here = min(Nc, Np - c0) >> 4;
         if (have)
           for (int qt = 0; qt < nq_here; ++qt) {
-            const float* qp = qs + (qt * 16 + j) * kTrLd + 8 * g;
-            const float* gp = gs + (qt * 16 + j) * kTrLd + 8 * g;
-            const float4 qa = *reinterpret_cast<const float4*>(qp), qb = *reinterpret_cast<const float4*>(qp + 4);
-            const float4 ga = *reinterpret_cast<const float4*>(gp), gb = *reinterpret_cast<const float4*>(gp + 4);
-            const float qr[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-            const float gr[8] = {ga.x, ga.y, ga.z, ga.w, gb.x, gb.y, gb.z, gb.w};
+            float qr[8], gr[8];
+            load_row(qr, qs + (qt * 16 + j) * kTrLd + 8 * g);
+            load_row(gr, gs + (qt * 16 + j) * kTrLd + 8 * g);
             f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < 8; ++t) {                 // D[i = query 4 g' + r][j = key]: A = query rows, B = key rows
@@ -563,8 +587,7 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float
             for (int r = 0; r < 4; ++r) {
               const float4 st = *reinterpret_cast<const float4*>(ss + (ql + r) * 4);
               const float P = __expf(sc[r] - st.x) * st.y;
-              const float kp_ = (c0 + ql + r < N && kn < L)
-                                    ? drop_keep(dr, ((((unsigned long long)s * heads + h) * N + c0 + ql + r) * T + f) * L + kn) : 0.f;
+              const float kp_ = (c0 + ql + r < N && kn < L) ? drop_keep(dr, drop_base(s, h, (unsigned long long)c0 + ql + r, f, heads, N, T, L) + kn) : 0.f;
               pk[r] = P * kp_;
               ds[r] = P * (kp_ * dp[r] - st.z);
             }
@@ -592,25 +615,14 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float
 }
 
 // ---- long frames (the full T*H*W layer: a frame is all H*W keys -- 4096 at 64 x 64): the same two query-side kernels with a
-//      frame's keys staged kSpChunk at a time.  The forward's running max / sum per 16-key tile is the one of
-//      tr_spatial_fwd_mfma_kernel (same tile order: the same statistics (max, 1 / sum) into `stats`, the same x layout), so the
+//      frame's keys staged kSpChunk at a time.  The forward's running max / sum per 16-key tile is fwd_tile, the step
+//      tr_spatial_fwd_mfma_kernel takes (same tile order: the same statistics (max, 1 / sum) into `stats`, the same x layout), so the
 //      key-side backward (tr_spatial_bwd_kv_mfma_kernel, which stages QUERIES in chunks and never holds a whole frame) serves
 //      both.  A wave owns kSpQT query tiles at a time, so each K / V fragment read from LDS feeds kSpQT tiles.  LDS: K and V
 //      chunks [kSpChunk][kTrLd] = 72 KiB (two workgroups per CU).  Dropout element indices are 64-bit (2.1e9 at 64 x 64 x 4).
 constexpr int kSpChunk = 256;   // keys of a frame per LDS stage (a multiple of 16)
 constexpr int kSpQT = 2;        // 16-query tiles per wave
-__host__ __device__ inline size_t spatial_chunk_lds() { return (size_t)2 * kSpChunk * kTrLd * sizeof(float); }
-
-// keys c0 .. c0 + ceil16(Lc) of frame f of (sequence s, head h) -> LDS [.][kTrLd], rows past the frame zero
-__device__ __forceinline__ void stage_chunk36(float* dst, const float* src, const RowMap& rm, int s, int f, int c0, int h, int C, int tid) {
-  const int Lc = min(kSpChunk, rm.L - c0), Lp = (Lc + 15) & ~15;
-  for (int i = tid; i < Lp * 8; i += 256) {
-    const int n = i >> 3, c4 = i & 7;
-    float4 v = {0.f, 0.f, 0.f, 0.f};
-    if (n < Lc) v = *reinterpret_cast<const float4*>(src + nat_row(rm, s * rm.N + f * rm.L + c0 + n) * C + h * 32 + c4 * 4);
-    *reinterpret_cast<float4*>(dst + n * kTrLd + c4 * 4) = v;
-  }
-}
+__host__ __device__ inline size_t spatial_chunk_lds() { return (size_t)2 * kSpChunk * kTrLd * sizeof(float); }   // K | V chunk, equal halves
 
 // grid: x = (sequence, head), y = blocks of 4 * kSpQT query tiles, z = frames (as tr_spatial_fwd_mfma_kernel)
 __global__ __launch_bounds__(256) void tr_spatial_fwd_chunk_kernel(const float* __restrict__ q, const float* __restrict__ k,
@@ -622,7 +634,7 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_chunk_kernel(const float* 
   const int s = blockIdx.x / heads, h = blockIdx.x - s * heads, N = rm.N, L = rm.L;
   const int nqt = (N + 15) >> 4, nqb = (nqt + 4 * kSpQT - 1) / (4 * kSpQT);
   float* ks = smem;
-  float* vs = smem + kSpChunk * kTrLd;
+  float* vs = smem + spatial_chunk_lds() / sizeof(float) / 2;
   const int fper = (T + (int)gridDim.z - 1) / (int)gridDim.z, f0 = (int)blockIdx.z * fper, f1 = min(T, f0 + fper);
   for (int f = f0; f < f1; ++f)
     for (int qb = (int)blockIdx.y; qb < nqb; qb += (int)gridDim.y) {
@@ -632,81 +644,37 @@ __global__ __launch_bounds__(256) void tr_spatial_fwd_chunk_kernel(const float* 
 #pragma unroll
       for (int u = 0; u < kSpQT; ++u) {
         const int qc = min((qb * 4 * kSpQT + u * 4 + wave) * 16 + j, N - 1);
-        const float* qp = q + nat_row(rm, s * N + qc) * C + h * 32 + 8 * g;
-        const float4 a = *reinterpret_cast<const float4*>(qp), b = *reinterpret_cast<const float4*>(qp + 4);
-        qr[u][0] = a.x * scale; qr[u][1] = a.y * scale; qr[u][2] = a.z * scale; qr[u][3] = a.w * scale;
-        qr[u][4] = b.x * scale; qr[u][5] = b.y * scale; qr[u][6] = b.z * scale; qr[u][7] = b.w * scale;
+        load_row(qr[u], q + nat_row(rm, s * N + qc) * C + h * 32 + 8 * g, scale);
         m[u] = -INFINITY;
         sum[u] = 0.f;
         acc[u][0] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc[u][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        base[u] = ((((unsigned long long)s * heads + h) * N + qc) * T + f) * L;
+        base[u] = drop_base(s, h, qc, f, heads, N, T, L);
       }
       for (int c0 = 0; c0 < L; c0 += kSpChunk) {
+        const int Lc = min(kSpChunk, L - c0);            // keys of this chunk
         __syncthreads();
-        stage_chunk36(ks, k, rm, s, f, c0, h, C, tid);
-        stage_chunk36(vs, v, rm, s, f, c0, h, C, tid);
+        stage_rows36(ks, k, rm, s, f * L + c0, Lc, h, C, tid);
+        stage_rows36(vs, v, rm, s, f * L + c0, Lc, h, C, tid);
         __syncthreads();
-        const int nkt = (min(kSpChunk, L - c0) + 15) >> 4;
+        const int nkt = (Lc + 15) >> 4;
         for (int kt = 0; kt < nkt; ++kt) {
-          const float* kp = ks + (kt * 16 + j) * kTrLd + 8 * g;
-          const float4 ka = *reinterpret_cast<const float4*>(kp), kb = *reinterpret_cast<const float4*>(kp + 4);
-          const float kr[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+          float kr[8], va[4][2];
+          load_row(kr, ks + (kt * 16 + j) * kTrLd + 8 * g);
           const int nl = kt * 16 + 4 * g, n0 = c0 + nl;          // my 4 keys: n0 .. n0 + 3 of the frame (nl .. within the chunk)
-          float vr[4][2];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            vr[r][0] = vs[(nl + r) * kTrLd + j];
-            vr[r][1] = vs[(nl + r) * kTrLd + j + 16];
-          }
+          load_cols(va, vs, nl, j);
 #pragma unroll
           for (int u = 0; u < kSpQT; ++u) {
             if ((qb * 4 * kSpQT + u * 4 + wave) >= nqt) continue;      // (uniform per wave)
-            f32x4 sc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int t = 0; t < 8; ++t) sc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[t], qr[u][t], sc, 0, 0, 0);
-            float tmax = -INFINITY;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              if (n0 + r >= L) sc[r] = -INFINITY;
-              tmax = fmaxf(tmax, sc[r]);
-            }
-            const float mn = fmaxf(m[u], xor_max16_32(tmax));
-            const float alpha = __expf(m[u] - mn);
-            float p[4], ps = 0.f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              p[r] = __expf(sc[r] - mn);
-              ps += p[r];
-              if (n0 + r < L) p[r] *= drop_keep(dr, base[u] + n0 + r);
-            }
-            sum[u] = sum[u] * alpha + xor_sum16_32(ps);
-            m[u] = mn;
-            acc[u][0] *= alpha;
-            acc[u][1] *= alpha;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[r][0], p[r], acc[u][0], 0, 0, 0);
-              acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[r][1], p[r], acc[u][1], 0, 0, 0);
-            }
+            fwd_tile(kr, qr[u], va, n0, L, dr, base[u], m[u], sum[u], acc[u]);
           }
         }
       }
 #pragma unroll
       for (int u = 0; u < kSpQT; ++u) {
         const int qn = (qb * 4 * kSpQT + u * 4 + wave) * 16 + j;
-        if (qn < N) {
-          const long long mq = nat_row(rm, s * N + qn);
-          const float inv = 1.f / sum[u];
-          float* xo = x + (mq * T + f) * C + h * 32 + 4 * g;
-          *reinterpret_cast<float4*>(xo) = float4{acc[u][0][0] * inv, acc[u][0][1] * inv, acc[u][0][2] * inv, acc[u][0][3] * inv};
-          *reinterpret_cast<float4*>(xo + 16) = float4{acc[u][1][0] * inv, acc[u][1][1] * inv, acc[u][1][2] * inv, acc[u][1][3] * inv};
-          if (g == 0) {
-            float* st = stats + ((((size_t)s * heads + h) * N + qn) * T + f) * 3;
-            st[0] = m[u];
-            st[1] = inv;
-          }
-        }
+        if (qn < N)
+          fwd_store(x + (nat_row(rm, s * N + qn) * T + f) * C + h * 32 + 4 * g, stat_ptr(stats, s, h, qn, f, heads, N, T), acc[u], m[u], sum[u], g);
       }
     }
 }
@@ -725,7 +693,7 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_chunk_kernel(const float
   const int s = blockIdx.x / heads, h = blockIdx.x - s * heads, N = rm.N, L = rm.L;
   const int nqt = (N + 15) >> 4, nqb = (nqt + 4 * kSpQT - 1) / (4 * kSpQT);
   float* ks = smem;
-  float* vs = smem + kSpChunk * kTrLd;
+  float* vs = smem + spatial_chunk_lds() / sizeof(float) / 2;
   for (int qb = (int)blockIdx.y; qb < nqb; qb += (int)gridDim.y) {
     float qr[kSpQT][8];
     long long mq[kSpQT];
@@ -735,10 +703,7 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_chunk_kernel(const float
     for (int u = 0; u < kSpQT; ++u) {
       qc[u] = min((qb * 4 * kSpQT + u * 4 + wave) * 16 + j, N - 1);
       mq[u] = nat_row(rm, s * N + qc[u]);
-      const float* qp = q + mq[u] * C + h * 32 + 8 * g;
-      const float4 a = *reinterpret_cast<const float4*>(qp), b = *reinterpret_cast<const float4*>(qp + 4);
-      qr[u][0] = a.x * scale; qr[u][1] = a.y * scale; qr[u][2] = a.z * scale; qr[u][3] = a.w * scale;
-      qr[u][4] = b.x * scale; qr[u][5] = b.y * scale; qr[u][6] = b.z * scale; qr[u][7] = b.w * scale;
+      load_row(qr[u], q + mq[u] * C + h * 32 + 8 * g, scale);
       acc[u][0] = f32x4{0.f, 0.f, 0.f, 0.f};
       acc[u][1] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -747,65 +712,34 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_chunk_kernel(const float
       unsigned long long base[kSpQT];
 #pragma unroll
       for (int u = 0; u < kSpQT; ++u) {
-        const float* gp = dx + (mq[u] * T + f) * C + h * 32 + 8 * g;
-        const float* xp = x + (mq[u] * T + f) * C + h * 32 + 8 * g;
-        const float4 c = *reinterpret_cast<const float4*>(gp), d = *reinterpret_cast<const float4*>(gp + 4);
-        const float4 e = *reinterpret_cast<const float4*>(xp), e2 = *reinterpret_cast<const float4*>(xp + 4);
-        dxr[u][0] = c.x; dxr[u][1] = c.y; dxr[u][2] = c.z; dxr[u][3] = c.w; dxr[u][4] = d.x; dxr[u][5] = d.y; dxr[u][6] = d.z; dxr[u][7] = d.w;
-        dsum[u] = xor_sum16_32(c.x * e.x + c.y * e.y + c.z * e.z + c.w * e.w + d.x * e2.x + d.y * e2.y + d.z * e2.z + d.w * e2.w);
-        const float* st = stats + ((((size_t)s * heads + h) * N + qc[u]) * T + f) * 3;
+        dsum[u] = load_dx_D(dxr[u], dx + (mq[u] * T + f) * C + h * 32 + 8 * g, x + (mq[u] * T + f) * C + h * 32 + 8 * g);
+        const float* st = stat_ptr(stats, s, h, qc[u], f, heads, N, T);
         m[u] = st[0];
         inv[u] = st[1];
-        base[u] = ((((unsigned long long)s * heads + h) * N + qc[u]) * T + f) * L;
+        base[u] = drop_base(s, h, qc[u], f, heads, N, T, L);
       }
       for (int c0 = 0; c0 < L; c0 += kSpChunk) {
         __syncthreads();
-        stage_chunk36(ks, k, rm, s, f, c0, h, C, tid);
-        stage_chunk36(vs, v, rm, s, f, c0, h, C, tid);
+        stage_rows36(ks, k, rm, s, f * L + c0, min(kSpChunk, L - c0), h, C, tid);
+        stage_rows36(vs, v, rm, s, f * L + c0, min(kSpChunk, L - c0), h, C, tid);
         __syncthreads();
         const int nkt = (min(kSpChunk, L - c0) + 15) >> 4;
         for (int kt = 0; kt < nkt; ++kt) {
-          const float* kp = ks + (kt * 16 + j) * kTrLd + 8 * g;
-          const float* vp = vs + (kt * 16 + j) * kTrLd + 8 * g;
-          const float4 ka = *reinterpret_cast<const float4*>(kp), kb = *reinterpret_cast<const float4*>(kp + 4);
-          const float4 va = *reinterpret_cast<const float4*>(vp), vb = *reinterpret_cast<const float4*>(vp + 4);
-          const float kr[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
-          const float vr[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
+          float kr[8], vr[8], ka[4][2];
+          load_row(kr, ks + (kt * 16 + j) * kTrLd + 8 * g);
+          load_row(vr, vs + (kt * 16 + j) * kTrLd + 8 * g);
           const int nl = kt * 16 + 4 * g, n0 = c0 + nl;
-          float kt_[4][2];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            kt_[r][0] = ks[(nl + r) * kTrLd + j];
-            kt_[r][1] = ks[(nl + r) * kTrLd + j + 16];
-          }
+          load_cols(ka, ks, nl, j);
 #pragma unroll
           for (int u = 0; u < kSpQT; ++u) {
             if ((qb * 4 * kSpQT + u * 4 + wave) >= nqt) continue;      // (uniform per wave)
-            f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-              sc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[t], qr[u][t], sc, 0, 0, 0);
-              dp = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[t], dxr[u][t], dp, 0, 0, 0);
-            }
-            float ds[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const bool valid = n0 + r < L;
-              const float P = valid ? __expf(sc[r] - m[u]) * inv[u] : 0.f;
-              const float kp_ = valid ? drop_keep(dr, base[u] + n0 + r) : 0.f;
-              ds[r] = P * (kp_ * dp[r] - dsum[u]);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(kt_[r][0], ds[r], acc[u][0], 0, 0, 0);
-              acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(kt_[r][1], ds[r], acc[u][1], 0, 0, 0);
-            }
+            bwd_q_tile(kr, vr, qr[u], dxr[u], ka, m[u], inv[u], dsum[u], n0, L, dr, base[u], acc[u]);
           }
         }
       }
 #pragma unroll
       for (int u = 0; u < kSpQT; ++u)
-        if (g == 0 && (qb * 4 * kSpQT + u * 4 + wave) * 16 + j < N) stats[((((size_t)s * heads + h) * N + qc[u]) * T + f) * 3 + 2] = dsum[u];
+        if (g == 0 && (qb * 4 * kSpQT + u * 4 + wave) * 16 + j < N) stat_ptr(stats, s, h, qc[u], f, heads, N, T)[2] = dsum[u];
     }
 #pragma unroll
     for (int u = 0; u < kSpQT; ++u) {
@@ -850,7 +784,7 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_kernel(const float* __re
       load_row<D>(dxr, dx + (mq * T + f) * C + h * D);
       float mx = -INFINITY;
       for (int n = 0; n < L; ++n) mx = fmaxf(mx, dot_lds<D>(qr, ks + n * D));
-      const unsigned long long base = ((((unsigned long long)s * heads + h) * N + qn) * T + f) * L;
+      const unsigned long long base = drop_base(s, h, qn, f, heads, N, T, L);
       float sum = 0.f, pd = 0.f;
       for (int n = 0; n < L; ++n) {
         const float p = __expf(dot_lds<D>(qr, ks + n * D) - mx);
@@ -865,7 +799,7 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_kernel(const float* __re
         const float dP = kp != 0.f ? kp * dot_lds<D>(dxr, vs + n * D) : 0.f;
         axpy_lds<D>(dqr, P * (dP - Dsum), ks + n * D);
       }
-      float* st = stats + ((((size_t)s * heads + h) * N + qn) * T + f) * 3;
+      float* st = stat_ptr(stats, s, h, qn, f, heads, N, T);
       st[0] = mx;
       st[1] = inv;
       st[2] = Dsum;
@@ -917,13 +851,13 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_kernel(const float* __r
         const long long mq = nat_row(rm, s * N + q0 + qi);
         *reinterpret_cast<float4*>(dxs + (qi * T + ff) * D + c4 * 4) = *reinterpret_cast<const float4*>(dx + (mq * T + ff) * C + h * D + c4 * 4);
       }
-      for (int i = tid; i < nq * T * 3; i += 256) sts[i] = stats[((((size_t)s * heads + h) * N + q0) * T) * 3 + i];
+      for (int i = tid; i < nq * T * 3; i += 256) sts[i] = stat_ptr(stats, s, h, q0, 0, heads, N, T)[i];
       __syncthreads();
       if (!act) continue;
       for (int qi = 0; qi < nq; ++qi) {
         const float* st = sts + (qi * T + f) * 3;
         const float P = __expf(dot_lds<D>(kr, qs + qi * D) - st[0]) * st[1];
-        const float kp = drop_keep(dr, ((((unsigned long long)s * heads + h) * N + q0 + qi) * T + f) * L + n);
+        const float kp = drop_keep(dr, drop_base(s, h, q0 + qi, f, heads, N, T, L) + n);
         const float* dxr = dxs + (qi * T + f) * D;
         const float dP = kp != 0.f ? kp * dot_lds<D>(vr, dxr) : 0.f;
         axpy_lds<D>(dkr, P * (dP - st[2]), qs + qi * D);      // qs is scale * q: the factor `scale` of dk rides along

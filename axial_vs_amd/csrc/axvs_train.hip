@@ -62,8 +62,7 @@ int tail_fwd(const Ctx& c, const TailParams& p, const Saved& s, float* out, floa
 
 // the full layer (WC/temporal_attention.py:133-155): one pass over all T*HW tokens of a clip (one sequence per clip, frames of HW keys;
 // natural row order [(B T), HW] is the sequence order), dropout sites 1 (attention map) and 2 (pass output), then the same tail
-inline RowMap traj_rowmap(const Dims& d) { return RowMap{d.T * (int)d.HW, (int)d.HW, 1, (long long)d.T * d.HW, d.HW, 1, 0}; }
-
+// (traj_rowmap: axvs_train_host.h)
 int traj_forward(const Ctx& c, const float* src, const float* pos, float* out, const AxvsTrajLayerParams& p, const Saved& s, float p_drop,
                  float p_attn, unsigned seed) {
   int rc;

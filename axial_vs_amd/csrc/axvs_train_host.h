@@ -176,21 +176,33 @@ int make_dims(Dims& d, int B, int T, int H, int W, int C, int heads, int F) {
   return AXVS_OK;
 }
 
-// Frame length the spatial half's kernels take: the fp32 MFMA kernels (head_dim 32) any (keys chunked through LDS beyond ~550);
-// the VALU kernels (head_dim 8 / 16 / 64, or option train_valu) hold a whole frame's K and V in LDS.
-int check_frame(int D, long long L) {
-  if (D == 32 && !g_train_valu) return AXVS_OK;
-  const long long maxL = 160 * 1024 / (2 * D * (long long)sizeof(float));
-  if (L > maxL)
-    return fail(AXVS_ERR_ARG, "training tier: head_dim=%d with frames of %lld keys: the VALU attention kernel holds a frame in LDS, at most %lld keys "
-                "(frames of any length need head_dim 32)", D, L, maxL);
-  return AXVS_OK;
+// The kernel family of the spatial half, decided here and nowhere else (the backward reads the statistics the forward leaves, so
+// both ask this function).  head_dim 32: the MFMA kernels -- a frame's K and V resident in LDS (Split: the 16-bit split-precision
+// forward for frames of at most 128 keys, unless g_train_attn_split is 0; Mfma: fp32 operands; the two share the backward), or, beyond the
+// ~550 keys LDS holds, Chunk: keys staged kSpChunk at a time.  Any other head_dim, or option train_valu: the VALU kernels.
+enum class SpatialTier { Valu, Split, Mfma, Chunk };
+constexpr size_t kMaxLds = 160 * 1024;
+
+SpatialTier spatial_tier(const Dims& d, const RowMap& rm) {
+  if (d.D != 32 || g_train_valu) return SpatialTier::Valu;
+  if (spatial_frame_lds(rm.L) > kMaxLds) return SpatialTier::Chunk;
+  return g_train_attn_split && rm.L <= 16 * kSpMaxTiles ? SpatialTier::Split : SpatialTier::Mfma;
+}
+// dynamic LDS of the VALU query-side kernels: K | V of a frame, [L][D] each
+inline size_t spatial_valu_lds(const Dims& d, const RowMap& rm) { return (size_t)2 * rm.L * d.D * sizeof(float); }
+
+// Frame length the spatial half's kernels take: the MFMA kernels any, the VALU kernels what LDS holds.
+int check_frame(const Dims& d, const RowMap& rm) {
+  if (spatial_tier(d, rm) != SpatialTier::Valu || spatial_valu_lds(d, rm) <= kMaxLds) return AXVS_OK;
+  return fail(AXVS_ERR_ARG, "training tier: head_dim=%d with frames of %d keys: the VALU attention kernel holds a frame in LDS, at most %lld keys "
+              "(frames of any length need head_dim 32)", d.D, rm.L, (long long)(kMaxLds / (2 * d.D * sizeof(float))));
 }
 
 // the full T*H*W layer: one frame is all HW tokens of an image
+inline RowMap traj_rowmap(const Dims& d) { return RowMap{d.T * (int)d.HW, (int)d.HW, 1, (long long)d.T * d.HW, d.HW, 1, 0}; }
 int make_traj_dims(Dims& d, int B, int T, int HW, int C, int heads, int F) {
   if (int rc = make_dims_any(d, B, T, 1, HW, C, heads, F)) return rc;
-  return check_frame(d.D, HW);
+  return check_frame(d, traj_rowmap(d));
 }
 
 struct PassSaved {
@@ -339,23 +351,22 @@ struct Ctx {
     e.res2 = res2;
     return g.nt(dY, sc.wt, dX, M, K, N, ld, e, exact || g_train_exact >= 2);
   }
-  int spatial_lds(const void* fn, size_t bytes) const { return bytes > 64 * 1024 ? ensure_max_lds(fn) : AXVS_OK; }
+  // launch 256-thread workgroups with `lds` bytes of dynamic LDS, raising the kernel's limit first where that is above the 64 KiB default
+  template <class... P, class... A>
+  int launch_lds(void (*kern)(P...), dim3 grid, size_t lds, A... args) const {
+    if (lds > 64 * 1024)
+      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, args...);
+    return AXVS_OK;
+  }
 };
 
-// The spatial half runs on the fp32 MFMA kernels (forward and both backward parts, or none of them: the backward reads the
-// statistics the forward leaves) when head_dim is 32 and a sequence's scaled q + dx rows fit in LDS.
 // queries the key-side backward kernel stages at a time: all of a sequence when they fit in LDS (the within-clip layer: <= 512),
 // else chunks of 512 (the cross-clip module over 12 clips of 128 queries)
 int spatial_kv_chunk(const RowMap& rm) {
   const int Np = (rm.N + 15) / 16 * 16;
   return Np <= 512 ? Np : 512;
 }
-bool mfma_spatial(const Dims& d, const RowMap& rm) {
-  const size_t lds_q = (size_t)2 * ((rm.L + 15) / 16 * 16) * kTrLd * sizeof(float);
-  return d.D == 32 && !g_train_valu && lds_q <= 160 * 1024;
-}
-// head_dim 32, frames too long for LDS: the chunked-key query-side kernels (the key side is tr_spatial_bwd_kv_mfma_kernel either way)
-bool chunk_spatial(const Dims& d, const RowMap& rm) { return d.D == 32 && !g_train_valu && !mfma_spatial(d, rm); }
 // grid of the chunked kernels: y counts blocks of 4 * kSpQT query tiles
 inline int chunk_tiles(const RowMap& rm) { return (((rm.N + 15) / 16 + 4 * kSpQT - 1) / (4 * kSpQT)) * 4; }
 
@@ -363,13 +374,72 @@ inline int chunk_tiles(const RowMap& rm) { return (((rm.N + 15) / 16 + 4 * kSpQT
 // are spread over more workgroups until there are about g_spatial_wgs of them -- every (tile, frame) is computed by exactly one
 // wave with the same instructions whatever the split.
 dim3 spatial_grid(int sh, int tiles, int frames) {
-  const int target = g_spatial_wgs;                  // workgroups wanted (option "train_spatial_wgs")
+  const int target = g_spatial_wgs;                  // workgroups wanted
   if (sh >= target) return dim3(sh, 1, 1);
   const int z = frames;
   int y = (target + sh * z - 1) / (sh * z);
   const int ymax = (tiles + 3) / 4;
   y = y > ymax ? ymax : (y < 1 ? 1 : y);
   return dim3(sh, y, z);
+}
+
+// the spatial half, forward (WC/temporal_attention.py:47-58): s.q, s.k, s.v -> s.x, and on the MFMA tiers (max, 1 / sum) -> s.st
+int spatial_fwd(const Ctx& c, const PassSaved& s, const RowMap& rm, int S, Drop attn_drop) {
+  const Dims& d = c.d;
+  const int sh = S * d.heads, nqt = (rm.N + 15) / 16;
+  switch (spatial_tier(d, rm)) {
+    case SpatialTier::Split:      // 16-bit matrix cores, three-piece operands, a frame's scores in registers
+      return c.launch_lds(tr_spatial_fwd_split_kernel, spatial_grid(sh, nqt, d.T), spatial_split_lds(rm.L), s.q, s.k, s.v, s.x, s.st, rm, d.T, d.C,
+                          d.heads, c.scale, attn_drop);
+    case SpatialTier::Mfma:       // fp32 MFMA, the frame in LDS
+      return c.launch_lds(tr_spatial_fwd_mfma_kernel, spatial_grid(sh, nqt, d.T), spatial_frame_lds(rm.L), s.q, s.k, s.v, s.x, s.st, rm, d.T, d.C,
+                          d.heads, c.scale, attn_drop);
+    case SpatialTier::Chunk:      // long frames: keys chunked through LDS
+      return c.launch_lds(tr_spatial_fwd_chunk_kernel, spatial_grid(sh, chunk_tiles(rm), d.T), spatial_chunk_lds(), s.q, s.k, s.v, s.x, s.st, rm, d.T,
+                          d.C, d.heads, c.scale, attn_drop);
+    case SpatialTier::Valu:
+      break;
+  }
+  if (int rc = check_frame(d, rm)) return rc;
+  AXVS_D_SWITCH(d.D, return c.launch_lds(tr_spatial_fwd_kernel<kD>, dim3(sh), spatial_valu_lds(d, rm), s.q, s.k, s.v, s.x, rm, d.T, d.C, d.heads,
+                                         c.scale, attn_drop))
+  return AXVS_OK;
+}
+
+// the spatial half, backward: c.sc.dx (gradient of s.x) -> c.sc.dq, dk, dv; D -> s.st[.., 2].  Split and Mfma share their backward.
+int spatial_bwd(const Ctx& c, const PassSaved& s, const RowMap& rm, int S, Drop attn_drop) {
+  const Dims& d = c.d;
+  const Scratch& sc = c.sc;
+  const int sh = S * d.heads, nqt = (rm.N + 15) / 16, T = d.T;
+  int rc;
+  switch (spatial_tier(d, rm)) {
+    case SpatialTier::Valu: {
+      if ((rc = check_frame(d, rm)) != AXVS_OK) return rc;
+      constexpr int QC = 32;      // queries the key-side kernel stages at a time: scaled q, dx of all T frames, statistics
+      const size_t lds_kv = (size_t)(QC * d.D + QC * T * d.D + QC * T * 3) * sizeof(float);
+      AXVS_D_SWITCH(d.D, {
+        if ((rc = c.launch_lds(tr_spatial_bwd_q_kernel<kD>, dim3(sh), spatial_valu_lds(d, rm), s.q, s.k, s.v, sc.dx, sc.dq, s.st, rm, T, d.C, d.heads,
+                               c.scale, attn_drop)) != AXVS_OK)
+          return rc;
+        return c.launch_lds(tr_spatial_bwd_kv_kernel<kD>, dim3(sh), lds_kv, s.q, s.k, s.v, sc.dx, s.st, sc.dk, sc.dv, rm, T, d.C, d.heads, c.scale,
+                            attn_drop, QC);
+      })
+      return AXVS_OK;
+    }
+    case SpatialTier::Chunk:
+      rc = c.launch_lds(tr_spatial_bwd_q_chunk_kernel, spatial_grid(sh, chunk_tiles(rm), 1), spatial_chunk_lds(), s.q, s.k, s.v, s.x, sc.dx, sc.dq, s.st,
+                        rm, T, d.C, d.heads, c.scale, attn_drop);
+      break;
+    case SpatialTier::Split:
+    case SpatialTier::Mfma:
+      rc = c.launch_lds(tr_spatial_bwd_q_mfma_kernel, spatial_grid(sh, nqt, 1), spatial_frame_lds(rm.L), s.q, s.k, s.v, s.x, sc.dx, sc.dq, s.st, rm, T,
+                        d.C, d.heads, c.scale, attn_drop);
+      break;
+  }
+  if (rc != AXVS_OK) return rc;
+  const int Nc = spatial_kv_chunk(rm);      // the key side never holds a whole frame: one kernel behind both query-side kernels
+  return c.launch_lds(tr_spatial_bwd_kv_mfma_kernel, spatial_grid(sh, (rm.L + 15) / 16, T), spatial_kv_lds(Nc), s.q, s.k, s.v, sc.dx, s.st, sc.dk, sc.dv,
+                      rm, T, d.C, d.heads, c.scale, attn_drop, Nc);
 }
 
 // one axial pass, forward: xout = xin + dropout1(TrajectoryAttention(q = k = xin + pos, v = xin))   WC/temporal_attention.py:35-76
@@ -387,29 +457,7 @@ int pass_fwd(const Ctx& c, const float* xin, const float* pos, float* xout, cons
   if ((rc = c.g.fwd(xin, w.q_w, s.q, M, C, C, 0.f, &eq, ex, pos)) != AXVS_OK) return rc;
   if ((rc = c.g.fwd(xin, w.k_w, s.k, M, C, C, 0.f, &ek, ex, pos)) != AXVS_OK) return rc;
   if ((rc = c.g.fwd(xin, w.v_w, s.v, M, C, C, 0.f, &ev, ex)) != AXVS_OK) return rc;
-  const size_t lds = (size_t)2 * rm.L * d.D * sizeof(float);
-  const size_t lds_mfma = (size_t)2 * ((rm.L + 15) / 16 * 16) * kTrLd * sizeof(float);
-  if (mfma_spatial(d, rm) && g_train_attn_split && rm.L <= 16 * kSpMaxTiles) {   // 16-bit matrix cores, three-piece operands, a frame's scores in registers
-    const size_t lds_split = spatial_split_lds(rm.L);
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_split_kernel), lds_split)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_fwd_split_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, d.T), dim3(256), lds_split, c.st, (const float*)s.q,
-                       (const float*)s.k, (const float*)s.v, s.x, s.st, rm, d.T, C, d.heads, c.scale, attn_drop);
-  } else if (mfma_spatial(d, rm)) {                                     // head_dim 32 (every shipped config): fp32 MFMA kernels
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_mfma_kernel), lds_mfma)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_fwd_mfma_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, d.T), dim3(256), lds_mfma, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, s.x, s.st, rm, d.T, C, d.heads, c.scale, attn_drop);
-  } else if (chunk_spatial(d, rm)) {                                    // head_dim 32, long frames: keys chunked through LDS
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_chunk_kernel), spatial_chunk_lds())) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_fwd_chunk_kernel, spatial_grid(S * d.heads, chunk_tiles(rm), d.T), dim3(256), spatial_chunk_lds(), c.st, (const float*)s.q,
-                       (const float*)s.k, (const float*)s.v, s.x, s.st, rm, d.T, C, d.heads, c.scale, attn_drop);
-  } else {
-  if ((rc = check_frame(d.D, rm.L)) != AXVS_OK) return rc;
-  AXVS_D_SWITCH(d.D, {
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_fwd_kernel<kD>), lds)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_fwd_kernel<kD>, dim3(S * d.heads), dim3(256), lds, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, s.x, rm, d.T, C, d.heads, c.scale, attn_drop);
-  })
-  }
+  if ((rc = spatial_fwd(c, s, rm, S, attn_drop)) != AXVS_OK) return rc;
   hipLaunchKernelGGL(tr_diag_gather_kernel, dim3(blocks((size_t)M * C / 4)), dim3(256), 0, c.st, (const float*)s.x, s.xd, M, d.T, d.HW, C);
   const GemmEpi epq{w.proj_q_b, c.scale, 0, none, 0.f}, epkv{w.proj_kv_b, 1.f, 0, none, 0.f};
   if ((rc = c.g.fwd(s.xd, w.proj_q_w, s.q2, M, C, C, 0.f, &epq, ex)) != AXVS_OK) return rc;
@@ -453,36 +501,7 @@ int pass_bwd(const Ctx& c, const float* d_out, const float* xin, const float* po
   if ((rc = c.wgrad(sc.dq2, s.xd, gw.proj_q_w, M, C, C, gw.proj_q_b, 0, 0, c.scale)) != AXVS_OK) return rc;
   if ((rc = c.dgrad(sc.dq2, w.proj_q_w, sc.dxd, M, C, C, 0.f, 0, false, c.scale)) != AXVS_OK) return rc;
   hipLaunchKernelGGL(tr_diag_scatter_add_kernel, dim3(blocks(MC / 4)), dim3(256), 0, c.st, sc.dx, (const float*)sc.dxd, M, T, d.HW, C);
-  // spatial half
-  const size_t lds = (size_t)2 * rm.L * d.D * sizeof(float);
-  constexpr int QC = 32;
-  const size_t lds2 = (size_t)(QC * d.D + QC * T * d.D + QC * T * 3) * sizeof(float);
-  const size_t lds_q = (size_t)2 * ((rm.L + 15) / 16 * 16) * kTrLd * sizeof(float);
-  const int kv_chunk = spatial_kv_chunk(rm);
-  const size_t lds_kv = (size_t)kv_chunk * (2 * kTrLd + 4) * sizeof(float);
-  if (mfma_spatial(d, rm) || chunk_spatial(d, rm)) {       // the forward was an MFMA kernel too: (max, 1 / sum) are in s.st
-    if (chunk_spatial(d, rm)) {
-      if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_chunk_kernel), spatial_chunk_lds())) != AXVS_OK) return rc;
-      hipLaunchKernelGGL(tr_spatial_bwd_q_chunk_kernel, spatial_grid(S * d.heads, chunk_tiles(rm), 1), dim3(256), spatial_chunk_lds(), c.st, (const float*)s.q,
-                         (const float*)s.k, (const float*)s.v, (const float*)s.x, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
-    } else {
-      if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_mfma_kernel), lds_q)) != AXVS_OK) return rc;
-      hipLaunchKernelGGL(tr_spatial_bwd_q_mfma_kernel, spatial_grid(S * d.heads, (rm.N + 15) / 16, 1), dim3(256), lds_q, c.st, (const float*)s.q, (const float*)s.k,
-                         (const float*)s.v, (const float*)s.x, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
-    }
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_kv_mfma_kernel), lds_kv)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_bwd_kv_mfma_kernel, spatial_grid(S * d.heads, (rm.L + 15) / 16, T), dim3(256), lds_kv, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, (const float*)sc.dx, (const float*)s.st, sc.dk, sc.dv, rm, T, C, d.heads, c.scale, attn_drop, kv_chunk);
-  } else {
-  if ((rc = check_frame(d.D, rm.L)) != AXVS_OK) return rc;
-  AXVS_D_SWITCH(d.D, {
-    if ((rc = c.spatial_lds(reinterpret_cast<const void*>(tr_spatial_bwd_q_kernel<kD>), lds)) != AXVS_OK) return rc;
-    hipLaunchKernelGGL(tr_spatial_bwd_q_kernel<kD>, dim3(S * d.heads), dim3(256), lds, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, (const float*)sc.dx, sc.dq, s.st, rm, T, C, d.heads, c.scale, attn_drop);
-    hipLaunchKernelGGL(tr_spatial_bwd_kv_kernel<kD>, dim3(S * d.heads), dim3(256), lds2, c.st, (const float*)s.q, (const float*)s.k,
-                       (const float*)s.v, (const float*)sc.dx, (const float*)s.st, sc.dk, sc.dv, rm, T, C, d.heads, c.scale, attn_drop, QC);
-  })
-  }
+  if ((rc = spatial_bwd(c, s, rm, S, attn_drop)) != AXVS_OK) return rc;
   // q / k / v projections
   const float* const xa = pos ? sc.a : xin;
   if (pos) c.add(xin, pos, sc.a, MC);
