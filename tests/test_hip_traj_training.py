@@ -7,6 +7,7 @@ import torch
 import __graft_entry__ as ge
 import axvs_oracle as orc
 from golden_util import rel_err, rel_l2
+from traj_train_cases import traj_layer_train_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -21,26 +22,6 @@ def built():
 
 def traj_shapes(C, F):
     return {k.replace("height_attn", "temporal_attn"): v for k, v in orc.axial_layer_param_shapes(C, F).items() if "width_attn" not in k}
-
-
-def traj_layer_train_ref(src, pos, w, heads, p_drop, p_attn, seed):
-    """TemporalTrajectoryAttentionLayer.forward in train() mode with the tier's dropout factors: differentiable torch code."""
-    B, T = pos.shape[:2]
-    C = src.shape[-1]
-    dt = src.dtype
-    x = src.reshape(B, -1, C)
-    N = x.shape[1]
-    L = N // T
-    keep = orc.dropout_keep(seed, 1, B * heads * N * T * L, p_drop, dt).reshape(B, heads, N, T, L) if p_drop > 0 else None
-    kq = x + pos.reshape(B, -1, C).to(dt)
-    y, _ = orc.trajectory_attention(kq, kq, x, orc._sub(w, "temporal_attn"), T, heads, want_attn=False, attn_keep=keep)
-    x = x + y * orc.dropout_keep(seed, 2, B * N * C, p_attn, dt).reshape(B, N, C)
-    z = orc._layer_norm(x.reshape(src.shape), w, "norm1")
-    F_ = w["linear1.weight"].shape[0]
-    M = B * N
-    r = torch.relu(orc._linear(z, w, "linear1")) * orc.dropout_keep(seed, 5, M * F_, p_drop, dt).reshape(*src.shape[:2], F_)
-    ff = orc._linear(r, w, "linear2") * orc.dropout_keep(seed, 6, M * C, p_drop, dt).reshape(src.shape)
-    return orc._layer_norm(z + ff, w, "norm2")
 
 
 def make_layer(C, F, w, p_dropout, p_attn_drop, seed, heads=8, **kw):
