@@ -33,7 +33,7 @@ thread_local int g_prof_cap = 0;
 thread_local int g_prof_next = 0;
 constexpr int kMaxStages = 32;
 thread_local const char* g_stage_names[kMaxStages] = {};
-constexpr int kMergeSmall = 128;         // 16-row-tile passes (T <= 4) of at most this many tiles run merged too (round 5, profiles/r5_merged_16row_tiles.txt)
+constexpr int kMergeSmall = 128;         // 16-row-tile passes (T <= 4) of at most this many tiles run merged too: -3 % per layer at 128 tiles in a stack with cold weights, +3 % at 256 (profiles/r5_merged_16row_tiles.txt)
 // ---- options (axvs_set_option; the comment above it is the list of the 15 keys) ----
 thread_local int g_generic_only = 0;     // option "generic_only": 1 = always use the shape-generic v1 kernels
 thread_local int* g_status = nullptr;     // axvs_set_status_buffer: word that kernels OR condition bits into (device memory, or pinned host memory)
@@ -56,7 +56,7 @@ thread_local int g_ffn_gelu = 0;         // option "ffn_gelu": the layer's FFN a
 // that are zero when registered; every launch leaves them zero) -- without a registered buffer the passes run as two launches.
 thread_local unsigned* g_sync = nullptr;
 thread_local size_t g_sync_words = 0;
-thread_local int g_merge_qkv_any = 0;    // option "merge_qkv_any": merged launches at every grid size (A/B; see run_traj)
+thread_local int g_merge_qkv_any = 0;    // option "merge_qkv_any": merged launches at every grid size (A/B; see plan_traj)
 thread_local int g_merge_small = kMergeSmall;   // option "plan_force" bits 16 / 32: 0 never, 1 at any size, n > 1: passes of at most n tiles of 16 rows (kMergeSmall)
 thread_local int g_out_dtype = 0;        // option "layer_out_dtype": 0 = the layer's output rows are fp32 (the reference's type); 1 / 2 = the kernel that ends the layer
                                          // (norm2 epilogue of the FFN) writes them as f16 / bf16 -- the map a batch-sharded caller gathers over the links
@@ -76,7 +76,7 @@ constexpr int kSmallBelow = 65;          // problems with fewer 64-row tiles tha
                                          // the 64-row forms (merged launch per pass, FFN riding in the width pass) are faster at every T -- round 5 sweep,
                                          // profiles/r5_planner_threshold.txt (128 until then: [1,2,256,48,80] 93.4 -> 79.5 us, [1,5,256,24,40] 94.6 -> 82.8)
 constexpr int kMergeMid = 1;             // merged q/k/v + trajectory launch on 32-row tiles (T = 5 .. 8): 1 = while the pass fits one round of the chip, 0 never,
-                                         // 2 always (profiles/r5_merged_32row_tiles.txt)
+                                         // 2 always: -4 .. -9 % per layer up to 256 tiles, +4 .. +15 % beyond (profiles/r5_merged_32row_tiles.txt)
 constexpr int kQkvSplitUpto = 64;        // the stand-alone q/k/v kernel runs one workgroup per (tile, q | k | v) up to this many tiles of 64 rows
 // Pieces of the 128 x 128 split-precision GEMM of axvs_gemm_nt.h, which runs the deformable attention's three projections when the
 // level set has >= 2048 rows.  4 (rounds 3 - 4): two bf16 pieces for value_proj (its output is rounded to 16 bits anyway) and for the
@@ -323,59 +323,133 @@ TrajLayerWs carve_traj_layer_ws(Carver& c, int B, int T, int HW, int C, int head
   return w;
 }
 
-// Full fusion (spatial half inside the temporal kernel, x never leaves LDS) needs: the fused kernels, no attention-map
-// output, 8..128 keys per frame (frames are padded to multiples of 16 rows in the q/k/v row space, V^T to 32-key steps: within 2x of
-// the padded rows for every L; below 8 keys the padding would more than double the work).  Any axis length: row tiles are cut
-// per sequence, partial key tiles are masked.
-// Frame counts the fused trajectory kernels exist for: T <= 8 (64- / 32-row tiles), and 9 .. 12 on 16-row tiles (x tile T * 8 KiB)
-// for problems with few rows -- whole-video cross-clip inference with up to 12 clips (Q * Tc rows per video).
-// (The choice depends on T alone, not on the number of rows of the call: the fused and the generic tier differ at the 16-bit level,
-//  and a clip's result must not depend on how many other clips share its batch -- batch sharding is bit-exact.)
-bool fused_frames(int T, long long /*rows*/) { return T <= 8 || (T <= 12 && !g_no_small_tiles); }
-bool can_fuse_attn(int C, int heads, int T, int L, bool want_attn, long long rows) {
-  return !g_generic_only && !g_no_attn_fusion && C == 256 && heads == 8 && fused_frames(T, rows) && !want_attn && L >= 8 && L <= 128;
-}
-// The FFN rides in the width-pass kernel only when that kernel has more than 64 tiles (kSmallBelow): with fewer 64-row tiles every
-// workgroup's private 1 MB FFN weight stream is pure latency (43 us per pass whether 16 or 64 workgroups run), and a 16-row
-// trajectory kernel (4x the workgroups) + the stand-alone FFN kernel is faster (BASELINE config 3: res4 / res5 levels).
-bool can_fuse_ffn_into_pass(int T, int F, long long M) {
-  return !g_no_ffn_fusion && !g_ffn_gelu && T <= 4 && F % 256 == 0 && F <= 4096 && (M >= (long long)kSmallBelow * 64 || g_no_small_tiles);
-}
-// (activation = gelu: the stand-alone fused FFN kernels have a GELU instantiation; only the width-pass kernel does not carry it)
-bool ffn_kernel_is_fused(int C, int heads, int F) { return !g_generic_only && C == 256 && heads == 8 && F % 256 == 0 && F <= 4096; }
-// few rows: one workgroup per (64-row tile, 256-unit chunk of the hidden layer) + a row-wise finishing kernel (axvs_ffn_split.h);
-// bit-identical to the one-workgroup-per-tile kernels, so the row count may decide
-// 65 .. 88 tiles (round 5): the same kernel with TWO consecutive chunks per workgroup -- tiles x F/512 workgroups, still one round of the chip -- where the
-// one-workgroup-per-tile kernel leaves half the CUs idle behind a private 1 MB stream (only reached when the FFN does not ride in the width pass: T >= 5, GELU)
-int ffn_split_mode(int C, int heads, int F, long long M) {      // 0: no split, 1: one chunk per workgroup, 2: two
-  if (!ffn_kernel_is_fused(C, heads, F) || g_no_small_tiles || F < 512) return 0;
-  if (M < (long long)kSmallBelow * 64) return 1;
-  return (g_ffn_split_pairs && F % 512 == 0 && M <= 88 * 64) ? 2 : 0;      // measured: -2.4 us at 75 tiles, -0.5 .. -0.9 at 80 .. 84, +0.9 at 96, +4.5 at 128 (partials + finishing kernel)
-}
-bool ffn_split_applies(int C, int heads, int F, long long M) { return ffn_split_mode(C, heads, F, M) != 0; }
-
-// 64-row tiles (MT = 4) of the fused trajectory kernel: T <= 4, and either the FFN rides along or there are enough tiles to
-// fill the chip (few tiles take 16-row tiles: 4x the workgroups) -- the choice launch_temporal makes
-bool traj_mt4(int T, long long tiles64, bool with_ffn) { return T <= 4 && (with_ffn || tiles64 >= kSmallBelow || g_no_small_tiles); }
-long long traj_tiles64(long long Mp, int N) { return (Mp / N) * ((N + 63) / 64); }
-// what one axial layer's launch sequence touches in the workspace (the same predicates run_traj / run_ffn dispatch on)
-struct LayerPlan {
-  bool lean_traj;     // both passes fully fused
-  bool need_buf2;     // the width pass writes rows for a separate FFN launch
-  bool need_ffn_tmp;  // generic FFN (LayerNorm / GEMM / GEMM / LayerNorm): fp32 scratch + 16-bit y and h
-  bool need_ffn_part; // chunk-per-workgroup FFN for few rows: [F/256][M][256] fp32 partial outputs
+// ---------------- the inference planner ----------------
+// Which kernel form a trajectory pass and an FFN take is decided HERE, once per call: plan_traj / plan_ffn read the shape, the
+// thread's options and the sync buffer, and everything else -- the workspace carve, the size queries, the launch sequences -- reads
+// the plan.  ("The inference planner", has the measurements behind the thresholds.)
+struct TrajPlan {
+  // kFused: spatial half inside the trajectory kernel, x never leaves LDS.  kTemporalFused: spatial_attn_kernel, then the trajectory
+  // kernel stages x from global.  kGeneric: GEMMs + row-wise kernels.
+  enum Tier { kFused, kTemporalFused, kGeneric } tier;
+  enum Qkv { kQkvKernel, kQkvKernel3, kQkvGemms } qkv;   // without a merged launch: qkv_fused_kernel, its (tile, q | k | v) grid, or three GEMMs
+  int L;            // frame length in the q/k/v row space: the fused tier pads frames to a multiple of 16 rows (RowMap), the others are dense
+  int nks;          // 32-key steps per frame
+  int rows;         // rows per tile of the trajectory kernel: 64, 32 or 16 (0: kGeneric)
+  int mq;           // merged q/k/v + trajectory launch: 0 = two launches, 1 = merged, 2 = merged and a row tile IS a frame (own K / V^T from registers)
+  bool with_ffn;    // the layer's FFN rides in this pass's kernel
+  bool reassoc;     // kGeneric: the reassociated temporal half
+  bool may_merge;   // (input) the caller's sequences may use the registered sync words: one trajectory call at a time per buffer
 };
-LayerPlan plan_layer(int B, int T, int H, int W, int C, int heads, int F, bool want_attn) {
-  LayerPlan p;
-  const long long rows = (long long)B * T * H * W;
-  p.lean_traj = can_fuse_attn(C, heads, T, H, want_attn, rows) && can_fuse_attn(C, heads, T, W, want_attn, rows);
-  p.need_buf2 = !(can_fuse_attn(C, heads, T, W, want_attn, rows) && can_fuse_ffn_into_pass(T, F, rows));
-  p.need_ffn_tmp = p.need_buf2 && !ffn_kernel_is_fused(C, heads, F);
-  p.need_ffn_part = p.need_buf2 && ffn_split_applies(C, heads, F, rows);
+
+// Frame counts the fused trajectory kernels exist for: T <= 8 (64- / 32-row tiles), and 9 .. 12 on 16-row tiles (x tile T * 8 KiB)
+// -- whole-video cross-clip inference with up to 12 clips.  T alone decides, never the number of rows: the fused and the generic
+// tier differ at the 16-bit level, and a clip's result must not depend on how many other clips share its batch.
+// kFused also needs q, k and v from ONE source, no attention-map output and 8 .. 128 keys per frame (V^T is padded to 32-key steps:
+// below 8 keys the padding would more than double the work).  Any axis length: row tiles are cut per sequence, partial key tiles masked.
+// F: the FFN that could ride in this pass (0: none).
+TrajPlan plan_traj(int S, int T, int L, int C, int heads, bool want_attn, bool same_src, int F, bool may_merge) {
+  TrajPlan p{};
+  p.may_merge = may_merge;
+  const bool kernels = !g_generic_only && C == 256 && heads == 8;
+  const bool few_rows_forms = !g_no_small_tiles;
+  p.tier = !(kernels && (T <= 8 || (T <= 12 && few_rows_forms))) ? TrajPlan::kGeneric
+           : same_src && !g_no_attn_fusion && !want_attn && L >= 8 && L <= 128 ? TrajPlan::kFused : TrajPlan::kTemporalFused;
+  p.L = p.tier == TrajPlan::kFused ? pad16(L) : L;
+  p.nks = (p.L + 31) / 32;
+  p.reassoc = p.tier == TrajPlan::kGeneric && kernels && !g_no_reassoc && T >= 12;   // (below ~12 frames the per-head GEMMs cost more than they save)
+  const int N = T * p.L;
+  const long long Mreal = (long long)S * T * L, Mp = (long long)S * N;
+  p.qkv = !(kernels && same_src) ? TrajPlan::kQkvGemms : ((Mp + 63) / 64 <= kQkvSplitUpto && few_rows_forms) ? TrajPlan::kQkvKernel3 : TrajPlan::kQkvKernel;
+  if (p.tier == TrajPlan::kGeneric) return p;
+  // The FFN rides only in a kernel of at least kSmallBelow tiles (counted in REAL rows): with fewer every workgroup's private 1 MB FFN
+  // weight stream is pure latency, and a 16-row trajectory kernel + the stand-alone FFN kernel is faster.  (GELU: only the stand-alone
+  // FFN kernels carry it.)
+  p.with_ffn = p.tier == TrajPlan::kFused && F > 0 && !g_no_ffn_fusion && !g_ffn_gelu && T <= 4 && F % 256 == 0 && F <= 4096 &&
+               (Mreal >= (long long)kSmallBelow * 64 || !few_rows_forms);
+  // 16-row tiles (4x the workgroups) below kSmallBelow tiles of 64 PADDED rows unless the FFN rides, and for T > 8; else 64 rows for T <= 4, 32 above
+  const long long tiles64 = p.tier == TrajPlan::kFused ? (long long)S * ((N + 63) / 64) : (Mp + 63) / 64;
+  p.rows = !p.with_ffn && (tiles64 < kSmallBelow || T > 8) && few_rows_forms ? 16 : T <= 4 ? 64 : 32;
+  // One launch per pass (the kernel computes q, k, v of its own rows, bit-identical to two launches): the fully fused tier on up to 3 key
+  // steps (register budget; 4 on 16-row tiles), T <= 4 or 32-row tiles, K / V^T byte offsets below 4 GiB, one registered arrival counter
+  // per sequence -- and a grid small enough that the sibling tiles of a hand-off start together:
+  //   64 rows: frames of 64 keys (mq = 2) at every size; other frames up to 640 tiles (option merge_qkv_any: any size)
+  //   32 rows: while the pass fits one round of the chip (kMergeMid)
+  //   16 rows: up to kMergeSmall tiles (plan_force 16 / 32: never / at any size)
+  const bool own_frame = p.rows == 64 && p.L == 64 && T >= 2;
+  const auto fits = [&] {
+    return p.rows == 64   ? own_frame || tiles64 <= 640 || g_merge_qkv_any
+           : p.rows == 32 ? kMergeMid && (kMergeMid == 2 || (long long)S * ((N + 31) / 32) <= cu_count())
+                          : g_merge_small && (g_merge_small == 1 || (long long)S * ((N + 15) / 16) <= g_merge_small);
+  };
+  const bool merge = p.tier == TrajPlan::kFused && may_merge && !g_no_merge_qkv && g_sync != nullptr && (size_t)S <= g_sync_words &&
+                     (T <= 4 || p.rows == 32) && p.nks <= (p.rows == 16 ? 4 : 3) && 2 * (long long)heads * 32 * Mp * 2 < (1ll << 32) && fits();
+  p.mq = !merge ? 0 : own_frame ? 2 : 1;
   return p;
 }
 
-bool sine_in_kernel(int C, int heads) { return !g_generic_only && C == 256 && heads == 8; }
+// A 128-row FFN tile takes 33 us where a 64-row tile takes 18 (one workgroup per CU; measured stand-alone, tools/ffn_wide_check.py):
+// the wide kernel pays when its rounds of the 256-CU chip are so much fewer (21504 rows: 1 x 33 against 2 x 18).
+bool ffn_wide_pays(long long M) {
+  const long long r64 = ((M + kRows - 1) / kRows + 255) / 256, r128 = ((M + kWideRows - 1) / kWideRows + 255) / 256;
+  return r64 > 1 && r128 * 11 < r64 * 6;
+}
+
+struct FfnPlan {
+  // kSplit1 / kSplit2: one workgroup per (64-row tile, one / two 256-unit chunks of the hidden layer) + a row-wise finishing kernel
+  // (axvs_ffn_split.h); kWide: 128-row tiles (axvs_ffn_wide.h); kFused: one workgroup per 64-row tile; kGeneric: LayerNorm / GEMM /
+  // GEMM / LayerNorm.  The first four are bit-identical, so the row count may decide between them.
+  enum Kind { kSplit2, kSplit1, kWide, kFused, kGeneric } kind;
+  int split;        // chunks per workgroup of the split form the SHAPE admits (0: none): what a layer's workspace holds partial outputs for,
+                    // also where a 16-bit output map keeps the call itself off that form
+  bool gelu;        // exact GELU instead of ReLU
+  int oflags;       // kOutF16 / kOutBf16: the norm2 epilogue writes 16-bit rows (0: fp32)
+  const char* refuse;   // non-null: no kernel form serves this call
+};
+// has_part: the caller provides [F/256][M][256] fp32 partial outputs; strided: X and out rows are frames a stride apart (RowStride)
+FfnPlan plan_ffn(int C, int heads, int F, long long M, bool has_part, bool strided) {
+  FfnPlan p{};
+  p.gelu = g_ffn_gelu != 0;
+  p.oflags = g_out_dtype ? (g_out_dtype == 1 ? kOutF16 : kOutBf16) : 0;
+  const bool kernels = !g_generic_only && C == 256 && heads == 8 && F % 256 == 0 && F <= 4096;
+  // few rows (below kSmallBelow tiles): one chunk per workgroup.  Up to 88 tiles: two consecutive chunks -- tiles x F/512 workgroups, still one
+  // round of the chip, where one workgroup per tile leaves half the CUs idle behind a private 1 MB stream (-2.4 us at 75 tiles, -0.5 .. -0.9 at
+  // 80 .. 84, +0.9 at 96, +4.5 at 128; only reached when the FFN does not ride in the width pass: T >= 5, GELU)
+  if (kernels && !g_no_small_tiles && F >= 512)
+    p.split = M < (long long)kSmallBelow * 64 ? 1 : (g_ffn_split_pairs && F % 512 == 0 && M <= 88 * 64) ? 2 : 0;
+  static_assert(kFfnTiles + (4096 + 5 * 256) * sizeof(float) <= 160 * 1024, "ffn_lds_bytes: every d_ffn the fused FFN kernels take fits the LDS");
+  if (!kernels) {
+    p.kind = FfnPlan::kGeneric;
+    p.refuse = p.oflags ? "layer_out_dtype: a 16-bit output map needs the fused FFN tier (C = 256, 8 heads, d_ffn a multiple of 256 up to 4096)"
+               : strided ? "internal: strided frames need the fused FFN kernels" : nullptr;
+  } else if (!p.oflags && has_part && p.split) {
+    p.kind = p.split == 2 ? FfnPlan::kSplit2 : FfnPlan::kSplit1;
+  } else if (!p.oflags && F <= 2048 && (g_ffn_wide == 1 || (g_ffn_wide == 0 && ffn_wide_pays(M)))) {
+    p.kind = FfnPlan::kWide;      // more 64-row tiles than CUs: 128-row tiles when that saves a round of the chip
+  } else {
+    p.kind = FfnPlan::kFused;
+  }
+  return p;
+}
+
+// One axial layer: the height pass, the width pass (the FFN may ride in it) and the FFN.  What the launch sequence touches in the
+// workspace is read off the same plans it dispatches on.
+struct LayerPlan {
+  TrajPlan h, w;
+  FfnPlan ffn;
+  bool pos_in_kernel;   // positions given as a sine specification are evaluated by the q/k/v kernels (else materialised first)
+  bool lean_traj() const { return h.tier == TrajPlan::kFused && w.tier == TrajPlan::kFused; }   // only q, k and V^T round-trip
+  bool need_buf2() const { return !w.with_ffn; }                                               // the width pass writes rows for a separate FFN launch
+  bool need_ffn_tmp() const { return need_buf2() && ffn.kind == FfnPlan::kGeneric; }           // fp32 scratch + 16-bit y and h
+  bool need_ffn_part() const { return need_buf2() && ffn.split != 0; }                          // [F/256][M][256] fp32 partial outputs
+};
+LayerPlan plan_layer(int B, int T, int H, int W, int C, int heads, int F, bool want_h_attn, bool want_w_attn, bool strided = false) {
+  LayerPlan p{};
+  p.h = plan_traj(B * W, T, H, C, heads, want_h_attn, true, 0, true);
+  p.w = plan_traj(B * H, T, W, C, heads, want_w_attn, true, F, true);
+  p.ffn = plan_ffn(C, heads, F, (long long)B * T * H * W, true, strided);
+  p.pos_in_kernel = p.h.qkv != TrajPlan::kQkvGemms && p.w.qkv != TrajPlan::kQkvGemms;
+  return p;
+}
 
 // members the plan does not need are null
 struct AxialWs {
@@ -389,15 +463,15 @@ struct AxialWs {
 AxialWs carve_axial_ws(Carver& c, const LayerPlan& plan, bool sine, long long span, int B, int T, int H, int W, int C, int heads, int F) {
   const long long M = (long long)B * T * H * W;
   AxialWs w{};
-  w.tw = carve_traj_ws(c, M, T, heads, plan.lean_traj, std::max(padded_rows(M, H), padded_rows(M, W)));      // q/k/v row space: frames padded to multiples of 16 rows
+  w.tw = carve_traj_ws(c, M, T, heads, plan.lean_traj(), std::max(padded_rows(M, H), padded_rows(M, W)));      // q/k/v row space: frames padded to multiples of 16 rows
   w.buf1 = c.take<float>((size_t)span * C);
-  if (plan.need_buf2) w.buf2 = c.take<float>((size_t)span * C);
-  if (plan.need_ffn_tmp) {
+  if (plan.need_buf2()) w.buf2 = c.take<float>((size_t)span * C);
+  if (plan.need_ffn_tmp()) {
     w.y16 = c.take<u16>((size_t)M * C);
     w.h16 = c.take<u16>((size_t)M * F);
   }
-  if (plan.need_ffn_part) w.ffn_part = c.take<float>((size_t)(F / 256) * M * C);
-  if (sine && !sine_in_kernel(C, heads)) w.pos = c.take<float>((size_t)M * C);
+  if (plan.need_ffn_part()) w.ffn_part = c.take<float>((size_t)(F / 256) * M * C);
+  if (sine && !plan.pos_in_kernel) w.pos = c.take<float>((size_t)M * C);
   return w;
 }
 
@@ -420,188 +494,116 @@ int launch_attn(const TrajWs& w, float* attn, int S, int N, int T, int L, int he
   return AXVS_OK;
 }
 
-// nks = 0: x staged from global (after spatial_attn_kernel); nks > 0: spatial half inside the kernel
+// f(std::integral_constant<int, i>{}) for a runtime i in 1 .. N: the template argument of a kernel family
+template <int N, class F>
+int by_int(int i, F&& f) {
+  if constexpr (N == 0) return fail(AXVS_ERR_ARG, "internal: no kernel is instantiated for %d", i);
+  else return i == N ? f(std::integral_constant<int, N>{}) : by_int<N - 1>(i, f);
+}
+
+// nks = 0: x staged from global (after spatial_attn_kernel); nks > 0: spatial half inside the kernel.  Tile rows: the plan's
+// (instantiated: 64 rows for T = 1 .. 4, 32 for 5 .. 8, 16 for 1 .. 12; the x tile takes T * 16 KiB of LDS per 32 rows).
 template <bool BF>
-int launch_temporal(const TrajWs& w, const TrajPacked& p, const float* res, float* out, RowMap rm, long long Mp, int N, int L, int T,
-                    float scale, hipStream_t st, int nks = 0, const FfnArgs* fa = nullptr, const OwnQkv* oq = nullptr) {
+int launch_temporal(const TrajPlan& pl, int nks, const TrajWs& w, const TrajPacked& p, const float* res, float* out, RowMap rm, long long Mp, int N,
+                    int T, float scale, hipStream_t st, const FfnArgs* fa = nullptr, const OwnQkv* oq = nullptr) {
   // output rows are addressed through the RowMap: the largest byte offset is that of the natural [rows, 256] fp32 tensor
   const int wt = ((g_row_span ? g_row_span : Mp) * 256 * 4 < (1ll << 32) ? 1 : 0) | (g_spatial_only && nks > 0 ? (oq ? g_spatial_only : 1) << 1 : 0) |
                  (fa != nullptr && g_out_dtype ? (g_out_dtype == 1 ? kOutF16 : kOutBf16) : 0);
-  // few rows (cross-clip queries: 512 per video): 16-row tiles give 4x the workgroups -- the spatial half is per-query work
-  const long long tiles64 = nks > 0 ? traj_tiles64(Mp, N) : (Mp + 63) / 64;
   if (oq && !(nks > 0 && T <= 8)) return fail(AXVS_ERR_ARG, "internal: own q,k,v need the in-kernel spatial half and T <= 8");
-  if (fa == nullptr && (tiles64 < kSmallBelow || T > 8) && !g_no_small_tiles) {       // (T > 8 exists on 16-row tiles only: fused_frames)
-    switch (T) {
-      case 1: return launch_temporal_n<BF, 1, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 2: return launch_temporal_n<BF, 2, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 3: return launch_temporal_n<BF, 3, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 4: return launch_temporal_n<BF, 4, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 5: return launch_temporal_n<BF, 5, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 6: return launch_temporal_n<BF, 6, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 7: return launch_temporal_n<BF, 7, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 8: return launch_temporal_n<BF, 8, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 9: return launch_temporal_n<BF, 9, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 10: return launch_temporal_n<BF, 10, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 11: return launch_temporal_n<BF, 11, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      case 12: return launch_temporal_n<BF, 12, 1>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-      default: break;
-    }
-  }
-  switch (T) {
-    case 1: return launch_temporal_n<BF, 1, 4>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-    case 2: return launch_temporal_n<BF, 2, 4>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-    case 3: return launch_temporal_n<BF, 3, 4>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-    case 4: return launch_temporal_n<BF, 4, 4>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-    case 5: return launch_temporal_n<BF, 5, 2>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-    case 6: return launch_temporal_n<BF, 6, 2>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);     // x tile: T * 16 KiB of LDS
-    case 7: return launch_temporal_n<BF, 7, 2>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-    case 8: return launch_temporal_n<BF, 8, 2>(nks, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
-    default: return fail(AXVS_ERR_ARG, "fused temporal kernel supports T <= 8");
-  }
+  return by_int<12>(T, [&](auto t) {
+    constexpr int kT = decltype(t)::value;
+    if (pl.rows == 16) return launch_temporal_n<BF, kT, 1>(nks, w, p, res, out, rm, Mp, N, pl.L, scale, st, fa, wt, oq);
+    if constexpr (kT <= 4) return launch_temporal_n<BF, kT, 4>(nks, w, p, res, out, rm, Mp, N, pl.L, scale, st, fa, wt, oq);
+    else if constexpr (kT <= 8) return launch_temporal_n<BF, kT, 2>(nks, w, p, res, out, rm, Mp, N, pl.L, scale, st, fa, wt, oq);
+    else return fail(AXVS_ERR_ARG, "fused temporal kernel supports T <= 8");
+  });
 }
 
+// One trajectory attention over sequence-ordered rows, by the plan `pl` of plan_traj(S, T, L, ...) for these arguments.
 // q/k/v inputs are fp32 token rows addressed through `rm`; `qk_add` (nullable) is added to the q and k inputs.
-// Result (+ bias, + optional residual `res`) goes to fp32 rows of `out` through `rm`.
+// Result (+ bias, + optional residual `res`) goes to fp32 rows of `out` through `rm`; where the plan lets the layer's FFN ride
+// (pl.with_ffn), norm2(FFN(norm1(...))) goes to `ffn_out` instead.
 template <bool BF>
-int run_traj(const float* qsrc, const float* ksrc, const float* vsrc, const float* qk_add, const float* res, float* out,
+int run_traj(const TrajPlan& pl, const float* qsrc, const float* ksrc, const float* vsrc, const float* qk_add, const float* res, float* out,
              float* attn, const TrajPacked& p, const TrajWs& w, RowMap rm, int S, int T, int L, int C, int heads,
-             hipStream_t st, int pass = 0, const FfnArgs* ffn = nullptr, float* ffn_out = nullptr, bool* ffn_done = nullptr,
-             const PosGen* posgen = nullptr,
-             bool may_merge = false /* the caller's sequences may use the registered sync words (one trajectory call at a time per buffer) */) {
-  static const char* const kNames[3][8] = {
-      {"qkv_proj", "spatial_attn", "proj_q", "proj_kv", "temporal_attn", "proj", "temporal_fused", "traj_fused"},
-      {"h.qkv_proj", "h.spatial_attn", "h.proj_q", "h.proj_kv", "h.temporal_attn", "h.proj", "h.temporal_fused", "h.traj_fused"},
-      {"w.qkv_proj", "w.spatial_attn", "w.proj_q", "w.proj_kv", "w.temporal_attn", "w.proj", "w.temporal_fused", "w.traj_fused"}};
+             hipStream_t st, int pass = 0, const FfnArgs* ffn = nullptr, float* ffn_out = nullptr, const PosGen* posgen = nullptr) {
+  static const char* const kNames[3][9] = {
+      {"qkv_proj", "spatial_attn", "proj_q", "proj_kv", "temporal_attn", "proj", "temporal_fused", "traj_fused", "qkv+traj"},
+      {"h.qkv_proj", "h.spatial_attn", "h.proj_q", "h.proj_kv", "h.temporal_attn", "h.proj", "h.temporal_fused", "h.traj_fused", "h.qkv+traj"},
+      {"w.qkv_proj", "w.spatial_attn", "w.proj_q", "w.proj_kv", "w.temporal_attn", "w.proj", "w.temporal_fused", "w.traj_fused", "w.qkv+traj"}};
   const char* const* nm = kNames[pass];
-  if (may_merge)      // never compute on top of a reported hand-off timeout (host-readable status word; no synchronisation)
+  if (pl.may_merge)      // never compute on top of a reported hand-off timeout (host-readable status word; no synchronisation)
     if (int rc = status_gate()) return rc;
-  const int Lreal = L;
   const int Cp = heads * 32, d = C / heads;
-  const long long Mreal = (long long)S * T * L;
-  if (Mreal * T > 2147483647LL / 4) return fail(AXVS_ERR_ARG, "too many tokens for 32-bit row indices");
+  if ((long long)S * T * L * T > 2147483647LL / 4) return fail(AXVS_ERR_ARG, "too many tokens for 32-bit row indices");
   const float scale = 1.0f / sqrtf((float)d);
-  const float kLog2e = 1.4426950408889634f;
-
-  const bool fuse_attn = qsrc == ksrc && vsrc == qsrc && can_fuse_attn(C, heads, T, L, attn != nullptr, Mreal);
-  const bool with_ffn = fuse_attn && ffn != nullptr && can_fuse_ffn_into_pass(T, ffn->F, Mreal);
+  const float qscale = scale * 1.4426950408889634f;      // q is pre-multiplied by scale * log2(e) for the exp2 softmax
   // The fused tier runs in the PADDED row space (RowMap): frames of roundup16(L) rows, the last ones of each frame clamped copies
   // that are computed and never stored -- every 16-row MFMA tile then lies inside one frame, K / V^T are stored 16 / 8 bytes per lane
   // and the merged launch applies for any frame length (the shipped VIPSeg maps: 49 x 85, 25 x 43).  Every other tier is dense.
-  if (fuse_attn && L % 16 != 0) {
-    L = pad16(L);
-    rm.Lv = Lreal;
-    rm.L = L;
-    rm.N = T * L;
+  if (pl.L != L) {
+    rm.Lv = L;
+    rm.L = pl.L;
+    rm.N = T * pl.L;
   }
-  const int N = T * L;
+  const int N = T * pl.L;
   const long long Mp = (long long)S * N;
   const int M = (int)Mp;
-  const int nks_fused = (L + 31) / 32;
-  // one launch per pass: the trajectory kernel computes q, k, v of its own rows (OwnQkv).  Needs the 64-row fused kernels with
-  // T <= 4, frames of a multiple of 16 keys (16-byte / 8-byte V^T stores) and at most 96 (register budget), byte offsets of K / V^T
-  // below 4 GiB (buffer addressing), one registered arrival counter per sequence.  Bit-identical to the two-launch form.
-  // Frames of 64 keys (a row tile IS a frame: its own K / V^T fragments never leave the registers, MQ = 2) gain at every size
-  // measured (4 - 9 % from [1,2,256,64,64] to [8,4,256,64,64]); other frame lengths (MQ = 1) gain while the grid stays within
-  // ~2 rounds of the chip (-3.5 % at 576 tiles, -7.5 % at 240) and LOSE beyond (+2.5 % at 1152 tiles, +8 % at 4608: sibling
-  // tiles start staggered there and every tile waits for the last one) -- option "merge_qkv_any" lifts the limit for A/B runs.
-  // Problems with few rows run 16-row tiles (launch_temporal: fewer than kSmallBelow tiles of 64 rows and no FFN riding along -- pyramid
-  // levels of 32 x 32 and below, the cross-clip queries).  Their merged form exists (MQ = 1 on 16-row tiles, bit-identical) but
-  // every 16-row workgroup then streams the 384 KB of q/k/v weights itself, which costs what the launch and the q round trip save:
-  // layer at [1,4,256,32,32] 59.0 vs 59.2 us, [1,4,256,16,16] 53.1 vs 56.0, [3,4,256,16,32] 105.3 vs 97.8 (768 tiles: siblings
-  // start staggered), cross-clip module 236.1 vs 237.3, BASELINE config 3 0.997 vs 0.989 ms -- off in rounds 3 - 4.
-  // Round 5: with the few-rows forms ending at 64 tiles of 64 rows (kSmallBelow) every 16-row grid fits one round of the chip and the case that lost is gone:
-  // back to back on warm weights the merged form gains at every size (-8 % per layer at 32 tiles of 16 rows, -7 % at 64, -3 % at 128, -1.5 % at 256), but in a
-  // stack of layers with their own, cold weights only up to 128 tiles (-3 %; +3 % at 256: 256 workgroups x 384 KB of q/k/v weights from HBM) -- merged up to
-  // kMergeSmall tiles per pass: BASELINE config 3 0.878 -> 0.864 ms, cross-clip module 226 -> 224.6 us (profiles/r5_merged_16row_tiles.txt).
-  const bool mt4 = traj_mt4(T, traj_tiles64(Mp, N), with_ffn);
-  const bool own_frame = mt4 && L == 64 && T >= 2;
-  const long long tiles = traj_tiles64(Mp, N);
-  const int tps = (N + 63) / 64;
-  // 32-row tiles (5 .. 8 frames per clip, more than 64 tiles of 64 rows; Tube-Link's T = 5 levels): the merged form exists too (MQ = 1, round 5).  Their x tile
-  // (T * 16 KiB) leaves room for ONE workgroup per CU, so the siblings of a hand-off start together only while the pass fits one round of the chip: -4 .. -9 % per
-  // layer up to 256 tiles, +4 .. +15 % beyond (profiles/r5_merged_32row_tiles.txt) -- merged iff tiles <= CUs (kMergeMid).
-  const bool mt2 = T > 4 && T <= 8 && (tiles >= kSmallBelow || g_no_small_tiles);
-  const bool mid_ok = mt2 && kMergeMid && (kMergeMid == 2 || (long long)S * ((N + 31) / 32) <= cu_count());
-  const bool merge = may_merge && fuse_attn && !g_generic_only && !g_no_merge_qkv &&
-                     g_sync != nullptr && (size_t)S <= g_sync_words && (T <= 4 || mt2) && L % 16 == 0 && nks_fused <= (mt4 || mt2 ? 3 : 4) &&
-                     2 * (long long)Cp * Mp * 2 < (1ll << 32) &&
-                     (!mt4 || own_frame || tiles <= 640 || g_merge_qkv_any) && (mt4 || mid_ok || (!mt2 && g_merge_small && (g_merge_small == 1 || (long long)S * ((N + 15) / 16) <= g_merge_small)));
-  if (merge) {
-    const OwnQkv oq{qsrc, qk_add, posgen ? *posgen : PosGen{}, p.wq, p.wk, p.wv, p.bq, p.bk, p.bv, scale * kLog2e, g_sync, g_status, g_sync_spin_limit};
-    int rc = launch_temporal<BF>(w, p, res, with_ffn ? ffn_out : out, rm, Mp, N, L, T, scale, st, nks_fused, with_ffn ? ffn : nullptr, &oq);
-    if (rc != AXVS_OK) return rc;
-    if (with_ffn) *ffn_done = true;
-    mark(st, with_ffn ? "w.qkv+traj+ffn" : pass == 1 ? "h.qkv+traj" : pass == 2 ? "w.qkv+traj" : "qkv+traj");
+  const FfnArgs* const fa = pl.with_ffn ? ffn : nullptr;
+  float* const dst = pl.with_ffn ? ffn_out : out;
+  const PosGen pg = posgen ? *posgen : PosGen{};
+  if (pl.mq) {      // one launch per pass: the trajectory kernel computes q, k, v of its own rows
+    const OwnQkv oq{qsrc, qk_add, pg, p.wq, p.wk, p.wv, p.bq, p.bk, p.bv, qscale, g_sync, g_status, g_sync_spin_limit};
+    if (int rc = launch_temporal<BF>(pl, pl.nks, w, p, res, dst, rm, Mp, N, T, scale, st, fa, &oq)) return rc;
+    mark(st, pl.with_ffn ? "w.qkv+traj+ffn" : nm[8]);
     return AXVS_OK;
   }
-  // q, k, v projections -> blocked 16-bit, q pre-multiplied by scale*log2(e) for the exp2 softmax
-  if (!g_generic_only && C == 256 && heads == 8 && qsrc == ksrc) {
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&qkv_fused_kernel<BF>))) return rc;
-    // the fused kernel reads the value rows from the same tensor as the q/k rows (+ optional additive term)
-    if (vsrc == qsrc) {
-      // (the V^T padding keys of frames that are not multiples of 32 keys are cleared by the kernel itself)
-      const unsigned qtiles = (unsigned)((Mp + 63) / 64);
-      // few tiles (cross-clip queries): one workgroup per (tile, q | k | v) -- a third of the weight stream each
-      hipLaunchKernelGGL((qkv_fused_kernel<BF>), dim3(qtiles, ((int)qtiles <= kQkvSplitUpto && !g_no_small_tiles) ? 3 : 1), dim3(512), kQkvLdsBytes, st, qsrc, qk_add, rm,
-                         p.wq, p.wk, p.wv, p.bq, p.bk, p.bv, w.q16, w.k16, w.v16, Mp, scale * kLog2e,
-                         fuse_attn ? w.vt16 : (u16*)nullptr, N, L, T, nks_fused, posgen ? *posgen : PosGen{},
-                         2 * (long long)Cp * Mp * 2 < (1ll << 32) ? 1 : 0 /* write-through stores */, g_status);
-      goto qkv_done;
-    }
-  }
-  {
+  // q, k, v projections -> blocked 16-bit
+  if (pl.qkv == TrajPlan::kQkvGemms) {
     if (posgen) return fail(AXVS_ERR_ARG, "internal: generated positions need the fused QKV kernel");
     ALoadRowsF32<BF> aq{qsrc, qk_add, rm, M, C}, ak{ksrc, qk_add, rm, M, C}, av{vsrc, nullptr, rm, M, C};
-    launch_gemm<BF>(aq, p.wq, EpiBlocked16<BF>{w.q16, Mp, p.bq, scale * kLog2e, Cp, 0}, M, Cp, C, st);
+    launch_gemm<BF>(aq, p.wq, EpiBlocked16<BF>{w.q16, Mp, p.bq, qscale, Cp, 0}, M, Cp, C, st);
     launch_gemm<BF>(ak, p.wk, EpiBlocked16<BF>{w.k16, Mp, p.bk, 1.f, 0, 0}, M, Cp, C, st);
     launch_gemm<BF>(av, p.wv, EpiBlocked16<BF>{w.v16, Mp, p.bv, 1.f, 0, 0}, M, Cp, C, st);
+  } else {
+    // the fused kernel reads the value rows from the same tensor as the q/k rows (+ optional additive term); few tiles: one workgroup
+    // per (tile, q | k | v) -- a third of the weight stream each.  (It clears the V^T padding keys of frames that are no multiple of 32 keys itself.)
+    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&qkv_fused_kernel<BF>))) return rc;
+    hipLaunchKernelGGL((qkv_fused_kernel<BF>), dim3((unsigned)((Mp + 63) / 64), pl.qkv == TrajPlan::kQkvKernel3 ? 3 : 1), dim3(512), kQkvLdsBytes, st, qsrc, qk_add, rm,
+                       p.wq, p.wk, p.wv, p.bq, p.bk, p.bv, w.q16, w.k16, w.v16, Mp, qscale,
+                       pl.tier == TrajPlan::kFused ? w.vt16 : (u16*)nullptr, N, pl.L, T, pl.nks, pg,
+                       2 * (long long)Cp * Mp * 2 < (1ll << 32) ? 1 : 0 /* write-through stores */, g_status);
   }
-qkv_done:
   mark(st, nm[0]);
-  if (fuse_attn) {
-    // the layer's FFN can ride along (64-row tiles, LDS budget): `out` then receives norm2(FFN(norm1(...)))
-    int rc = launch_temporal<BF>(w, p, res, with_ffn ? ffn_out : out, rm, Mp, N, L, T, scale, st, nks_fused, with_ffn ? ffn : nullptr);
-    if (rc != AXVS_OK) return rc;
-    if (with_ffn) *ffn_done = true;
-    mark(st, with_ffn ? "w.traj_fused+ffn" : nm[7]);
+  if (pl.tier == TrajPlan::kFused) {
+    if (int rc = launch_temporal<BF>(pl, pl.nks, w, p, res, dst, rm, Mp, N, T, scale, st, fa)) return rc;
+    mark(st, pl.with_ffn ? "w.traj_fused+ffn" : nm[7]);
     return AXVS_OK;
   }
 
   // spatial half
-  int nks = (L + 31) / 32, rc;
-  switch (nks) {
-    case 1: rc = launch_attn<BF, 1>(w, attn, S, N, T, L, heads, Mp, st); break;
-    case 2: rc = launch_attn<BF, 2>(w, attn, S, N, T, L, heads, Mp, st); break;
-    case 3: rc = launch_attn<BF, 3>(w, attn, S, N, T, L, heads, Mp, st); break;
-    case 4: rc = launch_attn<BF, 4>(w, attn, S, N, T, L, heads, Mp, st); break;
-    case 5: rc = launch_attn<BF, 5>(w, attn, S, N, T, L, heads, Mp, st); break;
-    case 6: rc = launch_attn<BF, 6>(w, attn, S, N, T, L, heads, Mp, st); break;
-    case 7: rc = launch_attn<BF, 7>(w, attn, S, N, T, L, heads, Mp, st); break;
-    case 8: rc = launch_attn<BF, 8>(w, attn, S, N, T, L, heads, Mp, st); break;
-    default: {   // more than 256 keys per frame (full T*H*W trajectory attention): chunked keys, online softmax
-      if (attn != nullptr) return fail(AXVS_ERR_ARG, "attention maps are not available for frames of more than 256 keys (L=%d)", L);
-      if (int rc2 = ensure_max_lds(reinterpret_cast<const void*>(&spatial_attn_long_kernel<BF>))) return rc2;
-      const int nwaves = (N + 31) / 32 >= 8 ? 8 : (N + 31) / 32;
-      dim3 grid((N + 32 * nwaves - 1) / (32 * nwaves), heads, S);
-      hipLaunchKernelGGL((spatial_attn_long_kernel<BF>), grid, dim3(64 * nwaves), (size_t)2 * 256 * 32 * sizeof(u16), st, w.q16, w.k16, w.v16,
-                         w.x16, N, T, L, heads, Mp);
-      rc = AXVS_OK;
-    }
+  if (pl.nks <= 8) {
+    if (int rc = by_int<8>(pl.nks, [&](auto nks) { return launch_attn<BF, decltype(nks)::value>(w, attn, S, N, T, L, heads, Mp, st); })) return rc;
+  } else {   // more than 256 keys per frame (full T*H*W trajectory attention): chunked keys, online softmax
+    if (attn != nullptr) return fail(AXVS_ERR_ARG, "attention maps are not available for frames of more than 256 keys (L=%d)", L);
+    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&spatial_attn_long_kernel<BF>))) return rc;
+    const int nwaves = (N + 31) / 32 >= 8 ? 8 : (N + 31) / 32;
+    dim3 grid((N + 32 * nwaves - 1) / (32 * nwaves), heads, S);
+    hipLaunchKernelGGL((spatial_attn_long_kernel<BF>), grid, dim3(64 * nwaves), (size_t)2 * 256 * 32 * sizeof(u16), st, w.q16, w.k16, w.v16,
+                       w.x16, N, T, L, heads, Mp);
   }
-  if (rc != AXVS_OK) return rc;
   mark(st, nm[1]);
 
   // temporal half + output projection + residual
-  if (!g_generic_only && C == 256 && heads == 8 && fused_frames(T, Mp)) {
-    rc = launch_temporal<BF>(w, p, res, out, rm, Mp, N, L, T, scale, st);
-    if (rc != AXVS_OK) return rc;
+  if (pl.tier == TrajPlan::kTemporalFused) {
+    if (int rc = launch_temporal<BF>(pl, 0, w, p, res, out, rm, Mp, N, T, scale, st)) return rc;
     mark(st, nm[6]);
     return AXVS_OK;
   }
   ALoadBlocked<BF> adiag{w.x16, Mp * T, M, T, N, L};
   launch_gemm<BF>(adiag, p.wpq, EpiRowsF32{w.q2, nullptr, p.bpq, identity_map(Mp), Cp, scale}, M, Cp, Cp, st);
   mark(st, nm[2]);
-  if (!g_generic_only && !g_no_reassoc && C == 256 && heads == 8 && T >= 12) {   // (below ~12 frames the per-head GEMMs cost more than they save)
+  if (pl.reassoc) {
     // Reassociated (see temporal_fused_kernel): proj_kv is applied to u_h = Wk2_h^T q2_h and z_h = sum_f a_f x_f instead of to
     // every frame slot of x -- 2 C^2 instead of 2 T C^2 MACs per token, and no [T*M, 2C] tensor.  Whole-video cross-clip
     // inference runs T = number of clips (tens): this is what keeps the temporal half linear in T.
@@ -631,15 +633,13 @@ qkv_done:
     }
     mark(st, nm[4]);
   } else {
-  ALoadBlocked<BF> aall{w.x16, Mp * T, M * T, 0, 1, 1};
-  launch_gemm<BF>(aall, p.wpkv, EpiRowsF32{w.kv2, nullptr, p.bpkv, identity_map(Mp * T), 2 * Cp, 1.f}, M * T, 2 * Cp, Cp, st);
-  mark(st, nm[3]);
-  {
-    long long threads = Mp * heads * 8;
+    ALoadBlocked<BF> aall{w.x16, Mp * T, M * T, 0, 1, 1};
+    launch_gemm<BF>(aall, p.wpkv, EpiRowsF32{w.kv2, nullptr, p.bpkv, identity_map(Mp * T), 2 * Cp, 1.f}, M * T, 2 * Cp, Cp, st);
+    mark(st, nm[3]);
+    const long long threads = Mp * heads * 8;
     hipLaunchKernelGGL((temporal_attn_kernel<BF>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, w.q2, w.kv2,
                        w.o16, Mp, T, heads);
-  }
-  mark(st, nm[4]);
+    mark(st, nm[4]);
   }
   ALoadBlocked<BF> ao{w.o16, Mp, M, 0, 1, 1};
   launch_gemm<BF>(ao, p.wp, EpiRowsF32{out, res, p.bp, rm, C, 1.f}, M, C, Cp, st);
@@ -647,89 +647,74 @@ qkv_done:
   return AXVS_OK;
 }
 
-// A 128-row FFN tile takes 33 us where a 64-row tile takes 18 (one workgroup per CU; measured stand-alone, tools/ffn_wide_check.py):
-// the wide kernel pays when its rounds of the 256-CU chip are so much fewer (21504 rows: 1 x 33 against 2 x 18).
-bool ffn_wide_pays(long long M) {
-  const long long r64 = ((M + kRows - 1) / kRows + 255) / 256, r128 = ((M + kWideRows - 1) / kWideRows + 255) / 256;
-  return r64 > 1 && r128 * 11 < r64 * 6;
+// f(std::bool_constant<GELU>) for the FFN activation (exact GELU or ReLU)
+template <class F>
+auto by_gelu(bool gelu, F&& f) {
+  return gelu ? f(std::true_type{}) : f(std::false_type{});
 }
 
-// norm1 -> linear1 -> ReLU -> linear2 -> +residual -> norm2 on fp32 rows X[M][C] (X is clobbered by the generic path)
+// norm1 -> linear1 -> ReLU / GELU -> linear2 -> +residual -> norm2 on fp32 rows X[M][C] (X is clobbered by the generic path), by the
+// plan `pl` of plan_ffn(C, heads, F, M, part != nullptr, rs.hw != 0)
 template <bool BF>
-int run_ffn(float* X, float* out, const LayerPacked& p, long long M, int C, int heads, int F, float* tmp, u16* y16, u16* h16,
-            hipStream_t st, float* part = nullptr /* [F/256][M][256] fp32: enables the chunk-per-workgroup form for few rows */,
+int run_ffn(const FfnPlan& pl, float* X, float* out, const LayerPacked& p, long long M, int C, int F, float* tmp, u16* y16, u16* h16,
+            hipStream_t st, float* part = nullptr /* [F/256][M][256] fp32 partial outputs of the split forms */,
             RowStride rs = RowStride{0, 0} /* X and out rows: frames of rs.hw rows, rs.hw + rs.extra rows apart (fused kernels only) */) {
-  const int oflags = g_out_dtype ? (g_out_dtype == 1 ? kOutF16 : kOutBf16) : 0;
-  if (oflags && !(ffn_kernel_is_fused(C, heads, F) && ffn_lds_bytes(F) <= 160 * 1024))
-    return fail(AXVS_ERR_ARG, "layer_out_dtype: a 16-bit output map needs the fused FFN tier (C = 256, 8 heads, d_ffn a multiple of 256 up to 4096)");
-  if (!oflags && part != nullptr && ffn_split_mode(C, heads, F, M) == 2) {
-    const dim3 sgrid((unsigned)((M + kRows - 1) / kRows), F / 512);
-    if (g_ffn_gelu) {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&ffn_split_kernel<BF, true, 2>))) return rc;
-      hipLaunchKernelGGL((ffn_split_kernel<BF, true, 2>), sgrid, dim3(512), kFfnSplitLds, st, (const float*)X, p.w1, p.b1, p.w2, p.g1, p.be1, part, M, F, rs);
-    } else {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&ffn_split_kernel<BF, false, 2>))) return rc;
-      hipLaunchKernelGGL((ffn_split_kernel<BF, false, 2>), sgrid, dim3(512), kFfnSplitLds, st, (const float*)X, p.w1, p.b1, p.w2, p.g1, p.be1, part, M, F, rs);
-    }
-    hipLaunchKernelGGL(ffn_finish_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const float*)X, (const float*)part, p.b2, p.g1, p.be1,
+  if (pl.refuse) return fail(AXVS_ERR_ARG, "%s", pl.refuse);
+  const unsigned tiles = (unsigned)((M + kRows - 1) / kRows);
+  switch (pl.kind) {
+    case FfnPlan::kSplit2:
+    case FfnPlan::kSplit1: {
+      const int rc = by_gelu(pl.gelu, [&](auto g) {
+        const auto launch = [&](auto cpw) {
+          const auto kern = &ffn_split_kernel<BF, decltype(g)::value, decltype(cpw)::value>;
+          if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
+          hipLaunchKernelGGL(kern, dim3(tiles, F / (256 * decltype(cpw)::value)), dim3(512), kFfnSplitLds, st, (const float*)X, p.w1, p.b1, p.w2, p.g1, p.be1, part, M, F, rs);
+          return (int)AXVS_OK;
+        };
+        return pl.kind == FfnPlan::kSplit2 ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 1>{});
+      });
+      if (rc != AXVS_OK) return rc;
+      hipLaunchKernelGGL(ffn_finish_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const float*)X, (const float*)part, p.b2, p.g1, p.be1,
                          p.g2, p.be2, out, M, F / 256, rs);
-    mark(st, "norm1+ffn+norm2");
-    return AXVS_OK;
-  }
-  if (!oflags && part != nullptr && ffn_split_mode(C, heads, F, M) == 1) {
-    const dim3 sgrid((unsigned)((M + kRows - 1) / kRows), F / 256);
-    if (g_ffn_gelu) {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&ffn_split_kernel<BF, true>))) return rc;
-      hipLaunchKernelGGL((ffn_split_kernel<BF, true>), sgrid, dim3(512), kFfnSplitLds, st, (const float*)X, p.w1, p.b1, p.w2, p.g1, p.be1, part, M, F, rs);
-    } else {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&ffn_split_kernel<BF>))) return rc;
-      hipLaunchKernelGGL((ffn_split_kernel<BF>), sgrid, dim3(512), kFfnSplitLds, st, (const float*)X, p.w1, p.b1, p.w2, p.g1, p.be1, part, M, F, rs);
+      break;
     }
-    hipLaunchKernelGGL(ffn_finish_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const float*)X, (const float*)part, p.b2, p.g1, p.be1,
-                         p.g2, p.be2, out, M, F / 256, rs);
-    mark(st, "norm1+ffn+norm2");
-    return AXVS_OK;
-  }
-  if (!oflags && ffn_kernel_is_fused(C, heads, F) && F <= 2048 && (g_ffn_wide == 1 || (g_ffn_wide == 0 && ffn_wide_pays(M)))) {
-    // more 64-row tiles than CUs: 128-row tiles when that saves a round of the chip (axvs_ffn_wide.h; bit-identical)
-    const size_t lds = ffn_wide_lds_bytes(F);
-    const dim3 wgrid((unsigned)((M + kWideRows - 1) / kWideRows));
-    if (g_ffn_gelu) {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&ffn_wide_kernel<BF, true>))) return rc;
-      hipLaunchKernelGGL((ffn_wide_kernel<BF, true>), wgrid, dim3(512), lds, st, (const float*)X, p.w1, p.b1, p.w2, p.b2, p.g1, p.be1, p.g2, p.be2, out, M, F, rs);
-    } else {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&ffn_wide_kernel<BF>))) return rc;
-      hipLaunchKernelGGL((ffn_wide_kernel<BF>), wgrid, dim3(512), lds, st, (const float*)X, p.w1, p.b1, p.w2, p.b2, p.g1, p.be1, p.g2, p.be2, out, M, F, rs);
+    case FfnPlan::kWide: {
+      const int rc = by_gelu(pl.gelu, [&](auto g) {
+        const auto kern = &ffn_wide_kernel<BF, decltype(g)::value>;
+        if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((M + kWideRows - 1) / kWideRows)), dim3(512), ffn_wide_lds_bytes(F), st, (const float*)X, p.w1, p.b1, p.w2, p.b2,
+                           p.g1, p.be1, p.g2, p.be2, out, M, F, rs);
+        return (int)AXVS_OK;
+      });
+      if (rc != AXVS_OK) return rc;
+      break;
     }
-    mark(st, "norm1+ffn+norm2");
-    return AXVS_OK;
-  }
-  if (ffn_kernel_is_fused(C, heads, F)) {
-    const size_t lds = ffn_lds_bytes(F);
-    if (lds > 160 * 1024) return fail(AXVS_ERR_ARG, "d_ffn=%d too large for the fused FFN kernel", F);
-    const dim3 fgrid((unsigned)((M + kRows - 1) / kRows));
-    if (g_ffn_gelu) {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&ffn_fused_kernel<BF, true>))) return rc;
-      hipLaunchKernelGGL((ffn_fused_kernel<BF, true>), fgrid, dim3(512), lds, st, X, p.w1, p.b1, p.w2, p.b2, p.g1, p.be1, p.g2, p.be2, out, M, F, rs, oflags);
-    } else {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&ffn_fused_kernel<BF>))) return rc;
-      hipLaunchKernelGGL((ffn_fused_kernel<BF>), fgrid, dim3(512), lds, st, X, p.w1, p.b1, p.w2, p.b2, p.g1, p.be1, p.g2, p.be2, out, M, F, rs, oflags);
+    case FfnPlan::kFused: {
+      const int rc = by_gelu(pl.gelu, [&](auto g) {
+        const auto kern = &ffn_fused_kernel<BF, decltype(g)::value>;
+        if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
+        hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), ffn_lds_bytes(F), st, X, p.w1, p.b1, p.w2, p.b2, p.g1, p.be1, p.g2, p.be2, out, M, F, rs, pl.oflags);
+        return (int)AXVS_OK;
+      });
+      if (rc != AXVS_OK) return rc;
+      break;
     }
-    mark(st, "norm1+ffn+norm2");
-    return AXVS_OK;
+    case FfnPlan::kGeneric: {
+      const unsigned lnblocks = (unsigned)((M + 3) / 4);
+      hipLaunchKernelGGL((layernorm_kernel<BF>), dim3(lnblocks), dim3(256), 0, st, X, p.g1, p.be1, tmp, y16, M, C, 1e-5f);
+      mark(st, "norm1");
+      ALoadBlocked<BF> ay{y16, M, (int)M, 0, 1, 1};
+      launch_gemm<BF>(ay, p.w1, EpiBlocked16<BF>{h16, M, p.b1, 1.f, 0, pl.gelu ? 2 : 1}, (int)M, F, C, st);
+      mark(st, "ffn.linear1");
+      ALoadBlocked<BF> ah{h16, M, (int)M, 0, 1, 1};
+      launch_gemm<BF>(ah, p.w2, EpiRowsF32{X, tmp, p.b2, identity_map(M), C, 1.f}, (int)M, C, F, st);
+      mark(st, "ffn.linear2");
+      hipLaunchKernelGGL((layernorm_kernel<BF>), dim3(lnblocks), dim3(256), 0, st, X, p.g2, p.be2, out, (u16*)nullptr, M, C, 1e-5f);
+      mark(st, "norm2");
+      return AXVS_OK;
+    }
   }
-  if (rs.hw) return fail(AXVS_ERR_ARG, "internal: strided frames need the fused FFN kernels");
-  const unsigned lnblocks = (unsigned)((M + 3) / 4);
-  hipLaunchKernelGGL((layernorm_kernel<BF>), dim3(lnblocks), dim3(256), 0, st, X, p.g1, p.be1, tmp, y16, M, C, 1e-5f);
-  mark(st, "norm1");
-  ALoadBlocked<BF> ay{y16, M, (int)M, 0, 1, 1};
-  launch_gemm<BF>(ay, p.w1, EpiBlocked16<BF>{h16, M, p.b1, 1.f, 0, g_ffn_gelu ? 2 : 1}, (int)M, F, C, st);
-  mark(st, "ffn.linear1");
-  ALoadBlocked<BF> ah{h16, M, (int)M, 0, 1, 1};
-  launch_gemm<BF>(ah, p.w2, EpiRowsF32{X, tmp, p.b2, identity_map(M), C, 1.f}, (int)M, C, F, st);
-  mark(st, "ffn.linear2");
-  hipLaunchKernelGGL((layernorm_kernel<BF>), dim3(lnblocks), dim3(256), 0, st, X, p.g2, p.be2, out, (u16*)nullptr, M, C, 1e-5f);
-  mark(st, "norm2");
+  mark(st, "norm1+ffn+norm2");
   return AXVS_OK;
 }
 
@@ -743,7 +728,8 @@ int traj_attn_fwd_t(const float* query, const float* key, const float* value, fl
   // the fused kernels always add a residual: feed zeros here (TrajectoryAttention.forward itself has none)
   if (hipMemsetAsync(w.zeros, 0, (size_t)S * T * L * C * sizeof(float), st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "memset failed");
   RowMap rm{T * L, L, 1, (long long)T * L, L, 1, 0};
-  int rc = run_traj<BF>(query, key, value, nullptr, w.zeros, out, attn, p, w.tw, rm, S, T, L, C, heads, st);
+  const TrajPlan plan = plan_traj(S, T, L, C, heads, attn != nullptr, query == key && value == query, 0, false);
+  int rc = run_traj<BF>(plan, query, key, value, nullptr, w.zeros, out, attn, p, w.tw, rm, S, T, L, C, heads, st);
   return rc != AXVS_OK ? rc : last_launch_status();
 }
 
@@ -775,7 +761,8 @@ int axial_layer_fwd_t(const float* src, const float* pos, float* out, const void
   if (g_out_dtype && (fs != 0 || which == 1))
     return fail(AXVS_ERR_ARG, "layer_out_dtype: a 16-bit output map exists for the whole layer / its width pass on contiguous frames only");
   Carver wc(ws);
-  const AxialWs w = carve_axial_ws(wc, plan_layer(B, T, H, W, C, heads, F, h_attn != nullptr || w_attn != nullptr), sine != nullptr, span, B, T, H, W, C, heads, F);
+  const LayerPlan plan = plan_layer(B, T, H, W, C, heads, F, h_attn != nullptr, w_attn != nullptr, fs != 0);
+  const AxialWs w = carve_axial_ws(wc, plan, sine != nullptr, span, B, T, H, W, C, heads, F);
   float* buf1 = w.buf1;
   float* const scratch1 = buf1;                // fp32 scratch of the generic FFN path (free once the width pass has read the rows)
   const long long sB = fs ? (long long)T * fs : (long long)T * H * W, sT = fs ? fs : (long long)H * W;
@@ -787,7 +774,7 @@ int axial_layer_fwd_t(const float* src, const float* pos, float* out, const void
   PosGen pgh{}, pgw{};
   const PosGen *ph = nullptr, *pw = nullptr;
   if (sine) {
-    if (sine_in_kernel(C, heads)) {
+    if (plan.pos_in_kernel) {
       pgh = make_posgen(*sine, T, H, W, C, 1);
       pgw = make_posgen(*sine, T, H, W, C, 0);
       ph = &pgh;
@@ -808,7 +795,7 @@ int axial_layer_fwd_t(const float* src, const float* pos, float* out, const void
   RowMap rmh{T * H, H, W, sB, sT, W, 1};
   int rc = AXVS_OK;
   if (which != 2) {
-    rc = run_traj<BF>(src, src, src, pos, src, which == 1 ? out : buf1, h_attn, p.th, w.tw, rmh, B * W, T, H, C, heads, st, 1, nullptr, nullptr, nullptr, ph, true);
+    rc = run_traj<BF>(plan.h, src, src, src, pos, src, which == 1 ? out : buf1, h_attn, p.th, w.tw, rmh, B * W, T, H, C, heads, st, 1, nullptr, nullptr, ph);
     if (rc != AXVS_OK) return rc;
     if (which == 1) return last_launch_status();
   } else {
@@ -817,13 +804,12 @@ int axial_layer_fwd_t(const float* src, const float* pos, float* out, const void
   // width pass: sequences (b, h), tokens (t, w)         :206-213
   RowMap rmw{T * W, W, H, sB, sT, 1, W};
   const FfnArgs fa{p.w1, p.w2, p.b1, p.b2, p.g1, p.be1, p.g2, p.be2, F};
-  bool ffn_done = false;
-  rc = run_traj<BF>(buf1, buf1, buf1, pos, buf1, w.buf2, w_attn, p.tw, w.tw, rmw, B * H, T, W, C, heads, st, 2, &fa, out, &ffn_done, pw, true);
+  rc = run_traj<BF>(plan.w, buf1, buf1, buf1, pos, buf1, w.buf2, w_attn, p.tw, w.tw, rmw, B * H, T, W, C, heads, st, 2, &fa, out, pw);
   if (rc != AXVS_OK) return rc;
-  if (ffn_done) return last_launch_status();   // the width-pass kernel ran norm1 -> FFN -> norm2 too and wrote `out`
+  if (plan.w.with_ffn) return last_launch_status();   // the width-pass kernel ran norm1 -> FFN -> norm2 too and wrote `out`
 
   // norm1 -> FFN -> norm2                               :181-185, :217-218
-  int rc2 = run_ffn<BF>(w.buf2, out, p, M, C, heads, F, scratch1, w.y16, w.h16, st, w.ffn_part, fs ? RowStride{H * W, fs - (long long)H * W} : RowStride{0, 0});
+  int rc2 = run_ffn<BF>(plan.ffn, w.buf2, out, p, M, C, F, scratch1, w.y16, w.h16, st, w.ffn_part, fs ? RowStride{H * W, fs - (long long)H * W} : RowStride{0, 0});
   if (rc2 != AXVS_OK) return rc2;
   return last_launch_status();
 }
@@ -843,9 +829,9 @@ int traj_layer_fwd_t(const float* src, const float* pos, float* out, const void*
   mark(st, "begin");
   // src [(B T), HW, C] is already the sequence order 'B (T HW) C': identity row map, T frames of HW keys
   RowMap rm{T * HW, HW, 1, (long long)T * HW, HW, 1, 0};
-  int rc = run_traj<BF>(src, src, src, pos, src, w.f.x, nullptr, pt, w.tw, rm, B, T, HW, C, heads, st, 0);
+  int rc = run_traj<BF>(plan_traj(B, T, HW, C, heads, false, true, 0, false), src, src, src, pos, src, w.f.x, nullptr, pt, w.tw, rm, B, T, HW, C, heads, st, 0);
   if (rc != AXVS_OK) return rc;
-  rc = run_ffn<BF>(w.f.x, out, pf, M, C, heads, F, w.f.tmp, w.f.y16, w.f.h16, st);
+  rc = run_ffn<BF>(plan_ffn(C, heads, F, M, false, false), w.f.x, out, pf, M, C, F, w.f.tmp, w.f.y16, w.f.h16, st);
   return rc != AXVS_OK ? rc : last_launch_status();
 }
 
@@ -925,12 +911,13 @@ int cc_layer_fwd_t(const float* x, float* out, const void* packed, int B, int Q,
   RowMap rm{Tc * Q, Q, 1, (long long)Q * Tc, 1, Tc, 0};
   const unsigned lnblocks = (unsigned)((R + 3) / 4);
   // the post-norm LayerNorm(x + attn(x)) rides in the trajectory kernel's row-wise epilogue when a fused kernel runs
-  const bool ln_in_kernel = !g_generic_only && fused_frames(Tc, R);
+  const TrajPlan plan = plan_traj(B, Tc, Q, 256, 8, false, true, 0, true);
+  const bool ln_in_kernel = plan.tier != TrajPlan::kGeneric;
   if (ln_in_kernel) {
     p.t.post_ln_g = p.norm_w;
     p.t.post_ln_b = p.norm_b;
   }
-  int rc = run_traj<BF>(x, x, x, nullptr, x, ln_in_kernel ? w.t2 : w.t1, nullptr, p.t, w.tw, rm, B, Tc, Q, 256, 8, st, 0, nullptr, nullptr, nullptr, nullptr, true);
+  int rc = run_traj<BF>(plan, x, x, x, nullptr, x, ln_in_kernel ? w.t2 : w.t1, nullptr, p.t, w.tw, rm, B, Tc, Q, 256, 8, st);
   if (rc != AXVS_OK) return rc;
   if (!ln_in_kernel) {
     hipLaunchKernelGGL((layernorm_kernel<BF>), dim3(lnblocks), dim3(256), 0, st, w.t1, p.norm_w, p.norm_b, w.t2, (u16*)nullptr, R, 256,
@@ -1468,7 +1455,7 @@ int axvs_traj_attn_fwd(const float* query, const float* key, const float* value,
 
 static size_t layer_ws_bytes(int B, int T, int H, int W, int C, int heads, int d_ffn, int want_attn_maps, int sine_pos, long long span) {
   Carver c(nullptr);
-  carve_axial_ws(c, plan_layer(B, T, H, W, C, heads, d_ffn, want_attn_maps != 0), sine_pos != 0, span, B, T, H, W, C, heads, d_ffn);
+  carve_axial_ws(c, plan_layer(B, T, H, W, C, heads, d_ffn, want_attn_maps != 0, want_attn_maps != 0), sine_pos != 0, span, B, T, H, W, C, heads, d_ffn);
   return c.off;
 }
 size_t axvs_axial_layer_workspace_bytes_ex(int B, int T, int H, int W, int C, int heads, int d_ffn, int want_attn_maps, int sine_pos) {
@@ -1482,7 +1469,8 @@ size_t axvs_axial_layer_workspace_bytes_strided(int B, int T, int H, int W, int 
 }
 
 int axvs_axial_layer_strided_ok(int C, int heads, int d_ffn) {
-  return !g_generic_only && sine_in_kernel(C, heads) && ffn_kernel_is_fused(C, heads, d_ffn) ? 1 : 0;
+  const LayerPlan plan = plan_layer(1, 1, 16, 16, C, heads, d_ffn, false, false, true);      // (neither answer depends on the shape)
+  return plan.pos_in_kernel && !plan.ffn.refuse ? 1 : 0;
 }
 
 int axvs_axial_layer_fwd_sine3d_strided(const float* src, const AxvsSinePos3D* pos, float* out, const void* packed, int B, int T, int H, int W,
@@ -1612,7 +1600,7 @@ static int ffn_fwd_checked(const float* x, float* out, const LayerPacked& p, lon
   if (hipMemcpyAsync(w.x, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     return fail(AXVS_ERR_LAUNCH, "copy failed");
   g_prof_next = 0;
-  int rc = by_dtype(dtype, [&](auto bf) { return run_ffn<bf()>(w.x, out, p, M, C, heads, d_ffn, w.tmp, w.y16, w.h16, st); });
+  int rc = by_dtype(dtype, [&](auto bf) { return run_ffn<bf()>(plan_ffn(C, heads, d_ffn, M, false, false), w.x, out, p, M, C, d_ffn, w.tmp, w.y16, w.h16, st); });
   return rc != AXVS_OK ? rc : last_launch_status();
 }
 
@@ -1975,7 +1963,7 @@ int axvs_msda_layer_fwd(const float* src, const float* pos, const float* referen
   const long long M = (long long)N * S;
   return by_dtype(dtype, [&](auto bf) {
     if (int rc = msda_fwd_t<bf()>(src, reference_points, ref_dim, src, padding_mask, lv, w.f.x, mp, N, S, S, C, heads, P, w.mws, st, pos, src)) return rc;
-    int rc = run_ffn<bf()>(w.f.x, out, lp, M, C, heads, d_ffn, w.f.tmp, w.f.y16, w.f.h16, st);
+    int rc = run_ffn<bf()>(plan_ffn(C, heads, d_ffn, M, false, false), w.f.x, out, lp, M, C, d_ffn, w.f.tmp, w.f.y16, w.f.h16, st);
     return rc != AXVS_OK ? rc : last_launch_status();
   });
 }

@@ -332,7 +332,7 @@ def test_ragged_axis_lengths_take_the_fused_tier(shape):
     out, _, _ = layer(dev(src), dev(pos))
     names = _stage_names()
     # the FFN rides in the width-pass kernel when that kernel has more than 64 row tiles (more 16-row workgroups than one round of the
-    # chip: kSmallBelow in csrc/axvs_api.hip; 128 until round 5); below that it is its own launch
+    # chip: `with_ffn` of plan_traj in csrc/axvs_api.hip, kSmallBelow; 128 until round 5); below that it is its own launch
     ffn_rides = T <= 4 and B * T * H * W >= 65 * 64
     # (round 5: frames are padded to multiples of 16 rows in the q/k/v row space, so ragged shapes with T <= 4 on 64-row tiles also
     #  take ONE launch per pass -- "h.qkv+traj" / "w.qkv+traj[+ffn]" -- where they used to take "h.qkv_proj" + "h.traj_fused")
