@@ -68,6 +68,13 @@ class AxvsCCHeadGrads(C.Structure):
                 ("act_head_w", _fp), ("act_head_b", _fp), ("pixel_bn", AxvsBNGrads)]
 
 
+class AxvsPanopticCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("N", "K1", "T", "h", "w", "image_h", "image_w", "two_stage", "crop_h", "crop_w", "H", "W",
+                                       "align_corners", "label_divisor")] + \
+               [(n, C.c_double) for n in ("pixel_confidence_threshold", "overlap_threshold", "class_threshold_thing", "class_threshold_stuff",
+                                          "reorder_class_weight", "reorder_mask_weight")]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -245,6 +252,9 @@ SIGNATURES = {
                                [C.c_longlong, C.c_int, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
     "axvs_set_criterion_bwd": (C.c_int, [_fp, C.POINTER(_fp), C.POINTER(_fp), _fp, C.c_int, C.POINTER(C.c_int)] + [C.c_int] * 4 +
                                [C.c_longlong, C.c_int, C.c_int, _fp, C.POINTER(_fp), C.POINTER(_fp), _fp]),
+    "axvs_video_panoptic_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsPanopticCfg)]),
+    "axvs_video_panoptic_table_ints": (C.c_size_t, [C.c_int]),
+    "axvs_video_panoptic_fwd": (C.c_int, [C.POINTER(AxvsPanopticCfg), _fp, _fp, C.c_int] + [_fp] * 6 + [C.c_longlong, _fp]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

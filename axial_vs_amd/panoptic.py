@@ -1,0 +1,147 @@
+"""Video panoptic post-processing on the device: resize, softmax over the mask slots, merge.
+
+Reference: MaXTron_Video-kMaX/maxtron_deeplab/maxtron_cc_model.py:442-458 (`video_seg_post_processing`: `F.interpolate` of the
+[N, T, h, w] mask logits to the padded image size, a crop, and for `scale_factor < 1` a second `F.interpolate`) and :460-571
+(`panoptic_mask_inference`: softmax over the N slots at full resolution, threshold, per-slot areas and mean scores, `argsort`, a
+Python loop over the slots with three `.item()` synchronisations each, a relabelling loop); maxtron_wc_model.py:440-551 is the same.
+Here both run in libaxvs.so in three launches (axial_vs_amd/csrc/axvs_panoptic.h); the fp32 [N, T, H, W] tensor -- 472 MB per frame
+at N = 128 and 720 x 1280 -- never exists, so neither `retry_if_cuda_oom` nor the `.cpu()` of the video-wise path is needed.
+
+Deviations from the reference, both on inputs it leaves open or gets wrong:
+  * slots with EQUAL reorder scores are merged in slot order (the lower index first); the reference's `argsort` leaves ties open;
+  * areas are counted as exact integers and compared as such; the reference's fp32 `.sum()` is inexact above 2^24 pixels per slot.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+import torch.nn.functional as F
+from torch import Tensor
+
+from . import _lib
+from .matching import _mask_dtype
+from .modules import _guarded, _stream, _workspace
+
+_id_tables: Dict[tuple, Tuple[Tensor, Tensor, Tensor]] = {}
+
+
+def _class_tables(thing_ids: Sequence[int], stuff_ids: Sequence[int], K: int, device: torch.device) -> Tuple[Tensor, Tensor, Tensor]:
+    """int32 [K] on the device: whether contiguous class id k is a thing (`k in thing_ids`), and its category id
+    (`sorted(thing_ids + stuff_ids)[k]`, maxtron_cc_model.py:491-494).  Cached: the lists are a model's metadata."""
+    key = (tuple(thing_ids), tuple(stuff_ids), K, str(device))
+    hit = _id_tables.get(key)
+    if hit is None:
+        all_ids = sorted(list(thing_ids) + list(stuff_ids))
+        if len(all_ids) < K:
+            raise RuntimeError(f"axial_vs_amd: mask_cls has {K} classes but thing_ids + stuff_ids name only {len(all_ids)}")
+        things = set(thing_ids)
+        host = torch.tensor([[int(k in things) for k in range(K)], [int(c) for c in all_ids[:K]]], dtype=torch.int32).pin_memory()
+        both = host.to(device, non_blocking=True)           # pinned + non_blocking: the upload does not synchronise either
+        hit = (both[0], both[1], host)                      # (the pinned source stays alive with the cache entry)
+        _id_tables[key] = hit
+    return hit
+
+
+def _tables(itab: Tensor, ftab: Tensor, N: int) -> Dict[str, Tensor]:
+    a = itab[4:].view(7, N)
+    return {"counts": itab[:4],                   # accepted things, segments, contested pixels, 0
+            "final_id": a[0], "rank": a[1], "label": a[2], "area": a[3],             # per slot; final_id -1: not painted
+            "thing_slot": a[4], "thing_category": a[5], "thing_ii": a[6],            # the accepted things in acceptance order, tail -1
+            "class_score": ftab[0], "mean_mask_score": ftab[1], "reorder_score": ftab[2]}
+
+
+@_guarded
+@torch.no_grad()
+def video_panoptic_inference(mask_cls: Tensor, mask_pred: Tensor, mask_embedding: Optional[Tensor], *, thing_ids: Sequence[int],
+                             stuff_ids: Sequence[int], label_divisor: int, class_threshold_thing: float, class_threshold_stuff: float,
+                             pixel_confidence_threshold: float, overlap_threshold: float, reorder_class_weight: float,
+                             reorder_mask_weight: float, align_corners: bool, image_size: Tuple[int, int], scale_factor: float,
+                             scaled_size: Tuple[int, int], out_size: Tuple[int, int], return_tables: bool = False):
+    """`video_seg_post_processing(mask_pred, align_corners, *image_size, scale_factor, *scaled_size, *out_size)` followed by
+    `panoptic_mask_inference(mask_cls, ., mask_embedding)`: returns the reference's pair `(panoptic_seg, dic_cat_idemb)` --
+    int32 [T, H, W] on the device (category_id * label_divisor + ii for things, category_id for stuff, -1 unassigned) and, per
+    thing category, the L2-normalised embeddings of its accepted slots in `ii` order.
+
+    mask_cls [N, K + 1], mask_pred [N, T, h, w] (fp32, fp16 or bf16; arithmetic in fp32), mask_embedding [N, C]: GPU tensors, there
+    is no CPU fallback.  N <= 512; pixel_confidence_threshold in (0.25, 1).  Slots with equal reorder scores merge in slot order
+    (ties go to the lower index).  Building the dict reads the slot table back: ONE synchronisation, at the end.
+    `return_tables=True` returns `(panoptic_seg, tables)` instead -- device tensors (`final_id`, `rank`, `label`, `area` per slot;
+    `thing_slot`, `thing_category`, `thing_ii` in acceptance order, tail -1; `counts`; the fp32 scores) -- and does not synchronise."""
+    if not mask_cls.is_cuda or not mask_pred.is_cuda or (mask_embedding is not None and not mask_embedding.is_cuda):
+        raise RuntimeError(f"axial_vs_amd: mask_cls / mask_pred / mask_embedding must be GPU tensors (got {mask_cls.device}, {mask_pred.device}); "
+                           "there is no CPU fallback")
+    if mask_pred.dim() != 4 or mask_cls.dim() != 2 or mask_cls.shape[0] != mask_pred.shape[0]:
+        raise RuntimeError(f"mask_pred {tuple(mask_pred.shape)} must be [N, T, h, w] and mask_cls {tuple(mask_cls.shape)} [N, K + 1]")
+    if mask_pred.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        mask_pred = mask_pred.float()
+    mask_pred, mask_cls = mask_pred.contiguous(), mask_cls.float().contiguous()
+    dev = mask_pred.device
+    N, T, h, w = mask_pred.shape
+    K1 = mask_cls.shape[1]
+    image_h, image_w = int(image_size[0]), int(image_size[1])
+    two = bool(scale_factor < 1)
+    if two:               # mask[:, :, :new_height, :new_width], then the second resize to (height, width)
+        crop_h, crop_w = min(int(scaled_size[0]), image_h), min(int(scaled_size[1]), image_w)
+        H, W = int(out_size[0]), int(out_size[1])
+    else:                 # mask[:, :, :height, :width]
+        crop_h = crop_w = 0
+        H, W = min(int(out_size[0]), image_h), min(int(out_size[1]), image_w)
+    cfg = _lib.AxvsPanopticCfg(N=N, K1=K1, T=T, h=h, w=w, image_h=image_h, image_w=image_w, two_stage=int(two), crop_h=crop_h, crop_w=crop_w,
+                               H=H, W=W, align_corners=int(bool(align_corners)), label_divisor=int(label_divisor),
+                               pixel_confidence_threshold=float(pixel_confidence_threshold), overlap_threshold=float(overlap_threshold),
+                               class_threshold_thing=float(class_threshold_thing), class_threshold_stuff=float(class_threshold_stuff),
+                               reorder_class_weight=float(reorder_class_weight), reorder_mask_weight=float(reorder_mask_weight))
+    L = _lib.lib()
+    need = L.axvs_video_panoptic_workspace_bytes(C.byref(cfg))
+    if need == 0:
+        _lib.check(-1, "axvs_video_panoptic_workspace_bytes")
+    is_thing, cat_id, _ = _class_tables(thing_ids, stuff_ids, K1 - 1, dev)
+    st = _stream(dev)
+    ws = _workspace(dev, need, st)
+    seg = torch.empty(T, H, W, dtype=torch.int32, device=dev)
+    itab = torch.empty(L.axvs_video_panoptic_table_ints(N), dtype=torch.int32, device=dev)
+    ftab = torch.empty(3, N, dtype=torch.float32, device=dev)
+    _lib.check(L.axvs_video_panoptic_fwd(C.byref(cfg), mask_cls.data_ptr(), mask_pred.data_ptr(), _mask_dtype(mask_pred), is_thing.data_ptr(),
+                                         cat_id.data_ptr(), seg.data_ptr(), itab.data_ptr(), ftab.data_ptr(), ws.data_ptr(), ws.numel(), st),
+               "axvs_video_panoptic_fwd")
+    tables = _tables(itab, ftab, N)
+    if return_tables:
+        return seg, tables
+    host = itab.cpu()                                       # the one synchronisation
+    n = int(host[0])
+    things = host[4:].view(7, N)[4:, :n]
+    dic_cat_idemb: Dict[int, List[Tensor]] = {}
+    if n and mask_embedding is not None:
+        emb = F.normalize(mask_embedding[tables["thing_slot"][:n].long()], p=2, dim=1)
+        for j, cat in enumerate(things[1].tolist()):
+            dic_cat_idemb.setdefault(cat, []).append(emb[j])
+    return seg, dic_cat_idemb
+
+
+class VideoPanopticPostProcessor:
+    """Drop-in for the pair `video_seg_post_processing` + `panoptic_mask_inference` of MaXTronCCDeepLab / MaXTronWCDeepLab:
+    constructed from the model's metadata ids and thresholds, called with the arguments the reference passes to
+    `video_seg_post_processing` after the three tensors of `panoptic_mask_inference`.  Returns `(panoptic_seg, dic_cat_idemb)`."""
+
+    def __init__(self, thing_ids: Sequence[int], stuff_ids: Sequence[int], label_divisor: int, class_threshold_thing: float,
+                 class_threshold_stuff: float, pixel_confidence_threshold: float, overlap_threshold: float, reorder_class_weight: float,
+                 reorder_mask_weight: float):
+        self.kw = dict(thing_ids=list(thing_ids), stuff_ids=list(stuff_ids), label_divisor=label_divisor, class_threshold_thing=class_threshold_thing,
+                       class_threshold_stuff=class_threshold_stuff, pixel_confidence_threshold=pixel_confidence_threshold,
+                       overlap_threshold=overlap_threshold, reorder_class_weight=reorder_class_weight, reorder_mask_weight=reorder_mask_weight)
+
+    @classmethod
+    def from_model(cls, model) -> "VideoPanopticPostProcessor":
+        """from a reference meta-architecture (its `metadata` and threshold attributes, maxtron_cc_model.py:460-494)"""
+        md = model.metadata
+        return cls(list(md.thing_dataset_id_to_contiguous_id.values()), list(md.stuff_dataset_id_to_contiguous_id.values()), md.label_divisor,
+                   model.class_threshold_thing, model.class_threshold_stuff, model.pixel_confidence_threshold, model.overlap_threshold,
+                   model.reorder_class_weight, model.reorder_mask_weight)
+
+    def __call__(self, mask_cls: Tensor, mask_pred: Tensor, mask_embedding: Optional[Tensor], align_corners: bool, image_h: int, image_w: int,
+                 scale_factor: float, scaled_h: int, scaled_w: int, height: int, width: int, return_tables: bool = False):
+        return video_panoptic_inference(mask_cls, mask_pred, mask_embedding, align_corners=align_corners, image_size=(image_h, image_w),
+                                        scale_factor=scale_factor, scaled_size=(scaled_h, scaled_w), out_size=(height, width),
+                                        return_tables=return_tables, **self.kw)

@@ -546,6 +546,40 @@ int axvs_set_criterion_bwd(const float* grad_losses, const float* const* pred_ma
                            int target_dtype, const int* m_per_video, int L, int B, int N, int K1, long long P, int masking_void_pixel,
                            int share_final_matching, const void* saved, float* const* d_pred_masks, float* const* d_pred_logits, void* stream);
 
+/* ---- Video panoptic post-processing (maxtron_cc_model.py:442-571, maxtron_wc_model.py:440-551: `video_seg_post_processing` +
+ *      `panoptic_mask_inference`) on the device, in three launches and without the [N,T,H,W] tensor: per output pixel the bilinearly
+ *      resized logits of the N slots (one stage + crop, or two stages with the crop between them; torch's align_corners True / False
+ *      index arithmetic), their softmax and the slots above pixel_confidence_threshold; then, in one workgroup, the class softmax, the
+ *      reorder (descending; EQUAL reorder scores go to the lower slot index, where the reference's argsort leaves ties open) and the
+ *      reference's sequential merge; then the relabelled map.  Areas are exact integers (the reference's fp32 sums are inexact above
+ *      2^24 pixels per slot) and the score sums are exact fixed-point integers: results are bit-equal from run to run.
+ *        mask_cls     fp32 [N][K1] (K1 = K + 1: the void class last)
+ *        mask_pred    [N][T][h][w], mask_dtype AXVS_F16 / AXVS_BF16 / AXVS_F32 (arithmetic in fp32)
+ *        is_thing, cat_id   DEVICE int32 [K]: per contiguous class id whether it is a thing, and its category id
+ *                     (sorted(thing_ids + stuff_ids)[label] in the reference)
+ *        out_map      int32 [T][H][W]: cat_id * label_divisor + ii for things (ii: acceptance order per category), cat_id for stuff, -1 unassigned
+ *        slot_ints    int32 [axvs_video_panoptic_table_ints(N)] = 4 + 7 N: {accepted things, segments, contested pixels, 0}, then per slot
+ *                     final id (-1: not painted), merge rank, class label, area; then the accepted things in acceptance order: slot, category id, ii
+ *                     (tail -1)
+ *        slot_floats  fp32 [3][N]: class score, mean mask score over the area, reorder score
+ *      cfg: the stage-1 resize goes to image_h x image_w; with two_stage the crop [:crop_h, :crop_w] of it is resized to H x W, otherwise
+ *      the map is its crop [:H, :W].  N <= 512, any K >= 1, T*H*W < 2^31, pixel_confidence_threshold in (0.25, 1) (at most three slots
+ *      pass per pixel); otherwise AXVS_ERR_ARG.  Arguments are checked before anything is launched; workspace_bytes travels as long long. */
+typedef struct AxvsPanopticCfg {
+  int N, K1, T, h, w;
+  int image_h, image_w;
+  int two_stage, crop_h, crop_w;
+  int H, W;
+  int align_corners, label_divisor;
+  double pixel_confidence_threshold, overlap_threshold, class_threshold_thing, class_threshold_stuff;
+  double reorder_class_weight, reorder_mask_weight;
+} AxvsPanopticCfg;
+size_t axvs_video_panoptic_workspace_bytes(const AxvsPanopticCfg* cfg);
+size_t axvs_video_panoptic_table_ints(int N);
+int axvs_video_panoptic_fwd(const AxvsPanopticCfg* cfg, const float* mask_cls, const void* mask_pred, int mask_dtype, const int* is_thing,
+                            const int* cat_id, int* out_map, int* slot_ints, float* slot_floats, void* workspace, long long workspace_bytes,
+                            void* stream);
+
 /* ---- PositionEmbeddingSine3D.forward(x, mask=None) in channels-last form
  *      WC/pos_embeddings.py:86-130: pos fp32 [B,T,H,W,C], C = 2*num_pos_feats. */
 int axvs_pos3d(float* pos, int B, int T, int H, int W, int C, float temperature, int normalize, float scale,
