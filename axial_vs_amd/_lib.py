@@ -75,6 +75,11 @@ class AxvsPanopticCfg(C.Structure):
                                           "reorder_class_weight", "reorder_mask_weight")]
 
 
+class AxvsVisCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("Q", "K1", "T", "num_frames", "h", "w", "image_h", "image_w", "crop_h", "crop_w", "H", "W", "num_things",
+                                       "k_cand", "k_out", "mask_bits")]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -255,6 +260,8 @@ SIGNATURES = {
     "axvs_video_panoptic_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsPanopticCfg)]),
     "axvs_video_panoptic_table_ints": (C.c_size_t, [C.c_int]),
     "axvs_video_panoptic_fwd": (C.c_int, [C.POINTER(AxvsPanopticCfg), _fp, _fp, C.c_int] + [_fp] * 6 + [C.c_longlong, _fp]),
+    "axvs_video_instance_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsVisCfg)]),
+    "axvs_video_instance_fwd": (C.c_int, [C.POINTER(AxvsVisCfg), _fp, _fp, C.c_int] + [_fp] * 4 + [C.c_longlong, _fp]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

@@ -580,6 +580,37 @@ int axvs_video_panoptic_fwd(const AxvsPanopticCfg* cfg, const float* mask_cls, c
                             const int* cat_id, int* out_map, int* slot_ints, float* slot_floats, void* workspace, long long workspace_bytes,
                             void* stream);
 
+/* ---- Video instance post-processing for Tube-Link VIS (mask2former_video_cc_head.py:1026-1034: the whole-video resize to
+ *      batch_input_shape; maskformer_fusion_head.py:405-462: `instance_postprocess` per frame with its second resize to ori_shape;
+ *      mask/utils.py:68-89: `mask2bbox`; mask2former_vis_video.py:184-193: the per-frame top 30) on the device, in four kernels and one memset and
+ *      without a resized [T,Q,H,W] tensor.  Both resizes are bilinear with align_corners=False.
+ *        mask_cls     fp32 [Q][K1] (K1 = C + 1: the void class last)
+ *        mask_pred    [T][Q][h][w], mask_dtype AXVS_F16 / AXVS_BF16 / AXVS_F32 (arithmetic in fp32); frames num_frames..T-1 are not read
+ *        out_masks    mask_bits 0: uint8 [num_frames][k_out][H][W]; mask_bits 1: 64-bit words [num_frames][k_out][H][ceil(W/64)], bit i of
+ *                     word j = pixel 64 j + i of the row, the bits past W zero.  Rows past a frame's count are empty masks.
+ *        table_ints   int32, in this order: {candidates kept, queries referenced}; candidate query [k_cand], candidate label [k_cand]
+ *                     (tail -1); area [num_frames][k_cand] (tail -1); count [num_frames]; then per frame the selected rows, tail -1:
+ *                     track id [num_frames][k_out] (1 + candidate position), label [.][k_out], query [.][k_out]
+ *        table_floats fp32, in this order: candidate class score [k_cand]; mask score [num_frames][k_cand]; detection score [.][k_cand];
+ *                     candidate box [.][k_cand][4]; selected box [num_frames][k_out][4]; selected score [num_frames][k_out] (tails -1)
+ *      Candidates: the k_cand largest softmax scores over Q x C in DESCENDING order, equal scores to the lower flat index (the
+ *      reference's topk(sorted=False) leaves the order open), then those with label < num_things, order kept.  Per frame and candidate:
+ *      binary = resized logit > 0, area (exact integer), mask score = sum(sigmoid * binary) / (area + 1e-6) from an exact fixed-point
+ *      sum (bit-equal from run to run), detection score = class score * mask score, box = {xmin, ymin, xmax + 1, ymax + 1} or zeros.
+ *      Selection: the k_out largest detection scores, equal scores to the lower candidate position.
+ *      Q <= 512, Q*C <= 2^17, 1 <= k_out <= k_cand <= min(Q*C, 256), 1 <= num_frames <= T, img_shape (crop) inside batch input (image),
+ *      H*W < 2^31; otherwise AXVS_ERR_ARG.  Arguments are checked before anything is launched; workspace_bytes travels as long long. */
+typedef struct AxvsVisCfg {
+  int Q, K1, T, num_frames, h, w;
+  int image_h, image_w;      /* batch_input_shape */
+  int crop_h, crop_w;        /* img_shape */
+  int H, W;                  /* ori_shape */
+  int num_things, k_cand, k_out, mask_bits;
+} AxvsVisCfg;
+size_t axvs_video_instance_workspace_bytes(const AxvsVisCfg* cfg);
+int axvs_video_instance_fwd(const AxvsVisCfg* cfg, const float* mask_cls, const void* mask_pred, int mask_dtype, void* out_masks,
+                            int* table_ints, float* table_floats, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- PositionEmbeddingSine3D.forward(x, mask=None) in channels-last form
  *      WC/pos_embeddings.py:86-130: pos fp32 [B,T,H,W,C], C = 2*num_pos_feats. */
 int axvs_pos3d(float* pos, int B, int T, int H, int W, int C, float temperature, int normalize, float scale,
