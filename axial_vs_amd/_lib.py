@@ -80,6 +80,11 @@ class AxvsVisCfg(C.Structure):
                                        "k_cand", "k_out", "mask_bits")]
 
 
+class AxvsTLLossCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("L", "B", "Q", "K1", "T", "h", "w", "Hg", "Wg", "num_points", "num_cand", "num_kept", "target_dtype")] + \
+               [(n, C.c_float) for n in ("cost_cls", "cost_mask", "cost_dice", "loss_cls", "loss_mask", "loss_dice", "dice_eps")]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -257,6 +262,12 @@ SIGNATURES = {
                                [C.c_longlong, C.c_int, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
     "axvs_set_criterion_bwd": (C.c_int, [_fp, C.POINTER(_fp), C.POINTER(_fp), _fp, C.c_int, C.POINTER(C.c_int)] + [C.c_int] * 4 +
                                [C.c_longlong, C.c_int, C.c_int, _fp, C.POINTER(_fp), C.POINTER(_fp), _fp]),
+    "axvs_tl_loss_saved_bytes": (C.c_size_t, [C.POINTER(AxvsTLLossCfg), C.POINTER(C.c_int)]),
+    "axvs_tl_loss_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsTLLossCfg), C.POINTER(C.c_int)]),
+    "axvs_tl_loss_fwd": (C.c_int, [C.POINTER(AxvsTLLossCfg), C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, C.POINTER(C.c_int)] + [_fp] * 12 +
+                         [C.c_longlong, _fp]),
+    "axvs_tl_loss_bwd": (C.c_int, [C.POINTER(AxvsTLLossCfg), _fp, C.POINTER(_fp), C.POINTER(_fp), _fp, C.POINTER(C.c_int), _fp, _fp, _fp,
+                                   C.POINTER(_fp), C.POINTER(_fp), _fp]),
     "axvs_video_panoptic_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsPanopticCfg)]),
     "axvs_video_panoptic_table_ints": (C.c_size_t, [C.c_int]),
     "axvs_video_panoptic_fwd": (C.c_int, [C.POINTER(AxvsPanopticCfg), _fp, _fp, C.c_int] + [_fp] * 6 + [C.c_longlong, _fp]),

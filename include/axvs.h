@@ -546,6 +546,50 @@ int axvs_set_criterion_bwd(const float* grad_losses, const float* const* pred_ma
                            int target_dtype, const int* m_per_video, int L, int B, int N, int K1, long long P, int masking_void_pixel,
                            int share_final_matching, const void* saved, float* const* d_pred_masks, float* const* d_pred_logits, void* stream);
 
+/* ---- Tube-Link's point-sampled training loss (Mask2FormerVideoCCHeadTube.loss / loss_single / _get_target_single,
+ *      models/video/tube_link_vis/mask2former_video_cc_head.py:519-694, with mmdet's ClassificationCost / CrossEntropyLossCost / DiceCost,
+ *      MaskHungarianAssigner, get_uncertain_point_coords_with_randomness, CrossEntropyLoss and the naive DiceLoss): matching cost at
+ *      num_points shared points, the device assignment, the k most uncertain of S candidate points per matched pair, the three losses
+ *      and their gradients for all (layer, video) problems of a step.  Forward: 5 launches (one more per 256 problems beyond the first
+ *      256), backward: 3; one stream, no host synchronisation, no copy to the host, no floating-point atomics (two runs give the same
+ *      bits).  The random coordinates are INPUTS, so every shape is known on the host before anything runs.
+ *        cls_scores / mask_preds   HOST arrays of L device pointers: fp32 [B][Q][K1] and fp32 [B][T][Q][h][w] (16-byte aligned).  The "long
+ *                                  image" of a query has T*h rows: row r is line r % h of frame r / h, and a sample near a frame boundary
+ *                                  blends the two frames, as the reference's flatten(1, 2) does
+ *        targets, labels           uint8 / fp32 [sum M_b][T][Hg][Wg] and int64 [sum M_b], concatenated over the videos (a label outside
+ *                                  0..K-1 is clamped); m_per_video: HOST int [B]
+ *        class_weight              fp32 [K1];  num_total_masks: DEVICE fp32 scalar, max(reduce_mean(G), 1) in the reference
+ *        match_coords              fp32 [L][B][num_points][2], cand_coords [L][G][S][2], rand_coords [L][G][num_points - k][2] in [0, 1):
+ *                                  (x along w, y along the T*h rows); G = sum_b min(Q, M_b); pair g of a layer is the g-th matched
+ *                                  query in (video, query) order
+ *        losses                    fp32 [L][3]: loss_cls, loss_mask, loss_dice of every layer, times their loss weights
+ *        rows, cols                int64 [L*B][min(Q, M_max)] in the layout of axvs_linear_sum_assignment_rect
+ *        cost                      NULL, or fp32 [L*B][Q][M_max]: the matching cost
+ *        sel_idx                   NULL, or int32 [L][G][k]: the kept candidates of every pair, in increasing order.  The k candidates with
+ *                                  the smallest |logit| are kept; among EQUAL |logit| the lower index (the reference's topk leaves ties open)
+ *        saved                     axvs_tl_loss_saved_bytes bytes the forward writes and the backward reads: O(L * G * num_points)
+ *        grad_losses               DEVICE fp32 [L][3];  d_cls_scores / d_mask_preds: HOST arrays of L device pointers shaped like the inputs,
+ *                                  a NULL entry skips that gradient.  Unmatched queries get exactly zero
+ *      L <= 16, B <= 64, Q <= 512, M_b <= 512, num_points <= 16384, S <= 65536, k <= min(num_points, S), T*h <= 8192; otherwise AXVS_ERR_ARG
+ *      (the size functions return 0 and axvs_last_error() names the bound). */
+typedef struct AxvsTLLossCfg {
+  int L, B, Q, K1, T, h, w, Hg, Wg;
+  int num_points, num_cand, num_kept;      /* P, S = int(P * oversample_ratio), k = int(importance_sample_ratio * P) */
+  int target_dtype;                        /* AXVS_U8 or AXVS_F32 */
+  float cost_cls, cost_mask, cost_dice;    /* weights of the three matching costs (2, 5, 5) */
+  float loss_cls, loss_mask, loss_dice;    /* weights of the three losses (2, 5, 5) */
+  float dice_eps;                          /* eps of DiceCost and DiceLoss (1) */
+} AxvsTLLossCfg;
+size_t axvs_tl_loss_saved_bytes(const AxvsTLLossCfg* cfg, const int* m_per_video);
+size_t axvs_tl_loss_workspace_bytes(const AxvsTLLossCfg* cfg, const int* m_per_video);
+int axvs_tl_loss_fwd(const AxvsTLLossCfg* cfg, const float* const* cls_scores, const float* const* mask_preds, const void* targets,
+                     const long long* labels, const int* m_per_video, const float* class_weight, const float* match_coords,
+                     const float* cand_coords, const float* rand_coords, const float* num_total_masks, float* losses, long long* rows,
+                     long long* cols, float* cost, int* sel_idx, void* saved, void* workspace, long long workspace_bytes, void* stream);
+int axvs_tl_loss_bwd(const AxvsTLLossCfg* cfg, const float* grad_losses, const float* const* cls_scores, const float* const* mask_preds,
+                     const void* targets, const int* m_per_video, const float* class_weight, const float* num_total_masks, const void* saved,
+                     float* const* d_cls_scores, float* const* d_mask_preds, void* stream);
+
 /* ---- Video panoptic post-processing (maxtron_cc_model.py:442-571, maxtron_wc_model.py:440-551: `video_seg_post_processing` +
  *      `panoptic_mask_inference`) on the device, in three launches and without the [N,T,H,W] tensor: per output pixel the bilinearly
  *      resized logits of the N slots (one stage + crop, or two stages with the crop between them; torch's align_corners True / False
