@@ -107,6 +107,22 @@ class AxvsTLHeadTrainCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "Q", "Tc", "frames_per_clip", "h", "w", "K1", "Cm", "num_layers")]
 
 
+class AxvsM2fLayerParams(C.Structure):
+    _fields_ = [(n, _fp) for n in ("cross_in_w", "cross_in_b", "cross_out_w", "cross_out_b", "norm0_w", "norm0_b", "self_in_w", "self_in_b",
+                                   "self_out_w", "self_out_b", "norm1_w", "norm1_b", "ffn1_w", "ffn1_b", "ffn2_w", "ffn2_b", "norm2_w", "norm2_b")]
+
+
+class AxvsM2fHeadParams(C.Structure):
+    _fields_ = [(n, _fp) for n in ("post_norm_w", "post_norm_b", "query_embed", "query_feat", "level_embed")] + \
+               [("mask_embed_w", _fp * 3), ("mask_embed_b", _fp * 3), ("cls_embed_w", _fp), ("cls_embed_b", _fp)]
+
+
+class AxvsM2fCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("N", "Q", "T", "C", "heads", "ffn", "num_layers", "num_levels", "K1", "h", "w")] + \
+               [("lh", C.c_int * 3), ("lw", C.c_int * 3), ("return_predictions", C.c_int), ("pos_normalize", C.c_int),
+                ("pos_temperature", C.c_float), ("pos_scale", C.c_float)]
+
+
 class AxvsMsdaParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
                                    "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
@@ -273,6 +289,14 @@ SIGNATURES = {
     "axvs_video_panoptic_fwd": (C.c_int, [C.POINTER(AxvsPanopticCfg), _fp, _fp, C.c_int] + [_fp] * 6 + [C.c_longlong, _fp]),
     "axvs_video_instance_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsVisCfg)]),
     "axvs_video_instance_fwd": (C.c_int, [C.POINTER(AxvsVisCfg), _fp, _fp, C.c_int] + [_fp] * 4 + [C.c_longlong, _fp]),
+    "axvs_m2f_decoder_packed_bytes": (C.c_size_t, [C.POINTER(AxvsM2fCfg)]),
+    "axvs_m2f_decoder_pack": (C.c_int, [C.POINTER(AxvsM2fLayerParams), C.POINTER(AxvsM2fHeadParams), C.POINTER(AxvsM2fCfg), _fp, _fp]),
+    "axvs_m2f_decoder_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsM2fCfg)]),
+    "axvs_m2f_decoder_fwd": (C.c_int, [C.POINTER(AxvsM2fCfg), _fp, _fp, C.POINTER(_fp)] + [_fp] * 6 + [C.c_longlong, _fp]),
+    "axvs_m2f_attn_mask_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsM2fCfg), C.c_int]),
+    "axvs_m2f_attn_mask_fwd": (C.c_int, [C.POINTER(AxvsM2fCfg), _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
+    "axvs_m2f_layer_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsM2fCfg), C.c_int]),
+    "axvs_m2f_layer_fwd": (C.c_int, [C.POINTER(AxvsM2fCfg), _fp, C.c_int] + [_fp] * 6 + [C.c_longlong, _fp]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

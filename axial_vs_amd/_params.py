@@ -120,6 +120,22 @@ def cc_module_params(mod) -> List[Tensor]:
     return cc_chain_params(mod, mod.num_layers) + cc_head_params(mod)
 
 
+def m2f_layer_params(layer) -> List[Tensor]:
+    """AxvsM2fLayerParams of one DetrTransformerDecoderLayer of the per-clip query decoder: cross-attention, norm, self-attention, norm,
+    FFN, norm."""
+    ca, sa, fcs = layer.attentions[0].attn, layer.attentions[1].attn, layer.ffns[0].layers
+    return ([ca.in_proj_weight, ca.in_proj_bias] + _wb(ca.out_proj, layer.norms[0]) + [sa.in_proj_weight, sa.in_proj_bias]
+            + _wb(sa.out_proj, layer.norms[1], fcs[0][0], fcs[1], layer.norms[2]))
+
+
+def m2f_head_params(mod) -> List[Tensor]:
+    """AxvsM2fHeadParams of a TubeLinkClipDecoder: post_norm, the three embeddings, the mask_embed weights, then their biases, cls_embed."""
+    me = mod.mask_embed
+    return (_wb(mod.transformer_decoder.post_norm) + [mod.query_embed.weight, mod.query_feat.weight, mod.level_embed.weight,
+                                                      me[0].weight, me[2].weight, me[4].weight, me[0].bias, me[2].bias, me[4].bias]
+            + _wb(mod.cls_embed))
+
+
 def tl_head_params(mod) -> List[Tensor]:
     """AxvsTLHeadParams of a TubeLinkCrossClipHead: post_norm, activation_proj, cls_embed, the three mask_embed weights, then their
     three biases."""

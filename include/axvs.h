@@ -833,6 +833,55 @@ int axvs_tl_heads_train_bwd(const float* d_cls, const float* d_masks, const floa
                             const AxvsTLHeadGrads* grads, float* d_queries, float* d_mask_feature, const AxvsTLHeadTrainCfg* cfg, void* saved,
                             size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Tube-Link's per-clip masked-attention query decoder (Mask2FormerVideoCCHeadTube.forward: the nine DetrTransformerDecoderLayers
+ * with forward_head_video in front of each; frozen and in eval() in training and inference alike, so forward only) --------------------
+ * All tensors fp32.  N (video, clip) pairs are independent and may be stacked.  Every contraction is fp32-accurate: the Linear layers on
+ * the three-piece split-precision GEMM, the mask logits and the attention on f32-input MFMAs.  Equal inputs give equal bits.
+ * Bounds (AXVS_ERR_ARG outside them): C 256, 8 heads, FFN 2048, 3 levels, 1..16 layers, Q <= 256, T <= 16, T*lh*lw < 2^24 per level,
+ * h*w < 2^24, N <= 4095.  Layer i attends to level i % 3.
+ * Parameters: a layer's tensors under the reference's names -- attentions.0 = cross-attention (in_proj [3C,C] / [3C], out_proj),
+ * norms.0, attentions.1 = self-attention, norms.1, ffns.0.layers.0.0 [F,C], ffns.0.layers.1 [C,F], norms.2. */
+typedef struct AxvsM2fLayerParams {
+  const float *cross_in_w, *cross_in_b, *cross_out_w, *cross_out_b, *norm0_w, *norm0_b;
+  const float *self_in_w, *self_in_b, *self_out_w, *self_out_b, *norm1_w, *norm1_b;
+  const float *ffn1_w, *ffn1_b, *ffn2_w, *ffn2_b, *norm2_w, *norm2_b;
+} AxvsM2fLayerParams;
+/* query_embed / query_feat [Q,C]; level_embed [3,C]; mask_embed: three Linear layers [C,C]; cls_embed [K1,C] */
+typedef struct AxvsM2fHeadParams {
+  const float *post_norm_w, *post_norm_b, *query_embed, *query_feat, *level_embed;
+  const float* mask_embed_w[3];
+  const float* mask_embed_b[3];
+  const float *cls_embed_w, *cls_embed_b;
+} AxvsM2fHeadParams;
+/* mask features [N,T,C,h,w]; level l memory [N,T,C,lh[l],lw[l]] (low to high resolution); K1 = classes + 1;
+ * pos_*: SinePositionalEncoding3D(num_feats = C/2) -- temperature, normalize, scale */
+typedef struct AxvsM2fCfg {
+  int N, Q, T, C, heads, ffn, num_layers, num_levels, K1, h, w;
+  int lh[3], lw[3];
+  int return_predictions, pos_normalize;
+  float pos_temperature, pos_scale;
+} AxvsM2fCfg;
+size_t axvs_m2f_decoder_packed_bytes(const AxvsM2fCfg* cfg);      /* depends on Q, K1, num_layers only; 0: cfg refused (axvs_last_error) */
+/* layers: num_layers structs.  Copies on `stream`; the parameter tensors must stay alive until they have run. */
+int axvs_m2f_decoder_pack(const AxvsM2fLayerParams* layers, const AxvsM2fHeadParams* head, const AxvsM2fCfg* cfg, void* packed, void* stream);
+size_t axvs_m2f_decoder_workspace_bytes(const AxvsM2fCfg* cfg);
+/* memories: host array of the three levels' device pointers.  query_out [N,Q,C]: the queries after the last layer.  With
+ * cfg->return_predictions: cls_pred [N,Q,K1] and mask_pred [N,T,Q,h,w] of the last layer (the one full-resolution mask einsum); else both
+ * may be NULL.  debug_bits / debug_flags (both or neither): every layer's attention mask as the layer consumed it, layer after layer --
+ * bits uint32 [N,Q,ceil(S_i/32)] (bit k & 31 of word k / 32 set = key k masked, S_i = T*lh*lw of level i % 3, bits past S_i zero) and
+ * flags int32 [N,Q] per layer (0 = every key masked: the query attends to all keys). */
+int axvs_m2f_decoder_fwd(const AxvsM2fCfg* cfg, const void* packed, const float* mask_features, const float* const* memories, float* query_out,
+                         float* cls_pred, float* mask_pred, unsigned* debug_bits, int* debug_flags, void* workspace, long long workspace_bytes,
+                         void* stream);
+/* Stage entries.  One mask head: x [N,Q,C] (queries before post_norm) -> bits [N,Q,ceil(S/32)], flags [N,Q] at `level`. */
+size_t axvs_m2f_attn_mask_workspace_bytes(const AxvsM2fCfg* cfg, int level);
+int axvs_m2f_attn_mask_fwd(const AxvsM2fCfg* cfg, const void* packed, const float* x, const float* mask_features, int level, unsigned* bits, int* flags,
+                           void* workspace, long long workspace_bytes, void* stream);
+/* One layer given its attention mask: x [N,Q,C], memory of level layer % 3 -> out [N,Q,C] (may be x). */
+size_t axvs_m2f_layer_workspace_bytes(const AxvsM2fCfg* cfg, int layer);
+int axvs_m2f_layer_fwd(const AxvsM2fCfg* cfg, const void* packed, int layer, const float* x, const float* memory, const unsigned* bits,
+                       const int* flags, float* out, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- test hooks, not part of the drop-in surface ----------------------------------------------------------------------------------
  * One call of the training tier's split-precision GEMM dispatch (tr_gemm_nt_kernel / tr_gemm_tn_kernel behind the host code every
  * training entry point above uses), with every operand, stride and epilogue field explicit: what tests/test_hip_train_gemm.py holds
