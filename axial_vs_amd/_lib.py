@@ -123,6 +123,26 @@ class AxvsM2fCfg(C.Structure):
                 ("pos_temperature", C.c_float), ("pos_scale", C.c_float)]
 
 
+KMAX_PREDICTOR_FIELDS = ("dw_w", "dw_b", "ph1_w", "ph1_b", "ph2_w", "ph2_b", "mh_w", "mh_b", "cls_w", "cls_b", "mask_ab")
+KMAX_LAYER_FIELDS = (("pix1_w", "pix1_b", "q1_w", "q1_b") + tuple("pred." + n for n in KMAX_PREDICTOR_FIELDS)
+                     + ("kv_w", "kv_b", "k3_w", "k3_b", "qkv_w", "qkv_b", "sim_ab", "rv_ab", "a3_w", "a3_b", "f1_w", "f1_b", "f2_w", "f2_b"))
+KMAX_HEAD_FIELDS = ("centers", "cep_w", "cep_b", "mep_w", "mep_b") + tuple("pred." + n for n in KMAX_PREDICTOR_FIELDS)
+
+
+class AxvsKmaxLayerParams(C.Structure):      # (the nested predictor struct is all pointers: flat here, "pred." -> "pred_")
+    _fields_ = [(n.replace(".", "_"), _fp) for n in KMAX_LAYER_FIELDS]
+
+
+class AxvsKmaxHeadParams(C.Structure):
+    _fields_ = [(n.replace(".", "_"), _fp) for n in KMAX_HEAD_FIELDS]
+
+
+class AxvsKmaxCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "T", "L", "K1", "num_layers")] + \
+               [("layer_level", C.c_int * 16), ("in_channels", C.c_int * 3), ("h", C.c_int * 3), ("w", C.c_int * 3)] + \
+               [(n, C.c_int) for n in ("pan_channels", "H", "W", "heads", "base_filters", "want_masks", "want_pixel_feature")]
+
+
 class AxvsMsdaParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
                                    "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
@@ -297,6 +317,13 @@ SIGNATURES = {
     "axvs_m2f_attn_mask_fwd": (C.c_int, [C.POINTER(AxvsM2fCfg), _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
     "axvs_m2f_layer_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsM2fCfg), C.c_int]),
     "axvs_m2f_layer_fwd": (C.c_int, [C.POINTER(AxvsM2fCfg), _fp, C.c_int] + [_fp] * 6 + [C.c_longlong, _fp]),
+    "axvs_kmax_decoder_packed_bytes": (C.c_size_t, [C.POINTER(AxvsKmaxCfg)]),
+    "axvs_kmax_decoder_pack": (C.c_int, [C.POINTER(AxvsKmaxLayerParams), C.POINTER(AxvsKmaxHeadParams), C.POINTER(AxvsKmaxCfg), _fp, _fp]),
+    "axvs_kmax_decoder_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsKmaxCfg)]),
+    "axvs_kmax_decoder_fwd": (C.c_int, [C.POINTER(AxvsKmaxCfg), _fp, C.POINTER(_fp)] + [_fp] * 8 + [C.c_longlong, _fp]),
+    "axvs_kmax_stage_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsKmaxCfg), C.c_int, C.c_int]),
+    "axvs_kmax_assign_fwd": (C.c_int, [C.POINTER(AxvsKmaxCfg), _fp, C.c_int] + [_fp] * 5 + [C.c_longlong, _fp]),
+    "axvs_kmax_layer_fwd": (C.c_int, [C.POINTER(AxvsKmaxCfg), _fp, C.c_int] + [_fp] * 5 + [C.c_longlong, _fp]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

@@ -7,8 +7,10 @@ and fills parameter and gradient structs from their pointers; the eval tier cast
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence
 
+import torch
 from torch import Tensor
 
 from . import _lib
@@ -142,3 +144,85 @@ def tl_head_params(mod) -> List[Tensor]:
     me = mod.mask_embed
     return (_wb(mod.transformer_decoder.post_norm, mod.activation_proj, mod.cls_embed)
             + [me[0].weight, me[2].weight, me[4].weight, me[0].bias, me[2].bias, me[4].bias])
+
+
+# ---- Video-kMaX's k-means query decoder -------------------------------------------------------------------------------------------------
+# AxvsKmaxLayerParams / AxvsKmaxHeadParams hold FOLDED tensors, so these functions return new float64 tensors, not the parameters: every
+# BatchNorm is the affine map a x + c on its running statistics (eps 1e-3), folded into the convolution in front of it where there is
+# one.  They read a mapping of the reference's own state-dict names (a module's parameters and buffers, or a checkpoint's tensors).
+KMAX_BN_EPS = 1e-3
+
+
+def kmax_predictor_shapes(K1: int) -> List[tuple]:
+    """(slot, shape) of AxvsKmaxPredictorParams, in order"""
+    return [("dw_w", (25, 256)), ("dw_b", (256,)), ("ph1_w", (256, 256)), ("ph1_b", (256,)), ("ph2_w", (128, 256)), ("ph2_b", (128,)),
+            ("mh_w", (128, 256)), ("mh_b", (128,)), ("cls_w", (K1, 256)), ("cls_b", (K1,)), ("mask_ab", (4,))]
+
+
+def kmax_layer_shapes(cin: int, K1: int) -> List[tuple]:
+    """(slot, shape) of AxvsKmaxLayerParams, in order (_lib.KMAX_LAYER_FIELDS)"""
+    return ([("pix1_w", (256, cin)), ("pix1_b", (256,)), ("q1_w", (256, 256)), ("q1_b", (256,))]
+            + [("pred." + n, s) for n, s in kmax_predictor_shapes(K1)]
+            + [("kv_w", (256, 260)), ("kv_b", (256,)), ("k3_w", (256, 256)), ("k3_b", (256,)), ("qkv_w", (512, 256)), ("qkv_b", (512,)),
+               ("sim_ab", (16,)), ("rv_ab", (512,)), ("a3_w", (256, 256)), ("a3_b", (256,)), ("f1_w", (2048, 256)), ("f1_b", (2048,)),
+               ("f2_w", (256, 2048)), ("f2_b", (256,))])
+
+
+def kmax_head_shapes(L: int, K1: int) -> List[tuple]:
+    """(slot, shape) of AxvsKmaxHeadParams, in order (_lib.KMAX_HEAD_FIELDS)"""
+    return ([("centers", (L, 256)), ("cep_w", (256, 256)), ("cep_b", (256,)), ("mep_w", (256, 256)), ("mep_b", (256,))]
+            + [("pred." + n, s) for n, s in kmax_predictor_shapes(K1)])
+
+
+def kmax_packed_bytes(L: int, K1: int, layer_channels: Sequence[int]) -> int:
+    """what axvs_kmax_decoder_packed_bytes returns: every slot rounded up to 256 bytes, the head first, then layer after layer"""
+    slots = kmax_head_shapes(L, K1) + [s for cin in layer_channels for s in kmax_layer_shapes(cin, K1)]
+    return sum((4 * math.prod(shape) + 255) // 256 * 256 for _, shape in slots)
+
+
+def _kmax_affine(sd, p: str):
+    """(a, c) of the BatchNorm `p`: a x + c"""
+    a = sd[p + "weight"].double() / (sd[p + "running_var"].double() + KMAX_BN_EPS).sqrt()
+    return a, sd[p + "bias"].double() - sd[p + "running_mean"].double() * a
+
+
+def _kmax_convbn(sd, p: str):
+    """(W [out, in * k], b [out]) of the ConvBN `p` with its norm (if it has one) folded in"""
+    w = sd[p + "conv.weight"].double().flatten(1)
+    b = sd[p + "conv.bias"].double() if p + "conv.bias" in sd else w.new_zeros(w.shape[0])
+    if p + "norm.weight" in sd:
+        a, c = _kmax_affine(sd, p + "norm.")
+        w, b = w * a[:, None], b * a + c
+    return w, b
+
+
+def kmax_predictor_folded(sd, p: str) -> List[Tensor]:
+    """AxvsKmaxPredictorParams of the kMaXPredictor `p`; the class bias carries add_bias_towards_void's constant"""
+    dw_w, dw_b = _kmax_convbn(sd, p + "_pixel_space_head_conv0bnact.")
+    cls_w, cls_b = _kmax_convbn(sd, p + "_transformer_class_head.")
+    cls_b = cls_b.clone()
+    cls_b[-1] += math.log((cls_b.numel() - 1) * 0.9 / (1 - 0.9))
+    a, c = _kmax_affine(sd, p + "_pixel_space_mask_batch_norm.")
+    return ([dw_w.t().contiguous(), dw_b, *_kmax_convbn(sd, p + "_pixel_space_head_conv1bnact."), *_kmax_convbn(sd, p + "_pixel_space_head_last_convbn."),
+             *_kmax_convbn(sd, p + "_transformer_mask_head."), cls_w, cls_b, torch.cat([a, c, a.new_zeros(2)])])
+
+
+def kmax_layer_folded(sd, p: str) -> List[Tensor]:
+    """AxvsKmaxLayerParams of the kMaXTransformerLayer `p`.  kv: the value projection acts on the per-cluster SUM of the pixel-space rows
+    (sum_p (A P_p + b) = A sum_p P_p + n b), under its own BatchNorm and `_kmeans_query_batch_norm_retrieved_value`; column 256 of kv_w
+    multiplies the cluster's pixel count n."""
+    vw, vb = _kmax_convbn(sd, p + "_pixel_v_conv_bn.")
+    a, c = _kmax_affine(sd, p + "_kmeans_query_batch_norm_retrieved_value.")
+    kv_w = torch.cat([vw * a[:, None], (vb * a)[:, None], vw.new_zeros(256, 3)], dim=1)
+    sa, sc = _kmax_affine(sd, p + "_query_self_attention._batch_norm_similarity.")
+    ra, rc = _kmax_affine(sd, p + "_query_self_attention._batch_norm_retrieved_value.")
+    return ([*_kmax_convbn(sd, p + "_pixel_conv1_bn_act."), *_kmax_convbn(sd, p + "_query_conv1_bn_act.")] + kmax_predictor_folded(sd, p + "_predictor.")
+            + [kv_w, c, *_kmax_convbn(sd, p + "_kmeans_query_conv3_bn."), *_kmax_convbn(sd, p + "_query_qkv_conv_bn."), torch.cat([sa, sc]),
+               torch.cat([ra, rc]), *_kmax_convbn(sd, p + "_query_conv3_bn."), *_kmax_convbn(sd, p + "_query_ffn_conv1_bn_act."),
+               *_kmax_convbn(sd, p + "_query_ffn_conv2_bn.")])
+
+
+def kmax_head_folded(sd) -> List[Tensor]:
+    """AxvsKmaxHeadParams of a MaXTronTransformerDecoder: `_cluster_centers.weight` is [256, L], the queries travel as rows [L, 256]"""
+    return ([sd["_cluster_centers.weight"].double().t().contiguous(), *_kmax_convbn(sd, "_class_embedding_projection."),
+             *_kmax_convbn(sd, "_mask_embedding_projection.")] + kmax_predictor_folded(sd, "_predictor."))

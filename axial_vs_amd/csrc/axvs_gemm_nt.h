@@ -127,7 +127,9 @@ constexpr size_t gemm_nt_lds() {
 // kernel of the common case carries none of that code (these kernels are sensitive to their size: +3 us per launch with both
 // loaders in one body)
 // ADD (with !GEN): the x + pos addend ld.a2 on the 16-byte path (the general loader takes it at run time).
-template <int NS, int TU = 0, bool GEN = false, bool ADD = false, bool F16 = false, bool AFF = false>
+// ACT: ep.relu also takes 2 (exact GELU in the ReLU's place) and 3 (exact GELU after the residuals: out = gelu(... + res)) -- the
+// Video-kMaX query decoder's ConvBN + gelu chains (axvs_kmax.hip); its own flag, so that no other instantiation carries the erf.
+template <int NS, int TU = 0, bool GEN = false, bool ADD = false, bool F16 = false, bool AFF = false, bool ACT = false>
 __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                                          float* __restrict__ C, long long M, int N, int K, GemmLd ld, GemmEpi ep) {
   extern __shared__ __attribute__((aligned(16))) char gsmem[];
@@ -328,7 +330,7 @@ __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const 
     // fp32 rows with ReLU / dropout / accumulate / residuals: the same arithmetic as the loop below, but per half (four rounds) every
     // load -- LDS, C for beta, the residuals -- is issued before the first use and each uniform condition is tested once per half
     const int c4 = tid & 31, gn = n0 + 4 * c4;
-    const bool cin = gn < N, drop = ep.dr.thr != 0, relu = ep.relu != 0;
+    const bool cin = gn < N, drop = ep.dr.thr != 0, relu = ACT ? ep.relu == 1 : ep.relu != 0;
     float4 b = {0.f, 0.f, 0.f, 0.f};
     if (ep.bias && cin) b = *reinterpret_cast<const float4*>(ep.bias + gn);
     const float mul = ep.mul;
@@ -365,6 +367,12 @@ __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const 
         float t[4] = {(v[i].x + b.x) * mul, (v[i].y + b.y) * mul, (v[i].z + b.z) * mul, (v[i].w + b.w) * mul};
 #pragma unroll
         for (int e = 0; e < 4; ++e) t[e] = relu ? fmaxf(t[e], 0.f) : t[e];
+        if constexpr (ACT) {
+          if (ep.relu == 2) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = gelu_exact(t[e]);
+          }
+        }
         if (drop) {
           const unsigned long long e0 = (unsigned long long)(m0 + (tid >> 5) + 16 * (4 * hf + i)) * N + gn;
 #pragma unroll
@@ -377,6 +385,12 @@ __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const 
           if (ep.beta != 0.f) t[e] += ox[e];
           if (ep.res) t[e] += ax[e];
           if (ep.res2) t[e] += bx[e];
+        }
+        if constexpr (ACT) {
+          if (ep.relu == 3) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = gelu_exact(t[e]);
+          }
         }
         if (ok[i]) *reinterpret_cast<float4*>(C + off[i]) = make_float4(t[0], t[1], t[2], t[3]);
       }

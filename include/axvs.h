@@ -882,6 +882,63 @@ size_t axvs_m2f_layer_workspace_bytes(const AxvsM2fCfg* cfg, int layer);
 int axvs_m2f_layer_fwd(const AxvsM2fCfg* cfg, const void* packed, int layer, const float* x, const float* memory, const unsigned* bits,
                        const int* flags, float* out, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Video-kMaX's k-means query decoder (MaXTronTransformerDecoder in eval mode: kMaXTransformerLayers over three feature levels and the
+ * final kMaXPredictor) ---------------------------------------------------------------------------------------------------------------
+ * All tensors fp32; forward only.  B clips of T frames: features [(B T), C_l, h_l, w_l] and panoptic features [(B T), 256, H, W] are viewed
+ * as the stacked maps b c (t h) w, as the reference views them (the predictor's depthwise 5 x 5 crosses frame boundaries).  Queries
+ * travel as rows [B, L, 256].  The [B, L, T*h*w] mask logits of a layer never exist: a pixel's cluster is the argmax of a z + b over
+ * the clusters, equal maxima to the lower index.  Equal inputs give equal bits, and a clip's bits do not depend on the clips beside it.
+ * Bounds (AXVS_ERR_ARG outside them): 1 <= L <= 256, K1 <= 256, in_channels multiples of 16 up to 2048, pan_channels 256, T <= 16,
+ * 1..16 layers over levels 0..2, heads 8, base_filters 128, T*h*w < 2^24 per map, h <= 16383, B <= 4095.
+ * Parameters arrive FOLDED (every BatchNorm as an affine map on its running statistics, eps 1e-3, folded in float64 by the caller into
+ * the convolution in front of it) and in the layouts the kernels read:
+ *   dw_w [25][256] (tap-major), ph1 [256][256], ph2 [128][256] + [128], mh [128][256] + [128], cls [K1][256] + [K1] (bias towards void
+ *   included), mask_ab [4] = (a, b, 0, 0) of the one-channel mask BatchNorm;
+ *   pix1 [256][C_l], q1 [256][256]; kv_w [256][260]: the value projection under both BatchNorms that follow it, column 256 = its bias
+ *   under the same (multiplied by the cluster's pixel count), 257..259 zero; kv_b [256]: the constant term; k3 [256][256];
+ *   qkv [512][256] (q 128, k 128, v 256 rows); sim_ab [16] = a[8], b[8] per head; rv_ab [512] = a[256], b[256]; a3 [256][256];
+ *   f1 [2048][256], f2 [256][2048]; centers [L][256]; cep / mep [256][256]. */
+typedef struct AxvsKmaxPredictorParams {
+  const float *dw_w, *dw_b, *ph1_w, *ph1_b, *ph2_w, *ph2_b, *mh_w, *mh_b, *cls_w, *cls_b, *mask_ab;
+} AxvsKmaxPredictorParams;
+typedef struct AxvsKmaxLayerParams {
+  const float *pix1_w, *pix1_b, *q1_w, *q1_b;
+  AxvsKmaxPredictorParams pred;
+  const float *kv_w, *kv_b, *k3_w, *k3_b, *qkv_w, *qkv_b, *sim_ab, *rv_ab, *a3_w, *a3_b, *f1_w, *f1_b, *f2_w, *f2_b;
+} AxvsKmaxLayerParams;
+typedef struct AxvsKmaxHeadParams {
+  const float *centers, *cep_w, *cep_b, *mep_w, *mep_b;
+  AxvsKmaxPredictorParams pred;
+} AxvsKmaxHeadParams;
+/* layer i reads level layer_level[i]; level l: in_channels[l] x h[l] x w[l]; panoptic features pan_channels x H x W; K1 = classes + 1;
+ * want_masks / want_pixel_feature: which of the two full-resolution outputs the final predictor writes */
+typedef struct AxvsKmaxCfg {
+  int B, T, L, K1, num_layers;
+  int layer_level[16];
+  int in_channels[3], h[3], w[3];
+  int pan_channels, H, W;
+  int heads, base_filters;
+  int want_masks, want_pixel_feature;
+} AxvsKmaxCfg;
+size_t axvs_kmax_decoder_packed_bytes(const AxvsKmaxCfg* cfg);      /* depends on L, K1, the layers' levels and in_channels; 0: cfg refused */
+/* layers: num_layers structs.  Copies on `stream`; the parameter tensors must stay alive until they have run. */
+int axvs_kmax_decoder_pack(const AxvsKmaxLayerParams* layers, const AxvsKmaxHeadParams* head, const AxvsKmaxCfg* cfg, void* packed, void* stream);
+size_t axvs_kmax_decoder_workspace_bytes(const AxvsKmaxCfg* cfg);
+/* features: host array of the three levels' device pointers (a level no layer reads may be NULL).  pred_logits [B,L,K1], pred_masks
+ * [B,L,T,H,W] (want_masks), pred_mask_embeddings [B,L,128], pixel_feature [B,128,T,H,W] (want_pixel_feature), cluster_centers [B,L,256].
+ * debug_idx (nullable): every layer's index map as the layer consumed it, int32 [B, T*h*w] of the layer's level, layer after layer. */
+int axvs_kmax_decoder_fwd(const AxvsKmaxCfg* cfg, const void* packed, const float* const* features, const float* panoptic, float* pred_logits,
+                          float* pred_masks, float* pred_mask_embeddings, float* pixel_feature, float* cluster_centers, int* debug_idx, void* workspace,
+                          long long workspace_bytes, void* stream);
+/* Stage entries (update_stage 0: axvs_kmax_assign_fwd, 1: axvs_kmax_layer_fwd).  query [B,L,256]; feature: the layer's level. */
+size_t axvs_kmax_stage_workspace_bytes(const AxvsKmaxCfg* cfg, int layer, int update_stage);
+/* the assignment of one layer: idx int32 [B, T*h*w], class_logits [B,L,K1] (the layer's own class head, bias towards void included) */
+int axvs_kmax_assign_fwd(const AxvsKmaxCfg* cfg, const void* packed, int layer, const float* query, const float* feature, int* idx, float* class_logits,
+                         void* workspace, long long workspace_bytes, void* stream);
+/* the same layer given its index map (an index outside 0..L-1 joins no cluster) -> out [B,L,256], the new query feature */
+int axvs_kmax_layer_fwd(const AxvsKmaxCfg* cfg, const void* packed, int layer, const float* query, const float* feature, const int* idx, float* out,
+                        void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- test hooks, not part of the drop-in surface ----------------------------------------------------------------------------------
  * One call of the training tier's split-precision GEMM dispatch (tr_gemm_nt_kernel / tr_gemm_tn_kernel behind the host code every
  * training entry point above uses), with every operand, stride and epilogue field explicit: what tests/test_hip_train_gemm.py holds
