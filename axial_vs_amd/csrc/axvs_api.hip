@@ -1195,22 +1195,8 @@ int launch_nt128(const float* X, const float* X2, const float* W, float* Y, long
                  int zsplit = 1 /* > 1: split-K -- workgroup z writes the partial product of its k-steps to Y + z M N (no epilogue terms) */) {
   tr::GemmLd ld{lda ? lda : K, K, N, 0, X2};
   if (zsplit > 1) ld.ksteps = ((K + tr::kGK - 1) / tr::kGK + zsplit - 1) / zsplit;
-  const dim3 grid((unsigned)((M + tr::kGT - 1) / tr::kGT), (unsigned)((N + tr::kGT - 1) / tr::kGT), (unsigned)(zsplit > 1 ? zsplit : 1));
-  const bool exact = kMsdaGemm == 3 || (kMsdaGemm == 4 && feeds_residual), gen = tr::gemm_nt_general(ld, K), add = X2 != nullptr;
-#define AXVS_NT128(NS_, GEN_, ADD_)                                                                                                  \
-  {                                                                                                                                   \
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr::tr_gemm_nt_kernel<NS_, 1, GEN_, ADD_>))) return rc;                \
-    hipLaunchKernelGGL((tr::tr_gemm_nt_kernel<NS_, 1, GEN_, ADD_>), grid, dim3(512), tr::gemm_nt_lds<NS_>(), st, X, W, Y, M, N, K, ld, e); \
-  }
-  if (gen) {
-    if (exact) AXVS_NT128(3, true, false) else AXVS_NT128(2, true, false)
-  } else if (add) {
-    if (exact) AXVS_NT128(3, false, true) else AXVS_NT128(2, false, true)
-  } else {
-    if (exact) AXVS_NT128(3, false, false) else AXVS_NT128(2, false, false)
-  }
-#undef AXVS_NT128
-  return AXVS_OK;
+  const bool exact = kMsdaGemm == 3 || (kMsdaGemm == 4 && feeds_residual);
+  return tr::gemm_nt(X, W, Y, M, N, K, ld, e, tr::GemmNtForm{exact ? 3 : 2}, zsplit > 1 ? zsplit : 1, st);
 }
 // rows from which the 128 x 128 kernel beats the 64 x 64 one (fewer rows: too few workgroups)
 inline bool use_nt128(long long rows, int C, int heads) { return kMsdaGemm && rows >= 2048 && C % 4 == 0 && C / heads == 32; }

@@ -1,6 +1,6 @@
 // C-ABI entry points of Video-kMaX's k-means query decoder (include/axvs.h: axvs_kmax_*) and the launch sequence behind them.
-// 1x1 convolutions with their folded BatchNorms: the three-piece split-precision GEMM of axvs_gemm_nt.h under this unit's own tag, with
-// the gelu epilogues (ACT); everything else: axvs_kmax.h.
+// 1x1 convolutions with their folded BatchNorms: the three-piece split-precision GEMM behind gemm_nt (axvs_gemm_nt.h), always in
+// its form with the gelu epilogues; everything else: axvs_kmax.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,7 +13,6 @@ using namespace axvs;
 
 namespace {
 
-constexpr int kTag = 3;            // this unit's instantiations of tr_gemm_nt_kernel (axvs_gemm_nt.h: one tag per translation unit)
 constexpr int C = kKmaxC, D = kKmaxD, kFfn = 2048;
 constexpr int kActNone = 0, kActGelu = 2, kActGeluAfterRes = 3;      // GemmEpi::relu under ACT
 
@@ -137,11 +136,7 @@ int linear(const float* X, long long lda, const float* W, const float* bias, flo
   tr::GemmLd ld{lda, K, ldc, 0, nullptr};
   tr::GemmEpi e{bias, 1.f, act, tr::Drop{0u, 0u, 0u, 1.f}, 0.f};
   e.res = res;
-  const dim3 grid((unsigned)((M + tr::kGT - 1) / tr::kGT), (unsigned)((N + tr::kGT - 1) / tr::kGT), 1u);
-  auto* const kern = tr::tr_gemm_nt_kernel<3, kTag, false, false, false, false, true>;
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
-  hipLaunchKernelGGL(kern, grid, dim3(512), tr::gemm_nt_lds<3>(), st, X, W, Y, M, N, K, ld, e);
-  return AXVS_OK;
+  return tr::gemm_nt(X, W, Y, M, N, K, ld, e, tr::GemmNtForm{3, false, true}, 1, st);
 }
 
 template <bool GELU>

@@ -1,5 +1,5 @@
 // C-ABI entry points of Tube-Link's per-clip masked-attention query decoder (include/axvs.h: axvs_m2f_*) and the launch sequence behind
-// them.  Linear layers: the three-piece split-precision GEMM of axvs_gemm_nt.h under this unit's own tag; everything else: axvs_m2f.h.
+// them.  Linear layers: the three-piece split-precision GEMM behind gemm_nt (axvs_gemm_nt.h); everything else: axvs_m2f.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,7 +12,6 @@ using namespace axvs;
 
 namespace {
 
-constexpr int kTag = 2;            // this unit's instantiations of tr_gemm_nt_kernel (axvs_gemm_nt.h: one tag per translation unit)
 constexpr int C = kM2fC;
 constexpr int kMaxSplits = 16;      // split-K partials of the GEMMs in front of a LayerNorm
 
@@ -120,15 +119,7 @@ int linear(const float* X, const float* X2, const float* W, const float* bias, f
   tr::GemmLd ld{K, K, ldc, 0, X2};
   tr::GemmEpi e{bias, 1.f, relu ? 1 : 0, tr::Drop{0u, 0u, 0u, 1.f}, 0.f};
   e.res = res;
-  const dim3 grid((unsigned)((M + tr::kGT - 1) / tr::kGT), (unsigned)((N + tr::kGT - 1) / tr::kGT), 1u);
-  if (X2) {
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr::tr_gemm_nt_kernel<3, kTag, false, true>))) return rc;
-    hipLaunchKernelGGL((tr::tr_gemm_nt_kernel<3, kTag, false, true>), grid, dim3(512), tr::gemm_nt_lds<3>(), st, X, W, Y, M, N, K, ld, e);
-  } else {
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr::tr_gemm_nt_kernel<3, kTag, false, false>))) return rc;
-    hipLaunchKernelGGL((tr::tr_gemm_nt_kernel<3, kTag, false, false>), grid, dim3(512), tr::gemm_nt_lds<3>(), st, X, W, Y, M, N, K, ld, e);
-  }
-  return AXVS_OK;
+  return tr::gemm_nt(X, W, Y, M, N, K, ld, e, tr::GemmNtForm{3}, 1, st);
 }
 
 // The GEMMs in front of a LayerNorm: M = N*Q rows alone are one or two row tiles, so the contraction is split over workgroups (ksteps
@@ -138,11 +129,8 @@ int linear_split(const float* X, const float* W, float* P, long long M, int K, i
   if (z > kMaxSplits) return fail(AXVS_ERR_ARG, "split-K: %d partials, at most %d", z, kMaxSplits);
   tr::GemmLd ld{K, K, C, ksteps, nullptr};
   const tr::GemmEpi e{nullptr, 1.f, 0, tr::Drop{0u, 0u, 0u, 1.f}, 0.f};
-  const dim3 grid((unsigned)((M + tr::kGT - 1) / tr::kGT), (unsigned)((C + tr::kGT - 1) / tr::kGT), (unsigned)z);
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(tr::tr_gemm_nt_kernel<3, kTag, false, false>))) return rc;
-  hipLaunchKernelGGL((tr::tr_gemm_nt_kernel<3, kTag, false, false>), grid, dim3(512), tr::gemm_nt_lds<3>(), st, X, W, P, M, C, K, ld, e);
   *nparts = z;
-  return AXVS_OK;
+  return tr::gemm_nt(X, W, P, M, C, K, ld, e, tr::GemmNtForm{3}, z, st);
 }
 
 M2fMap level_map(const AxvsM2fCfg* c, int l, bool mem) { return M2fMap{c->T, mem ? c->lh[l] : c->h, mem ? c->lw[l] : c->w, c->lh[l], c->lw[l]}; }

@@ -1,5 +1,5 @@
 // Training tier of the axial-trajectory attention layer: fp32 activations in natural [B,T,H,W] row order, the
-// attention / softmax / dropout / LayerNorm kernels here, the Linear layers' GEMMs (forward, dgrad, wgrad) in axvs_gemm_nt.h /
+// attention / softmax / dropout / LayerNorm kernels here, the Linear layers' GEMMs (forward, dgrad, wgrad) in axvs_gemm_nt.hip /
 // axvs_train_gemm.h (split-precision bf16 MFMA).  Host side: axvs_train_host.h (shapes, buffers, the tier choice and the launches of a
 // trajectory pass), entry points in axvs_train.hip.  Nothing here is on the inference path; that stays on the fused 16-bit MFMA kernels (axvs_fused.h).
 //

@@ -328,12 +328,6 @@ int md_backward(const Ctx& c, const MdShape& m, const MdScratch& x, const float*
 
 using namespace axvs;
 
-#ifdef AXVS_STAMPS_TR
-extern "C" int axvs_debug_read_stamps_tr(unsigned long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(axvs::g_stamps), sizeof(unsigned long long) * n);
-}
-#endif
-
 extern "C" {
 
 size_t axvs_axial_layer_train_saved_bytes(int B, int T, int H, int W, int C, int heads, int d_ffn) {
@@ -784,13 +778,14 @@ int axvs_test_train_gemm(AxvsTestGemm* t, void* scratch, void* stream) {
   GemmLd stat{0, 0, 0, 0};
   stat.stat_part = t->stat_part; stat.stat_shift = t->stat_shift; stat.stat_nblk = t->stat_nblk; stat.stat_blk0 = t->stat_blk0;
   stat.stat_rows = t->stat_rows;
+  const bool gelu = t->relu > 1;      // (NT, FWD) the GELU epilogues: their own instantiation, which exists for three pieces (exact) only
   // the host-side refusals first: they need no device
   int rc;
   switch (t->op) {
-    case AXVS_TEST_GEMM_NT: rc = Gemm::check_nt(t->N, t->K, ld); break;
-    case AXVS_TEST_GEMM_FWD: rc = Gemm::check_nt(t->N, t->K, GemmLd{t->K, t->K, t->N, 0, t->a2}); break;
+    case AXVS_TEST_GEMM_NT: rc = Gemm::check_nt(t->N, t->K, ld, e, t->exact != 0, gelu); break;
+    case AXVS_TEST_GEMM_FWD: rc = Gemm::check_nt(t->N, t->K, GemmLd{t->K, t->K, t->N, 0, t->a2}, e, t->exact != 0, gelu); break;
     case AXVS_TEST_GEMM_WGRAD: rc = Gemm::check_wgrad(t->N, t->K, t->lda ? t->lda : t->N, t->ldb ? t->ldb : t->K); break;
-    case AXVS_TEST_GEMM_DGRAD: rc = Gemm::check_nt(t->K, t->N, GemmLd{t->lda ? t->lda : t->N, t->N, t->K, 0}); break;
+    case AXVS_TEST_GEMM_DGRAD: rc = Gemm::check_nt(t->K, t->N, GemmLd{t->lda ? t->lda : t->N, t->N, t->K, 0}, GemmEpi{}, t->exact != 0 || g_train_exact >= 2); break;
     case AXVS_TEST_GEMM_TN_DIRECT:
       if (t->M > INT32_MAX) return fail(AXVS_ERR_ARG, "einsum GEMM: Mc=%lld rows > 2^31 - 1", t->M);
       rc = Gemm::check_tn(t->N, t->lda, t->stat_part != nullptr, t->grp_rows);
@@ -806,8 +801,8 @@ int axvs_test_train_gemm(AxvsTestGemm* t, void* scratch, void* stream) {
   carve_test_gemm(b, *t, c.sc);
   t_gemm_variant = 0;
   switch (t->op) {
-    case AXVS_TEST_GEMM_NT: rc = c.g.nt(t->a, t->b, t->c, t->M, t->N, t->K, ld, e, t->exact != 0, t->zsplits > 0 ? t->zsplits : 1); break;
-    case AXVS_TEST_GEMM_FWD: rc = c.g.fwd(t->a, t->b, t->c, t->M, t->N, t->K, t->beta, &e, t->exact != 0, t->a2); break;
+    case AXVS_TEST_GEMM_NT: rc = c.g.nt(t->a, t->b, t->c, t->M, t->N, t->K, ld, e, t->exact != 0, t->zsplits > 0 ? t->zsplits : 1, gelu); break;
+    case AXVS_TEST_GEMM_FWD: rc = c.g.fwd(t->a, t->b, t->c, t->M, t->N, t->K, t->beta, &e, t->exact != 0, t->a2, gelu); break;
     case AXVS_TEST_GEMM_WGRAD: rc = c.wgrad(t->a, t->b, t->c, t->M, t->N, t->K, t->db, t->lda, t->ldb, t->mul); break;
     case AXVS_TEST_GEMM_DGRAD:
       rc = c.dgrad(t->a, t->b, t->c, t->M, t->N, t->K, t->beta, t->lda, t->exact != 0, t->mul, t->res, t->res2);

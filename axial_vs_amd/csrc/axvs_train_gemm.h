@@ -10,6 +10,7 @@
 //   tr_gemm_nt_kernel   C[M,N] = epilogue(A[M,K] B[N,K]^T)     forward Linear (x W^T) and, through a transposed copy of the weight,
 //                                                            the input gradients (dY W); epilogue: + bias, * mul, ReLU, dropout by
 //                                                            element index, + beta C  -- what used to be separate elementwise launches
+//                                                            (axvs_gemm_nt.hip, behind gemm_nt() of axvs_gemm_nt.h: the inference path calls it too)
 //   tr_gemm_tn_kernel   P[s][N,K] = sum_{m in split s} dY[m,N] X[m,K]     weight gradients: the contraction runs over the rows, so both
 //                                                            operand tiles sit in LDS contraction-major and reach the MFMA through the
 //                                                            transposing LDS load (ds_read_b64_tr_b16); partial sums per row split are

@@ -12,8 +12,8 @@ namespace {
 using namespace tr;
 
 // ---- the Linear layers' GEMMs: split-precision bf16 MFMA kernels (axvs_train_gemm.h) ------------------------------------------------
-// The instantiation the last Gemm launch of this thread ran (include/axvs.h, AxvsTestGemm::variant, has the encoding): set in
-// launch_nt / launch_tn, the only places that launch the GEMM kernels, and reported by axvs_test_train_gemm.
+// The instantiation the last Gemm launch of this thread ran (include/axvs.h, AxvsTestGemm::variant, has the encoding): set by
+// gemm_nt (through nt) and launch_tn, the only places that launch the GEMM kernels, and reported by axvs_test_train_gemm.
 inline thread_local int t_gemm_variant = 0;
 
 struct Gemm {
@@ -25,22 +25,25 @@ struct Gemm {
     if (hipGetDevice(&dev) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "hipGetDevice failed");
     return AXVS_OK;
   }
-  // The GEMM kernels take more dynamic LDS than the default limit: each launcher raises the limit of the instantiation it is about to
-  // launch.  `seen_dev` is that instantiation's own thread_local: the device it was last raised on, so a repeat launch costs a compare
-  // (a thread that alternates between devices falls through to ensure_max_lds, which remembers every (device, kernel) pair).
+  // The dY^T X kernels take more dynamic LDS than the default limit: launch_tn raises the limit of the instantiation it is about to
+  // launch (gemm_nt does the same).  `seen_dev` is that instantiation's own thread_local: the device it was last raised on, so a repeat launch
+  // costs a compare (a thread that alternates between devices falls through to ensure_max_lds, which remembers every (device, kernel) pair).
   int raise_lds(const void* fn, int& seen_dev) const {
     if (seen_dev == dev) return AXVS_OK;
     if (int rc = ensure_max_lds(fn)) return rc;
     seen_dev = dev;
     return AXVS_OK;
   }
+  // The policy of nt(): affine A operand (an input-gradient GEMM): two pieces; torch.autocast: one 16-bit piece per operand (1: bf16,
+  // 2: fp16), whatever the caller's `exact`
+  static GemmNtForm nt_form(const GemmLd& ld, bool exact, bool gelu = false) {
+    if (ld.aff) return GemmNtForm{2, false, gelu};
+    return g_train_amp ? GemmNtForm{1, g_train_amp == 2, gelu} : GemmNtForm{exact ? 3 : 2, false, gelu};
+  }
   // The argument checks of nt(), wgrad_partials() and tn_direct(): they run before anything touches the device (axvs_test_train_gemm
   // calls them ahead of init(), so a refused call needs no GPU).
-  static int check_nt(int N, int K, const GemmLd& ld) {
-    if (N % 4 || ld.c % 4 || (ld.al_a == 4 && ld.a % 4) || (ld.al_b == 4 && ld.b % 4))
-      return fail(AXVS_ERR_ARG, "training GEMM: N=%d and the row strides must be multiples of 4 (K=%d)", N, K);
-    if (ld.aff && !ld.a2) return fail(AXVS_ERR_ARG, "training GEMM: the affine loader needs its second operand");
-    return AXVS_OK;
+  static int check_nt(int N, int K, const GemmLd& ld, const GemmEpi& e, bool exact, bool gelu = false) {
+    return gemm_nt_check(N, K, ld, e, nt_form(ld, exact, gelu));
   }
   // (the weight-gradient kernel always runs its 16-byte loader: both row strides must keep every row 16-byte aligned)
   static int check_wgrad(int N, int K, long long ldy, long long ldx) {
@@ -52,14 +55,6 @@ struct Gemm {
   static int check_tn(int N, long long lda, bool stat, int grp_rows) {
     if (N % 4 || lda % 4) return fail(AXVS_ERR_ARG, "einsum GEMM: N=%d must be a multiple of 4", N);
     if (grp_rows > 0 && stat) return fail(AXVS_ERR_ARG, "einsum GEMM: grouped output rows take no statistics");
-    return AXVS_OK;
-  }
-  template <int NS, bool GEN = false, bool ADD = false, bool F16 = false, bool AFF = false>
-  int launch_nt(dim3 grid, const float* X, const float* W, float* Y, long long M, int N, int K, const GemmLd& ld, const GemmEpi& e) const {
-    static thread_local int lds_dev = kNoDevice;
-    if (int rc = raise_lds(reinterpret_cast<const void*>(tr_gemm_nt_kernel<NS, 0, GEN, ADD, F16, AFF>), lds_dev)) return rc;
-    t_gemm_variant = 0x100 | NS | GEN << 2 | ADD << 3 | F16 << 4 | AFF << 5;
-    hipLaunchKernelGGL((tr_gemm_nt_kernel<NS, 0, GEN, ADD, F16, AFF>), grid, dim3(512), gemm_nt_lds<NS>(), st, X, W, Y, M, N, K, ld, e);
     return AXVS_OK;
   }
   template <bool GEN, int AMP = 0, bool STATS = false, bool GRP = false>
@@ -74,38 +69,17 @@ struct Gemm {
   // row-major:  Y[M,N] = beta Y + epilogue(X[M,K] W[N,K]^T); epilogue (optional): + bias, * mul, ReLU, dropout by element index
   // exact: three bf16 pieces per operand (fp32 accuracy) -- for the GEMM in front of the ReLU (see tr_gemm_nt_kernel)
   // ld (optional): row strides of X, W, Y (sub-matrices of wider buffers); ld.ksteps > 0 with zsplits: split-K partials [z][M][ld.c]
-  int nt(const float* X, const float* W, float* Y, long long M, int N, int K, GemmLd ld, const GemmEpi& e, bool exact, int zsplits = 1) const {
-    if (int rc = check_nt(N, K, ld)) return rc;
-    if (M <= 0) return AXVS_OK;
-    const dim3 grid((unsigned)((M + kGT - 1) / kGT), (unsigned)((N + kGT - 1) / kGT), (unsigned)zsplits);
-    // (a deeper register prefetch for grids of a few workgroups was measured and does not pay: these launches are bound by their
-    //  fixed cost -- ~11 us whatever K -- not by the load round trips of the k-loop)
-    const bool gen = gemm_nt_general(ld, K), add = ld.a2 != nullptr;   // (the general loader takes the addend at run time)
-    if (ld.aff)                       // affine A operand (two-piece products: an input-gradient GEMM)
-      return gen ? launch_nt<2, true, false, false, true>(grid, X, W, Y, M, N, K, ld, e) : launch_nt<2, false, false, false, true>(grid, X, W, Y, M, N, K, ld, e);
-    if (g_train_amp == 2) {           // torch.autocast: one 16-bit piece per operand (1: bf16, 2: fp16), whatever the caller's `exact`
-      if (gen) return launch_nt<1, true, false, true>(grid, X, W, Y, M, N, K, ld, e);
-      if (add) return launch_nt<1, false, true, true>(grid, X, W, Y, M, N, K, ld, e);
-      return launch_nt<1, false, false, true>(grid, X, W, Y, M, N, K, ld, e);
-    }
-    if (g_train_amp) {
-      if (gen) return launch_nt<1, true>(grid, X, W, Y, M, N, K, ld, e);
-      if (add) return launch_nt<1, false, true>(grid, X, W, Y, M, N, K, ld, e);
-      return launch_nt<1>(grid, X, W, Y, M, N, K, ld, e);
-    }
-    if (exact && gen) return launch_nt<3, true>(grid, X, W, Y, M, N, K, ld, e);
-    if (exact && add) return launch_nt<3, false, true>(grid, X, W, Y, M, N, K, ld, e);
-    if (exact) return launch_nt<3>(grid, X, W, Y, M, N, K, ld, e);
-    if (gen) return launch_nt<2, true>(grid, X, W, Y, M, N, K, ld, e);
-    if (add) return launch_nt<2, false, true>(grid, X, W, Y, M, N, K, ld, e);
-    return launch_nt<2>(grid, X, W, Y, M, N, K, ld, e);
+  // gelu: the instantiation whose epilogue takes e.relu = 2 / 3 (GemmNtForm)
+  int nt(const float* X, const float* W, float* Y, long long M, int N, int K, GemmLd ld, const GemmEpi& e, bool exact, int zsplits = 1,
+         bool gelu = false) const {
+    return gemm_nt(X, W, Y, M, N, K, ld, e, nt_form(ld, exact, gelu), zsplits, st, dev, &t_gemm_variant);
   }
   // X2 (nullable): added to X element-wise in the loader (q = k = Linear(x + pos) without an x + pos buffer)
   int fwd(const float* X, const float* W, float* Y, long long M, int N, int K, float beta = 0.f, const GemmEpi* ep = nullptr,
-          bool exact = false, const float* X2 = nullptr) const {
+          bool exact = false, const float* X2 = nullptr, bool gelu = false) const {
     GemmEpi e = ep ? *ep : GemmEpi{nullptr, 1.f, 0, Drop{0u, 0u, 0u, 1.f}, 0.f};
     e.beta = beta;
-    return nt(X, W, Y, M, N, K, GemmLd{K, K, N, 0, X2}, e, exact);
+    return nt(X, W, Y, M, N, K, GemmLd{K, K, N, 0, X2}, e, exact, 1, gelu);
   }
   // dW[N,K] = dY[M,N]^T X[M,K]: the reduction runs over the M rows and the output is small, so the rows are split kSplit ways
   // into `part` ([kSplit + 1][N*K]); the caller sums the partials (deterministic).  ldy / ldx: row strides of dY / X (0: N / K).
@@ -344,12 +318,13 @@ struct Ctx {
   int dgrad(const float* dY, const float* W, float* dX, long long M, int N, int K, float beta, long long ldy = 0, bool exact = false,
             float mul = 1.f, const float* res = nullptr, const float* res2 = nullptr) const {
     const GemmLd ld{ldy ? ldy : N, N, K, 0};
-    if (int rc = Gemm::check_nt(K, N, ld)) return rc;      // (before the transpose: a refused call launches nothing)
-    hipLaunchKernelGGL(tr_transpose_kernel, dim3((K + 31) / 32, (N + 31) / 32), dim3(256), 0, st, W, sc.wt, N, K);
     GemmEpi e{nullptr, mul, 0, Drop{0u, 0u, 0u, 1.f}, beta};
     e.res = res;
     e.res2 = res2;
-    return g.nt(dY, sc.wt, dX, M, K, N, ld, e, exact || g_train_exact >= 2);
+    exact = exact || g_train_exact >= 2;
+    if (int rc = Gemm::check_nt(K, N, ld, e, exact)) return rc;      // (before the transpose: a refused call launches nothing)
+    hipLaunchKernelGGL(tr_transpose_kernel, dim3((K + 31) / 32, (N + 31) / 32), dim3(256), 0, st, W, sc.wt, N, K);
+    return g.nt(dY, sc.wt, dX, M, K, N, ld, e, exact);
   }
   // launch 256-thread workgroups with `lds` bytes of dynamic LDS, raising the kernel's limit first where that is above the 64 KiB default
   template <class... P, class... A>

@@ -955,8 +955,11 @@ int axvs_kmax_layer_fwd(const AxvsKmaxCfg* cfg, const void* packed, int layer, c
  *                                c + (n / grp_rows) grp_ld + (n % grp_rows) ldc
  *   Epilogue of NT / FWD: (acc + bias) * mul, ReLU, dropout of element row * N + col (drop_thr = floor(p 2^24), drop_scale = 1 / (1 - p); 0: none),
  *   + beta c, + res, + res2 (both [M][ldc]); out16 != NULL: one f16 (kind16 1) / bf16 (2) value per element in the blocked layout [ceil(N/32)][M][32]
- *   instead, rows with zero_rows[row] != 0 written as zeros.
- *   variant (out): the instantiation launched last, 0x100 | NS | GEN << 2 | ADD << 3 | F16 << 4 | AFF << 5 for tr_gemm_nt_kernel<NS, 0, GEN, ADD, F16, AFF>,
+ *   instead, rows with zero_rows[row] != 0 written as zeros.  relu = 2: exact GELU in the ReLU's place, relu = 3: exact GELU after the sums (out =
+ *   gelu(... + res + res2)) -- the ACT instantiation the query decoders' Linear layers run: three pieces (`exact`, no train_amp), 16-byte rows, K % 4 == 0,
+ *   no a2, fp32 rows out; anything else is refused.
+ *   variant (out): the instantiation launched last, 0x100 | NS | GEN << 2 | ADD << 3 | F16 << 4 | AFF << 5 | ACT << 6 for
+ *   tr_gemm_nt_kernel<NS, GEN, ADD, F16, AFF, ACT> (every caller in the library launches these same instantiations: axvs_gemm_nt.hip holds them all),
  *   0x200 | GEN | AMP << 1 | STATS << 3 | GRP << 4 for tr_gemm_tn_kernel<GEN, AMP, STATS, GRP>; 0 when nothing was launched.
  *   scratch: axvs_test_train_gemm_scratch_bytes(t) bytes (0 for NT, FWD and TN_DIRECT).  Refusals before any device work return AXVS_ERR_ARG. */
 #define AXVS_TEST_GEMM_NT 0

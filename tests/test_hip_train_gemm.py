@@ -11,6 +11,7 @@ f16, 2^-8 for bf16).  tol is per arithmetic class -- which class a call ran in i
 
     class   arithmetic                                        worst ratio measured on an MI355X   tol     (per-product worst case)
     ns3     three bf16 pieces per operand (exact forwards)    3.86e-7                             1e-6    (~6e-7: 2^-24 pieces, six fp32 adds)
+    gelu    ns3 with an exact-GELU epilogue (relu = 2 / 3)    3.16e-7                             1e-6    (as ns3; see below)
     ns2     two pieces (input and weight gradients, einsum)   2.57e-5                             5e-5    (3 * 2^-16 = 4.6e-5)
     f16     one fp16 piece (train_amp = 2)                    8.44e-4                             2e-3    (2^-10 = 9.8e-4)
     bf16    one bf16 piece (train_amp = 1)                    7.35e-3                             1.6e-2  (2^-7 = 7.8e-3)
@@ -20,6 +21,10 @@ typical product; the worst one is 2^-16 per operand residual plus the dropped lo
 worst ratio and at least the per-product worst case, and test_bounds_reject_the_next_coarser_arithmetic shows each one rejects the
 arithmetic one class coarser on the same inputs (K = 1: ns2 2.1e-5 against the ns3 bound, f16 8.4e-4 against ns2's, bf16 7.3e-3
 against f16's).
+The gelu class: the kernel applies 0.5 x (1 + erf(x / sqrt 2)) to an ns3 result x.  |gelu'| <= 1.129, so the error of x, at most tol times
+the element's magnitude term, comes out at most 1.13 times larger: the magnitude term of everything in front of the GELU is multiplied by
+1.13 (GELU_SLOPE) and the ns3 tol carries over.  The device erff's own error is not derived but measured: it is part of the 3.16e-7 above
+(against float64 erf, relative to the scaled magnitude), and 1e-6 is within 4x of that and not below ns3's per-product worst case.
 Output buffers carry NaN guards (rows past M, columns past N inside the row stride, the slot past the last split-K partial, rows between
 output groups, unwritten statistics slots): they must come back bit-identical, and NaN operand padding turns any read outside an
 operand's extent into a NaN in the result."""
@@ -36,7 +41,7 @@ import axvs_oracle as orc
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL = {"ns3": 1e-6, "ns2": 5e-5, "f16": 2e-3, "bf16": 1.6e-2}      # (the table above)
+TOL = {"ns3": 1e-6, "gelu": 1e-6, "ns2": 5e-5, "f16": 2e-3, "bf16": 1.6e-2}      # (the table above)
 U16 = {1: (2.0 ** -11, 2.0 ** -25), 2: (2.0 ** -8, 1e-38)}   # kind16 -> (rounding unit, absolute floor) of the 16-bit output
 MEASURED = {k: 0.0 for k in TOL}
 SEEN = []          # (variant launched, variant the dispatch rules give, case) of every call in this file
@@ -54,8 +59,8 @@ def lib():
 
 
 # ---- instantiation ids (AxvsTestGemm::variant) and the dispatch rules of Gemm (axvs_train.hip) --------------------------------------
-def nt_var(ns, gen=False, add=False, f16=False, aff=False):
-    return 0x100 | ns | gen << 2 | add << 3 | f16 << 4 | aff << 5
+def nt_var(ns, gen=False, add=False, f16=False, aff=False, act=False):
+    return 0x100 | ns | gen << 2 | add << 3 | f16 << 4 | aff << 5 | act << 6
 
 
 def tn_var(gen, amp=0, stats=False, grp=False):
@@ -64,7 +69,7 @@ def tn_var(gen, amp=0, stats=False, grp=False):
 
 def vname(v):
     if v >> 8 == 1:
-        flags = [n for n, b in (("GEN", 4), ("ADD", 8), ("F16", 16), ("AFF", 32)) if v & b]
+        flags = [n for n, b in (("GEN", 4), ("ADD", 8), ("F16", 16), ("AFF", 32), ("ACT", 64)) if v & b]
         return f"nt<{v & 3}{''.join(',' + f for f in flags)}>"
     if v >> 8 == 2:
         flags = [n for n, b in (("GEN", 1), ("STATS", 8), ("GRP", 16)) if v & b]
@@ -75,6 +80,8 @@ def vname(v):
 def vclass(v):
     if v >> 8 == 1:
         ns = v & 3
+        if v & 64:
+            return "gelu"
         return "ns3" if ns == 3 else "ns2" if ns == 2 else ("f16" if v & 16 else "bf16")
     amp = (v >> 1) & 3
     return "ns2" if amp == 0 else "bf16" if amp == 1 else "f16"
@@ -88,6 +95,7 @@ def registered():
         out |= {nt_var(ns, gen, add) for ns in (2, 3)}                   # split precision: two pieces, or three when exact
         out |= {nt_var(1, gen, add, f16) for f16 in (False, True)}       # train_amp 1 (bf16) / 2 (fp16): one piece
     out |= {nt_var(2, gen, aff=True) for gen in (False, True)}           # the affine loader: two pieces, no addend
+    out |= {nt_var(3, act=True)}                                         # the GELU epilogues: three pieces, 16-byte loader, no addend
     out |= {tn_var(False, amp) for amp in (0, 1, 2)}                     # weight gradient: 16-byte loader, follows train_amp
     for gen in (False, True):                                            # einsum: plain, with statistics, or grouped output rows
         out |= {tn_var(gen), tn_var(gen, stats=True), tn_var(gen, grp=True)}
@@ -99,10 +107,13 @@ def amp_mode():
     return _lib.current_amp()
 
 
-def expect_nt(K, exact, al_a=4, al_b=4, a2=False, aff=False):
+def expect_nt(K, exact, al_a=4, al_b=4, a2=False, aff=False, gelu=0):
     """K % 4 != 0 or a row alignment below 16 bytes: the general loader; the addend without it: ADD; the affine loader: two pieces
-    whatever `exact` and train_amp; train_amp: one 16-bit piece whatever `exact`; else three pieces iff exact."""
+    whatever `exact` and train_amp; train_amp: one 16-bit piece whatever `exact`; else three pieces iff exact.  relu = 2 / 3 (the
+    GELU epilogues): the one ACT instantiation -- any other combination with them is refused (test_train_gemm_cpu.py)."""
     gen = al_a != 4 or al_b != 4 or K % 4 != 0
+    if gelu:
+        return nt_var(3, act=True)
     if aff:
         return nt_var(2, gen, aff=True)
     amp = amp_mode()
@@ -207,10 +218,18 @@ def drop_factors(M, N, p, seed, site):
 
 
 # ---- nt / fwd / dgrad --------------------------------------------------------------------------------------------------------------
+def gelu64(x):
+    return 0.5 * x * (1.0 + torch.erf(x / 2.0 ** 0.5))
+
+
+GELU_SLOPE = 1.13      # |gelu'| <= 1.129: an error of the argument comes out at most this much larger
+
+
 def nt_case(M, N, K, exact=1, seed=0, op="nt", al_a=4, al_b=4, ldc_pad=0, stride=0, a2=False, aff_rows=0, bias=False, mul=1.0, relu=False,
-            p_drop=0.0, beta=0.0, res=False, res2=False, kind16=0, zero_rows=False, ksteps=0, zsplits=1):
+            p_drop=0.0, beta=0.0, res=False, res2=False, kind16=0, zero_rows=False, ksteps=0, zsplits=1, gelu=0):
+    """gelu (AxvsTestGemm::relu): 2 = exact GELU in the ReLU's place, 3 = exact GELU after the sums"""
     g = torch.Generator().manual_seed(1000 + seed)
-    what = (f"{op} M={M} N={N} K={K} exact={exact} al={al_a}/{al_b} ldc+{ldc_pad} a2={a2} aff={aff_rows} bias={bias} mul={mul} relu={relu} "
+    what = (f"{op} M={M} N={N} K={K} exact={exact} al={al_a}/{al_b} ldc+{ldc_pad} a2={a2} aff={aff_rows} bias={bias} mul={mul} relu={relu} gelu={gelu} "
             f"p={p_drop} beta={beta} res={res}/{res2} out16={kind16} ksteps={ksteps}x{zsplits} amp={amp_mode()}")
     a, b = rnd(g, M, K), rnd(g, N, K)
     lda, offa = layout(K, al_a, stride)
@@ -219,7 +238,7 @@ def nt_case(M, N, K, exact=1, seed=0, op="nt", al_a=4, al_b=4, ldc_pad=0, stride
         lda, offa, ldb, offb, ldc_pad = K, 0, K, 0, 0
     A, B = Mat(a, lda, offa), Mat(b, ldb, offb)
     ldc = N + ldc_pad
-    kw = dict(exact=exact, mul=mul, relu=int(relu), beta=beta)
+    kw = dict(exact=exact, mul=mul, relu=gelu or int(relu), beta=beta)
     if op == "nt":
         kw.update(al_a=al_a, al_b=al_b)
     a64, mag_a = a.double(), a.double().abs()
@@ -257,6 +276,8 @@ def nt_case(M, N, K, exact=1, seed=0, op="nt", al_a=4, al_b=4, ldc_pad=0, stride
     ref, magr = ref * mul, magr * abs(mul)
     if relu:
         ref = ref.clamp_min(0.0)
+    if gelu == 2:
+        ref, magr = gelu64(ref), GELU_SLOPE * magr
     if p_drop:
         f = drop_factors(M, N, p_drop, 1234 + seed, 7)
         kw.update(drop_seed=1234 + seed, drop_site=7, drop_thr=int(p_drop * 2 ** 24), drop_scale=1.0 / (1.0 - p_drop))
@@ -273,6 +294,8 @@ def nt_case(M, N, K, exact=1, seed=0, op="nt", al_a=4, al_b=4, ldc_pad=0, stride
             keep.append(R)
             kw[name] = R.ptr
             ref, magr = ref + r.double(), magr + r.double().abs()
+    if gelu == 3:
+        ref, magr = gelu64(ref), GELU_SLOPE * magr
     if ksteps:
         kw.update(ksteps=ksteps, zsplits=zsplits + 1)     # one more z than the k-steps need: it must write a zero partial
         Cm = Mat(nan((nz + 1) * M, N), ldc)
@@ -289,7 +312,7 @@ def nt_case(M, N, K, exact=1, seed=0, op="nt", al_a=4, al_b=4, ldc_pad=0, stride
             zr_d = zr.cuda()
             keep.append(zr_d)
             kw["zero_rows"] = zr_d.data_ptr()
-    expect = expect_nt(K, exact, al_a if op == "nt" else 4, al_b if op == "nt" else 4, a2 and not aff_rows, aff_rows > 0)
+    expect = expect_nt(K, exact, al_a if op == "nt" else 4, al_b if op == "nt" else 4, a2 and not aff_rows, aff_rows > 0, gelu)
     v = call(op, M, N, K, A, B, Cm, expect, what, **kw)
     cls = vclass(v)
     if kind16:
@@ -338,6 +361,16 @@ EPILOGUES = [dict(), dict(bias=True), dict(mul=-0.75), dict(relu=True), dict(p_d
 def test_nt_epilogue_terms(shape, e):
     M, N, K, exact = shape
     nt_case(M, N, K, exact, seed=50 + e, ldc_pad=12, stride=1, **EPILOGUES[e])
+
+
+@pytest.mark.parametrize("gelu", [2, 3], ids=["in_relus_place", "after_residual"])
+@pytest.mark.parametrize("M,N,K", [(m, n, k) for m in (1, 129) for n in (4, 132) for k in (4, 36)])
+def test_nt_gelu_epilogues(M, N, K, gelu):
+    """The ACT instantiation (the query decoders' Linear layers): out = gelu((A B^T + bias) mul) + res, or gelu(... + res), against
+    float64 0.5 x (1 + erf(x / sqrt 2)); one partial tile in each dimension."""
+    nt_case(M, N, K, 1, seed=40 + gelu, gelu=gelu, bias=True, mul=1.5, res=True, ldc_pad=8, stride=1)
+    nt_case(M, N, K, 1, seed=42 + gelu, gelu=gelu, mul=-0.75)
+    nt_case(M, N, K, 1, seed=44 + gelu, gelu=gelu, bias=True, beta=1.0, res=True, res2=True, p_drop=0.25)
 
 
 @pytest.mark.parametrize("K", [64, 33, 1000])
@@ -582,7 +615,7 @@ def test_bounds_reject_the_next_coarser_arithmetic(K):
 def test_zz_every_registered_instantiation_was_launched_by_its_rule():
     """Last in the file: every instantiation Gemm::init registers was launched, and every call of the file launched the one the
     dispatch rules document (K % 4 != 0 or unaligned rows -> GEN; an addend without GEN -> ADD; AMP -> one piece whatever `exact`, F16
-    iff fp16; the affine loader -> two pieces; wgrad -> the 16-byte tn loader; tn_direct -> GEN unless 16-byte rows and K % 4 == 0).
+    iff fp16; the affine loader -> two pieces; relu = 2 / 3 -> ACT; wgrad -> the 16-byte tn loader; tn_direct -> GEN unless 16-byte rows and K % 4 == 0).
     Small calls of each rule run here too, so the test stands alone when the file is run in part."""
     nt_case(1, 4, 4, 1, seed=90)
     nt_case(1, 4, 4, 0, seed=89)
@@ -592,6 +625,7 @@ def test_zz_every_registered_instantiation_was_launched_by_its_rule():
     nt_case(1, 4, 4, 1, seed=94, al_a=1)
     nt_case(1, 4, 4, 0, seed=95, aff_rows=1)
     nt_case(1, 4, 5, 1, seed=96, aff_rows=1)
+    nt_case(1, 4, 4, 1, seed=107, gelu=2)
     for mode in (1, 2):
         with amp(mode):
             nt_case(1, 4, 4, 1, seed=97)
@@ -608,7 +642,7 @@ def test_zz_every_registered_instantiation_was_launched_by_its_rule():
     assert not wrong, wrong[:5]
     reached = {v for v, _, _ in SEEN}
     want = registered()
-    assert len(want) == 22, sorted(map(vname, want))
+    assert len(want) == 23, sorted(map(vname, want))
     missing = sorted(map(vname, want - reached))
     assert not missing, f"registered but never launched: {missing}"
     assert reached <= want, f"launched but not registered: {sorted(map(vname, reached - want))}"

@@ -88,6 +88,14 @@ REFUSALS = [
     ("tn_direct", dict(M=1 << 31), ["Mc=2147483648", "2^31"]),
     ("nt", dict(M=0), ["non-positive"]),
     ("wgrad", dict(M=0, N=64, K=64), ["non-positive"]),
+    # relu = 2 / 3 (the GELU epilogues): one instantiation, three pieces on the 16-byte loader without a second operand
+    ("nt", dict(relu=2, exact=0), ["GELU", "three pieces"]),
+    ("nt", dict(relu=2, exact=1, a2=True, aff=True, aff_rows=8), ["GELU", "no second operand"]),
+    ("nt", dict(relu=2, exact=1, al_a=2), ["GELU", "16-byte rows"]),
+    ("nt", dict(relu=3, exact=1, a2=True), ["GELU", "no second operand"]),
+    ("nt", dict(relu=3, exact=1, K=30, lda=32, ldb=32), ["GELU", "K % 4 == 0"]),
+    ("nt", dict(relu=2, exact=1, out16=True, kind16=1), ["GELU", "fp32 rows only"]),
+    ("fwd", dict(relu=3, exact=0), ["GELU", "three pieces"]),
 ]
 
 
