@@ -304,6 +304,17 @@ SIGNATURES = {
                          [C.c_longlong, _fp]),
     "axvs_tl_loss_bwd": (C.c_int, [C.POINTER(AxvsTLLossCfg), _fp, C.POINTER(_fp), C.POINTER(_fp), _fp, C.POINTER(C.c_int), _fp, _fp, _fp,
                                    C.POINTER(_fp), C.POINTER(_fp), _fp]),
+    "axvs_pixel_sample": (C.c_int, [_fp, C.c_int, C.POINTER(C.c_int), _fp] + [C.c_int] * 4 + [C.c_longlong, C.POINTER(_fp), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, _fp, _fp, _fp, C.c_int, _fp]),
+    "axvs_pixel_insdis_saved_bytes": (C.c_size_t, [C.c_int] * 3),
+    "axvs_pixel_insdis_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "axvs_pixel_insdis_fwd": (C.c_int, [C.POINTER(_fp), _fp, C.c_int, C.POINTER(C.c_int), _fp] + [C.c_int] * 6 + [C.c_longlong, _fp, C.c_int, C.c_int,
+                                        _fp, _fp, _fp, C.c_longlong, _fp]),
+    "axvs_pixel_insdis_bwd": (C.c_int, [_fp, C.POINTER(_fp), _fp, C.c_int, C.POINTER(C.c_int), _fp] + [C.c_int] * 6 + [C.c_longlong, _fp, C.c_int,
+                                        C.c_int, _fp, C.POINTER(_fp), _fp, C.c_longlong, _fp]),
+    "axvs_pixel_semantic_saved_bytes": (C.c_size_t, [C.c_int] * 2),
+    "axvs_pixel_semantic_fwd": (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_int, _fp, _fp, _fp]),
+    "axvs_pixel_semantic_bwd": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_int, _fp, _fp, _fp]),
     "axvs_video_panoptic_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsPanopticCfg)]),
     "axvs_video_panoptic_table_ints": (C.c_size_t, [C.c_int]),
     "axvs_video_panoptic_fwd": (C.c_int, [C.POINTER(AxvsPanopticCfg), _fp, _fp, C.c_int] + [_fp] * 6 + [C.c_longlong, _fp]),

@@ -590,6 +590,47 @@ int axvs_tl_loss_bwd(const AxvsTLLossCfg* cfg, const float* grad_losses, const f
                      const void* targets, const int* m_per_video, const float* class_weight, const float* num_total_masks, const void* saved,
                      float* const* d_cls_scores, float* const* d_mask_preds, void* stream);
 
+/* ---- The sampled pixel losses of the within-clip criterion (wc_criterion.py:62-142, :271-305, :341-415): Gumbel top-k sampling of
+ *      k out of P = T*H*W pixels, `loss_pixel_insdis` of every layer, `loss_aux_semantic`, and their gradients.  One stream, no host
+ *      synchronisation, no K x K tensor, no floating-point atomics (two runs give the same bits).  The uniform noise is an INPUT.
+ *      With t the matched targets of a matching and video: area[i] = sum_p t[i,p], pix_area[p] = sum_i t[i,p] area[i], void[p] =
+ *      sum_i t[i,p] < 1, key[p] = log(reciprocal(max(pix_area, 1)) * P) * temperature + void * -99999 + -log(-log u[p]), each fp32
+ *      operation rounded once in this order.  The samples of a row are its k largest keys (equal keys: the lower pixel first), stored
+ *      in increasing pixel order.
+ *        targets, m_per_video, cols, kmax   as axvs_set_criterion_fwd takes them: cols int64 [LM*B][kmax] is the matcher's; LM matchings
+ *        noise                     HOST array of R device pointers: fp32 [B][P] in [0, 1) per noise row
+ *        row_matching / row_temperature / row_k   HOST [R]: the matching a row samples from, its temperature, its k (0: nothing selected)
+ *        area, keys                device buffers the call fills: fp32 [LM*B][kmax] (NULL when kmax = 0) and fp32 [R][B][P] (the keys)
+ *        idx                       int32 [R][B][kstride]: entries 0 .. k_r - 1 of a row are written
+ *      axvs_pixel_insdis_*: per layer l and video b with F = pixel_feature[l][b][:, idx] and G = the matched targets at idx (matching 0
+ *      when share_final_matching, else matching l), S = F^T F / 0.3 on the f32-input MFMA, g = G^T G, c_j = sum_k g[k,j],
+ *      loss_j = (logsumexp_k S[k,j] c_j - sum_k g[k,j] S[k,j]) / max(c_j, 1); losses[l] = mean_b sum_j loss_j / max(#{loss_j != 0}, 1).
+ *        pixel_feature / d_pixel_feature   HOST arrays of L device pointers, fp32 [B][C][P]; d_pixel_feature[l] must be ZERO-FILLED by
+ *                                  the caller (only the sampled pixels are written), a NULL entry skips that layer
+ *        idx                       int32 [L][B][kstride], distinct pixels per row (what axvs_pixel_sample wrote)
+ *        saved                     axvs_pixel_insdis_saved_bytes: O(L*B*k); grad_losses: DEVICE fp32 [L]
+ *      axvs_pixel_semantic_*: cross-entropy of pred fp32 [B][Cs][P] against sem int64 [B][P] at idx int32 [B][kstride]; a class of -1,
+ *      num_classes or outside 0 .. Cs-1 is ignored; the same nonzero-count mean.  d_pred must be zero-filled by the caller.
+ *      L <= 16, B <= 64, N <= 512, M_b <= 512, C a multiple of 4 up to 256, Cs <= 256, k <= min(8192, P), P <= 2^20, R <= 17; otherwise
+ *      AXVS_ERR_ARG with the offending value named.  workspace_bytes travels as long long. */
+int axvs_pixel_sample(const void* targets, int target_dtype, const int* m_per_video, const long long* cols, int kmax, int LM, int B, int N,
+                      long long P, const float* const* noise, const int* row_matching, const float* row_temperature, const int* row_k, int R,
+                      float* area, float* keys, int* idx, int kstride, void* stream);
+size_t axvs_pixel_insdis_saved_bytes(int L, int B, int k);
+size_t axvs_pixel_insdis_workspace_bytes(int L, int B, int C, int kmax, int k);
+int axvs_pixel_insdis_fwd(const float* const* pixel_feature, const void* targets, int target_dtype, const int* m_per_video, const long long* cols,
+                          int kmax, int share_final_matching, int L, int B, int N, int C, long long P, const int* idx, int k, int kstride,
+                          float* losses, void* saved, void* workspace, long long workspace_bytes, void* stream);
+int axvs_pixel_insdis_bwd(const float* grad_losses, const float* const* pixel_feature, const void* targets, int target_dtype,
+                          const int* m_per_video, const long long* cols, int kmax, int share_final_matching, int L, int B, int N, int C,
+                          long long P, const int* idx, int k, int kstride, const void* saved, float* const* d_pixel_feature, void* workspace,
+                          long long workspace_bytes, void* stream);
+size_t axvs_pixel_semantic_saved_bytes(int B, int k);
+int axvs_pixel_semantic_fwd(const float* pred, const long long* sem, const int* idx, int k, int kstride, int B, int Cs, long long P,
+                            int num_classes, float* loss, void* saved, void* stream);
+int axvs_pixel_semantic_bwd(const float* grad_loss, const float* pred, const long long* sem, const int* idx, int k, int kstride, int B, int Cs,
+                            long long P, int num_classes, const void* saved, float* d_pred, void* stream);
+
 /* ---- Video panoptic post-processing (maxtron_cc_model.py:442-571, maxtron_wc_model.py:440-551: `video_seg_post_processing` +
  *      `panoptic_mask_inference`) on the device, in three launches and without the [N,T,H,W] tensor: per output pixel the bilinearly
  *      resized logits of the N slots (one stage + crop, or two stages with the crop between them; torch's align_corners True / False
