@@ -143,6 +143,24 @@ class AxvsKmaxCfg(C.Structure):
                [(n, C.c_int) for n in ("pan_channels", "H", "W", "heads", "base_filters", "want_masks", "want_pixel_feature")]
 
 
+KPIX_AXIS_FIELDS = ("qkv_w", "qkv_b", "eq", "ek", "ev", "sim_a", "out_ab")
+KPIX_BLOCK_FIELDS = (("sc_w", "sc_b", "c1_w", "c1_b", "c2_w", "c2_b") + tuple("height." + n for n in KPIX_AXIS_FIELDS)
+                     + tuple("width." + n for n in KPIX_AXIS_FIELDS) + ("c3_w", "c3_b"))
+KPIX_FUSE_FIELDS = ("ln_w", "ln_b", "low_w", "low_b", "high_w", "high_b")
+
+
+class AxvsKpixBlockParams(C.Structure):      # (the nested axis structs are all pointers: flat here, "height." -> "height_")
+    _fields_ = [(n.replace(".", "_"), _fp) for n in KPIX_BLOCK_FIELDS]
+
+
+class AxvsKpixFuseParams(C.Structure):
+    _fields_ = [(n, _fp) for n in KPIX_FUSE_FIELDS]
+
+
+class AxvsKpixCfg(C.Structure):
+    _fields_ = [("N", C.c_int)] + [(n, C.c_int * 4) for n in ("in_channels", "h", "w", "base", "blocks", "axial")] + [("heads", C.c_int)]
+
+
 class AxvsMsdaParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
                                    "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
@@ -335,6 +353,13 @@ SIGNATURES = {
     "axvs_kmax_stage_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsKmaxCfg), C.c_int, C.c_int]),
     "axvs_kmax_assign_fwd": (C.c_int, [C.POINTER(AxvsKmaxCfg), _fp, C.c_int] + [_fp] * 5 + [C.c_longlong, _fp]),
     "axvs_kmax_layer_fwd": (C.c_int, [C.POINTER(AxvsKmaxCfg), _fp, C.c_int] + [_fp] * 5 + [C.c_longlong, _fp]),
+    "axvs_kmax_pix_packed_bytes": (C.c_size_t, [C.POINTER(AxvsKpixCfg)]),
+    "axvs_kmax_pix_pack": (C.c_int, [C.POINTER(AxvsKpixBlockParams), C.POINTER(AxvsKpixFuseParams), _fp, _fp, C.POINTER(AxvsKpixCfg), _fp, _fp]),
+    "axvs_kmax_pix_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsKpixCfg)]),
+    "axvs_kmax_pix_decoder_fwd": (C.c_int, [C.POINTER(AxvsKpixCfg), _fp, C.POINTER(_fp), C.POINTER(_fp), _fp, C.c_longlong, _fp]),
+    "axvs_kmax_pix_axial_attn_fwd": (C.c_int, [C.POINTER(AxvsKpixCfg), _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "axvs_kmax_pix_block_fwd": (C.c_int, [C.POINTER(AxvsKpixCfg), _fp, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
+    "axvs_kmax_pix_fuse_fwd": (C.c_int, [C.POINTER(AxvsKpixCfg), _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_longlong, _fp]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

@@ -226,3 +226,63 @@ def kmax_head_folded(sd) -> List[Tensor]:
     """AxvsKmaxHeadParams of a MaXTronTransformerDecoder: `_cluster_centers.weight` is [256, L], the queries travel as rows [L, 256]"""
     return ([sd["_cluster_centers.weight"].double().t().contiguous(), *_kmax_convbn(sd, "_class_embedding_projection."),
              *_kmax_convbn(sd, "_mask_embedding_projection.")] + kmax_predictor_folded(sd, "_predictor."))
+
+
+# ---- Video-kMaX's pixel decoder ---------------------------------------------------------------------------------------------------------
+# AxvsKpixBlockParams / AxvsKpixFuseParams hold FOLDED float64 tensors as well (a slot the configuration does not have is None); the
+# names are kMaXPixelDecoder's own state-dict names.
+def kmax_pix_block_cin(in_channels0: int, dec_channels: Sequence[int], stage: int, j: int) -> int:
+    return 4 * dec_channels[stage] if j > 0 else in_channels0 if stage == 0 else dec_channels[stage]
+
+
+def kmax_pix_axis_shapes(b: int) -> List[tuple]:
+    """(slot, shape) of AxvsKpixAxisParams, in order (_lib.KPIX_AXIS_FIELDS)"""
+    return [("qkv_w", (4 * b, 2 * b)), ("qkv_b", (4 * b,)), ("eq", (509, b // 8)), ("ek", (509, b // 8)), ("ev", (509, b // 4)), ("sim_a", (24,)),
+            ("out_ab", (3, 2 * b))]
+
+
+def kmax_pix_block_shapes(cin: int, b: int, axial: bool) -> List[tuple]:
+    """(slot, shape or None) of AxvsKpixBlockParams, in order (_lib.KPIX_BLOCK_FIELDS)"""
+    mid, sc = (2 * b if axial else b), cin != 4 * b
+    axis = kmax_pix_axis_shapes(b) if axial else [(n, None) for n, _ in kmax_pix_axis_shapes(b)]
+    return ([("sc_w", (4 * b, cin) if sc else None), ("sc_b", (4 * b,) if sc else None), ("c1_w", (mid, cin)), ("c1_b", (mid,)),
+             ("c2_w", None if axial else (9, b, b)), ("c2_b", None if axial else (b,))]
+            + [("height." + n, s) for n, s in axis] + [("width." + n, s) for n, s in axis] + [("c3_w", (4 * b, mid)), ("c3_b", (4 * b,))])
+
+
+def kmax_pix_fuse_shapes(low: int, high: int, b: int) -> List[tuple]:
+    """(slot, shape or None) of AxvsKpixFuseParams, in order (_lib.KPIX_FUSE_FIELDS)"""
+    return [("ln_w", (high,)), ("ln_b", (high,)), ("low_w", (b, low) if low != b else None), ("low_b", (b,) if low != b else None),
+            ("high_w", (b, high) if high != b else None), ("high_b", (b,) if high != b else None)]
+
+
+def kmax_pix_axis_folded(sd, p: str) -> List[Tensor]:
+    """AxvsKpixAxisParams of the AxialAttention `p`: the qkv BatchNorm folded into the projection; of the similarity BatchNorm only the
+    gains (its offsets are constant over the keys and cancel in the softmax); the retrieved-output BatchNorm as two gain rows and the
+    sum of the two offset halves (the reference sums the two halves after the norm)."""
+    w = sd[p + "qkv_transform.conv.weight"].double().flatten(1)
+    a, c = _kmax_affine(sd, p + "_batch_norm_qkv.")
+    sa, _ = _kmax_affine(sd, p + "_batch_norm_similarity.")
+    ra, rc = _kmax_affine(sd, p + "_batch_norm_retrieved_output.")
+    dv = ra.numel() // 2
+    return [w * a[:, None], c, sd[p + "_query_rpe._embeddings.weight"].double(), sd[p + "_key_rpe._embeddings.weight"].double(),
+            sd[p + "_value_rpe._embeddings.weight"].double(), sa, torch.stack([ra[:dv], ra[dv:], rc[:dv] + rc[dv:]])]
+
+
+def kmax_pix_block_folded(sd, p: str) -> List[Optional[Tensor]]:
+    """AxvsKpixBlockParams of the SingleBlock `p`; the 3 x 3 weight goes tap-major [9][out][in]"""
+    sc = list(_kmax_convbn(sd, p + "_shortcut.")) if p + "_shortcut.conv.weight" in sd else [None, None]
+    if p + "_conv2_bn_act.conv.weight" in sd:
+        w, b = _kmax_convbn(sd, p + "_conv2_bn_act.")
+        mid = [w.view(w.shape[0], -1, 9).permute(2, 0, 1).contiguous(), b] + [None] * 14
+    else:
+        mid = [None, None] + kmax_pix_axis_folded(sd, p + "_attention._height_axis.") + kmax_pix_axis_folded(sd, p + "_attention._width_axis.")
+    return sc + list(_kmax_convbn(sd, p + "_conv1_bn_act.")) + mid + list(_kmax_convbn(sd, p + "_conv3_bn."))
+
+
+def kmax_pix_fuse_folded(sd, index: int) -> List[Optional[Tensor]]:
+    """AxvsKpixFuseParams of `_resized_fuses.{index}` with the LayerNorm of its high-resolution input, `_in_norms.{index + 1}`"""
+    p = f"_resized_fuses.{index}."
+    low = list(_kmax_convbn(sd, p + "_conv_bn_low.")) if p + "_conv_bn_low.conv.weight" in sd else [None, None]
+    high = list(_kmax_convbn(sd, p + "_conv_bn_high.")) if p + "_conv_bn_high.conv.weight" in sd else [None, None]
+    return [sd[f"_in_norms.{index + 1}.weight"].double(), sd[f"_in_norms.{index + 1}.bias"].double()] + low + high

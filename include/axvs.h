@@ -980,6 +980,60 @@ int axvs_kmax_assign_fwd(const AxvsKmaxCfg* cfg, const void* packed, int layer, 
 int axvs_kmax_layer_fwd(const AxvsKmaxCfg* cfg, const void* packed, int layer, const float* query, const float* feature, const int* idx, float* out,
                         void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Video-kMaX's pixel decoder (kMaXPixelDecoder in eval mode: four stages of SingleBlocks from stride 32 down to stride 4, a
+ * ResizedFuse in front of stages 1..3) ------------------------------------------------------------------------------------------------
+ * All tensors fp32; forward only.  N frames, each on its own: features[i] [N, in_channels[i], h[i], w[i]], stage 0 the coarsest.
+ * Stage i: blocks[i] SingleBlocks of base filter base[i], axial[i] != 0: axial-attention blocks (1x1 -> height-axis and width-axis
+ * attention with relative positions, 8 heads, key depth base/8, value depth 2*base/8 -> 1x1), else bottleneck blocks (1x1 -> 3x3 ->
+ * 1x1); a stage's output has 4 * base[i] channels.  Equal inputs give equal bits, and a frame's bits do not depend on the frames beside it.
+ * Bounds (AXVS_ERR_ARG outside them): heads 8; 1..16 blocks per stage; axial base filter 512, 256 or 128 and axis lengths h, w <= 128
+ * (<= 80 at base filter 512: what the attention kernel's LDS holds), N * max(h, w) <= 65535; bottleneck base filter a multiple of 32
+ * up to 256; in_channels multiples of 16 up to 2048; N*h*w < 2^24 per stage, N <= 4096.
+ * Parameters arrive FOLDED (every BatchNorm as an affine map on its running statistics, eps 1e-3, folded in float64 by the caller into
+ * the convolution in front of it) and in the layouts the kernels read.  A block: sc [4b][cin] + [4b] (only when cin != 4b, else NULL),
+ * c1 [mid][cin] + [mid] (mid = 2b axial, b bottleneck), c2 [9][b][b] tap-major + [b] (bottleneck only), c3 [4b][mid] + [4b]; an axis
+ * (axial only): qkv [4b][2b] + [4b] (q b, k b, v 2b rows, heads outermost), eq / ek [509][b/8], ev [509][2b/8] (row r + 254 for the
+ * offset r = m - l), sim_a [24] the gains of the similarity BatchNorm (channel part*8 + head; its offsets cancel in the softmax),
+ * out_ab [3][2b]: the gains of the retrieved content and of the retrieved positions, then the sum of the two offsets.
+ * A fuse (in front of stage i): ln [in_channels[i]] x 2 the LayerNorm (eps 1e-6) of the high-resolution input, low [b][4 b_prev] + [b]
+ * (only when 4 b_prev != b), high [b][in_channels[i]] + [b] (only when in_channels[i] != b). */
+typedef struct AxvsKpixAxisParams {
+  const float *qkv_w, *qkv_b, *eq, *ek, *ev, *sim_a, *out_ab;
+} AxvsKpixAxisParams;
+typedef struct AxvsKpixBlockParams {
+  const float *sc_w, *sc_b, *c1_w, *c1_b, *c2_w, *c2_b;
+  AxvsKpixAxisParams height, width;
+  const float *c3_w, *c3_b;
+} AxvsKpixBlockParams;
+typedef struct AxvsKpixFuseParams {
+  const float *ln_w, *ln_b, *low_w, *low_b, *high_w, *high_b;
+} AxvsKpixFuseParams;
+typedef struct AxvsKpixCfg {
+  int N;
+  int in_channels[4], h[4], w[4];
+  int base[4], blocks[4], axial[4];
+  int heads;
+} AxvsKpixCfg;
+size_t axvs_kmax_pix_packed_bytes(const AxvsKpixCfg* cfg);      /* depends on the channels, blocks and stage types only; 0: cfg refused */
+/* blocks: sum(cfg->blocks) structs, stage after stage; fuses: three; ln0: the LayerNorm of features[0].  Copies on `stream`; the
+ * parameter tensors must stay alive until they have run. */
+int axvs_kmax_pix_pack(const AxvsKpixBlockParams* blocks, const AxvsKpixFuseParams* fuses, const float* ln0_w, const float* ln0_b, const AxvsKpixCfg* cfg,
+                       void* packed, void* stream);
+size_t axvs_kmax_pix_workspace_bytes(const AxvsKpixCfg* cfg);   /* enough for the decoder and for every stage entry below */
+/* features, outputs: host arrays of four device pointers; outputs[i] [N, 4 base[i], h[i], w[i]]: the raw (pre-gelu) output of stage i */
+int axvs_kmax_pix_decoder_fwd(const AxvsKpixCfg* cfg, const void* packed, const float* const* features, float* const* outputs, void* workspace,
+                              long long workspace_bytes, void* stream);
+/* Stage entries.  block_index counts the blocks of all stages; the block's stage gives h, w and the base filter b.
+ * One axis pass (axis 0: the columns of a frame, 1: its rows) on qkv rows [N, h, w, 4b] (after the qkv BatchNorm) -> out [N, h, w, 2b]. */
+int axvs_kmax_pix_axial_attn_fwd(const AxvsKpixCfg* cfg, const void* packed, int block_index, int axis, const float* qkv, float* out, void* stream);
+/* one SingleBlock: x [N, cin, h, w] -> out [N, 4b, h, w] */
+int axvs_kmax_pix_block_fwd(const AxvsKpixCfg* cfg, const void* packed, int block_index, const float* x, float* out, void* workspace,
+                            long long workspace_bytes, void* stream);
+/* one ResizedFuse (fuse_index 0..2, in front of stage fuse_index + 1), the LayerNorm of its high-resolution input included:
+ * low [N, 4 b_prev, h_prev, w_prev], high = features[fuse_index + 1] -> out [N, b, h, w] */
+int axvs_kmax_pix_fuse_fwd(const AxvsKpixCfg* cfg, const void* packed, int fuse_index, const float* low, const float* high, float* out, void* workspace,
+                           long long workspace_bytes, void* stream);
+
 /* ---- test hooks, not part of the drop-in surface ----------------------------------------------------------------------------------
  * One call of the training tier's split-precision GEMM dispatch (tr_gemm_nt_kernel / tr_gemm_tn_kernel behind the host code every
  * training entry point above uses), with every operand, stride and epilogue field explicit: what tests/test_hip_train_gemm.py holds
