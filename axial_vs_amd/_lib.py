@@ -161,6 +161,22 @@ class AxvsKpixCfg(C.Structure):
     _fields_ = [("N", C.c_int)] + [(n, C.c_int * 4) for n in ("in_channels", "h", "w", "base", "blocks", "axial")] + [("heads", C.c_int)]
 
 
+CNX_DOWN_FIELDS = ("ln_w", "ln_b", "w", "b")
+CNX_BLOCK_FIELDS = ("dw_w", "dw_b", "ln_w", "ln_b", "w1", "b1", "w2", "b2", "grn_gamma")
+
+
+class AxvsCnxDownParams(C.Structure):
+    _fields_ = [(n, _fp) for n in CNX_DOWN_FIELDS]
+
+
+class AxvsCnxBlockParams(C.Structure):
+    _fields_ = [(n, _fp) for n in CNX_BLOCK_FIELDS]
+
+
+class AxvsCnxCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("N", "H", "W")] + [(n, C.c_int * 4) for n in ("dims", "depths", "h", "w")] + [("v2", C.c_int)]
+
+
 class AxvsMsdaParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
                                    "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
@@ -360,6 +376,14 @@ SIGNATURES = {
     "axvs_kmax_pix_axial_attn_fwd": (C.c_int, [C.POINTER(AxvsKpixCfg), _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
     "axvs_kmax_pix_block_fwd": (C.c_int, [C.POINTER(AxvsKpixCfg), _fp, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
     "axvs_kmax_pix_fuse_fwd": (C.c_int, [C.POINTER(AxvsKpixCfg), _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_longlong, _fp]),
+    "axvs_cnx_packed_bytes": (C.c_size_t, [C.POINTER(AxvsCnxCfg)]),
+    "axvs_cnx_pack": (C.c_int, [C.POINTER(AxvsCnxDownParams), C.POINTER(AxvsCnxBlockParams), C.POINTER(AxvsCnxCfg), _fp, _fp]),
+    "axvs_cnx_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsCnxCfg)]),
+    "axvs_cnx_fwd": (C.c_int, [C.POINTER(AxvsCnxCfg), _fp, _fp, C.POINTER(_fp), _fp, C.c_longlong, _fp]),
+    "axvs_cnx_stem_fwd": (C.c_int, [C.POINTER(AxvsCnxCfg), _fp, _fp, _fp, _fp, C.c_longlong, _fp]),
+    "axvs_cnx_down_fwd": (C.c_int, [C.POINTER(AxvsCnxCfg), _fp, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
+    "axvs_cnx_dwln_fwd": (C.c_int, [C.POINTER(AxvsCnxCfg), _fp, C.c_int, _fp, _fp, _fp]),
+    "axvs_cnx_block_fwd": (C.c_int, [C.POINTER(AxvsCnxCfg), _fp, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

@@ -286,3 +286,46 @@ def kmax_pix_fuse_folded(sd, index: int) -> List[Optional[Tensor]]:
     low = list(_kmax_convbn(sd, p + "_conv_bn_low.")) if p + "_conv_bn_low.conv.weight" in sd else [None, None]
     high = list(_kmax_convbn(sd, p + "_conv_bn_high.")) if p + "_conv_bn_high.conv.weight" in sd else [None, None]
     return [sd[f"_in_norms.{index + 1}.weight"].double(), sd[f"_in_norms.{index + 1}.bias"].double()] + low + high
+
+
+# ---- ConvNeXt / ConvNeXtV2 backbone -------------------------------------------------------------------------------------------------------
+# AxvsCnxDownParams / AxvsCnxBlockParams hold FOLDED float64 tensors in the kernels' layouts; the names are the reference ConvNeXt's own
+# state-dict names.
+def convnext_down_shapes(dims: Sequence[int], i: int) -> List[tuple]:
+    """(slot, shape) of AxvsCnxDownParams for downsample layer i (0: the stem), in order (_lib.CNX_DOWN_FIELDS)"""
+    ln, k = (dims[0], 48) if i == 0 else (dims[i - 1], 4 * dims[i - 1])
+    return [("ln_w", (ln,)), ("ln_b", (ln,)), ("w", (dims[i], k)), ("b", (dims[i],))]
+
+
+def convnext_block_shapes(dim: int, v2: bool) -> List[tuple]:
+    """(slot, shape or None) of AxvsCnxBlockParams, in order (_lib.CNX_BLOCK_FIELDS)"""
+    return [("dw_w", (49, dim)), ("dw_b", (dim,)), ("ln_w", (dim,)), ("ln_b", (dim,)), ("w1", (4 * dim, dim)), ("b1", (4 * dim,)),
+            ("w2", (dim, 4 * dim)), ("b2", (dim,)), ("grn_gamma", (4 * dim,) if v2 else None)]
+
+
+def convnext_down_folded(sd, i: int) -> List[Tensor]:
+    """AxvsCnxDownParams of `downsample_layers.{i}`.  The stem (conv, then LayerNorm) keeps its weight's own (c, ky, kx) order: the gather
+    kernel writes its patches in it.  Layers 1..3 (LayerNorm, then conv): the weight goes to the patch order (ky, kx, c)."""
+    p = f"downsample_layers.{i}."
+    conv, ln = (p + "0.", p + "1.") if i == 0 else (p + "1.", p + "0.")
+    w = sd[conv + "weight"].double()
+    w = w.flatten(1) if i == 0 else w.permute(0, 2, 3, 1).flatten(1)
+    return [sd[ln + "weight"].double(), sd[ln + "bias"].double(), w.contiguous(), sd[conv + "bias"].double()]
+
+
+def convnext_block_folded(sd, p: str) -> List[Optional[Tensor]]:
+    """AxvsCnxBlockParams of the block `p`.  V1: the layer scale `gamma` (where the block has one) folded into pwconv2.  V2 (the block has
+    `grn.gamma`): gamma (x Nx) + beta + x = x (1 + gamma Nx) + beta, so pwconv2's bias becomes W2 beta + b2 and the per-frame factor
+    reaches the weight on the device."""
+    w2, b2 = sd[p + "pwconv2.weight"].double(), sd[p + "pwconv2.bias"].double()
+    grn = None
+    if p + "grn.gamma" in sd:
+        grn = sd[p + "grn.gamma"].double().flatten()
+        # (a product and a row sum, not `@`: torch's first matrix product on a device allocates its BLAS workspace, 128 MiB that stay)
+        b2 = (w2 * sd[p + "grn.beta"].double().flatten()[None, :]).sum(1) + b2
+    elif p + "gamma" in sd:
+        g = sd[p + "gamma"].double()
+        w2, b2 = w2 * g[:, None], b2 * g
+    dw = sd[p + "dwconv.weight"].double()
+    return [dw.view(dw.shape[0], 49).t().contiguous(), sd[p + "dwconv.bias"].double(), sd[p + "norm.weight"].double(), sd[p + "norm.bias"].double(),
+            sd[p + "pwconv1.weight"].double(), sd[p + "pwconv1.bias"].double(), w2.contiguous(), b2, grn]

@@ -1034,6 +1034,48 @@ int axvs_kmax_pix_block_fwd(const AxvsKpixCfg* cfg, const void* packed, int bloc
 int axvs_kmax_pix_fuse_fwd(const AxvsKpixCfg* cfg, const void* packed, int fuse_index, const float* low, const float* high, float* out, void* workspace,
                            long long workspace_bytes, void* stream);
 
+/* ---- ConvNeXt / ConvNeXtV2 backbone (eval forward; csrc/axvs_convnext.hip) ---------------------------------------------------------------
+ * All tensors fp32; forward only.  N frames, each on its own.  image [N, 3, H, W] -> stem / stage maps of dims[i] channels, h[0] =
+ * floor((H + 3) / 4), w[0] likewise, h[i] = floor((h[i-1] + 1) / 2): the reference's zero padding in front of each patchify convolution.
+ * Stage i: depths[i] blocks (depthwise 7 x 7 -> LayerNorm -> Linear 4x + gelu -> [v2: GRN] -> Linear + residual).  Activations are rows
+ * [N][h][w][C] (channels-last) between the entries; only axvs_cnx_fwd writes NCHW.  Equal inputs give equal bits, and a frame's bits do
+ * not depend on the frames beside it.
+ * Bounds (AXVS_ERR_ARG outside them): dims multiples of 16 in 16..2048; 1..64 blocks per stage; N in 1..4096; h, w in 1..16383 and
+ * N*h*w < 2^24 per stage.  axvs_cnx_fwd also wants h / w to be the sizes H / W give; the step entries read h[stage], w[stage] alone.
+ * Parameters arrive FOLDED by the caller (float64) and in the layouts the kernels read.  Stem (downs[0]): w [dims[0]][48] (the
+ * convolution weight's own (c, ky, kx) order), b, and ln: the LayerNorm BEHIND it.  downs[i], i = 1..3: ln [dims[i-1]] x 2 the LayerNorm in
+ * FRONT, w [dims[i]][4 dims[i-1]] in patch order (ky, kx, c), b.  A block: dw_w [49][C] (tap ky*7 + kx, channel fastest), dw_b, ln x 2,
+ * w1 [4C][C], b1, w2 [C][4C], b2 -- v1: gamma folded into w2 and b2; v2: b2 = W2 beta + b2 and grn_gamma [4C] (NULL for v1). */
+typedef struct AxvsCnxDownParams {
+  const float *ln_w, *ln_b, *w, *b;
+} AxvsCnxDownParams;
+typedef struct AxvsCnxBlockParams {
+  const float *dw_w, *dw_b, *ln_w, *ln_b, *w1, *b1, *w2, *b2, *grn_gamma;
+} AxvsCnxBlockParams;
+typedef struct AxvsCnxCfg {
+  int N, H, W;
+  int dims[4], depths[4], h[4], w[4];
+  int v2;
+} AxvsCnxCfg;
+size_t axvs_cnx_packed_bytes(const AxvsCnxCfg* cfg);      /* depends on dims, depths and v2 only; 0: cfg refused */
+/* downs: four structs (the stem first); blocks: sum(cfg->depths), stage after stage.  Copies on `stream`; the parameter tensors must stay
+ * alive until they have run. */
+int axvs_cnx_pack(const AxvsCnxDownParams* downs, const AxvsCnxBlockParams* blocks, const AxvsCnxCfg* cfg, void* packed, void* stream);
+size_t axvs_cnx_workspace_bytes(const AxvsCnxCfg* cfg);   /* enough for the network and for every step entry below */
+/* outputs: a host array of five device pointers -- stem, res2 .. res5 as [N, dims, h, w]; NULL: that map is not written */
+int axvs_cnx_fwd(const AxvsCnxCfg* cfg, const void* packed, const float* image, float* const* outputs, void* workspace, long long workspace_bytes,
+                 void* stream);
+/* Step entries, rows in and out.  image [N, 3, H, W] -> out [N, h[0], w[0], dims[0]] (patches, convolution, LayerNorm) */
+int axvs_cnx_stem_fwd(const AxvsCnxCfg* cfg, const void* packed, const float* image, float* out, void* workspace, long long workspace_bytes, void* stream);
+/* downsample layer `index` (1..3): x [N, h[index-1], w[index-1], dims[index-1]] -> out [N, h[index], w[index], dims[index]] */
+int axvs_cnx_down_fwd(const AxvsCnxCfg* cfg, const void* packed, int index, const float* x, float* out, void* workspace, long long workspace_bytes,
+                      void* stream);
+/* block_index counts the blocks of all stages; the block's stage gives h, w and C.  Depthwise 7 x 7 + LayerNorm: x [N, h, w, C] -> out alike */
+int axvs_cnx_dwln_fwd(const AxvsCnxCfg* cfg, const void* packed, int block_index, const float* x, float* out, void* stream);
+/* one whole block: x [N, h, w, C] -> out alike (out != x) */
+int axvs_cnx_block_fwd(const AxvsCnxCfg* cfg, const void* packed, int block_index, const float* x, float* out, void* workspace, long long workspace_bytes,
+                       void* stream);
+
 /* ---- test hooks, not part of the drop-in surface ----------------------------------------------------------------------------------
  * One call of the training tier's split-precision GEMM dispatch (tr_gemm_nt_kernel / tr_gemm_tn_kernel behind the host code every
  * training entry point above uses), with every operand, stride and epilogue field explicit: what tests/test_hip_train_gemm.py holds
