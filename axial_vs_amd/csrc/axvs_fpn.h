@@ -11,33 +11,53 @@
 
 namespace axvs {
 
-// GroupNorm statistics from per-block partial sums, in a fixed order (bit-identical from run to run): part [N][nblk][P][2] holds
-// (sum, sum of squares) per block and entry; group g owns entries [g*cpp, (g+1)*cpp) (cpp = 1: per-group partials of gn_stats_kernel,
-// cpp = channels per group: per-channel partials of fpn_conv3x3_kernel).  stats [N][G][2] = (mean, rstd).  Grid (G, N), 256 threads.
-__global__ __launch_bounds__(256) void fpn_gn_finalize_kernel(const float* __restrict__ part, int nblk, int P, int cpp, int G, double cnt, float eps,
-                                                              float* __restrict__ stats) {
-  __shared__ double ss[256], sq[256];
+constexpr int kFpnTH = 8, kFpnTW = 16, kFpnPS = 40;      // tile rows / columns; LDS pixel stride in 16-bit elements (80 B: spreads the banks)
+
+// GroupNorm statistics from per-block partials, in a fixed order (bit-identical from run to run): part [N][nblk][P][2] holds
+// (mean, M2 = sum of squares about that mean) per block and entry, the centred form of gn_stats_kernel (axvs_glue.h: no variance by
+// E[y^2] - mean^2); group g owns entries [g*cpp, (g+1)*cpp) (cpp = 1: per-group partials of gn_stats_kernel, cpp = channels per
+// group: per-channel partials of fpn_conv3x3_kernel).  An entry's count follows from its block: ntx = 0: 64-row blocks of HW = H*W
+// rows x `per_row` values (gn_stats_kernel), ntx > 0: the valid pixels of a kFpnTH x kFpnTW tile of an H x W map (fpn_conv3x3_kernel).
+// First the mean, then M2 about it.  stats [N][G][2] = (mean, rstd).  Grid (G, N), 256 threads.
+__device__ __forceinline__ double fpn_gn_block_count(long long b, int H, int W, int ntx, int per_row) {
+  if (ntx == 0) return (double)(gn_block_rows((int)b, H * W) * per_row);
+  const int ty = (int)(b / ntx), tx = (int)(b - (long long)ty * ntx);
+  return (double)(min(kFpnTH, H - kFpnTH * ty) * min(kFpnTW, W - kFpnTW * tx));
+}
+
+__global__ __launch_bounds__(256) void fpn_gn_finalize_kernel(const float* __restrict__ part, int nblk, int P, int cpp, int G, int H, int W, int ntx, int per_row,
+                                                              double cnt, float eps, float* __restrict__ stats) {
+  __shared__ double sh[256];
   const int g = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
-  double s = 0.0, q = 0.0;
   const long long items = (long long)nblk * cpp;
+  const float* pg = part + ((long long)n * nblk * P + (long long)g * cpp) * 2;
+  auto total = [&](double v) {            // fixed tree over the 256 threads; every thread returns the same bits
+    __syncthreads();
+    sh[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) sh[tid] += sh[tid + o];
+      __syncthreads();
+    }
+    return sh[0];
+  };
+  double s = 0.0;
   for (long long i = tid; i < items; i += 256) {
     const long long b = i / cpp;
-    const int j = (int)(i - b * cpp);
-    const float2 v = *reinterpret_cast<const float2*>(part + (((long long)n * nblk + b) * P + (long long)g * cpp + j) * 2);
-    s += v.x;
-    q += v.y;
+    s += fpn_gn_block_count(b, H, W, ntx, per_row) * (double)pg[(b * P + (i - b * cpp)) * 2];
   }
-  ss[tid] = s;
-  sq[tid] = q;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) { ss[tid] += ss[tid + o]; sq[tid] += sq[tid + o]; }
-    __syncthreads();
+  const double mu = total(s) / cnt;
+  double q = 0.0;
+  for (long long i = tid; i < items; i += 256) {
+    const long long b = i / cpp;
+    const float2 v = *reinterpret_cast<const float2*>(pg + (b * P + (i - b * cpp)) * 2);
+    const double d = (double)v.x - mu;
+    q += (double)v.y + fpn_gn_block_count(b, H, W, ntx, per_row) * d * d;
   }
+  const double m2 = total(q);
   if (tid == 0) {
-    const double mu = ss[0] / cnt, var = fmax(sq[0] / cnt - mu * mu, 0.0);
     stats[((long long)n * G + g) * 2] = (float)mu;
-    stats[((long long)n * G + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    stats[((long long)n * G + g) * 2 + 1] = (float)(1.0 / sqrt(m2 / cnt + (double)eps));
   }
 }
 
@@ -109,9 +129,8 @@ __global__ void fpn_pack3x3_kernel(const float* __restrict__ w, u16* __restrict_
 // (M fragments) x 4 N fragments of 16x16x32 MFMAs.  Per 32-channel input chunk the (8+2) x (16+2) halo tile is staged in LDS once (zeros
 // outside the map: the padding) and read by all nine taps; the next chunk's global loads are in flight during the current chunk's MFMAs
 // (two LDS buffers, one barrier per chunk).  Weights come from L2 in fragment order.
-// Epilogue: raw fp32 rows y [N*H*W][Cout] and, per (frame, tile, channel), (sum, sum of squares) over the tile's pixels ->
+// Epilogue: raw fp32 rows y [N*H*W][Cout] and, per (frame, tile, channel), (mean, sum of squares about it) over the tile's pixels ->
 // part [N][tiles][Cout][2] (lanes of a channel combined by a fixed xor butterfly).
-constexpr int kFpnTH = 8, kFpnTW = 16, kFpnPS = 40;      // tile rows / columns; LDS pixel stride in 16-bit elements (80 B: spreads the banks)
 constexpr int kFpnHalo = (kFpnTH + 2) * (kFpnTW + 2);
 
 template <bool BF>
@@ -189,7 +208,7 @@ __global__ __launch_bounds__(256) void fpn_conv3x3_kernel(const u16* __restrict_
   for (int f = 0; f < 4; ++f) {
     if (f >= nfr) break;
     const int ch = n0 + 16 * f + fi;
-    float s = 0.f, q = 0.f;
+    float s = 0.f;
 #pragma unroll
     for (int mi = 0; mi < kFpnTH; ++mi) {
       const int gy = ty0 + mi;
@@ -200,15 +219,27 @@ __global__ __launch_bounds__(256) void fpn_conv3x3_kernel(const u16* __restrict_
           const float v = acc[mi][f][r];
           y[(((long long)n * H + gy) * W + gx) * Cout + ch] = v;
           s += v;
-          q += v * v;
         }
       }
     }
     s += __shfl_xor(s, 16, 64);
-    q += __shfl_xor(q, 16, 64);
     s += __shfl_xor(s, 32, 64);
+    // the tile's mean (the same bits on the four lanes of a channel), then the squares about it: the accumulators are still in registers
+    const float mu = s / (float)(min(kFpnTH, H - ty0) * min(kFpnTW, W - tx0));
+    float q = 0.f;
+#pragma unroll
+    for (int mi = 0; mi < kFpnTH; ++mi) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (ty0 + mi < H && tx0 + 4 * fg + r < W) {
+          const float d = acc[mi][f][r] - mu;
+          q += d * d;
+        }
+      }
+    }
+    q += __shfl_xor(q, 16, 64);
     q += __shfl_xor(q, 32, 64);
-    if (fg == 0) *reinterpret_cast<float2*>(part + (((long long)n * ntiles + tile) * Cout + ch) * 2) = float2{s, q};
+    if (fg == 0) *reinterpret_cast<float2*>(part + (((long long)n * ntiles + tile) * Cout + ch) * 2) = float2{mu, q};
   }
 }
 

@@ -95,11 +95,20 @@ struct ALoadTokensSplit3 {
 };
 
 // GroupNorm statistics over token rows y [N*HW][C], deterministic (no atomics: a 1-ulp change of a statistic flips 16-bit
-// roundings downstream and shows up as run-to-run differences of whole f16 ulps).  Stage 1: one workgroup = 64 rows of one
-// sample, thread = 4 consecutive channels -> per-channel sums in LDS -> per-group partials [N][nblk][G][2] in channel order.
-// Stage 2 (gn_finalize_kernel): partials summed in block order -> stats [N][G][2] = (sum, sum of squares).
+// roundings downstream and shows up as run-to-run differences of whole f16 ulps), and CENTRED: the variance is never formed as
+// E[y^2] - mean^2 (a projection of post-ReLU backbone maps has groups whose mean is tens of standard deviations; the raw second
+// moment loses (mean / std)^2 ulps there, torch's group_norm only mean / std).  Every level carries (count, mean, M2 = sum of
+// squares about its own mean); the counts follow from the indices and are not stored.  A parent of children i is, in a fixed order,
+//     mean = ref + sum_i n_i (mean_i - ref) / n      (ref = the first child's mean: the sum is of std-sized terms, so the mean is
+//     M2   = sum_i M2_i + n_i (mean_i - mean)^2       rounded at ITS size once per level, not once per addend)
+// Stage 1: one workgroup = 64 rows of one sample, thread = 4 consecutive channels of every RG-th row, one sweep with the thread's
+// first row y0 as the reference: a = sum (y - y0), q = sum (y - y0)^2 -> mean = y0 + a / n, M2 = q - a^2 / n per (row group,
+// channel) in LDS -> per (block, group), row groups then channels: partial [N][nblk][G][2] = (mean, M2) of the block's rows x cg values.
+// Stage 2: the blocks' partials merged in block order by whoever needs them (gn_apply_kernel's prologue, fpn_gn_finalize_kernel).
+__device__ __forceinline__ int gn_block_rows(int b, int HW) { return min(64, HW - 64 * b); }      // rows of 64-row block b
+
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ y, float* __restrict__ partial, int HW, int C, int G) {
-  extern __shared__ float chs[];                        // [RG][C] sums | [RG][C] sums of squares (RG row groups)
+  extern __shared__ float chs[];                        // [RG][C] means | [RG][C] M2 about them (RG row groups)
   const int n = blockIdx.y, r0 = blockIdx.x * 64, tid = threadIdx.x;
   const int rows = min(64, HW - r0);
   // threads = `lanes` float4 columns x RG row groups (C = 256: 64 x 4, 16 rows each, loads independent of one another): the
@@ -109,26 +118,43 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
   float* chq = chs + RG * C;
   for (int c0 = 0; c0 < n4; c0 += lanes) {
     const int c4 = c0 + col;
-    float4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
     if (g < RG && c4 < n4) {
+      const float* yc = y + ((long long)n * HW + r0) * C + c4 * 4;
+      float4 a = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f}, v0 = {0.f, 0.f, 0.f, 0.f};
+      if (g < rows) v0 = *reinterpret_cast<const float4*>(yc + (long long)g * C);
 #pragma unroll 4
       for (int r = g; r < rows; r += RG) {
-        const float4 v = *reinterpret_cast<const float4*>(y + ((long long)n * HW + r0 + r) * C + c4 * 4);
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        q.x += v.x * v.x; q.y += v.y * v.y; q.z += v.z * v.z; q.w += v.w * v.w;
+        const float4 v = *reinterpret_cast<const float4*>(yc + (long long)r * C);
+        const float4 d = {v.x - v0.x, v.y - v0.y, v.z - v0.z, v.w - v0.w};
+        a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
+        q.x += d.x * d.x; q.y += d.y * d.y; q.z += d.z * d.z; q.w += d.w * d.w;
       }
-      *reinterpret_cast<float4*>(chs + g * C + c4 * 4) = s;
-      *reinterpret_cast<float4*>(chq + g * C + c4 * 4) = q;
+      const float inv = 1.f / (float)max(1, (rows - g + RG - 1) / RG);      // my rows: g, g + RG, ...  (none: the entry is not read)
+      *reinterpret_cast<float4*>(chs + g * C + c4 * 4) = float4{v0.x + a.x * inv, v0.y + a.y * inv, v0.z + a.z * inv, v0.w + a.w * inv};
+      *reinterpret_cast<float4*>(chq + g * C + c4 * 4) =
+          float4{fmaxf(q.x - a.x * a.x * inv, 0.f), fmaxf(q.y - a.y * a.y * inv, 0.f), fmaxf(q.z - a.z * a.z * inv, 0.f), fmaxf(q.w - a.w * a.w * inv, 0.f)};
     }
   }
   __syncthreads();
-  const int cg = C / G;
+  const int cg = C / G, jn = min(RG, rows);
   for (int gg = tid; gg < G; gg += 256) {
-    float s = 0.f, q = 0.f;
-    for (int j = 0; j < RG; ++j)                          // fixed order: row groups, then channels
-      for (int c = gg * cg; c < (gg + 1) * cg; ++c) { s += chs[j * C + c]; q += chq[j * C + c]; }
+    const float ref = chs[gg * cg];
+    float s = 0.f;
+    for (int j = 0; j < jn; ++j) {                        // fixed order: row groups, then channels
+      const float nj = (float)((rows - j + RG - 1) / RG);
+      for (int c = gg * cg; c < (gg + 1) * cg; ++c) s += nj * (chs[j * C + c] - ref);
+    }
+    const float mu = ref + s / (float)(rows * cg);
+    float m2 = 0.f;
+    for (int j = 0; j < jn; ++j) {
+      const float nj = (float)((rows - j + RG - 1) / RG);
+      for (int c = gg * cg; c < (gg + 1) * cg; ++c) {
+        const float d = chs[j * C + c] - mu;
+        m2 += chq[j * C + c] + nj * d * d;
+      }
+    }
     float* o = partial + (((long long)n * gridDim.x + blockIdx.x) * G + gg) * 2;
-    o[0] = s; o[1] = q;
+    o[0] = mu; o[1] = m2;
   }
 }
 
@@ -147,32 +173,46 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
   const int cg = C / G;
   const float cnt = (float)HW * cg;
   {
-    // statistics of my groups from the blocks' partial sums, in a fixed order (every workgroup that needs a group computes the same
-    // bits): one wave per group, lanes stride over the blocks, xor butterfly
+    // statistics of my groups from the blocks' (mean, M2), in a fixed order (every workgroup that needs a group computes the same
+    // bits): one wave per group, lanes stride over the blocks, xor butterfly; first the mean (about block 0's), then M2 about it
     const int g_first = c0 / cg, g_last = min(c0 + 63, C - 1) / cg, lane = tid & 63;
     for (int g = g_first + (tid >> 6); g <= g_last; g += 4) {
-      float s = 0.f, q = 0.f;
+      const float* pg = partial + ((long long)n * nblk * G + g) * 2;
       // eight partials per lane in flight at a time, added in block order as before (round 6: one dependent load per 64 blocks made this prologue a
-      // chain of L2 round trips in front of EVERY workgroup's 16 KB of work on the large maps: 257 blocks at the shipped VIPSeg res3 size)
-      for (int b0 = lane; b0 < nblk; b0 += 64 * 8) {
-        float2 pv[8];
+      // chain of L2 round trips in front of EVERY workgroup's 16 KB of work on the large maps: 257 blocks at the shipped VIPSeg res3 size);
+      // the first eight stay in registers for the second sweep, blocks past 512 are read again
+      float2 pv[8];
+      float nb[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int b = b0 + 64 * u;
-          pv[u] = b < nblk ? *reinterpret_cast<const float2*>(partial + (((long long)n * nblk + b) * G + g) * 2) : float2{0.f, 0.f};
-        }
+      for (int u = 0; u < 8; ++u) {
+        const int b = lane + 64 * u;
+        pv[u] = b < nblk ? *reinterpret_cast<const float2*>(pg + (long long)b * G * 2) : float2{0.f, 0.f};
+        nb[u] = b < nblk ? (float)(gn_block_rows(b, HW) * cg) : 0.f;
+      }
+      const float ref = pg[0];                // block 0's mean: the reference of this level (the same bits in every lane and workgroup)
+      float s = 0.f;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { s += pv[u].x; q += pv[u].y; }
+      for (int u = 0; u < 8; ++u) s += nb[u] * (pv[u].x - ref);
+      for (int b = lane + 512; b < nblk; b += 64) s += (float)(gn_block_rows(b, HW) * cg) * (pg[(long long)b * G * 2] - ref);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      const float mu = ref + s / cnt;
+      float q = 0.f;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const float d = pv[u].x - mu;
+        q += pv[u].y + nb[u] * d * d;
+      }
+      for (int b = lane + 512; b < nblk; b += 64) {
+        const float2 p = *reinterpret_cast<const float2*>(pg + (long long)b * G * 2);
+        const float d = p.x - mu;
+        q += p.y + (float)(gn_block_rows(b, HW) * cg) * d * d;
       }
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o, 64);
-        q += __shfl_xor(q, o, 64);
-      }
+      for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
       if (lane == 0) {
-        const float mu = s / cnt;
         gmu[g - g_first] = mu;
-        grs[g - g_first] = rsqrtf(fmaxf(q / cnt - mu * mu, 0.f) + eps);
+        grs[g - g_first] = 1.f / sqrtf(q / cnt + eps);      // correctly rounded steps (rsqrtf is an approximation of a few ulps; one lane per group pays)
       }
     }
     __syncthreads();

@@ -3,7 +3,7 @@
 // backbone maps and its output maps.  fp32 tensors, the GEMMs on the training tier's split-precision kernels (axvs_train_gemm.h: three bf16 pieces
 // forward -- fp32 accuracy --, two backward), GroupNorm statistics and their gradients in fp32 with fixed summation orders (no atomics).
 //   forward   y = x W^T + b            [M = N HW rows, Cout]                   (token rows; an NCHW input is transposed once)
-//             mean, rstd per (sample n, group g) over HW x Cout/G values
+//             mean, rstd per (sample n, group g) over HW x Cout/G values, centred at every level (block, channel, group): no E[y^2] - mean^2
 //             out = (y - mean) rstd gamma + beta
 //   backward  xhat = (y - mean) rstd;   A[n,c] = sum_p d_out,  B[n,c] = sum_p d_out xhat
 //             d_beta = sum_n A,  d_gamma = sum_n B,  S1[n,g] = sum_{c in g} gamma_c A[n,c],  S2[n,g] = sum_{c in g} gamma_c B[n,c]
@@ -72,8 +72,12 @@ __global__ __launch_bounds__(256) void gt_gather_tokens_kernel(const float* __re
   *reinterpret_cast<float4*>(dst + r * C + c4 * 4) = *reinterpret_cast<const float4*>(src + n * batch_stride + p * ld + c4 * 4);
 }
 
-// Per-(sample, 64-row block, channel) column sums: a = sum v, b = sum v w with w = 1 (statistics: v = y, "b" = sum y^2 through w = y) or w = xhat (backward).
-// MODE 0: (sum y, sum y^2);  MODE 1: (sum d, sum d xhat), xhat = (y - mean[n,g]) rstd[n,g].   part [N][nblk][C][2], fixed order inside the block.
+// Per-(sample, 64-row block, channel) column sums, part [N][nblk][C][2], fixed order inside the block.
+// MODE 0 (forward statistics): (mean of y, M2 = sum of squares of y about it) of the block's rows of the channel.  Never sum y^2, nor y itself: a group whose
+//         mean is tens of standard deviations loses (mean / std)^2 ulps in E[y^2] - mean^2, and a long fp32 sum of such values rounds at the sum's size at
+//         every step.  One sweep with the block's first row y0 as the reference: a = sum (y - y0), q = sum (y - y0)^2, mean = y0 + a / rows,
+//         M2 = q - a^2 / rows.  Merged upwards as in axvs_glue.h's gn_stats_kernel (gt_merge_blocks_kernel, gt_group_stats_kernel).
+// MODE 1 (backward): (sum d, sum d xhat), xhat = (y - mean[n,g]) rstd[n,g].
 template <int MODE>
 __global__ __launch_bounds__(256) void gt_block_colsums_kernel(const float* __restrict__ v, const float* __restrict__ y, const float* __restrict__ stats /* [N][G][2] */,
                                                                float* __restrict__ part, int HW, int C, int G) {
@@ -90,24 +94,33 @@ __global__ __launch_bounds__(256) void gt_block_colsums_kernel(const float* __re
         rs[k] = stats[((long long)n * G + g) * 2 + 1];
       }
     }
+    float4 sh = {0.f, 0.f, 0.f, 0.f}, e = {0.f, 0.f, 0.f, 0.f};      // MODE 0: the reference (first row), sums of (y - reference)
+    if (MODE == 0) sh = *reinterpret_cast<const float4*>(v + ((long long)n * HW + r0) * C + c4 * 4);
     for (int r = 0; r < rows; ++r) {
       const long long o = ((long long)n * HW + r0 + r) * C + c4 * 4;
       const float4 d = *reinterpret_cast<const float4*>(v + o);
-      a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
       if (MODE == 0) {
-        b.x += d.x * d.x; b.y += d.y * d.y; b.z += d.z * d.z; b.w += d.w * d.w;
+        const float4 t = {d.x - sh.x, d.y - sh.y, d.z - sh.z, d.w - sh.w};
+        e.x += t.x; e.y += t.y; e.z += t.z; e.w += t.w;
+        b.x += t.x * t.x; b.y += t.y * t.y; b.z += t.z * t.z; b.w += t.w * t.w;
       } else {
+        a.x += d.x; a.y += d.y; a.z += d.z; a.w += d.w;
         const float4 yy = *reinterpret_cast<const float4*>(y + o);
         b.x += d.x * ((yy.x - mu[0]) * rs[0]); b.y += d.y * ((yy.y - mu[1]) * rs[1]);
         b.z += d.z * ((yy.z - mu[2]) * rs[2]); b.w += d.w * ((yy.w - mu[3]) * rs[3]);
       }
+    }
+    if (MODE == 0) {
+      const float inv = 1.f / (float)rows;
+      a = float4{sh.x + e.x * inv, sh.y + e.y * inv, sh.z + e.z * inv, sh.w + e.w * inv};
+      b = float4{fmaxf(b.x - e.x * e.x * inv, 0.f), fmaxf(b.y - e.y * e.y * inv, 0.f), fmaxf(b.z - e.z * e.z * inv, 0.f), fmaxf(b.w - e.w * e.w * inv, 0.f)};
     }
     float* o = part + (((long long)n * gridDim.x + blockIdx.x) * C + c4 * 4) * 2;
     o[0] = a.x; o[1] = b.x; o[2] = a.y; o[3] = b.y; o[4] = a.z; o[5] = b.z; o[6] = a.w; o[7] = b.w;
   }
 }
 
-// ab [N][C][2] = sum over the blocks (block order)
+// ab [N][C][2] = sum over the blocks (block order): the backward's (sum d, sum d xhat)
 __global__ __launch_bounds__(256) void gt_sum_blocks_kernel(const float* __restrict__ part, float* __restrict__ ab, int nblk, int C, long long total /* N * C */) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -121,16 +134,40 @@ __global__ __launch_bounds__(256) void gt_sum_blocks_kernel(const float* __restr
   ab[i * 2] = a; ab[i * 2 + 1] = b;
 }
 
-// forward statistics: stats [N][G] = (mean, rstd) from ab = (sum y, sum y^2) per (n, c), channels of a group in order
-__global__ __launch_bounds__(256) void gt_group_stats_kernel(const float* __restrict__ ab, float* __restrict__ stats, int C, int G, float cnt, float eps, int total /* N * G */) {
+// forward statistics, blocks -> channel: ab [N][C][2] = (mean, M2 about it) of the channel from the blocks' (mean, M2) in block order, about block 0's mean
+__global__ __launch_bounds__(256) void gt_merge_blocks_kernel(const float* __restrict__ part, float* __restrict__ ab, int nblk, int C, int HW, long long total /* N * C */) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long long n = i / C;
+  const int c = (int)(i - n * C);
+  const float* p = part + ((long long)n * nblk * C + c) * 2;
+  const float ref = p[0];
+  float s = 0.f;
+  for (int k = 0; k < nblk; ++k) s += (float)min(64, HW - 64 * k) * (p[(long long)k * C * 2] - ref);
+  const float mu = ref + s / (float)HW;
+  float m2 = 0.f;
+  for (int k = 0; k < nblk; ++k) {
+    const float d = p[(long long)k * C * 2] - mu;
+    m2 += p[(long long)k * C * 2 + 1] + (float)min(64, HW - 64 * k) * d * d;
+  }
+  ab[i * 2] = mu; ab[i * 2 + 1] = m2;
+}
+
+// forward statistics, channels -> group: stats [N][G] = (mean, rstd) from ab = (mean, M2) per (n, c) over HW values each, channels of a group in order, in double
+__global__ __launch_bounds__(256) void gt_group_stats_kernel(const float* __restrict__ ab, float* __restrict__ stats, int C, int G, int HW, float eps, int total /* N * G */) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int n = i / G, g = i - n * G, cg = C / G;
-  double s = 0.0, q = 0.0;       // (a few hundred channel sums per group: double keeps E[y^2] - mean^2 from cancelling)
-  for (int c = g * cg; c < (g + 1) * cg; ++c) { s += ab[((long long)n * C + c) * 2]; q += ab[((long long)n * C + c) * 2 + 1]; }
-  const double mu = s / cnt, var = q / cnt - mu * mu;
+  const float* a = ab + ((long long)n * C + (long long)g * cg) * 2;
+  double s = 0.0, m2 = 0.0;
+  for (int c = 0; c < cg; ++c) s += a[c * 2];
+  const double mu = s / cg;
+  for (int c = 0; c < cg; ++c) {
+    const double d = (double)a[c * 2] - mu;
+    m2 += (double)a[c * 2 + 1] + HW * d * d;
+  }
   stats[i * 2] = (float)mu;
-  stats[i * 2 + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
+  stats[i * 2 + 1] = (float)(1.0 / sqrt(m2 / ((double)HW * cg) + (double)eps));
 }
 
 // out = (y - mean) rstd gamma + beta on token rows (contiguous y; out rows at n * out_batch_stride + p * out_ld)

@@ -680,9 +680,8 @@ int axvs_conv1x1_gn_train_fwd(const float* x, int in_layout, long long in_batch_
   if (int rc = c.g.fwd(xt, p->conv_w, b.y, M, Cout, Cin, 0.f, &e, true)) return rc;
   hipLaunchKernelGGL((gt_block_colsums_kernel<0>), dim3((unsigned)nblk, (unsigned)N), dim3(256), 0, st, (const float*)b.y, (const float*)nullptr, (const float*)nullptr, b.part,
                      HW, Cout, groups);
-  hipLaunchKernelGGL(gt_sum_blocks_kernel, dim3(blocks((size_t)N * Cout)), dim3(256), 0, st, (const float*)b.part, b.ab, nblk, Cout, (long long)N * Cout);
-  hipLaunchKernelGGL(gt_group_stats_kernel, dim3(blocks((size_t)N * groups)), dim3(256), 0, st, (const float*)b.ab, b.stats, Cout, groups,
-                     (float)((double)HW * (Cout / groups)), eps, N * groups);
+  hipLaunchKernelGGL(gt_merge_blocks_kernel, dim3(blocks((size_t)N * Cout)), dim3(256), 0, st, (const float*)b.part, b.ab, nblk, Cout, HW, (long long)N * Cout);
+  hipLaunchKernelGGL(gt_group_stats_kernel, dim3(blocks((size_t)N * groups)), dim3(256), 0, st, (const float*)b.ab, b.stats, Cout, groups, HW, eps, N * groups);
   const long long t4 = M * Cout / 4;
   if (out_layout == 1) {
     hipLaunchKernelGGL(gt_gn_apply_kernel, dim3(blocks((size_t)t4)), dim3(256), 0, st, (const float*)b.y, (const float*)b.stats, p->gn_w, p->gn_b, out, HW, Cout, groups,
