@@ -131,6 +131,10 @@ class Restatement:
         self.p = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in params.items()}
         self.case, self.dtype = case, dtype
 
+    def softmax(self, sim):
+        """the query self-attention's softmax over the keys: a method, so that a test can record its scores or state it wrongly"""
+        return F.softmax(sim, dim=-1)
+
     def bn(self, x, p):
         q = self.p
         return F.batch_norm(x, q[p + "running_mean"], q[p + "running_var"], q[p + "weight"], q[p + "bias"], False, 0.01, EPS)
@@ -180,7 +184,7 @@ class Restatement:
         q, k, v = torch.split(qkv, [128, 128, 256], dim=1)
         q, k, v = q.reshape(N, 8, 16, L), k.reshape(N, 8, 16, L), v.reshape(N, 8, 32, L)
         sim = self.bn(torch.einsum("bhdl,bhdm->bhlm", q, k), p + "_query_self_attention._batch_norm_similarity.")
-        got = torch.einsum("bhlm,bhdm->bhdl", F.softmax(sim, dim=-1), v).reshape(N, 256, L)
+        got = torch.einsum("bhlm,bhdm->bhdl", self.softmax(sim), v).reshape(N, 256, L)
         got = F.gelu(self.bn(got, p + "_query_self_attention._batch_norm_retrieved_value."))
         query = F.gelu(query + self.convbn(got, p + "_query_conv3_bn."))
         ffn = self.convbn(self.convbn(query, p + "_query_ffn_conv1_bn_act.", True), p + "_query_ffn_conv2_bn.")
