@@ -159,6 +159,19 @@ __device__ __forceinline__ void load_cols(float (&a)[4][2], const float* tile, i
   }
 }
 
+// The same operands less channels j and 16 + j of a reference key (c0, c1), for dq = sum_n dS_n k_n.  sum_n dS_n is 0 in exact
+// arithmetic, so any reference gives the same dq; what fp32 leaves of that sum (P is rebuilt from the forward's statistics on scores
+// accumulated in another order, so sum_n P_n is 1 only to ~|s| 2^-23) then multiplies the keys' spread and not their common part.  With
+// a k.bias 800 times the usual the common part cost dq 2e-4 (profiles/traj_train_regimes_parity.txt).  Padding rows carry dS = 0.
+__device__ __forceinline__ void load_cols_less(float (&a)[4][2], const float* tile, int nl, int j, float c0, float c1) {
+  load_cols(a, tile, nl, j);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    a[r][0] -= c0;
+    a[r][1] -= c1;
+  }
+}
+
 // dynamic LDS of the LDS-resident query-side kernels: K | V of a frame, [ceil16(L)][kTrLd] each (two equal halves)
 __host__ __device__ inline size_t spatial_frame_lds(int L) { return (size_t)2 * ceil16(L) * kTrLd * sizeof(float); }
 
@@ -461,6 +474,7 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_mfma_kernel(const float*
     stage_rows36(ks, k, rm, s, f * L, L, h, C, tid);
     stage_rows36(vs, v, rm, s, f * L, L, h, C, tid);
     __syncthreads();
+    const float k0a = ks[j], k0b = ks[j + 16];      // key 0 of the frame, channels j and 16 + j: the reference of load_cols_less
     for (int qt = (int)blockIdx.y * 4 + wave; qt < nqt; qt += 4 * (int)gridDim.y) {
       const int qn = qt * 16 + j, qc = min(qn, N - 1);
       const long long mq = nat_row(rm, s * N + qc);
@@ -476,7 +490,7 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_mfma_kernel(const float*
         load_row(kr, ks + (kt * 16 + j) * kTrLd + 8 * g);
         load_row(vr, vs + (kt * 16 + j) * kTrLd + 8 * g);
         const int n0 = kt * 16 + 4 * g;
-        load_cols(ka, ks, n0, j);
+        load_cols_less(ka, ks, n0, j, k0a, k0b);
         bwd_q_tile(kr, vr, qr, dxr, ka, m, inv, dsum, n0, L, dr, base, acc);
       }
       if (qn < N) {
@@ -539,8 +553,10 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_kv_mfma_kernel(const float
     }
     for (int n = tid; n < Nc; n += 256) {
       const float* st = stat_ptr(stats, s, h, min(c0 + n, N - 1), f, heads, N, T);
-      // padding queries: 1/sum = 0 makes their probabilities vanish
-      *reinterpret_cast<float4*>(ss + n * 4) = float4{st[0], c0 + n < N ? st[1] : 0.f, st[2], 0.f};
+      // padding queries: 1/sum = 0 makes their probabilities vanish.  Their staged q is zero, so their scores are 0: the maximum is
+      // 0 too, not the last live query's -- under that one __expf(0 - max) is inf once a live maximum lies below -88.7, and inf * 0 = NaN
+      const bool live = c0 + n < N;
+      *reinterpret_cast<float4*>(ss + n * 4) = float4{live ? st[0] : 0.f, live ? st[1] : 0.f, st[2], 0.f};
     }
   };
   if (nchunks == 1) stage_q(0);
@@ -718,18 +734,23 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_chunk_kernel(const float
         inv[u] = st[1];
         base[u] = drop_base(s, h, qc[u], f, heads, N, T, L);
       }
+      float k0a = 0.f, k0b = 0.f;                  // key 0 of the frame, channels j and 16 + j: the reference of load_cols_less
       for (int c0 = 0; c0 < L; c0 += kSpChunk) {
         __syncthreads();
         stage_rows36(ks, k, rm, s, f * L + c0, min(kSpChunk, L - c0), h, C, tid);
         stage_rows36(vs, v, rm, s, f * L + c0, min(kSpChunk, L - c0), h, C, tid);
         __syncthreads();
+        if (c0 == 0) {
+          k0a = ks[j];
+          k0b = ks[j + 16];
+        }
         const int nkt = (min(kSpChunk, L - c0) + 15) >> 4;
         for (int kt = 0; kt < nkt; ++kt) {
           float kr[8], vr[8], ka[4][2];
           load_row(kr, ks + (kt * 16 + j) * kTrLd + 8 * g);
           load_row(vr, vs + (kt * 16 + j) * kTrLd + 8 * g);
           const int nl = kt * 16 + 4 * g, n0 = c0 + nl;
-          load_cols(ka, ks, nl, j);
+          load_cols_less(ka, ks, nl, j, k0a, k0b);
 #pragma unroll
           for (int u = 0; u < kSpQT; ++u) {
             if ((qb * 4 * kSpQT + u * 4 + wave) >= nqt) continue;      // (uniform per wave)
@@ -797,7 +818,9 @@ __global__ __launch_bounds__(256) void tr_spatial_bwd_q_kernel(const float* __re
         const float P = __expf(dot_lds<D>(qr, ks + n * D) - mx) * inv;
         const float kp = drop_keep(dr, base + n);
         const float dP = kp != 0.f ? kp * dot_lds<D>(dxr, vs + n * D) : 0.f;
-        axpy_lds<D>(dqr, P * (dP - Dsum), ks + n * D);
+        const float dS = P * (dP - Dsum);
+#pragma unroll
+        for (int i = 0; i < D; ++i) dqr[i] += dS * (ks[n * D + i] - ks[i]);      // less key 0 of the frame: see load_cols_less
       }
       float* st = stat_ptr(stats, s, h, qn, f, heads, N, T);
       st[0] = mx;
