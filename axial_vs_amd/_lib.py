@@ -458,6 +458,15 @@ def check(rc: int, what: str) -> None:
         raise RuntimeError(f"axial_vs_amd: {what} failed (code {rc}): {msg}")
 
 
+def size_query(name: str, *args) -> int:
+    """`name(*args)` of a `*_bytes` function whose refusal is 0 (the configuration is outside the kernels' bounds): raised with the
+    library's message."""
+    need = getattr(lib(), name)(*args)
+    if need == 0:
+        check(-1, name)
+    return need
+
+
 # ---- torch.autocast -> 16-bit products in the training tier -------------------------------------------------------------------------
 # Under autocast the reference's nn.Linear layers multiply 16-bit operands with fp32 accumulation.  The training tier does the same
 # when it is called under autocast: library option "train_amp" (1: bf16 pieces, 2: fp16 pieces, one per operand) for the duration

@@ -22,7 +22,7 @@ from torch import Tensor
 from . import _lib
 from ._params import m2f_head_params, m2f_layer_params
 from .matching import match_clips
-from .modules import _cached_pack, _dev_f32, _guarded, _stream, _workspace
+from .modules import _cached_pack, _dev_f32, _guarded, _pack_folded, _stream, _workspace_for
 
 _ORDER = ("cross_attn", "norm", "self_attn", "norm", "ffn", "norm")
 
@@ -140,20 +140,10 @@ class TubeLinkClipDecoder(nn.Module):
                                pos_normalize=int(self.pos_normalize), pos_temperature=self.pos_temperature, pos_scale=self.pos_scale)
 
     def _pack(self) -> Tensor:
-        def build(dt):
-            L = _lib.lib()
-            cfg = self._cfg(1, 1, 1, 1, [(1, 1)] * 3)
+        def build(dt):      # (nothing to fold: the parameters themselves, refused one by one when they are not on the GPU)
             layers = [[_dev_f32(t.detach(), "parameter") for t in m2f_layer_params(lay)] for lay in self.transformer_decoder.layers]
             head = [_dev_f32(t.detach(), "parameter") for t in m2f_head_params(self)]
-            dev = head[0].device
-            ls = (_lib.AxvsM2fLayerParams * self.num_layers)(*[_lib.fill(_lib.AxvsM2fLayerParams, [t.data_ptr() for t in ts]) for ts in layers])
-            hs = _lib.fill(_lib.AxvsM2fHeadParams, [t.data_ptr() for t in head])
-            need = L.axvs_m2f_decoder_packed_bytes(C.byref(cfg))
-            if need == 0:
-                _lib.check(-1, "axvs_m2f_decoder_packed_bytes")
-            buf = torch.zeros(need, dtype=torch.uint8, device=dev)
-            _lib.check(L.axvs_m2f_decoder_pack(ls, C.byref(hs), C.byref(cfg), buf.data_ptr(), _stream(dev)), "axvs_m2f_decoder_pack")
-            return buf
+            return _pack_folded("axvs_m2f_decoder", self._cfg(1, 1, 1, 1, [(1, 1)] * 3), [(_lib.AxvsM2fLayerParams, layers), (_lib.AxvsM2fHeadParams, [head])])
         return _cached_pack(self, "m2f", "f32", (self,), build)
 
     def _inputs(self, mask_features: Tensor, memorys: Sequence[Tensor]):
@@ -178,11 +168,8 @@ class TubeLinkClipDecoder(nn.Module):
         cfg = self._cfg(N, T, h, w, sizes, return_predictions)
         L, dev, Q, nl = _lib.lib(), mf.device, self.num_queries, self.num_layers
         packed = self._pack()
-        need = L.axvs_m2f_decoder_workspace_bytes(C.byref(cfg))
-        if need == 0:
-            _lib.check(-1, "axvs_m2f_decoder_workspace_bytes")
         st = _stream(dev)
-        ws = _workspace(dev, need, st)
+        ws = _workspace_for("axvs_m2f_decoder_workspace_bytes", dev, st, C.byref(cfg))
         out = torch.empty(N, Q, 256, dtype=torch.float32, device=dev)
         cls = torch.empty(N, Q, self.num_classes + 1, dtype=torch.float32, device=dev) if return_predictions else None
         masks = torch.empty(N, T, Q, h, w, dtype=torch.float32, device=dev) if return_predictions else None
@@ -219,11 +206,8 @@ class TubeLinkClipDecoder(nn.Module):
         if x.shape != (N, Q, 256):
             raise RuntimeError(f"x {tuple(x.shape)} must be [N={N},Q={Q},256]")
         packed = self._pack()
-        need = L.axvs_m2f_attn_mask_workspace_bytes(C.byref(cfg), level)
-        if need == 0:
-            _lib.check(-1, "axvs_m2f_attn_mask_workspace_bytes")
         st = _stream(dev)
-        ws = _workspace(dev, need, st)
+        ws = _workspace_for("axvs_m2f_attn_mask_workspace_bytes", dev, st, C.byref(cfg), level)
         W = (T * level_size[0] * level_size[1] + 31) // 32
         bits = torch.empty(N, Q, W, dtype=torch.int32, device=dev)
         flags = torch.empty(N, Q, dtype=torch.int32, device=dev)
@@ -248,11 +232,8 @@ class TubeLinkClipDecoder(nn.Module):
             raise RuntimeError(f"x {tuple(x.shape)}, bits {tuple(bits.shape)}, flags {tuple(flags.shape)} must be [N,Q,256], int32 [N,Q,{W}], int32 [N,Q]")
         bits, flags = bits.contiguous(), flags.contiguous()
         packed = self._pack()
-        need = L.axvs_m2f_layer_workspace_bytes(C.byref(cfg), index)
-        if need == 0:
-            _lib.check(-1, "axvs_m2f_layer_workspace_bytes")
         st = _stream(dev)
-        ws = _workspace(dev, need, st)
+        ws = _workspace_for("axvs_m2f_layer_workspace_bytes", dev, st, C.byref(cfg), index)
         out = torch.empty_like(x)
         _lib.check(L.axvs_m2f_layer_fwd(C.byref(cfg), packed.data_ptr(), index, x.data_ptr(), mem.data_ptr(), bits.data_ptr(), flags.data_ptr(),
                                         out.data_ptr(), ws.data_ptr(), ws.numel(), st), "axvs_m2f_layer_fwd")

@@ -23,7 +23,7 @@ from torch import Tensor
 
 from . import _lib
 from ._params import convnext_block_folded, convnext_down_folded
-from .modules import _cached_pack, _dev_f32, _on, _stream, _workspace
+from .modules import _cached_pack, _dev_f32, _on, _pack_folded, _stream, _workspace_for
 
 ShapeSpec = namedtuple("ShapeSpec", ["channels", "stride"])       # what `output_shape()` holds: the two fields the pixel decoders read
 
@@ -63,32 +63,10 @@ def _cfg(N: int, H: int, W: int, sizes, depths, dims, v2: bool) -> _lib.AxvsCnxC
 
 def _pack(sd: Mapping[str, Tensor], depths, dims, v2: bool) -> Tensor:
     """fold (float64) and pack: one blob of fp32 tensors in the kernels' layouts"""
-    Lb = _lib.lib()
-    ref = sd["downsample_layers.0.0.weight"]
-    if not ref.is_cuda:
-        raise RuntimeError(f"axial_vs_amd: parameters must be GPU tensors (got {ref.device}); there is no CPU fallback")
-    f32 = lambda ts: [None if t is None else t.float().contiguous() for t in ts]
-    ptr = lambda ts: [None if t is None else t.data_ptr() for t in ts]
-    cfg = _cfg(1, 1, 1, [(1, 1)] * 4, depths, dims, v2)
-    need = Lb.axvs_cnx_packed_bytes(C.byref(cfg))
-    if need == 0:
-        _lib.check(-1, "axvs_cnx_packed_bytes")
-    with torch.no_grad():
-        sd = {k: v.detach() for k, v in sd.items()}
-        downs = [f32(convnext_down_folded(sd, i)) for i in range(4)]
-        blocks = [f32(convnext_block_folded(sd, f"stages.{i}.{j}.")) for i in range(4) for j in range(int(depths[i]))]
-    ds = (_lib.AxvsCnxDownParams * 4)(*[_lib.fill(_lib.AxvsCnxDownParams, ptr(ts)) for ts in downs])
-    bs = (_lib.AxvsCnxBlockParams * len(blocks))(*[_lib.fill(_lib.AxvsCnxBlockParams, ptr(ts)) for ts in blocks])
-    buf = torch.zeros(need, dtype=torch.uint8, device=ref.device)
-    _lib.check(Lb.axvs_cnx_pack(ds, bs, C.byref(cfg), buf.data_ptr(), _stream(ref.device)), "axvs_cnx_pack")
-    return buf      # (the folded tensors die with this frame: the allocator hands their memory out again in stream order)
-
-
-def _ws(cfg, dev, st):
-    need = _lib.lib().axvs_cnx_workspace_bytes(C.byref(cfg))
-    if need == 0:
-        _lib.check(-1, "axvs_cnx_workspace_bytes")
-    return _workspace(dev, need, st)
+    sd = {k: v.detach() for k, v in sd.items()}
+    downs = (convnext_down_folded(sd, i) for i in range(4))
+    blocks = (convnext_block_folded(sd, f"stages.{i}.{j}.") for i in range(4) for j in range(int(depths[i])))
+    return _pack_folded("axvs_cnx", _cfg(1, 1, 1, [(1, 1)] * 4, depths, dims, v2), [(_lib.AxvsCnxDownParams, downs), (_lib.AxvsCnxBlockParams, blocks)])
 
 
 def _image(x: Tensor) -> Tensor:
@@ -103,7 +81,7 @@ def _run(packed: Tensor, x: Tensor, depths, dims, v2: bool, want: Sequence[str])
     dev = x.device
     cfg = _cfg(N, H, W, sizes, depths, dims, v2)
     st = _stream(dev)
-    ws = _ws(cfg, dev, st)
+    ws = _workspace_for("axvs_cnx_workspace_bytes", dev, st, C.byref(cfg))
     shape = {"stem": (dims[0], sizes[0])}
     shape.update({f"res{i + 2}": (dims[i], sizes[i]) for i in range(4)})
     outs = {k: torch.empty(N, int(shape[k][0]), *shape[k][1], dtype=torch.float32, device=dev) for k in _NAMES if k in want}
@@ -230,7 +208,7 @@ class _Backbone(nn.Module):
         with _on(x.device):
             cfg = _cfg(N, H, W, sizes, self._depths, self._dims, self._v2)
             st = _stream(x.device)
-            ws = _ws(cfg, x.device, st)
+            ws = _workspace_for("axvs_cnx_workspace_bytes", x.device, st, C.byref(cfg))
             out = torch.empty(N, *sizes[0], self._dims[0], dtype=torch.float32, device=x.device)
             _lib.check(_lib.lib().axvs_cnx_stem_fwd(C.byref(cfg), self._packed().data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), st),
                        "axvs_cnx_stem_fwd")
@@ -248,7 +226,7 @@ class _Backbone(nn.Module):
         with _on(x.device):
             cfg = _cfg(N, 1, 1, sizes, self._depths, self._dims, self._v2)
             st = _stream(x.device)
-            ws = _ws(cfg, x.device, st)
+            ws = _workspace_for("axvs_cnx_workspace_bytes", x.device, st, C.byref(cfg))
             out = torch.empty(N, *sizes[index], self._dims[index], dtype=torch.float32, device=x.device)
             _lib.check(_lib.lib().axvs_cnx_down_fwd(C.byref(cfg), self._packed().data_ptr(), index, x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), st),
                        "axvs_cnx_down_fwd")
@@ -264,7 +242,7 @@ class _Backbone(nn.Module):
             st = _stream(x.device)
             out = torch.empty_like(x)
             if whole:
-                ws = _ws(cfg, x.device, st)
+                ws = _workspace_for("axvs_cnx_workspace_bytes", x.device, st, C.byref(cfg))
                 _lib.check(_lib.lib().axvs_cnx_block_fwd(C.byref(cfg), self._packed().data_ptr(), self._locate(stage, index), x.data_ptr(), out.data_ptr(),
                                                          ws.data_ptr(), ws.numel(), st), "axvs_cnx_block_fwd")
             else:

@@ -15,7 +15,7 @@
 //   cnx_grn_gx_kernel       GRN: chunk sums in chunk order -> Gx
 //   cnx_grn_scale_kernel    GRN: Gx -> s = 1 + gamma Gx / (mean_c Gx + 1e-6) per frame
 //   cnx_scale_w_kernel      W2 diag(s_n): pwconv2's weight of one frame
-//   cnx_to_nchw_kernel      rows [N*h*w][C] -> [N, C, h, w]
+// and rows [N*h*w][C] -> [N, C, h, w] for the outputs: rows_to_nchw_kernel (axvs_eval_host.h).
 // No kernel waits for another workgroup and none adds floating-point numbers atomically: equal inputs give equal bits, and a frame's
 // bits do not depend on the frames stacked beside it.
 #pragma once
@@ -258,33 +258,6 @@ __global__ __launch_bounds__(256) void cnx_scale_w_kernel(const float* __restric
   if (i >= n4) return;
   const float4 a = reinterpret_cast<const float4*>(w)[i], f = *reinterpret_cast<const float4*>(s + (i * 4) % K);
   reinterpret_cast<float4*>(out)[i] = float4{a.x * f.x, a.y * f.y, a.z * f.z, a.w * f.w};
-}
-
-// ---- rows [N*hw][C] -> [N, C, hw]: a 32 (pixels) x 64 (channels) tile through LDS.  grid (ceil(hw/32) * ceil(C/64), N), 256 threads ----
-__global__ __launch_bounds__(256) void cnx_to_nchw_kernel(const float* __restrict__ rows, float* __restrict__ out, int C, int hw) {
-  __shared__ float tile[32][65];
-  const int tid = threadIdx.x;
-  const int cchunks = (C + 63) / 64;
-  const int p0 = (int)(blockIdx.x / cchunks) * 32, c0 = (int)(blockIdx.x % cchunks) * 64;
-  const size_t n = blockIdx.y;
-  {
-    const int c = tid & 63, pr = tid >> 6;
-    if (c0 + c < C) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int p = p0 + pr + 4 * j;
-        if (p < hw) tile[pr + 4 * j][c] = rows[(n * hw + p) * C + c0 + c];
-      }
-    }
-  }
-  __syncthreads();
-  const int tx = tid & 31, cy = tid >> 5, p = p0 + tx;
-  if (p >= hw) return;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = c0 + cy + 8 * j;
-    if (c < C) out[(n * C + c) * (size_t)hw + p] = tile[tx][cy + 8 * j];
-  }
 }
 
 }  // namespace axvs

@@ -1,6 +1,7 @@
 // C-ABI entry points of the ConvNeXt / ConvNeXtV2 backbone (include/axvs.h: axvs_cnx_*) and the launch sequence behind them.
 // Every Linear layer -- the two kinds of patchify convolution over gathered patches, pwconv1 with its gelu, pwconv2 with the residual --
-// is one call of the three-piece split-precision GEMM behind gemm_nt (axvs_gemm_nt.h); everything else: axvs_convnext.h.
+// is one linear() of axvs_eval_host.h (with the slot-list helpers of the pack and locate()): the three-piece split-precision GEMM in its
+// form with the gelu epilogues; everything else: axvs_convnext.h.
 // V2's GRN reaches pwconv2 as a per-frame scaled copy of its weight, W2 diag(s_n): one GEMM per frame, the hidden rows are read once
 // more for their sums of squares and never rewritten.
 #include <hip/hip_runtime.h>
@@ -8,15 +9,13 @@
 #include <algorithm>
 
 #include "axvs_convnext.h"
-#include "axvs_gemm_nt.h"
-#include "axvs_host.h"
+#include "axvs_eval_host.h"
 
 using namespace axvs;
 
 namespace {
 
 constexpr int kStages = 4, kMaxDepth = 64;
-constexpr int kActNone = 0, kActGelu = 2;      // GemmEpi::relu under ACT
 
 // the slots of AxvsCnxDownParams / AxvsCnxBlockParams, in declaration order (axial_vs_amd/_params.py states the same order)
 enum { DN_LN_W, DN_LN_B, DN_W, DN_B, DN_N };
@@ -74,10 +73,9 @@ CnxW cnx_weights(void* blob, const AxvsCnxCfg* c) {
   size_t n[BK_N];
   for (int i = 0; i < kStages; ++i) {
     down_sizes(c, i, n);
-    for (int s = 0; s < DN_N; ++s) w.down[i][s] = cv.f(n[s]);
+    carve_slots(cv, n, DN_N, w.down[i]);
     block_sizes(c, i, n);
-    for (int j = 0; j < c->depths[i]; ++j)
-      for (int s = 0; s < BK_N; ++s) w.block[i][j][s] = n[s] ? cv.f(n[s]) : nullptr;
+    for (int j = 0; j < c->depths[i]; ++j) carve_slots(cv, n, BK_N, w.block[i][j]);
   }
   w.bytes = cv.off;
   return w;
@@ -107,33 +105,16 @@ CnxWs cnx_carve(void* ws, const AxvsCnxCfg* c) {
   return w;
 }
 
-int ws_check(long long have, size_t need) {
-  if (have < 0 || (size_t)have < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", have, need);
-  return AXVS_OK;
-}
-
 // ---- launches -------------------------------------------------------------------------------------------------------------------------------
-// Y[M][N] = act(X[M][K] W[N][K]^T + bias) (+ res[M][N]): three bf16 pieces per operand
-int linear(const float* X, const float* W, const float* bias, float* Y, long long M, int N, int K, int act, const float* res, hipStream_t st) {
-  tr::GemmLd ld{K, K, N, 0, nullptr};
-  tr::GemmEpi e{bias, 1.f, act, tr::Drop{0u, 0u, 0u, 1.f}, 0.f};
-  e.res = res;
-  return tr::gemm_nt(X, W, Y, M, N, K, ld, e, tr::GemmNtForm{3, false, true}, 1, st);
-}
-
 void row_ln(const float* src, const float* g, const float* b, float* dst, int C, size_t P, hipStream_t st) {
   hipLaunchKernelGGL(cnx_row_ln_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, src, g, b, dst, C, P);
-}
-
-void to_nchw(const float* rows, float* out, int N, int C, int hw, hipStream_t st) {
-  hipLaunchKernelGGL(cnx_to_nchw_kernel, dim3((unsigned)((hw + 31) / 32 * ((C + 63) / 64)), (unsigned)N), dim3(256), 0, st, rows, out, C, hw);
 }
 
 // image -> out rows [P0][dims[0]]
 int stem(const AxvsCnxCfg* c, float* const* p, const CnxWs& w, const float* image, float* out, hipStream_t st) {
   const size_t P = pixels_of(c, 0), total = P * 12;
   hipLaunchKernelGGL(cnx_stem_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, image, w.t, c->H, c->W, c->h[0], c->w[0], total);
-  if (int rc = linear(w.t, p[DN_W], p[DN_B], out, (long long)P, c->dims[0], 48, kActNone, nullptr, st)) return rc;
+  if (int rc = linear(w.t, 48, p[DN_W], p[DN_B], out, (long long)P, c->dims[0], 48, c->dims[0], kActNone, nullptr, kForm3Gelu, st)) return rc;
   row_ln(out, p[DN_LN_W], p[DN_LN_B], out, c->dims[0], P, st);
   return AXVS_OK;
 }
@@ -144,7 +125,7 @@ int down(const AxvsCnxCfg* c, int i, float* const* p, const CnxWs& w, const floa
   const size_t P = pixels_of(c, i), total = P * 4;
   hipLaunchKernelGGL(cnx_down_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, x, (const float*)p[DN_LN_W], (const float*)p[DN_LN_B], w.t, C,
                      c->h[i - 1], c->w[i - 1], c->h[i], c->w[i], total);
-  return linear(w.t, p[DN_W], p[DN_B], out, (long long)P, c->dims[i], 4 * C, kActNone, nullptr, st);
+  return linear(w.t, 4 * C, p[DN_W], p[DN_B], out, (long long)P, c->dims[i], 4 * C, c->dims[i], kActNone, nullptr, kForm3Gelu, st);
 }
 
 template <int TH>
@@ -170,8 +151,8 @@ int block(const AxvsCnxCfg* c, int i, float* const* p, const CnxWs& w, const flo
   const int C = c->dims[i], K = 4 * C, hw = c->h[i] * c->w[i];
   const long long P = (long long)pixels_of(c, i);
   if (int rc = dwln(c, i, p, x, w.t, st)) return rc;
-  if (int rc = linear(w.t, p[BK_W1], p[BK_B1], w.hid, P, K, C, kActGelu, nullptr, st)) return rc;
-  if (!c->v2) return linear(w.hid, p[BK_W2], p[BK_B2], y, P, C, K, kActNone, x, st);
+  if (int rc = linear(w.t, C, p[BK_W1], p[BK_B1], w.hid, P, K, C, K, kActGelu, nullptr, kForm3Gelu, st)) return rc;
+  if (!c->v2) return linear(w.hid, K, p[BK_W2], p[BK_B2], y, P, C, K, C, kActNone, x, kForm3Gelu, st);
   const int nch = grn_chunks(c, i);
   hipLaunchKernelGGL(cnx_sumsq_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)nch, (unsigned)c->N), dim3(256), 0, st, (const float*)w.hid, w.part, K, hw);
   hipLaunchKernelGGL(cnx_grn_gx_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)c->N), dim3(256), 0, st, (const float*)w.part, w.s, K, nch);
@@ -181,20 +162,9 @@ int block(const AxvsCnxCfg* c, int i, float* const* p, const CnxWs& w, const flo
     hipLaunchKernelGGL(cnx_scale_w_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float*)p[BK_W2], (const float*)(w.s + (size_t)n * K), w.w2s, K,
                        n4);
     const size_t r0 = (size_t)n * hw;
-    if (int rc = linear(w.hid + r0 * K, w.w2s, p[BK_B2], y + r0 * C, hw, C, K, kActNone, x + r0 * C, st)) return rc;
+    if (int rc = linear(w.hid + r0 * K, K, w.w2s, p[BK_B2], y + r0 * C, hw, C, K, C, kActNone, x + r0 * C, kForm3Gelu, st)) return rc;
   }
   return AXVS_OK;
-}
-
-int locate(const AxvsCnxCfg* c, int index, int* stage, int* j) {        // block `index` of the whole network -> (stage, block of the stage)
-  for (int i = 0; i < kStages; ++i) {
-    if (index >= 0 && index < c->depths[i]) {
-      *stage = i, *j = index;
-      return AXVS_OK;
-    }
-    index -= c->depths[i];
-  }
-  return fail(AXVS_ERR_ARG, "block index outside the network's blocks");
 }
 
 }  // namespace
@@ -210,22 +180,13 @@ int axvs_cnx_pack(const AxvsCnxDownParams* downs, const AxvsCnxBlockParams* bloc
   hipStream_t st = static_cast<hipStream_t>(stream);
   const CnxW w = cnx_weights(packed, cfg);
   size_t n[BK_N];
-  auto copy = [&](float* const* dst, const void* src_struct, int slots, const char* what, int index) {
-    const float* const* src = reinterpret_cast<const float* const*>(src_struct);
-    for (int s = 0; s < slots; ++s) {
-      if (!n[s]) continue;
-      if (!src[s]) return fail(AXVS_ERR_ARG, "null pointer (%s %d, parameter %d)", what, index, s);
-      if (hipMemcpyAsync(dst[s], src[s], n[s] * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
-    }
-    return (int)AXVS_OK;
-  };
   int index = 0;
   for (int i = 0; i < kStages; ++i) {
     down_sizes(cfg, i, n);
-    if (int rc = copy(w.down[i], downs + i, DN_N, "downsample layer", i)) return rc;
+    if (int rc = copy_slots(w.down[i], downs + i, n, DN_N, "downsample layer", i, st)) return rc;
     block_sizes(cfg, i, n);
     for (int j = 0; j < cfg->depths[i]; ++j, ++index)
-      if (int rc = copy(w.block[i][j], blocks + index, BK_N, "block", index)) return rc;
+      if (int rc = copy_slots(w.block[i][j], blocks + index, n, BK_N, "block", index, st)) return rc;
   }
   return AXVS_OK;
 }
@@ -241,14 +202,14 @@ int axvs_cnx_fwd(const AxvsCnxCfg* cfg, const void* packed, const float* image, 
   if (int rc = cnx_check_sizes(cfg)) return rc;
   if (!packed || !image || !outputs || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const CnxWs w = cnx_carve(workspace, cfg);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const CnxW p = cnx_weights(const_cast<void*>(packed), cfg);
   float *cur = w.x, *nxt = w.y;
   for (int i = 0; i < kStages; ++i) {
     if (i == 0) {
       if (int rc = stem(cfg, p.down[0], w, image, cur, st)) return rc;
-      if (outputs[0]) to_nchw(cur, outputs[0], cfg->N, cfg->dims[0], cfg->h[0] * cfg->w[0], st);
+      if (outputs[0]) rows_to_nchw(cur, outputs[0], cfg->N, cfg->dims[0], cfg->h[0] * cfg->w[0], st);
     } else {
       if (int rc = down(cfg, i, p.down[i], w, cur, nxt, st)) return rc;
       std::swap(cur, nxt);
@@ -257,7 +218,7 @@ int axvs_cnx_fwd(const AxvsCnxCfg* cfg, const void* packed, const float* image, 
       if (int rc = block(cfg, i, p.block[i][j], w, cur, nxt, st)) return rc;
       std::swap(cur, nxt);
     }
-    if (outputs[i + 1]) to_nchw(cur, outputs[i + 1], cfg->N, cfg->dims[i], cfg->h[i] * cfg->w[i], st);
+    if (outputs[i + 1]) rows_to_nchw(cur, outputs[i + 1], cfg->N, cfg->dims[i], cfg->h[i] * cfg->w[i], st);
   }
   return last_launch_status();
 }
@@ -268,7 +229,7 @@ int axvs_cnx_stem_fwd(const AxvsCnxCfg* cfg, const void* packed, const float* im
     return fail(AXVS_ERR_ARG, "image %d x %d (in 1..65535) must give the stem's map %d x %d", cfg->H, cfg->W, cfg->h[0], cfg->w[0]);
   if (!packed || !image || !out || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const CnxWs w = cnx_carve(workspace, cfg);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   const CnxW p = cnx_weights(const_cast<void*>(packed), cfg);
   if (int rc = stem(cfg, p.down[0], w, image, out, static_cast<hipStream_t>(stream))) return rc;
   return last_launch_status();
@@ -282,7 +243,7 @@ int axvs_cnx_down_fwd(const AxvsCnxCfg* cfg, const void* packed, int index, cons
     return fail(AXVS_ERR_ARG, "downsample layer %d: map %d x %d does not give %d x %d", index, cfg->h[index - 1], cfg->w[index - 1], cfg->h[index], cfg->w[index]);
   if (!packed || !x || !out || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const CnxWs w = cnx_carve(workspace, cfg);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   const CnxW p = cnx_weights(const_cast<void*>(packed), cfg);
   if (int rc = down(cfg, index, p.down[index], w, x, out, static_cast<hipStream_t>(stream))) return rc;
   return last_launch_status();
@@ -291,7 +252,7 @@ int axvs_cnx_down_fwd(const AxvsCnxCfg* cfg, const void* packed, int index, cons
 int axvs_cnx_dwln_fwd(const AxvsCnxCfg* cfg, const void* packed, int block_index, const float* x, float* out, void* stream) {
   if (int rc = cnx_check(cfg)) return rc;
   int i, j;
-  if (int rc = locate(cfg, block_index, &i, &j)) return rc;
+  if (int rc = locate(cfg->depths, block_index, "network's", &i, &j)) return rc;
   if (!packed || !x || !out || x == out) return fail(AXVS_ERR_ARG, "null pointer, or out == x");
   const CnxW p = cnx_weights(const_cast<void*>(packed), cfg);
   if (int rc = dwln(cfg, i, p.block[i][j], x, out, static_cast<hipStream_t>(stream))) return rc;
@@ -302,10 +263,10 @@ int axvs_cnx_block_fwd(const AxvsCnxCfg* cfg, const void* packed, int block_inde
                        void* stream) {
   if (int rc = cnx_check(cfg)) return rc;
   int i, j;
-  if (int rc = locate(cfg, block_index, &i, &j)) return rc;
+  if (int rc = locate(cfg->depths, block_index, "network's", &i, &j)) return rc;
   if (!packed || !x || !out || !workspace || x == out) return fail(AXVS_ERR_ARG, "null pointer, or out == x");
   const CnxWs w = cnx_carve(workspace, cfg);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   const CnxW p = cnx_weights(const_cast<void*>(packed), cfg);
   if (int rc = block(cfg, i, p.block[i][j], w, x, out, static_cast<hipStream_t>(stream))) return rc;
   return last_launch_status();

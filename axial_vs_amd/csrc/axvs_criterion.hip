@@ -81,7 +81,7 @@ int axvs_set_criterion_fwd(const float* const* pred_masks, const float* const* p
   if (!losses || !saved || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   if (kmax > 0 && (!targets || !labels || !rows || !cols || !matched_dice || !matched_cls)) return fail(AXVS_ERR_ARG, "null pointer");
   const size_t need = axvs_set_criterion_workspace_bytes(L, B, N, K1, P);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, need);
+  if (int rc = check_ws(workspace_bytes, need)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nprob = L * B, share = share_final_matching != 0, masking = masking_void_pixel != 0;
   const CritPlan pl = crit_plan(nprob, P);

@@ -1,5 +1,5 @@
 // Host-side plumbing shared by the translation units of libaxvs.so: error string, launch status, the bump allocator over
-// caller-owned buffers and its workspace check, per-device kernel attributes, the
+// caller-owned buffers and its workspace checks (unsigned and signed sizes), per-device kernel attributes, the
 // packed-weight / workspace views of one trajectory attention, and the launcher of the fused trajectory kernels (whose
 // instantiations are compiled one (operand type, frame count) pair per translation unit: axvs_temporal_inst.hip).
 #pragma once
@@ -63,6 +63,11 @@ struct Carver {  // bump allocator over a caller-owned buffer (nullptr: size onl
 
 inline int check_ws(size_t have, size_t need) {
   if (have < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %zu < %zu", have, need);
+  return AXVS_OK;
+}
+// the entries whose ABI takes a signed size: a negative one is too small as well
+inline int check_ws(long long have, size_t need) {
+  if (have < 0 || (size_t)have < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", have, need);
   return AXVS_OK;
 }
 

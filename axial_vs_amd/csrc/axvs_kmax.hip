@@ -1,12 +1,11 @@
 // C-ABI entry points of Video-kMaX's k-means query decoder (include/axvs.h: axvs_kmax_*) and the launch sequence behind them.
-// 1x1 convolutions with their folded BatchNorms: the three-piece split-precision GEMM behind gemm_nt (axvs_gemm_nt.h), always in
-// its form with the gelu epilogues; everything else: axvs_kmax.h.
+// 1x1 convolutions with their folded BatchNorms: linear() of axvs_eval_host.h (with the slot-list helpers of the pack), the three-piece
+// split-precision GEMM always in its form with the gelu epilogues; everything else: axvs_kmax.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "axvs_gemm_nt.h"
-#include "axvs_host.h"
+#include "axvs_eval_host.h"
 #include "axvs_kmax.h"
 
 using namespace axvs;
@@ -14,7 +13,6 @@ using namespace axvs;
 namespace {
 
 constexpr int C = kKmaxC, D = kKmaxD, kFfn = 2048;
-constexpr int kActNone = 0, kActGelu = 2, kActGeluAfterRes = 3;      // GemmEpi::relu under ACT
 
 // the slots of AxvsKmaxLayerParams / AxvsKmaxHeadParams, in declaration order (axial_vs_amd/_params.py states the same order)
 enum { PR_DW_W, PR_DW_B, PR_PH1_W, PR_PH1_B, PR_PH2_W, PR_PH2_B, PR_MH_W, PR_MH_B, PR_CLS_W, PR_CLS_B, PR_MASK_AB, PR_N };
@@ -84,10 +82,10 @@ KmaxW kmax_weights(void* blob, const AxvsKmaxCfg* c) {
   KmaxW w;
   size_t n[LY_N > HD_N ? LY_N : HD_N];
   head_sizes(c, n);
-  for (int s = 0; s < HD_N; ++s) w.head[s] = cv.f(n[s]);
+  carve_slots(cv, n, HD_N, w.head);
   for (int i = 0; i < c->num_layers; ++i) {
     layer_sizes(c, i, n);
-    for (int s = 0; s < LY_N; ++s) w.layer[i][s] = cv.f(n[s]);
+    carve_slots(cv, n, LY_N, w.layer[i]);
   }
   w.bytes = cv.off;
   return w;
@@ -130,15 +128,6 @@ KmaxWs kmax_carve(void* ws, const AxvsKmaxCfg* c, int what, int arg) {
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------------------------------
-// Y[M][N] (row stride ldc) = act((X[M][K] (row stride lda) W[N][K]^T + bias) (+ res[M][ldc])): three bf16 pieces per operand
-int linear(const float* X, long long lda, const float* W, const float* bias, float* Y, long long M, int N, int K, long long ldc, int act, const float* res,
-           hipStream_t st) {
-  tr::GemmLd ld{lda, K, ldc, 0, nullptr};
-  tr::GemmEpi e{bias, 1.f, act, tr::Drop{0u, 0u, 0u, 1.f}, 0.f};
-  e.res = res;
-  return tr::gemm_nt(X, W, Y, M, N, K, ld, e, tr::GemmNtForm{3, false, true}, 1, st);
-}
-
 template <bool GELU>
 void to_cl(const float* src, float* out, int BT, int Cin, int h, int w, hipStream_t st) {
   const dim3 grid((unsigned)((w + 31) / 32 * ((Cin + 63) / 64)), (unsigned)h, (unsigned)BT);
@@ -150,8 +139,8 @@ int predictor_pixels(const AxvsKmaxCfg* c, float* const* pr, const KmaxWs& w, co
   const long long P = (long long)c->B * TH * wd;
   hipLaunchKernelGGL(kmax_dw5_kernel, dim3((unsigned)((wd + 7) / 8 * 4), (unsigned)((TH + 3) / 4), (unsigned)c->B), dim3(256), 0, st, in,
                      (const float*)pr[PR_DW_W], (const float*)pr[PR_DW_B], w.pb, TH, wd);
-  if (int rc = linear(w.pb, C, pr[PR_PH1_W], pr[PR_PH1_B], mid, P, C, C, C, kActGelu, nullptr, st)) return rc;
-  return linear(mid, C, pr[PR_PH2_W], pr[PR_PH2_B], w.pf, P, D, C, D, kActNone, nullptr, st);
+  if (int rc = linear(w.pb, C, pr[PR_PH1_W], pr[PR_PH1_B], mid, P, C, C, C, kActGelu, nullptr, kForm3Gelu, st)) return rc;
+  return linear(mid, C, pr[PR_PH2_W], pr[PR_PH2_B], w.pf, P, D, C, D, kActNone, nullptr, kForm3Gelu, st);
 }
 
 // The assignment of layer i: x [B*L][256], gx = gelu(level feature) rows -> w.qs (query space), w.pa (pixel space), idx [B*S]
@@ -159,10 +148,10 @@ int assign(const AxvsKmaxCfg* c, int i, const KmaxW& p, const KmaxWs& w, const f
   float* const* y = p.layer[i];
   const int l = c->layer_level[i], S = (int)pixels_of(c, l);
   const long long R = (long long)c->B * c->L, P = (long long)c->B * S;
-  if (int rc = linear(gx, c->in_channels[l], y[LY_PIX1_W], y[LY_PIX1_B], w.pa, P, C, c->in_channels[l], C, kActGelu, nullptr, st)) return rc;
-  if (int rc = linear(x, C, y[LY_Q1_W], y[LY_Q1_B], w.qs, R, C, C, C, kActGelu, nullptr, st)) return rc;
+  if (int rc = linear(gx, c->in_channels[l], y[LY_PIX1_W], y[LY_PIX1_B], w.pa, P, C, c->in_channels[l], C, kActGelu, nullptr, kForm3Gelu, st)) return rc;
+  if (int rc = linear(x, C, y[LY_Q1_W], y[LY_Q1_B], w.qs, R, C, C, C, kActGelu, nullptr, kForm3Gelu, st)) return rc;
   if (int rc = predictor_pixels(c, y + LY_PRED, w, w.pa, w.pc, c->T * c->h[l], c->w[l], st)) return rc;
-  if (int rc = linear(w.qs, C, y[LY_PRED + PR_MH_W], y[LY_PRED + PR_MH_B], w.mk, R, D, C, D, kActNone, nullptr, st)) return rc;
+  if (int rc = linear(w.qs, C, y[LY_PRED + PR_MH_W], y[LY_PRED + PR_MH_B], w.mk, R, D, C, D, kActNone, nullptr, kForm3Gelu, st)) return rc;
   hipLaunchKernelGGL((kmax_assign_kernel<false>), dim3((unsigned)((S + 127) / 128), (unsigned)c->B), dim3(256), 0, st, (const float*)w.pf, (const float*)w.mk,
                      (const float*)y[LY_PRED + PR_MASK_AB], c->L, S, idx, (float*)nullptr, (float*)nullptr);
   return AXVS_OK;
@@ -179,27 +168,22 @@ int update(const AxvsKmaxCfg* c, int i, const KmaxW& p, const KmaxWs& w, const f
   hipLaunchKernelGGL(kmax_sum_kernel, dim3((unsigned)nchunk, (unsigned)((L + kKmaxLChunk - 1) / kKmaxLChunk), (unsigned)c->B), dim3(256), 0, st,
                      (const float*)w.pa, idx, L, S, chunk, nchunk, w.part, w.pcnt);
   hipLaunchKernelGGL(kmax_sum_reduce_kernel, dim3((unsigned)R), dim3(256), 0, st, (const float*)w.part, (const int*)w.pcnt, w.saug, L, nchunk);
-  if (int rc = linear(w.saug, kKmaxAug, y[LY_KV_W], y[LY_KV_B], w.u, R, C, kKmaxAug, C, kActNone, nullptr, st)) return rc;
-  if (int rc = linear(w.u, C, y[LY_K3_W], y[LY_K3_B], w.x1, R, C, C, C, kActNone, x, st)) return rc;
+  if (int rc = linear(w.saug, kKmaxAug, y[LY_KV_W], y[LY_KV_B], w.u, R, C, kKmaxAug, C, kActNone, nullptr, kForm3Gelu, st)) return rc;
+  if (int rc = linear(w.u, C, y[LY_K3_W], y[LY_K3_B], w.x1, R, C, C, C, kActNone, x, kForm3Gelu, st)) return rc;
   // self-attention, from the query space of the incoming queries
-  if (int rc = linear(w.qs, C, y[LY_QKV_W], y[LY_QKV_B], w.qkv, R, 2 * C, C, 2 * C, kActNone, nullptr, st)) return rc;
+  if (int rc = linear(w.qs, C, y[LY_QKV_W], y[LY_QKV_B], w.qkv, R, 2 * C, C, 2 * C, kActNone, nullptr, kForm3Gelu, st)) return rc;
   hipLaunchKernelGGL(kmax_attn_kernel, dim3(kKmaxHeads, (unsigned)c->B), dim3(256), 0, st, (const float*)w.qkv, (const float*)y[LY_SIM_AB],
                      (const float*)y[LY_RV_AB], w.att, L);
-  if (int rc = linear(w.att, C, y[LY_A3_W], y[LY_A3_B], w.x2, R, C, C, C, kActGeluAfterRes, w.x1, st)) return rc;
+  if (int rc = linear(w.att, C, y[LY_A3_W], y[LY_A3_B], w.x2, R, C, C, C, kActGeluAfterRes, w.x1, kForm3Gelu, st)) return rc;
   // FFN
-  if (int rc = linear(w.x2, C, y[LY_F1_W], y[LY_F1_B], w.hid, R, kFfn, C, kFfn, kActGelu, nullptr, st)) return rc;
-  return linear(w.hid, kFfn, y[LY_F2_W], y[LY_F2_B], x_out, R, C, kFfn, C, kActGeluAfterRes, w.x2, st);
+  if (int rc = linear(w.x2, C, y[LY_F1_W], y[LY_F1_B], w.hid, R, kFfn, C, kFfn, kActGelu, nullptr, kForm3Gelu, st)) return rc;
+  return linear(w.hid, kFfn, y[LY_F2_W], y[LY_F2_B], x_out, R, C, kFfn, C, kActGeluAfterRes, w.x2, kForm3Gelu, st);
 }
 
 void class_logits(const AxvsKmaxCfg* c, float* const* pr, const float* emb, float* out, hipStream_t st) {
   const int R = c->B * c->L;
   hipLaunchKernelGGL(kmax_cls_kernel, dim3((unsigned)(((size_t)R * c->K1 + 255) / 256)), dim3(256), 0, st, emb, (const float*)pr[PR_CLS_W],
                      (const float*)pr[PR_CLS_B], out, R, c->K1);
-}
-
-int ws_check(long long have, size_t need) {
-  if (have < 0 || (size_t)have < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", have, need);
-  return AXVS_OK;
 }
 
 }  // namespace
@@ -215,20 +199,11 @@ int axvs_kmax_decoder_pack(const AxvsKmaxLayerParams* layers, const AxvsKmaxHead
   hipStream_t st = static_cast<hipStream_t>(stream);
   const KmaxW w = kmax_weights(packed, cfg);
   size_t n[LY_N > HD_N ? LY_N : HD_N];
-  auto copy = [&](float* const* dst, const void* src_struct, int slots, const char* what, int index) {
-    const float* const* src = reinterpret_cast<const float* const*>(src_struct);
-    for (int s = 0; s < slots; ++s) {
-      if (!src[s]) return fail(AXVS_ERR_ARG, "null pointer (%s %d, parameter %d)", what, index, s);
-      if (hipMemcpyAsync(dst[s], src[s], n[s] * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
-    }
-    return (int)AXVS_OK;
-  };
   head_sizes(cfg, n);
-  if (int rc = copy(w.head, head, HD_N, "head", 0)) return rc;
+  if (int rc = copy_slots(w.head, head, n, HD_N, "head", 0, st)) return rc;
   for (int i = 0; i < cfg->num_layers; ++i) {
     layer_sizes(cfg, i, n);
-    if (int rc = copy(w.layer[i], layers + i, LY_N, "layer", i)) return rc;
+    if (int rc = copy_slots(w.layer[i], layers + i, n, LY_N, "layer", i, st)) return rc;
   }
   return AXVS_OK;
 }
@@ -246,7 +221,7 @@ int axvs_kmax_decoder_fwd(const AxvsKmaxCfg* cfg, const void* packed, const floa
   if ((cfg->want_masks && !pred_masks) || (cfg->want_pixel_feature && !pixel_feature) || ((cfg->want_masks || cfg->want_pixel_feature) && !panoptic))
     return fail(AXVS_ERR_ARG, "null pointer (an output flag without its buffer, or without the panoptic features)");
   const KmaxWs w = kmax_carve(workspace, cfg, 0, 0);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const KmaxW p = kmax_weights(const_cast<void*>(packed), cfg);
   const int R = cfg->B * cfg->L, nl = cfg->num_layers, BT = cfg->B * cfg->T;
@@ -267,10 +242,10 @@ int axvs_kmax_decoder_fwd(const AxvsKmaxCfg* cfg, const void* packed, const floa
   // the final predictor
   const long long Rl = R;
   float* const* pr = p.head + HD_PRED;
-  if (int rc = linear(cluster_centers, C, p.head[HD_CEP_W], p.head[HD_CEP_B], w.ce, Rl, C, C, C, kActGelu, nullptr, st)) return rc;
-  if (int rc = linear(cluster_centers, C, p.head[HD_MEP_W], p.head[HD_MEP_B], w.me, Rl, C, C, C, kActGelu, nullptr, st)) return rc;
+  if (int rc = linear(cluster_centers, C, p.head[HD_CEP_W], p.head[HD_CEP_B], w.ce, Rl, C, C, C, kActGelu, nullptr, kForm3Gelu, st)) return rc;
+  if (int rc = linear(cluster_centers, C, p.head[HD_MEP_W], p.head[HD_MEP_B], w.me, Rl, C, C, C, kActGelu, nullptr, kForm3Gelu, st)) return rc;
   class_logits(cfg, pr, w.ce, pred_logits, st);
-  if (int rc = linear(w.me, C, pr[PR_MH_W], pr[PR_MH_B], pred_mask_embeddings, Rl, D, C, D, kActNone, nullptr, st)) return rc;
+  if (int rc = linear(w.me, C, pr[PR_MH_W], pr[PR_MH_B], pred_mask_embeddings, Rl, D, C, D, kActNone, nullptr, kForm3Gelu, st)) return rc;
   if (cfg->want_masks || cfg->want_pixel_feature) {
     const int S = (int)pan_pixels(cfg);
     to_cl<false>(panoptic, w.pa, BT, C, cfg->H, cfg->W, st);
@@ -293,7 +268,7 @@ int axvs_kmax_assign_fwd(const AxvsKmaxCfg* cfg, const void* packed, int layer, 
   if (layer < 0 || layer >= cfg->num_layers) return fail(AXVS_ERR_ARG, "layer=%d must be in 0..%d", layer, cfg->num_layers - 1);
   if (!packed || !query || !feature || !idx || !class_logits_out || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const KmaxWs w = kmax_carve(workspace, cfg, 1, layer);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const KmaxW p = kmax_weights(const_cast<void*>(packed), cfg);
   const int l = cfg->layer_level[layer];
@@ -309,15 +284,15 @@ int axvs_kmax_layer_fwd(const AxvsKmaxCfg* cfg, const void* packed, int layer, c
   if (layer < 0 || layer >= cfg->num_layers) return fail(AXVS_ERR_ARG, "layer=%d must be in 0..%d", layer, cfg->num_layers - 1);
   if (!packed || !query || !feature || !idx || !out || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const KmaxWs w = kmax_carve(workspace, cfg, 2, layer);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const KmaxW p = kmax_weights(const_cast<void*>(packed), cfg);
   float* const* y = p.layer[layer];
   const int l = cfg->layer_level[layer];
   const long long R = (long long)cfg->B * cfg->L, P = (long long)cfg->B * pixels_of(cfg, l);
   to_cl<true>(feature, w.gx[l], cfg->B * cfg->T, cfg->in_channels[l], cfg->h[l], cfg->w[l], st);
-  if (int rc = linear(w.gx[l], cfg->in_channels[l], y[LY_PIX1_W], y[LY_PIX1_B], w.pa, P, C, cfg->in_channels[l], C, kActGelu, nullptr, st)) return rc;
-  if (int rc = linear(query, C, y[LY_Q1_W], y[LY_Q1_B], w.qs, R, C, C, C, kActGelu, nullptr, st)) return rc;
+  if (int rc = linear(w.gx[l], cfg->in_channels[l], y[LY_PIX1_W], y[LY_PIX1_B], w.pa, P, C, cfg->in_channels[l], C, kActGelu, nullptr, kForm3Gelu, st)) return rc;
+  if (int rc = linear(query, C, y[LY_Q1_W], y[LY_Q1_B], w.qs, R, C, C, C, kActGelu, nullptr, kForm3Gelu, st)) return rc;
   if (int rc = update(cfg, layer, p, w, query, idx, out, st)) return rc;
   return last_launch_status();
 }

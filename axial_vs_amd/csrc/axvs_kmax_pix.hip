@@ -1,13 +1,13 @@
 // C-ABI entry points of Video-kMaX's pixel decoder (include/axvs.h: axvs_kmax_pix_*) and the launch sequence behind them.
-// 1x1 convolutions with their folded BatchNorms: the three-piece split-precision GEMM behind gemm_nt (axvs_gemm_nt.h), in its form with
-// the gelu epilogues, the block's residual as `res`; everything else: axvs_kmax_pix.h.  The gelu in front of a block or a fuse
-// convolution is a pass of its own (the raw stage outputs are results); the gelu behind the width-axis attention rides in that kernel.
+// 1x1 convolutions with their folded BatchNorms: linear() of axvs_eval_host.h (with the slot-list helpers of the pack and locate()), the
+// three-piece split-precision GEMM in its form with the gelu epilogues, the block's residual as `res`; everything else: axvs_kmax_pix.h.
+// The gelu in front of a block or a fuse convolution is a pass of its own (the raw stage outputs are results); the gelu behind the
+// width-axis attention rides in that kernel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "axvs_gemm_nt.h"
-#include "axvs_host.h"
+#include "axvs_eval_host.h"
 #include "axvs_kmax_pix.h"
 
 using namespace axvs;
@@ -15,7 +15,6 @@ using namespace axvs;
 namespace {
 
 constexpr int kStages = 4, kMaxBlocks = 16;
-constexpr int kActNone = 0, kActGelu = 2;      // GemmEpi::relu under ACT
 
 // the slots of AxvsKpixBlockParams / AxvsKpixFuseParams, in declaration order (axial_vs_amd/_params.py states the same order)
 enum { AX_QKV_W, AX_QKV_B, AX_EQ, AX_EK, AX_EV, AX_SIM, AX_OUT, AX_N };
@@ -90,11 +89,11 @@ KpixW kpix_weights(void* blob, const AxvsKpixCfg* c) {
   for (int i = 0; i < kStages; ++i) {
     if (i > 0) {
       fuse_sizes(c, i, n);
-      for (int s = 0; s < FU_N; ++s) w.fuse[i][s] = n[s] ? cv.f(n[s]) : nullptr;
+      carve_slots(cv, n, FU_N, w.fuse[i]);
     }
     for (int j = 0; j < c->blocks[i]; ++j) {
       block_sizes(c, i, j, n);
-      for (int s = 0; s < BK_N; ++s) w.block[i][j][s] = n[s] ? cv.f(n[s]) : nullptr;
+      carve_slots(cv, n, BK_N, w.block[i][j]);
     }
   }
   w.bytes = cv.off;
@@ -131,14 +130,6 @@ KpixWs kpix_carve(void* ws, const AxvsKpixCfg* c) {
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------------------------------
-// Y[M][N] = act(X[M][K] W[N][K]^T + bias) (+ res[M][N]): three bf16 pieces per operand
-int linear(const float* X, const float* W, const float* bias, float* Y, long long M, int N, int K, int act, const float* res, hipStream_t st) {
-  tr::GemmLd ld{K, K, N, 0, nullptr};
-  tr::GemmEpi e{bias, 1.f, act, tr::Drop{0u, 0u, 0u, 1.f}, 0.f};
-  e.res = res;
-  return tr::gemm_nt(X, W, Y, M, N, K, ld, e, tr::GemmNtForm{3, false, true}, 1, st);
-}
-
 void gelu(const float* x, float* y, size_t n, hipStream_t st) {
   hipLaunchKernelGGL(kpix_gelu_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, x, y, n / 4);
 }
@@ -147,10 +138,6 @@ void innorm(const float* src, const float* g, const float* b, float* out, int N,
   const dim3 grid((unsigned)((hw + 31) / 32), (unsigned)N);
   if (act) hipLaunchKernelGGL((kpix_innorm_kernel<true>), grid, dim3(256), 0, st, src, g, b, out, C, hw);
   else hipLaunchKernelGGL((kpix_innorm_kernel<false>), grid, dim3(256), 0, st, src, g, b, out, C, hw);
-}
-
-void to_nchw(const float* rows, float* out, int N, int C, int hw, hipStream_t st) {
-  hipLaunchKernelGGL(kpix_to_nchw_kernel, dim3((unsigned)((hw + 31) / 32 * ((C + 63) / 64)), (unsigned)N), dim3(256), 0, st, rows, out, C, hw);
 }
 
 void to_rows(const float* src, float* out, int N, int C, int h, int w, hipStream_t st) {
@@ -197,21 +184,21 @@ int block(const AxvsKpixCfg* c, int i, int j, float* const* p, const KpixWs& w, 
   gelu(x, w.g, (size_t)P * cin, st);
   const float* res = w.g;
   if (p[BK_SC_W]) {
-    if (int rc = linear(w.g, p[BK_SC_W], p[BK_SC_B], w.sc, P, cout, cin, kActNone, nullptr, st)) return rc;
+    if (int rc = linear(w.g, cin, p[BK_SC_W], p[BK_SC_B], w.sc, P, cout, cin, cout, kActNone, nullptr, kForm3Gelu, st)) return rc;
     res = w.sc;
   }
-  if (int rc = linear(w.g, p[BK_C1_W], p[BK_C1_B], w.h1, P, mid, cin, kActGelu, nullptr, st)) return rc;
+  if (int rc = linear(w.g, cin, p[BK_C1_W], p[BK_C1_B], w.h1, P, mid, cin, mid, kActGelu, nullptr, kForm3Gelu, st)) return rc;
   if (c->axial[i]) {
     float* const* hp = p + BK_HEIGHT;
     float* const* wp = p + BK_WIDTH;
-    if (int rc = linear(w.h1, hp[AX_QKV_W], hp[AX_QKV_B], w.qkv, P, 4 * b, mid, kActNone, nullptr, st)) return rc;
+    if (int rc = linear(w.h1, mid, hp[AX_QKV_W], hp[AX_QKV_B], w.qkv, P, 4 * b, mid, 4 * b, kActNone, nullptr, kForm3Gelu, st)) return rc;
     if (int rc = attn(c, i, 0, hp, w.qkv, w.a1, 0, st)) return rc;
-    if (int rc = linear(w.a1, wp[AX_QKV_W], wp[AX_QKV_B], w.qkv, P, 4 * b, mid, kActNone, nullptr, st)) return rc;
+    if (int rc = linear(w.a1, mid, wp[AX_QKV_W], wp[AX_QKV_B], w.qkv, P, 4 * b, mid, 4 * b, kActNone, nullptr, kForm3Gelu, st)) return rc;
     if (int rc = attn(c, i, 1, wp, w.qkv, w.a2, 1, st)) return rc;
-    return linear(w.a2, p[BK_C3_W], p[BK_C3_B], y, P, cout, mid, kActNone, res, st);
+    return linear(w.a2, mid, p[BK_C3_W], p[BK_C3_B], y, P, cout, mid, cout, kActNone, res, kForm3Gelu, st);
   }
   if (int rc = conv3(w.h1, p[BK_C2_W], p[BK_C2_B], w.a1, c->N, b, c->h[i], c->w[i], st)) return rc;
-  return linear(w.a1, p[BK_C3_W], p[BK_C3_B], y, P, cout, mid, kActNone, res, st);
+  return linear(w.a1, mid, p[BK_C3_W], p[BK_C3_B], y, P, cout, mid, cout, kActNone, res, kForm3Gelu, st);
 }
 
 PanAxis axis_of(int in, int out, int ac) {
@@ -227,12 +214,12 @@ int fuse(const AxvsKpixCfg* c, int i, float* const* p, const KpixWs& w, const fl
   const float* lo = low;
   if (p[FU_LOW_W]) {
     gelu(low, w.g, (size_t)Pl * lowc, st);
-    if (int rc = linear(w.g, p[FU_LOW_W], p[FU_LOW_B], w.lo, Pl, b, lowc, kActNone, nullptr, st)) return rc;
+    if (int rc = linear(w.g, lowc, p[FU_LOW_W], p[FU_LOW_B], w.lo, Pl, b, lowc, b, kActNone, nullptr, kForm3Gelu, st)) return rc;
     lo = w.lo;
   }
   if (p[FU_HIGH_W]) {
     innorm(high, p[FU_LN_W], p[FU_LN_B], w.g, c->N, highc, c->h[i] * c->w[i], true, st);
-    if (int rc = linear(w.g, p[FU_HIGH_W], p[FU_HIGH_B], out, Ph, b, highc, kActNone, nullptr, st)) return rc;
+    if (int rc = linear(w.g, highc, p[FU_HIGH_W], p[FU_HIGH_B], out, Ph, b, highc, b, kActNone, nullptr, kForm3Gelu, st)) return rc;
   } else {
     innorm(high, p[FU_LN_W], p[FU_LN_B], out, c->N, highc, c->h[i] * c->w[i], false, st);
   }
@@ -240,22 +227,6 @@ int fuse(const AxvsKpixCfg* c, int i, float* const* p, const KpixWs& w, const fl
   hipLaunchKernelGGL(kpix_resize_add_kernel, dim3((unsigned)(((size_t)Ph * b / 4 + 255) / 256)), dim3(256), 0, st, lo, (const float*)out, out, c->N, b,
                      axis_of(c->h[i - 1], c->h[i], ac), axis_of(c->w[i - 1], c->w[i], ac), ac);
   return AXVS_OK;
-}
-
-int ws_check(long long have, size_t need) {
-  if (have < 0 || (size_t)have < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", have, need);
-  return AXVS_OK;
-}
-
-int locate(const AxvsKpixCfg* c, int index, int* stage, int* j) {        // block `index` of the whole decoder -> (stage, block of the stage)
-  for (int i = 0; i < kStages; ++i) {
-    if (index >= 0 && index < c->blocks[i]) {
-      *stage = i, *j = index;
-      return AXVS_OK;
-    }
-    index -= c->blocks[i];
-  }
-  return fail(AXVS_ERR_ARG, "block index outside the decoder's blocks");
 }
 
 }  // namespace
@@ -272,30 +243,17 @@ int axvs_kmax_pix_pack(const AxvsKpixBlockParams* blocks, const AxvsKpixFusePara
   hipStream_t st = static_cast<hipStream_t>(stream);
   const KpixW w = kpix_weights(packed, cfg);
   size_t n[BK_N];
-  auto copy1 = [&](float* dst, const float* src, size_t count) {
-    if (hipMemcpyAsync(dst, src, count * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
-    return (int)AXVS_OK;
-  };
-  auto copy = [&](float* const* dst, const void* src_struct, int slots, const char* what, int index) {
-    const float* const* src = reinterpret_cast<const float* const*>(src_struct);
-    for (int s = 0; s < slots; ++s) {
-      if (!n[s]) continue;
-      if (!src[s]) return fail(AXVS_ERR_ARG, "null pointer (%s %d, parameter %d)", what, index, s);
-      if (int rc = copy1(dst[s], src[s], n[s])) return rc;
-    }
-    return (int)AXVS_OK;
-  };
-  if (int rc = copy1(w.ln0_w, ln0_w, cfg->in_channels[0])) return rc;
-  if (int rc = copy1(w.ln0_b, ln0_b, cfg->in_channels[0])) return rc;
+  if (int rc = copy_f(w.ln0_w, ln0_w, cfg->in_channels[0], st)) return rc;
+  if (int rc = copy_f(w.ln0_b, ln0_b, cfg->in_channels[0], st)) return rc;
   int index = 0;
   for (int i = 0; i < kStages; ++i) {
     if (i > 0) {
       fuse_sizes(cfg, i, n);
-      if (int rc = copy(w.fuse[i], fuses + (i - 1), FU_N, "fuse", i - 1)) return rc;
+      if (int rc = copy_slots(w.fuse[i], fuses + (i - 1), n, FU_N, "fuse", i - 1, st)) return rc;
     }
     for (int j = 0; j < cfg->blocks[i]; ++j, ++index) {
       block_sizes(cfg, i, j, n);
-      if (int rc = copy(w.block[i][j], blocks + index, BK_N, "block", index)) return rc;
+      if (int rc = copy_slots(w.block[i][j], blocks + index, n, BK_N, "block", index, st)) return rc;
     }
   }
   return AXVS_OK;
@@ -313,7 +271,7 @@ int axvs_kmax_pix_decoder_fwd(const AxvsKpixCfg* cfg, const void* packed, const 
   for (int i = 0; i < kStages; ++i)
     if (!features[i] || !outputs[i]) return fail(AXVS_ERR_ARG, "null pointer (stage %d features or output)", i);
   const KpixWs w = kpix_carve(workspace, cfg);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const KpixW p = kpix_weights(const_cast<void*>(packed), cfg);
   float *cur = w.x, *nxt = w.y;
@@ -327,7 +285,7 @@ int axvs_kmax_pix_decoder_fwd(const AxvsKpixCfg* cfg, const void* packed, const 
       if (int rc = block(cfg, i, j, p.block[i][j], w, cur, nxt, st)) return rc;
       std::swap(cur, nxt);
     }
-    to_nchw(cur, outputs[i], cfg->N, 4 * cfg->base[i], cfg->h[i] * cfg->w[i], st);
+    rows_to_nchw(cur, outputs[i], cfg->N, 4 * cfg->base[i], cfg->h[i] * cfg->w[i], st);
   }
   return last_launch_status();
 }
@@ -335,7 +293,7 @@ int axvs_kmax_pix_decoder_fwd(const AxvsKpixCfg* cfg, const void* packed, const 
 int axvs_kmax_pix_axial_attn_fwd(const AxvsKpixCfg* cfg, const void* packed, int block_index, int axis, const float* qkv, float* out, void* stream) {
   if (int rc = kpix_check(cfg)) return rc;
   int i, j;
-  if (int rc = locate(cfg, block_index, &i, &j)) return rc;
+  if (int rc = locate(cfg->blocks, block_index, "decoder's", &i, &j)) return rc;
   if (!cfg->axial[i] || axis < 0 || axis > 1) return fail(AXVS_ERR_ARG, "block %d is not an axial block, or axis=%d is not 0 / 1", block_index, axis);
   if (!packed || !qkv || !out) return fail(AXVS_ERR_ARG, "null pointer");
   const KpixW p = kpix_weights(const_cast<void*>(packed), cfg);
@@ -347,15 +305,15 @@ int axvs_kmax_pix_block_fwd(const AxvsKpixCfg* cfg, const void* packed, int bloc
                             long long workspace_bytes, void* stream) {
   if (int rc = kpix_check(cfg)) return rc;
   int i, j;
-  if (int rc = locate(cfg, block_index, &i, &j)) return rc;
+  if (int rc = locate(cfg->blocks, block_index, "decoder's", &i, &j)) return rc;
   if (!packed || !x || !out || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const KpixWs w = kpix_carve(workspace, cfg);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const KpixW p = kpix_weights(const_cast<void*>(packed), cfg);
   to_rows(x, w.x, cfg->N, block_cin(cfg, i, j), cfg->h[i], cfg->w[i], st);
   if (int rc = block(cfg, i, j, p.block[i][j], w, w.x, w.y, st)) return rc;
-  to_nchw(w.y, out, cfg->N, 4 * cfg->base[i], cfg->h[i] * cfg->w[i], st);
+  rows_to_nchw(w.y, out, cfg->N, 4 * cfg->base[i], cfg->h[i] * cfg->w[i], st);
   return last_launch_status();
 }
 
@@ -365,12 +323,12 @@ int axvs_kmax_pix_fuse_fwd(const AxvsKpixCfg* cfg, const void* packed, int fuse_
   if (fuse_index < 0 || fuse_index > 2) return fail(AXVS_ERR_ARG, "fuse_index=%d must be in 0..2", fuse_index);
   if (!packed || !low || !high || !out || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const KpixWs w = kpix_carve(workspace, cfg);
-  if (int rc = ws_check(workspace_bytes, w.bytes)) return rc;
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const KpixW p = kpix_weights(const_cast<void*>(packed), cfg);
   const int i = fuse_index + 1;
   to_rows(low, w.y, cfg->N, 4 * cfg->base[i - 1], cfg->h[i - 1], cfg->w[i - 1], st);
   if (int rc = fuse(cfg, i, p.fuse[i], w, w.y, high, w.x, st)) return rc;
-  to_nchw(w.x, out, cfg->N, cfg->base[i], cfg->h[i] * cfg->w[i], st);
+  rows_to_nchw(w.x, out, cfg->N, cfg->base[i], cfg->h[i] * cfg->w[i], st);
   return last_launch_status();
 }

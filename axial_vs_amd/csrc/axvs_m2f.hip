@@ -1,11 +1,11 @@
 // C-ABI entry points of Tube-Link's per-clip masked-attention query decoder (include/axvs.h: axvs_m2f_*) and the launch sequence behind
-// them.  Linear layers: the three-piece split-precision GEMM behind gemm_nt (axvs_gemm_nt.h); everything else: axvs_m2f.h.
+// them.  Linear layers: linear() of axvs_eval_host.h on the three-piece split-precision GEMM in its ReLU form (kForm3), x + query_pos as
+// the addend X2, and linear_split() below; everything else: axvs_m2f.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "axvs_gemm_nt.h"
-#include "axvs_host.h"
+#include "axvs_eval_host.h"
 #include "axvs_m2f.h"
 
 using namespace axvs;
@@ -113,15 +113,6 @@ M2fWs m2f_carve(void* ws, const AxvsM2fCfg* c, int what, int arg) {
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------------------------------
-// Y[M][N] (row stride ldc) = epilogue((X (+ X2))[M][K] W[N][K]^T + bias): ReLU, + res[M][ldc]; three bf16 pieces per operand
-int linear(const float* X, const float* X2, const float* W, const float* bias, float* Y, long long M, int N, int K, long long ldc, bool relu,
-           const float* res, hipStream_t st) {
-  tr::GemmLd ld{K, K, ldc, 0, X2};
-  tr::GemmEpi e{bias, 1.f, relu ? 1 : 0, tr::Drop{0u, 0u, 0u, 1.f}, 0.f};
-  e.res = res;
-  return tr::gemm_nt(X, W, Y, M, N, K, ld, e, tr::GemmNtForm{3}, 1, st);
-}
-
 // The GEMMs in front of a LayerNorm: M = N*Q rows alone are one or two row tiles, so the contraction is split over workgroups (ksteps
 // 32-wide steps each); the partials P[z][M][C] are added, with bias and residual, by m2f_ln_kernel.  Returns the number of partials.
 int linear_split(const float* X, const float* W, float* P, long long M, int K, int ksteps, hipStream_t st, int* nparts) {
@@ -148,8 +139,8 @@ int project_level(const AxvsM2fCfg* c, int l, const float* memory, const M2fW& p
   hipLaunchKernelGGL((m2f_to_cl_kernel<true>), grid, dim3(256), 0, st, memory, w.val_in, w.key_in, (const float*)(p.level_embed + l * C), level_map(c, l, true),
                      c->pos_temperature, c->pos_normalize, c->pos_scale);
   const long long rows = (long long)c->N * keys_of(c, l);
-  if (int rc = linear(w.key_in, nullptr, wk, bk, w.K[l], rows, nl * C, C, (long long)nl * C, false, nullptr, st)) return rc;
-  return linear(w.val_in, nullptr, wv, bv, w.V[l], rows, nl * C, C, (long long)nl * C, false, nullptr, st);
+  if (int rc = linear(w.key_in, C, wk, bk, w.K[l], rows, nl * C, C, (long long)nl * C, kActNone, nullptr, kForm3, st)) return rc;
+  return linear(w.val_in, C, wv, bv, w.V[l], rows, nl * C, C, (long long)nl * C, kActNone, nullptr, kForm3, st);
 }
 
 void logits_grid(int Q, int S, int Z, dim3* grid, int* per_y) {
@@ -162,9 +153,9 @@ void logits_grid(int Q, int S, int Z, dim3* grid, int* per_y) {
 // y (post-normed queries) -> mask_embed MLP -> w.me
 int mask_embed(const AxvsM2fCfg* c, const M2fW& p, const M2fWs& w, const float* y, hipStream_t st) {
   const long long R = (long long)c->N * c->Q;
-  if (int rc = linear(y, nullptr, p.me_w[0], p.me_b[0], w.h1, R, C, C, C, true, nullptr, st)) return rc;
-  if (int rc = linear(w.h1, nullptr, p.me_w[1], p.me_b[1], w.h2, R, C, C, C, true, nullptr, st)) return rc;
-  return linear(w.h2, nullptr, p.me_w[2], p.me_b[2], w.me, R, C, C, C, false, nullptr, st);
+  if (int rc = linear(y, C, p.me_w[0], p.me_b[0], w.h1, R, C, C, C, kActRelu, nullptr, kForm3, st)) return rc;
+  if (int rc = linear(w.h1, C, p.me_w[1], p.me_b[1], w.h2, R, C, C, C, kActRelu, nullptr, kForm3, st)) return rc;
+  return linear(w.h2, C, p.me_w[2], p.me_b[2], w.me, R, C, C, C, kActNone, nullptr, kForm3, st);
 }
 
 // the mask head in front of a layer of level l, from the post-normed queries y: bits [N*Q][ceil(S/32)], flags [N*Q] (cleared by the caller)
@@ -206,25 +197,20 @@ int layer(const AxvsM2fCfg* c, int i, const M2fW& p, const M2fWs& w, const float
   const size_t ps = (size_t)R * C;
   int np = 1;
   // cross-attention: q = (x + query_pos) Wq^T + bq
-  if (int rc = linear(x_in, w.qpos, y.wq, y.bq, w.qp, R, C, C, C, false, nullptr, st)) return rc;
+  if (int rc = linear(x_in, C, y.wq, y.bq, w.qp, R, C, C, C, kActNone, nullptr, kForm3, st, w.qpos)) return rc;
   attention(c, w, w.qp, C, K, ldkv, V, ldkv, S, bits, flags, st);
   if (int rc = linear_split(w.att, y.cross_out_w, w.t, R, C, 2, st, &np)) return rc;
   layer_norm(w.t, np, ps, y.cross_out_b, x_in, y.norm0_w, y.norm0_b, w.x1, nullptr, nullptr, nullptr, nullptr, rows, st);
   // self-attention: q = k = x + query_pos, v = x
-  if (int rc = linear(w.x1, w.qpos, y.self_in_w, y.self_in_b, w.qk, R, 2 * C, C, 2 * C, false, nullptr, st)) return rc;
-  if (int rc = linear(w.x1, nullptr, y.self_in_w + (size_t)2 * C * C, y.self_in_b + 2 * C, w.v, R, C, C, C, false, nullptr, st)) return rc;
+  if (int rc = linear(w.x1, C, y.self_in_w, y.self_in_b, w.qk, R, 2 * C, C, 2 * C, kActNone, nullptr, kForm3, st, w.qpos)) return rc;
+  if (int rc = linear(w.x1, C, y.self_in_w + (size_t)2 * C * C, y.self_in_b + 2 * C, w.v, R, C, C, C, kActNone, nullptr, kForm3, st)) return rc;
   attention(c, w, w.qk, 2 * C, w.qk + C, 2 * C, w.v, C, c->Q, nullptr, nullptr, st);
   if (int rc = linear_split(w.att, y.self_out_w, w.t, R, C, 2, st, &np)) return rc;
   layer_norm(w.t, np, ps, y.self_out_b, w.x1, y.norm1_w, y.norm1_b, w.x2, nullptr, nullptr, nullptr, nullptr, rows, st);
   // FFN: the second GEMM contracts 2048 channels -- 16 partials of 4 steps
-  if (int rc = linear(w.x2, nullptr, y.ffn1_w, y.ffn1_b, w.hid, R, c->ffn, C, c->ffn, true, nullptr, st)) return rc;
+  if (int rc = linear(w.x2, C, y.ffn1_w, y.ffn1_b, w.hid, R, c->ffn, C, c->ffn, kActRelu, nullptr, kForm3, st)) return rc;
   if (int rc = linear_split(w.hid, y.ffn2_w, w.t, R, c->ffn, 4, st, &np)) return rc;
   layer_norm(w.t, np, ps, y.ffn2_b, w.x2, y.norm2_w, y.norm2_b, x_out, y_out ? p.post_norm_w : nullptr, p.post_norm_b, y_out, flags_next, rows, st);
-  return AXVS_OK;
-}
-
-int copy_f(float* dst, const float* src, size_t n, hipStream_t st) {
-  if (hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(AXVS_ERR_LAUNCH, "hipMemcpyAsync failed");
   return AXVS_OK;
 }
 
@@ -289,7 +275,7 @@ int axvs_m2f_decoder_fwd(const AxvsM2fCfg* cfg, const void* packed, const float*
   if (cfg->return_predictions && (!cls_pred || !mask_pred)) return fail(AXVS_ERR_ARG, "null pointer (return_predictions without cls_pred / mask_pred)");
   if ((debug_bits == nullptr) != (debug_flags == nullptr)) return fail(AXVS_ERR_ARG, "debug_bits and debug_flags come together");
   const M2fWs w = m2f_carve(workspace, cfg, 0, 0);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < w.bytes) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, w.bytes);
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const M2fW p = m2f_weights(const_cast<void*>(packed), cfg);
   const int R = cfg->N * cfg->Q, nl = cfg->num_layers;
@@ -342,7 +328,7 @@ int axvs_m2f_attn_mask_fwd(const AxvsM2fCfg* cfg, const void* packed, const floa
   if (level < 0 || level > 2) return fail(AXVS_ERR_ARG, "level=%d must be in 0..2", level);
   if (!packed || !x || !mask_features || !bits || !flags || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const M2fWs w = m2f_carve(workspace, cfg, 1, level);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < w.bytes) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, w.bytes);
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const M2fW p = m2f_weights(const_cast<void*>(packed), cfg);
   const int R = cfg->N * cfg->Q;
@@ -363,7 +349,7 @@ int axvs_m2f_layer_fwd(const AxvsM2fCfg* cfg, const void* packed, int layer_inde
   if (layer_index < 0 || layer_index >= cfg->num_layers) return fail(AXVS_ERR_ARG, "layer=%d must be in 0..%d", layer_index, cfg->num_layers - 1);
   if (!packed || !x || !memory || !bits || !flags || !out || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const M2fWs w = m2f_carve(workspace, cfg, 2, layer_index);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < w.bytes) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, w.bytes);
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const M2fW p = m2f_weights(const_cast<void*>(packed), cfg);
   const int R = cfg->N * cfg->Q, l = layer_index % 3, j = layer_index / 3;

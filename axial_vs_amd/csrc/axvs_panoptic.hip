@@ -109,7 +109,7 @@ int axvs_video_panoptic_fwd(const AxvsPanopticCfg* cfg, const float* mask_cls, c
     return fail(AXVS_ERR_ARG, "mask dtype %d is not AXVS_F16 / AXVS_BF16 / AXVS_F32", mask_dtype);
   if (!mask_cls || !mask_pred || !is_thing || !cat_id || !out_map || !slot_ints || !slot_floats || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const PanWs w = pan_carve(workspace, cfg);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < w.bytes) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, w.bytes);
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int ac = cfg->align_corners != 0, two = cfg->two_stage != 0;
   PanGeom g;

@@ -172,7 +172,7 @@ int axvs_pixel_insdis_fwd(const float* const* pixel_feature, const void* targets
     c.ly.feat[l] = pixel_feature[l];
   }
   const size_t need = axvs_pixel_insdis_workspace_bytes(L, B, C, kmax, k);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, need);
+  if (int rc = check_ws(workspace_bytes, need)) return rc;
   c.Kp = ceil16(k), c.Cp = ceil16(C), c.Mp = ceil16(kmax);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const InsdisWs w = insdis_ws(workspace, L, B, C, kmax, k);
@@ -205,7 +205,7 @@ int axvs_pixel_insdis_bwd(const float* grad_losses, const float* const* pixel_fe
     c.ly.dfeat[l] = d_pixel_feature[l];      // NULL: that layer's gradient is skipped
   }
   const size_t need = axvs_pixel_insdis_workspace_bytes(L, B, C, kmax, k);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, need);
+  if (int rc = check_ws(workspace_bytes, need)) return rc;
   if (k == 0) return AXVS_OK;
   c.Kp = ceil16(k), c.Cp = ceil16(C), c.Mp = ceil16(kmax);
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -128,7 +128,7 @@ int axvs_tl_loss_fwd(const AxvsTLLossCfg* cfg, const float* const* cls_scores, c
   if (s.G > 0 && s.P - s.k > 0 && !rand_coords) return fail(AXVS_ERR_ARG, "null pointer (rand_coords)");
   size_t need = 0;
   const TLWork wk = tl_work_views(workspace, s, &need);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, need);
+  if (int rc = check_ws(workspace_bytes, need)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const TLSaved sv = tl_saved_views(saved, s, nullptr);
   const int nprob = s.L * s.B;

@@ -92,7 +92,7 @@ int axvs_video_instance_fwd(const AxvsVisCfg* cfg, const float* mask_cls, const 
     return fail(AXVS_ERR_ARG, "mask dtype %d is not AXVS_F16 / AXVS_BF16 / AXVS_F32", mask_dtype);
   if (!mask_cls || !mask_pred || !out_masks || !table_ints || !table_floats || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
   const VisWs w = vis_carve(workspace, cfg);
-  if (workspace_bytes < 0 || (size_t)workspace_bytes < w.bytes) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %lld < %zu", workspace_bytes, w.bytes);
+  if (int rc = check_ws(workspace_bytes, w.bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int F = cfg->num_frames, K = cfg->k_cand, Ko = cfg->k_out;
   const VisTabs tb = vis_tabs(table_ints, table_floats, F, K, Ko);

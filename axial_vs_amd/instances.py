@@ -29,7 +29,7 @@ from torch import Tensor
 
 from . import _lib
 from .matching import _mask_dtype
-from .modules import _guarded, _stream, _workspace
+from .modules import _guarded, _stream, _workspace_for
 
 
 def _al(n: int) -> int:
@@ -99,11 +99,8 @@ def _launch(mask_cls: Tensor, mask_pred: Tensor, num_frames, batch_input_shape, 
                           crop_h=int(img_shape[0]), crop_w=int(img_shape[1]), H=H, W=W, num_things=int(num_things_classes), k_cand=K, k_out=Ko,
                           mask_bits=int(bits))
     L = _lib.lib()
-    need = L.axvs_video_instance_workspace_bytes(C.byref(cfg))
-    if need == 0:
-        _lib.check(-1, "axvs_video_instance_workspace_bytes")
     st = _stream(dev)
-    ws = _workspace(dev, need, st)
+    ws = _workspace_for("axvs_video_instance_workspace_bytes", dev, st, C.byref(cfg))
     buf = torch.empty(_offsets(F, K, Ko, H, W, bits)[0][3], dtype=torch.uint8, device=dev)      # tables and masks: one buffer, one copy to the host
     masks, ti, tf, tables = _views(buf, F, K, Ko, H, W, bits)
     _lib.check(L.axvs_video_instance_fwd(C.byref(cfg), mask_cls.data_ptr(), mask_pred.data_ptr(), _mask_dtype(mask_pred), masks.data_ptr(),

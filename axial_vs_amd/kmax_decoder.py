@@ -27,7 +27,7 @@ from torch import Tensor
 
 from . import _lib
 from ._params import kmax_head_folded, kmax_layer_folded
-from .modules import _cached_pack, _dev_f32, _guarded, _stream, _workspace
+from .modules import _cached_pack, _dev_f32, _guarded, _pack_folded, _stream, _workspace_for
 
 _BOTTLENECK, _KEY, _VALUE, _HEADS, _FFN, _MASK = 256, 128, 256, 8, 2048, 128
 
@@ -128,24 +128,10 @@ def _cfg(B: int, T: int, L: int, K1: int, dec_layers, in_channels, sizes, pan, w
 
 def _pack(sd: Mapping[str, Tensor], dec_layers, in_channels, L: int, K1: int) -> Tensor:
     """fold (float64) and pack: one blob of fp32 tensors in the kernels' layouts"""
-    Lb = _lib.lib()
-    nl = sum(int(n) for n in dec_layers)
-    ref = sd["_cluster_centers.weight"]
-    if not ref.is_cuda:
-        raise RuntimeError(f"axial_vs_amd: parameters must be GPU tensors (got {ref.device}); there is no CPU fallback")
-    with torch.no_grad():
-        sd = {k: v.detach() for k, v in sd.items()}
-        head = [t.float().contiguous() for t in kmax_head_folded(sd)]
-        layers = [[t.float().contiguous() for t in kmax_layer_folded(sd, f"_kmax_transformer_layers.{i}.")] for i in range(nl)]
-    cfg = _cfg(1, 1, L, K1, dec_layers, in_channels, [(1, 1)] * 3, (256, 1, 1))
-    ls = (_lib.AxvsKmaxLayerParams * nl)(*[_lib.fill(_lib.AxvsKmaxLayerParams, [t.data_ptr() for t in ts]) for ts in layers])
-    hs = _lib.fill(_lib.AxvsKmaxHeadParams, [t.data_ptr() for t in head])
-    need = Lb.axvs_kmax_decoder_packed_bytes(C.byref(cfg))
-    if need == 0:
-        _lib.check(-1, "axvs_kmax_decoder_packed_bytes")
-    buf = torch.zeros(need, dtype=torch.uint8, device=ref.device)
-    _lib.check(Lb.axvs_kmax_decoder_pack(ls, C.byref(hs), C.byref(cfg), buf.data_ptr(), _stream(ref.device)), "axvs_kmax_decoder_pack")
-    return buf      # (the folded tensors die with this frame: the allocator hands their memory out again in stream order)
+    sd = {k: v.detach() for k, v in sd.items()}
+    layers = (kmax_layer_folded(sd, f"_kmax_transformer_layers.{i}.") for i in range(sum(int(n) for n in dec_layers)))
+    return _pack_folded("axvs_kmax_decoder", _cfg(1, 1, L, K1, dec_layers, in_channels, [(1, 1)] * 3, (256, 1, 1)),
+                        [(_lib.AxvsKmaxLayerParams, layers), (_lib.AxvsKmaxHeadParams, [kmax_head_folded(sd)])])
 
 
 def _clips(BT: int, num_clip_frames: int, cross_clip_training: bool):
@@ -174,11 +160,8 @@ def _run(packed: Tensor, feats, pan, B, T, L, K1, dec_layers, in_channels, want_
     sizes = [tuple(f.shape[-2:]) for f in feats]
     H, W = pan.shape[-2:]
     cfg = _cfg(B, T, L, K1, dec_layers, in_channels, sizes, (256, H, W), want_masks, want_pixel_feature)
-    need = Lb.axvs_kmax_decoder_workspace_bytes(C.byref(cfg))
-    if need == 0:
-        _lib.check(-1, "axvs_kmax_decoder_workspace_bytes")
     st = _stream(dev)
-    ws = _workspace(dev, need, st)
+    ws = _workspace_for("axvs_kmax_decoder_workspace_bytes", dev, st, C.byref(cfg))
     f32 = dict(dtype=torch.float32, device=dev)
     logits = torch.empty(B, L, K1, **f32)
     masks = torch.empty(B, L, T, H, W, **f32) if want_masks else None
@@ -291,11 +274,8 @@ class KMaXTransformerDecoder(nn.Module):
         if q.shape != (B, L, 256):
             raise RuntimeError(f"axial_vs_amd: query {tuple(q.shape)} must be [{B}, {L}, 256]")
         packed = self._packed()
-        need = Lb.axvs_kmax_stage_workspace_bytes(C.byref(cfg), index, 0)
-        if need == 0:
-            _lib.check(-1, "axvs_kmax_stage_workspace_bytes")
         st = _stream(dev)
-        ws = _workspace(dev, need, st)
+        ws = _workspace_for("axvs_kmax_stage_workspace_bytes", dev, st, C.byref(cfg), index, 0)
         idx = torch.empty(B, T * f.shape[-2] * f.shape[-1], dtype=torch.int32, device=dev)
         cls = torch.empty(B, L, self._num_classes + 1, dtype=torch.float32, device=dev)
         _lib.check(Lb.axvs_kmax_assign_fwd(C.byref(cfg), packed.data_ptr(), index, q.data_ptr(), f.data_ptr(), idx.data_ptr(), cls.data_ptr(), ws.data_ptr(),
@@ -314,11 +294,8 @@ class KMaXTransformerDecoder(nn.Module):
             raise RuntimeError(f"axial_vs_amd: query {tuple(q.shape)}, index_map {tuple(index_map.shape)} must be [{B}, {L}, 256], GPU int32 [{B}, {S}]")
         index_map = index_map.contiguous()
         packed = self._packed()
-        need = Lb.axvs_kmax_stage_workspace_bytes(C.byref(cfg), index, 1)
-        if need == 0:
-            _lib.check(-1, "axvs_kmax_stage_workspace_bytes")
         st = _stream(dev)
-        ws = _workspace(dev, need, st)
+        ws = _workspace_for("axvs_kmax_stage_workspace_bytes", dev, st, C.byref(cfg), index, 1)
         out = torch.empty(B, L, 256, dtype=torch.float32, device=dev)
         _lib.check(Lb.axvs_kmax_layer_fwd(C.byref(cfg), packed.data_ptr(), index, q.data_ptr(), f.data_ptr(), index_map.data_ptr(), out.data_ptr(),
                                           ws.data_ptr(), ws.numel(), st), "axvs_kmax_layer_fwd")

@@ -27,7 +27,7 @@ from torch import Tensor
 from . import _lib
 from ._params import kmax_pix_block_cin, kmax_pix_block_folded, kmax_pix_fuse_folded
 from .kmax_decoder import _BN, _ConvBN
-from .modules import _cached_pack, _dev_f32, _on, _stream, _workspace
+from .modules import _cached_pack, _dev_f32, _on, _pack_folded, _stream, _workspace_for
 
 _HEADS, _TABLE, _STRIDES = 8, 509, (32, 16, 8, 4)
 _LDS_BYTES = 160 * 1024
@@ -87,26 +87,11 @@ def _cfg(N: int, in_channels, sizes, dec_layers, dec_channels, layer_types) -> _
 
 def _pack(sd: Mapping[str, Tensor], in_channels, dec_layers, dec_channels, layer_types) -> Tensor:
     """fold (float64) and pack: one blob of fp32 tensors in the kernels' layouts"""
-    Lb = _lib.lib()
-    ref = sd["_in_norms.0.weight"]
-    if not ref.is_cuda:
-        raise RuntimeError(f"axial_vs_amd: parameters must be GPU tensors (got {ref.device}); there is no CPU fallback")
-    f32 = lambda ts: [None if t is None else t.float().contiguous() for t in ts]
-    ptr = lambda ts: [None if t is None else t.data_ptr() for t in ts]
-    with torch.no_grad():
-        sd = {k: v.detach() for k, v in sd.items()}
-        blocks = [f32(kmax_pix_block_folded(sd, f"_stages.{i}._blocks.{j}.")) for i in range(4) for j in range(int(dec_layers[i]))]
-        fuses = [f32(kmax_pix_fuse_folded(sd, i)) for i in range(3)]
-        ln0 = f32([sd["_in_norms.0.weight"], sd["_in_norms.0.bias"]])
-    cfg = _cfg(1, in_channels, [(1, 1)] * 4, dec_layers, dec_channels, layer_types)
-    bs = (_lib.AxvsKpixBlockParams * len(blocks))(*[_lib.fill(_lib.AxvsKpixBlockParams, ptr(ts)) for ts in blocks])
-    fs = (_lib.AxvsKpixFuseParams * 3)(*[_lib.fill(_lib.AxvsKpixFuseParams, ptr(ts)) for ts in fuses])
-    need = Lb.axvs_kmax_pix_packed_bytes(C.byref(cfg))
-    if need == 0:
-        _lib.check(-1, "axvs_kmax_pix_packed_bytes")
-    buf = torch.zeros(need, dtype=torch.uint8, device=ref.device)
-    _lib.check(Lb.axvs_kmax_pix_pack(bs, fs, ln0[0].data_ptr(), ln0[1].data_ptr(), C.byref(cfg), buf.data_ptr(), _stream(ref.device)), "axvs_kmax_pix_pack")
-    return buf      # (the folded tensors die with this frame: the allocator hands their memory out again in stream order)
+    sd = {k: v.detach() for k, v in sd.items()}
+    blocks = (kmax_pix_block_folded(sd, f"_stages.{i}._blocks.{j}.") for i in range(4) for j in range(int(dec_layers[i])))
+    fuses = (kmax_pix_fuse_folded(sd, i) for i in range(3))
+    return _pack_folded("axvs_kmax_pix", _cfg(1, in_channels, [(1, 1)] * 4, dec_layers, dec_channels, layer_types),
+                        [(_lib.AxvsKpixBlockParams, blocks), (_lib.AxvsKpixFuseParams, fuses)], extra=[sd["_in_norms.0.weight"], sd["_in_norms.0.bias"]])
 
 
 def _features(feats: Sequence[Tensor], in_channels) -> list:
@@ -118,13 +103,6 @@ def _features(feats: Sequence[Tensor], in_channels) -> list:
         if f.dim() != 4 or f.shape[0] != N or f.shape[1] != c:
             raise RuntimeError(f"axial_vs_amd: feature {tuple(f.shape)} must be [{N}, {c}, h, w]")
     return out
-
-
-def _ws(cfg, dev, st):
-    need = _lib.lib().axvs_kmax_pix_workspace_bytes(C.byref(cfg))
-    if need == 0:
-        _lib.check(-1, "axvs_kmax_pix_workspace_bytes")
-    return _workspace(dev, need, st)
 
 
 def _check_sizes(feats, spatial_shape) -> None:
@@ -140,7 +118,7 @@ def _run(packed: Tensor, feats, in_channels, dec_layers, dec_channels, layer_typ
     dev, N = feats[0].device, feats[0].shape[0]
     cfg = _cfg(N, in_channels, sizes, dec_layers, dec_channels, layer_types)
     st = _stream(dev)
-    ws = _ws(cfg, dev, st)
+    ws = _workspace_for("axvs_kmax_pix_workspace_bytes", dev, st, C.byref(cfg))
     outs = [torch.empty(N, 4 * int(b), h, w, dtype=torch.float32, device=dev) for b, (h, w) in zip(dec_channels, sizes)]
     fp = (C.c_void_p * 4)(*[f.data_ptr() for f in feats])
     op = (C.c_void_p * 4)(*[o.data_ptr() for o in outs])
@@ -334,7 +312,7 @@ class KMaXPixelDecoder(nn.Module):
         with _on(x.device):
             cfg = self._stage_cfg({stage: (h, w)}, N)
             st = _stream(x.device)
-            ws = _ws(cfg, x.device, st)
+            ws = _workspace_for("axvs_kmax_pix_workspace_bytes", x.device, st, C.byref(cfg))
             out = torch.empty(N, 4 * b, h, w, dtype=torch.float32, device=x.device)
             _lib.check(_lib.lib().axvs_kmax_pix_block_fwd(C.byref(cfg), self._packed().data_ptr(), self._locate(stage, index), x.data_ptr(), out.data_ptr(),
                                                           ws.data_ptr(), ws.numel(), st), "axvs_kmax_pix_block_fwd")
@@ -355,7 +333,7 @@ class KMaXPixelDecoder(nn.Module):
         with _on(low.device):
             cfg = self._stage_cfg({i - 1: tuple(low.shape[-2:]), i: tuple(high.shape[-2:])}, N)
             st = _stream(low.device)
-            ws = _ws(cfg, low.device, st)
+            ws = _workspace_for("axvs_kmax_pix_workspace_bytes", low.device, st, C.byref(cfg))
             out = torch.empty(N, self._dec_channels[i], *high.shape[-2:], dtype=torch.float32, device=low.device)
             _lib.check(_lib.lib().axvs_kmax_pix_fuse_fwd(C.byref(cfg), self._packed().data_ptr(), index, low.data_ptr(), high.data_ptr(), out.data_ptr(),
                                                          ws.data_ptr(), ws.numel(), st), "axvs_kmax_pix_fuse_fwd")

@@ -72,6 +72,11 @@ def _workspace(device: torch.device, nbytes: int, stream_handle: Optional[int] =
     return buf
 
 
+def _workspace_for(name: str, device: torch.device, stream_handle: int, *args) -> Tensor:
+    """`_workspace` of what the size query `name(*args)` asks for; the query's refusal (0) is raised with the library's message."""
+    return _workspace(device, _lib.size_query(name, *args), stream_handle)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -226,6 +231,34 @@ def _pack_weights(name: str, struct, tensors, dims, dt: str) -> Tensor:
     buf = torch.zeros(getattr(L, name + "_packed_bytes")(*dims), dtype=torch.uint8, device=dev)
     _lib.check(getattr(L, name + "_pack")(C.byref(ps), buf.data_ptr(), *dims, _lib.DTYPES[dt], _stream(dev)), name + "_pack")
     return buf
+
+
+def _pack_folded(name: str, cfg, groups, extra=()) -> Tensor:
+    """One `<name>_pack(arrays..., extra pointers..., cfg, blob, stream)` call of the eval-forward modules on folded parameters, into a
+    blob of `<name>_packed_bytes(cfg)`.  `groups`: per struct array of the call, in its order, (struct class, tensor lists), each list in
+    the struct's order (_params.py) with None for a slot the configuration does not have; `extra`: tensors that travel as plain
+    pointers.  The lists may come from a generator: each one is cast to fp32 as it arrives, so the float64 folds do not pile up."""
+    L = _lib.lib()
+    need = _lib.size_query(name + "_packed_bytes", C.byref(cfg))
+    keep = []                                   # the fp32 tensors, alive until the pack is enqueued
+
+    def ptrs(ts):
+        ts = [None if t is None else t.detach().float().contiguous() for t in ts]
+        for t in ts:
+            if t is not None and not t.is_cuda:
+                raise RuntimeError(f"axial_vs_amd: parameters must be GPU tensors (got {t.device}); there is no CPU fallback")
+        keep.append(ts)
+        return [_ptr(t) for t in ts]
+    with torch.no_grad():
+        arrays = []
+        for struct, lists in groups:
+            filled = [_lib.fill(struct, ptrs(ts)) for ts in lists]
+            arrays.append((struct * len(filled))(*filled))
+        extra = ptrs(extra)
+    dev = next(t for ts in keep for t in ts if t is not None).device
+    buf = torch.zeros(need, dtype=torch.uint8, device=dev)
+    _lib.check(getattr(L, name + "_pack")(*arrays, *extra, C.byref(cfg), buf.data_ptr(), _stream(dev)), name + "_pack")
+    return buf      # (the folded tensors die with this frame: the allocator hands their memory out again in stream order)
 
 
 class _on:

@@ -22,7 +22,7 @@ from torch import Tensor
 
 from . import _lib
 from .matching import _mask_dtype
-from .modules import _guarded, _stream, _workspace
+from .modules import _guarded, _stream, _workspace_for
 
 _id_tables: Dict[tuple, Tuple[Tensor, Tensor, Tensor]] = {}
 
@@ -94,12 +94,9 @@ def video_panoptic_inference(mask_cls: Tensor, mask_pred: Tensor, mask_embedding
                                class_threshold_thing=float(class_threshold_thing), class_threshold_stuff=float(class_threshold_stuff),
                                reorder_class_weight=float(reorder_class_weight), reorder_mask_weight=float(reorder_mask_weight))
     L = _lib.lib()
-    need = L.axvs_video_panoptic_workspace_bytes(C.byref(cfg))
-    if need == 0:
-        _lib.check(-1, "axvs_video_panoptic_workspace_bytes")
-    is_thing, cat_id, _ = _class_tables(thing_ids, stuff_ids, K1 - 1, dev)
     st = _stream(dev)
-    ws = _workspace(dev, need, st)
+    ws = _workspace_for("axvs_video_panoptic_workspace_bytes", dev, st, C.byref(cfg))
+    is_thing, cat_id, _ = _class_tables(thing_ids, stuff_ids, K1 - 1, dev)
     seg = torch.empty(T, H, W, dtype=torch.int32, device=dev)
     itab = torch.empty(L.axvs_video_panoptic_table_ints(N), dtype=torch.int32, device=dev)
     ftab = torch.empty(3, N, dtype=torch.float32, device=dev)

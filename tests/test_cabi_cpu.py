@@ -770,3 +770,67 @@ def test_every_training_entry_point_refuses_buffers_one_byte_short():
             err = L.axvs_last_error().decode()
             assert rc == -2, (name, rc, err)
             assert f"{short} < {need}" in err and "training buffers too small" in err, (name, err)
+
+
+def _negative_workspace_calls():
+    """(entry point, call with `ws` workspace bytes) for one *_fwd of each unit whose ABI takes `long long workspace_bytes`, at the
+    smallest configuration the unit accepts.  Pointers are made up as in _short_workspace_calls."""
+    from axial_vs_amd import _lib
+    L = _lib.lib()
+    by = ctypes.byref
+    p = [ctypes.c_void_p(0x10000 * (i + 1)) for i in range(12)]
+    i3, i4 = ctypes.c_int * 3, ctypes.c_int * 4
+    arr = lambda n: (ctypes.c_void_p * n)(*[0x100000 * (i + 1) for i in range(n)])
+    one = (ctypes.c_int * 1)(1)
+    m2f = _lib.AxvsM2fCfg(N=1, Q=1, T=1, C=256, heads=8, ffn=2048, num_layers=1, num_levels=3, K1=1, h=1, w=1, lh=i3(1, 1, 1), lw=i3(1, 1, 1),
+                          return_predictions=0, pos_normalize=1, pos_temperature=10000.0, pos_scale=6.283185307179586)
+    kmax = _lib.AxvsKmaxCfg(B=1, T=1, L=1, K1=1, num_layers=1, in_channels=i3(16, 16, 16), h=i3(1, 1, 1), w=i3(1, 1, 1), pan_channels=256, H=1, W=1,
+                            heads=8, base_filters=128, want_masks=0, want_pixel_feature=0)
+    kpix = _lib.AxvsKpixCfg(N=1, in_channels=i4(16, 16, 16, 16), h=i4(1, 1, 1, 1), w=i4(1, 1, 1, 1), base=i4(32, 32, 32, 32), blocks=i4(1, 1, 1, 1),
+                            axial=i4(0, 0, 0, 0), heads=8)
+    cnx = _lib.AxvsCnxCfg(N=1, H=1, W=1, dims=i4(16, 16, 16, 16), depths=i4(1, 1, 1, 1), h=i4(1, 1, 1, 1), w=i4(1, 1, 1, 1), v2=0)
+    vis = _lib.AxvsVisCfg(Q=1, K1=2, T=1, num_frames=1, h=1, w=1, image_h=1, image_w=1, crop_h=1, crop_w=1, H=1, W=1, num_things=0, k_cand=1, k_out=1,
+                          mask_bits=0)
+    pan = _lib.AxvsPanopticCfg(N=1, K1=2, T=1, h=1, w=1, image_h=1, image_w=1, two_stage=0, crop_h=0, crop_w=0, H=1, W=1, align_corners=0,
+                               label_divisor=0, pixel_confidence_threshold=0.4, overlap_threshold=0.8, class_threshold_thing=0.7,
+                               class_threshold_stuff=0.5, reorder_class_weight=1.0, reorder_mask_weight=1.0)
+    tl = _lib.AxvsTLLossCfg(L=1, B=1, Q=1, K1=2, T=1, h=1, w=1, Hg=1, Wg=1, num_points=1, num_cand=0, num_kept=0, target_dtype=_lib.AXVS_U8,
+                            cost_cls=2, cost_mask=5, cost_dice=5, loss_cls=2, loss_mask=5, loss_dice=5, dice_eps=1)
+    return [
+        ("axvs_m2f_decoder_fwd", lambda ws: L.axvs_m2f_decoder_fwd(by(m2f), p[0], p[1], arr(3), p[2], None, None, None, None, p[3], ws, None)),
+        ("axvs_kmax_decoder_fwd", lambda ws: L.axvs_kmax_decoder_fwd(by(kmax), p[0], arr(3), None, p[1], None, p[2], None, p[3], None, p[4], ws, None)),
+        ("axvs_kmax_pix_decoder_fwd", lambda ws: L.axvs_kmax_pix_decoder_fwd(by(kpix), p[0], arr(4), arr(4), p[1], ws, None)),
+        ("axvs_cnx_fwd", lambda ws: L.axvs_cnx_fwd(by(cnx), p[0], p[1], arr(5), p[2], ws, None)),
+        ("axvs_video_instance_fwd", lambda ws: L.axvs_video_instance_fwd(by(vis), p[0], p[1], _lib.AXVS_F32, p[2], p[3], p[4], p[5], ws, None)),
+        ("axvs_video_panoptic_fwd",
+         lambda ws: L.axvs_video_panoptic_fwd(by(pan), p[0], p[1], _lib.AXVS_F32, p[2], p[3], p[4], p[5], p[6], p[7], ws, None)),
+        ("axvs_set_criterion_fwd",
+         lambda ws: L.axvs_set_criterion_fwd(arr(1), arr(1), p[0], _lib.AXVS_U8, p[1], one, p[2], p[3], p[4], p[5], 1, 1, 1, 1, 2, 1, 1, 1, p[6], p[7], p[8],
+                                             ws, None)),
+        ("axvs_pixel_insdis_fwd",
+         lambda ws: L.axvs_pixel_insdis_fwd(arr(1), p[0], _lib.AXVS_U8, one, p[1], 1, 1, 1, 1, 1, 4, 1, p[2], 1, 1, p[3], p[4], p[5], ws, None)),
+        ("axvs_tl_loss_fwd",
+         lambda ws: L.axvs_tl_loss_fwd(by(tl), arr(1), arr(1), p[0], p[1], one, p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], None, None, p[10], p[11],
+                                       ws, None)),
+    ]
+
+
+def test_every_signed_workspace_size_refuses_a_negative_one():
+    """The units whose ABI takes `long long workspace_bytes` (the query decoders, the pixel decoder, the backbone, the two post-processing
+    units and the three loss units) share one workspace check: a negative size is too small, whatever it would be as an unsigned number.
+    AXVS_ERR_WORKSPACE (-2) with the size in the text, before any device work.  One entry point per unit: the names come from
+    SIGNATURES, so a new unit with a signed size has to add its case."""
+    from axial_vs_amd import _lib
+    L = _lib.lib()
+    calls = _negative_workspace_calls()
+    signed = {n for n, (_, args) in _lib.SIGNATURES.items() if n.endswith("_fwd") and "_train_" not in n and args[-2:] == [ctypes.c_longlong, _lib._fp]}
+    units = ("axvs_m2f_", "axvs_kmax_pix_", "axvs_kmax_", "axvs_cnx_", "axvs_video_instance_", "axvs_video_panoptic_", "axvs_set_criterion_",
+             "axvs_pixel_", "axvs_tl_loss_")                     # (the first prefix that fits: axvs_kmax_pix_ in front of axvs_kmax_)
+    unit_of = lambda n: next((u for u in units if n.startswith(u)), n)
+    assert {n for n, _ in calls} <= signed
+    assert sorted(unit_of(n) for n, _ in calls) == sorted({unit_of(n) for n in signed}) == sorted(units)
+    for name, call in calls:
+        rc = call(-1)
+        err = L.axvs_last_error().decode()
+        assert rc == -2, (name, rc, err)
+        assert "workspace too small" in err and "-1" in err, (name, err)
