@@ -199,6 +199,11 @@ class AxvsFpnLevelParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("lateral_w", "lateral_gn_w", "lateral_gn_b", "output_w", "output_gn_w", "output_gn_b", "mask_w", "mask_b")]
 
 
+def ptrs(ts) -> C.Array:
+    """Host array of the tensors' device pointers (NULL for None): what an entry point takes as `const T* const*`."""
+    return (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
 def fill(cls, ptrs):
     """A `cls` with `ptrs` assigned to its fields in declaration order: a nested Structure is filled recursively, a ctypes array takes
     as many pointers as it has elements.  A gradient struct has its parameter struct's layout (include/axvs.h), so this fills both."""

@@ -36,10 +36,6 @@ MAX_SAMPLE_K, MAX_FEATURE_CHANNELS, MAX_PIXELS = 8192, 256, 1 << 20             
 _SLOT = {"loss_ce": 0, "loss_mask": 1, "loss_dice": 2}
 
 
-def _ptrs(ts) -> C.Array:
-    return (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
-
-
 class _SetCriterion(torch.autograd.Function):
     """losses [L, 3] (loss_ce, loss_mask, loss_dice per layer) of L layers' (pred_masks, pred_logits); the matcher's results and the
     ground truth are constants (process_gt runs under no_grad on detached masks)."""
@@ -62,7 +58,7 @@ class _SetCriterion(torch.autograd.Function):
             saved, saved_ptr, scratch = place(dev, nbytes("axvs_set_criterion_saved_bytes", L, B, N),
                                               nbytes("axvs_set_criterion_workspace_bytes", L, B, N, K1, P))
             mv = (C.c_int * B)(*m)
-            _lib.check(lib.axvs_set_criterion_fwd(_ptrs(masks), _ptrs(logits), None if tcat is None else tcat.data_ptr(), tdt,
+            _lib.check(lib.axvs_set_criterion_fwd(_lib.ptrs(masks), _lib.ptrs(logits), None if tcat is None else tcat.data_ptr(), tdt,
                                                   None if lcat is None else lcat.data_ptr(), mv, rows.data_ptr(), cols.data_ptr(), dice.data_ptr(),
                                                   cls.data_ptr(), kmax, L, B, N, K1, P, int(masking), int(share), losses.data_ptr(), saved_ptr,
                                                   scratch.data_ptr(), scratch.numel(), _stream(dev)), "axvs_set_criterion_fwd")
@@ -86,9 +82,9 @@ class _SetCriterion(torch.autograd.Function):
             need = ctx.needs_input_grad[7:]
             dm = [torch.empty_like(x) if need[i] else None for i, x in enumerate(masks)]
             dl = [torch.empty_like(x) if need[L + i] else None for i, x in enumerate(logits)]
-            _lib.check(_lib.lib().axvs_set_criterion_bwd(g.data_ptr(), _ptrs(masks), _ptrs(logits), None if ctx.tcat is None else ctx.tcat.data_ptr(),
+            _lib.check(_lib.lib().axvs_set_criterion_bwd(g.data_ptr(), _lib.ptrs(masks), _lib.ptrs(logits), None if ctx.tcat is None else ctx.tcat.data_ptr(),
                                                          tdt, (C.c_int * B)(*m), L, B, N, K1, P, int(masking), int(share), saved.data_ptr(),
-                                                         _ptrs(dm), _ptrs(dl), _stream(dev)), "axvs_set_criterion_bwd")
+                                                         _lib.ptrs(dm), _lib.ptrs(dl), _stream(dev)), "axvs_set_criterion_bwd")
         grads = [None if d is None else d.reshape(s) for d, s in zip(dm + dl, ctx.in_shapes)]
         return (None,) * 7 + tuple(cast(grads, ctx.in_dtypes))
 
@@ -216,7 +212,7 @@ class _PixelInsdis(torch.autograd.Function):
             losses = torch.empty(L, dtype=torch.float32, device=dev)
             saved, saved_ptr, scratch = place(dev, nbytes("axvs_pixel_insdis_saved_bytes", L, B, k),
                                               nbytes("axvs_pixel_insdis_workspace_bytes", L, B, Cf, kmax, k))
-            _lib.check(lib.axvs_pixel_insdis_fwd(_ptrs(fs), None if tcat is None else tcat.data_ptr(), tdt, (C.c_int * B)(*m),
+            _lib.check(lib.axvs_pixel_insdis_fwd(_lib.ptrs(fs), None if tcat is None else tcat.data_ptr(), tdt, (C.c_int * B)(*m),
                                                  None if kmax == 0 else cols.data_ptr(), kmax, int(share), L, B, N, Cf, P, idx.data_ptr(), k,
                                                  int(idx.shape[-1]), losses.data_ptr(), saved_ptr, scratch.data_ptr(), scratch.numel(),
                                                  _stream(dev)), "axvs_pixel_insdis_fwd")
@@ -239,9 +235,9 @@ class _PixelInsdis(torch.autograd.Function):
             need = ctx.needs_input_grad[4:]
             df = [torch.zeros_like(x) if need[i] else None for i, x in enumerate(fs)]       # only the sampled pixels are written
             scratch = _workspace(dev, nbytes("axvs_pixel_insdis_workspace_bytes", L, B, Cf, kmax, k))
-            _lib.check(_lib.lib().axvs_pixel_insdis_bwd(g.data_ptr(), _ptrs(fs), None if ctx.tcat is None else ctx.tcat.data_ptr(), tdt,
+            _lib.check(_lib.lib().axvs_pixel_insdis_bwd(g.data_ptr(), _lib.ptrs(fs), None if ctx.tcat is None else ctx.tcat.data_ptr(), tdt,
                                                         (C.c_int * B)(*m), None if kmax == 0 else ctx.cols.data_ptr(), kmax, int(share), L, B, N,
-                                                        Cf, P, idx.data_ptr(), k, int(idx.shape[-1]), saved.data_ptr(), _ptrs(df),
+                                                        Cf, P, idx.data_ptr(), k, int(idx.shape[-1]), saved.data_ptr(), _lib.ptrs(df),
                                                         scratch.data_ptr(), scratch.numel(), _stream(dev)), "axvs_pixel_insdis_bwd")
         grads = [None if d is None else d.reshape(s) for d, s in zip(df, ctx.in_shapes)]
         return (None,) * 4 + tuple(cast(grads, ctx.in_dtypes))
@@ -357,7 +353,7 @@ def _sampled_losses(st: _Step, targets, num_classes: int, names: Sequence[str], 
         keys = torch.empty(R, B, P, dtype=torch.float32, device=dev)
         area = torch.empty(max(1, LM * B * kmax), dtype=torch.float32, device=dev)
         _lib.check(_lib.lib().axvs_pixel_sample(None if tcat is None else tcat.data_ptr(), tdt, (C.c_int * B)(*st.m),
-                                                None if kmax == 0 else st.cols.data_ptr(), kmax, LM, B, st.N, P, _ptrs([r[0] for r in rows]),
+                                                None if kmax == 0 else st.cols.data_ptr(), kmax, LM, B, st.N, P, _lib.ptrs([r[0] for r in rows]),
                                                 (C.c_int * R)(*[r[1] for r in rows]), (C.c_float * R)(*[r[2] for r in rows]),
                                                 (C.c_int * R)(*[r[3] for r in rows]), R, area.data_ptr(), keys.data_ptr(), idx.data_ptr(),
                                                 kstride, _stream(dev)), "axvs_pixel_sample")

@@ -15,6 +15,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWave = 64;     // CDNA wavefront
 constexpr int kBlk = 32;      // K-block width of the "blocked" 16-bit activation/weight layout
+constexpr int kLsapMax = 512; // rows / columns of one assignment problem (axvs_lsap.h: the duals and the path live in LDS)
 
 // 16-bit MFMA operand type: fp16 (BF=false) or bf16 (BF=true).  Accumulation is always fp32.
 template <bool BF>

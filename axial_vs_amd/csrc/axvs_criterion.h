@@ -25,23 +25,20 @@
 //                          (zero for an unmatched query).  The upstream gradients of the 3 L scalars are read from device memory.
 // criterion_logits_bwd_kernel   d pred_logits, one wave per query row.
 #pragma once
-#include "axvs_common.h"
+#include "axvs_targets.h"
 
 namespace axvs {
 
-constexpr int kCritMaxLayers = 16, kCritMaxVideos = 64;      // the matcher's limits (axvs_matcher.h)
-constexpr int kCritMaxN = 512, kCritMaxM = 512;             // the assignment kernel's bounds (axvs_lsap.h)
-constexpr int kCritF32 = 2, kCritU8 = 3;                    // AXVS_F32 / AXVS_U8 targets
 constexpr int kCritNPW = 32;          // queries per wave of the register-column kernels: N <= 4 * 32
 constexpr int kCritTP = 64;           // pixels per tile, one per lane
 
 struct CritArgs {
-  const float* masks[kCritMaxLayers];     // per layer: pred_masks fp32 [B][N][P]
-  const float* logits[kCritMaxLayers];    // per layer: pred_logits fp32 [B][N][K1]
-  float* dmasks[kCritMaxLayers];          // backward: d pred_masks (NULL: skipped)
-  float* dlogits[kCritMaxLayers];         // backward: d pred_logits (NULL: skipped)
-  int m[kCritMaxVideos];
-  int off[kCritMaxVideos];
+  const float* masks[kMaxLayers];     // per layer: pred_masks fp32 [B][N][P]
+  const float* logits[kMaxLayers];    // per layer: pred_logits fp32 [B][N][K1]
+  float* dmasks[kMaxLayers];          // backward: d pred_masks (NULL: skipped)
+  float* dlogits[kMaxLayers];         // backward: d pred_logits (NULL: skipped)
+  int m[kMaxVideos];
+  int off[kMaxVideos];
 };
 
 // what the forward saves for the backward, all O(L * B * N): views into one caller-owned buffer of crit_saved_words() 4-byte words
@@ -72,12 +69,6 @@ __host__ __device__ inline CritSaved crit_saved_views(void* base, int L, int B, 
 }
 // floats of one workgroup's partial sums: A = sum prob void, Bq = sum prob (1 - void), I, T per query, then (sum ce, #{ce != 0})
 __host__ __device__ inline long long crit_part_stride(int N) { return 4ll * N + 2; }
-
-template <int TDT>
-__device__ __forceinline__ float crit_target(const void* p, long long i) {
-  if constexpr (TDT == kCritU8) return (float)static_cast<const unsigned char*>(p)[i];
-  else return static_cast<const float*>(p)[i];
-}
 
 // grid LM * B, 256 threads
 __global__ __launch_bounds__(256) void criterion_index_kernel(CritArgs a, const long long* __restrict__ rows, const long long* __restrict__ cols,
@@ -164,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void criterion_fwd_kernel(CritArgs a, const
         mx = fmaxf(mx, x[j]);
         const int r = sinv[q];
         if (r >= 0) {
-          const float t = ok ? crit_target<TDT>(targets, (long long)r * P + pix) : 0.f;
+          const float t = ok ? load_f32<TDT>(targets, (long long)r * P + pix) : 0.f;
           ts += t;
           tx += t * x[j];
         }
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void criterion_fwd_kernel(CritArgs a, const
         sB[j] += vd ? 0.f : pr;
         const int r = sinv[q];
         if (r >= 0) {
-          const float t = ok ? crit_target<TDT>(targets, (long long)r * P + pix) : 0.f;
+          const float t = ok ? load_f32<TDT>(targets, (long long)r * P + pix) : 0.f;
           sT[j] += t;
           sI[j] += keep ? pr * t : 0.f;
         }
@@ -224,11 +215,11 @@ template <int TDT>
 __global__ __launch_bounds__(256) void criterion_fwd_any_kernel(CritArgs a, const void* __restrict__ targets, const int* __restrict__ inv, int B, int N,
                                                                 long long P, int tiles_per_wg, int masking, int share, float* __restrict__ part) {
   __shared__ float sx[2][4][4][kCritTP];
-  __shared__ int sinv[kCritMaxN];
-  __shared__ float sacc[4][kCritMaxN];
+  __shared__ int sinv[kMaxQueries];
+  __shared__ float sacc[4][kMaxQueries];
   const int z = blockIdx.y, l = z / B, b = z - l * B, zm = share ? b : z;
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
-  for (int n = tid; n < kCritMaxN; n += 256) {
+  for (int n = tid; n < kMaxQueries; n += 256) {
     sinv[n] = n < N ? inv[(long long)zm * N + n] : -1;
     sacc[0][n] = 0.f; sacc[1][n] = 0.f; sacc[2][n] = 0.f; sacc[3][n] = 0.f;
   }
@@ -246,7 +237,7 @@ __global__ __launch_bounds__(256) void criterion_fwd_any_kernel(CritArgs a, cons
       mx = fmaxf(mx, xv);
       const int r = sinv[q];
       if (r >= 0) {
-        const float t = ok ? crit_target<TDT>(targets, (long long)r * P + pix) : 0.f;
+        const float t = ok ? load_f32<TDT>(targets, (long long)r * P + pix) : 0.f;
         ts += t;
         tx += t * xv;
       }
@@ -262,7 +253,7 @@ __global__ __launch_bounds__(256) void criterion_fwd_any_kernel(CritArgs a, cons
       float vI = 0.f, vT = 0.f;
       const int r = sinv[q];
       if (r >= 0) {
-        const float t = ok ? crit_target<TDT>(targets, (long long)r * P + pix) : 0.f;
+        const float t = ok ? load_f32<TDT>(targets, (long long)r * P + pix) : 0.f;
         vT = wave_sum(t);
         vI = wave_sum(keep ? pr * t : 0.f);
       }
@@ -287,7 +278,7 @@ __global__ __launch_bounds__(256) void criterion_fwd_any_kernel(CritArgs a, cons
 // grid L, 256 threads: the videos of a layer one after the other
 __global__ __launch_bounds__(256) void criterion_finish_kernel(CritArgs a, const float* __restrict__ part, int npb, int B, int N, int K1, int masking,
                                                                int share, CritSaved s, float* __restrict__ losses) {
-  __shared__ float sf[kCritMaxN], sd[kCritMaxN];
+  __shared__ float sf[kMaxQueries], sd[kMaxQueries];
   const int l = blockIdx.x, tid = threadIdx.x;
   const long long stride = crit_part_stride(N);
   float lce = 0.f, lmask = 0.f, ldice = 0.f;        // thread 0 only
@@ -405,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void criterion_bwd_kernel(CritArgs a, const
         mx = fmaxf(mx, x[j]);
         const int r = sinv[q];
         if (r >= 0) {
-          t[j] = ok ? crit_target<TDT>(targets, (long long)r * P + pix) : 0.f;
+          t[j] = ok ? load_f32<TDT>(targets, (long long)r * P + pix) : 0.f;
           ts += t[j];
         }
       }
@@ -441,15 +432,15 @@ template <int TDT>
 __global__ __launch_bounds__(256) void criterion_bwd_any_kernel(CritArgs a, const void* __restrict__ targets, const float* __restrict__ gout, int B, int N,
                                                                 long long P, int tiles_per_wg, int masking, int share, CritSaved s) {
   __shared__ float sx[2][4][4][kCritTP];
-  __shared__ int sinv[kCritMaxN];
-  __shared__ float ca[kCritMaxN], cb[kCritMaxN];
+  __shared__ int sinv[kMaxQueries];
+  __shared__ float ca[kMaxQueries], cb[kMaxQueries];
   const int z = blockIdx.y, l = z / B, b = z - l * B, zm = share ? b : z;
   float* dx0 = a.dmasks[l];
   if (!dx0) return;
   dx0 += (long long)b * N * P;
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
-  for (int n = tid; n < kCritMaxN; n += 256) sinv[n] = n < N ? s.inv[(long long)zm * N + n] : -1;
-  crit_dice_coefs(s, z, zm, N, B, gout[3 * l + 2], ca, cb, kCritMaxN);
+  for (int n = tid; n < kMaxQueries; n += 256) sinv[n] = n < N ? s.inv[(long long)zm * N + n] : -1;
+  crit_dice_coefs(s, z, zm, N, B, gout[3 * l + 2], ca, cb, kMaxQueries);
   __syncthreads();
   const float gm = gout[3 * l + 1] / ((float)B * s.cnt[2 * z]);
   const float* x0 = a.masks[l] + (long long)b * N * P;
@@ -462,13 +453,13 @@ __global__ __launch_bounds__(256) void criterion_bwd_any_kernel(CritArgs a, cons
     for (int q = g; q < N; q += 4) {
       mx = fmaxf(mx, ok ? x0[(long long)q * P + pix] : 0.f);
       const int r = sinv[q];
-      if (r >= 0) ts += ok ? crit_target<TDT>(targets, (long long)r * P + pix) : 0.f;
+      if (r >= 0) ts += ok ? load_f32<TDT>(targets, (long long)r * P + pix) : 0.f;
     }
     float se = 0.f, sd = 0.f;
     for (int q = g; q < N; q += 4) {
       const float e = expf((ok ? x0[(long long)q * P + pix] : 0.f) - mx);
       const int r = sinv[q];
-      const float t = (r >= 0 && ok) ? crit_target<TDT>(targets, (long long)r * P + pix) : 0.f;
+      const float t = (r >= 0 && ok) ? load_f32<TDT>(targets, (long long)r * P + pix) : 0.f;
       se += e;
       sd += e * (ca[q] + cb[q] * t);
     }
@@ -480,7 +471,7 @@ __global__ __launch_bounds__(256) void criterion_bwd_any_kernel(CritArgs a, cons
       for (int q = g; q < N; q += 4) {
         const float pr = expf(x0[(long long)q * P + pix] - mx) * px.f;
         const int r = sinv[q];
-        const float t = r >= 0 ? crit_target<TDT>(targets, (long long)r * P + pix) : 0.f;
+        const float t = r >= 0 ? load_f32<TDT>(targets, (long long)r * P + pix) : 0.f;
         dx0[(long long)q * P + pix] = keep ? gm * (pr * px.s2 - t) + pr * (ca[q] + cb[q] * t - sdot) : 0.f;
       }
     }

@@ -4,7 +4,6 @@
 #include <algorithm>
 #include <cstring>
 
-#include "axvs_host.h"
 #include "axvs_criterion.h"
 
 using namespace axvs;
@@ -14,56 +13,28 @@ namespace {
 // workgroups per problem of the pixel kernels: two per CU over all problems, at least 4 pixel tiles each (a workgroup ends with one
 // cross-lane reduction per query, about a tile's worth of work), and at most 2^22 pixels each (the nonzero count of a workgroup is
 // kept in fp32)
-struct CritPlan { int npb, tiles_per_wg; };
-CritPlan crit_plan(int nprob, long long P) {
-  const long long ntiles = (P + kCritTP - 1) / kCritTP;
-  long long npb = std::min<long long>((512 + nprob - 1) / nprob, (ntiles + 3) / 4);
-  npb = std::max<long long>(npb, (ntiles + 65535) / 65536);
-  npb = std::max<long long>(npb, 1);
-  const long long per = (ntiles + npb - 1) / npb;
-  return {(int)((ntiles + per - 1) / per), (int)per};
-}
-
-int crit_check_shape(int L, int B, int N, int K1, long long P) {
-  if (L <= 0 || L > kCritMaxLayers || B <= 0 || B > kCritMaxVideos)
-    return fail(AXVS_ERR_ARG, "L=%d must be in 1..%d and B=%d in 1..%d", L, kCritMaxLayers, B, kCritMaxVideos);
-  if (N <= 0 || N > kCritMaxN) return fail(AXVS_ERR_ARG, "N=%d queries must be in 1..%d (the assignment kernel's bound)", N, kCritMaxN);
-  if (K1 < 2 || P <= 0 || P > (1ll << 40)) return fail(AXVS_ERR_ARG, "need K + 1 = %d >= 2 logits and P = %lld >= 1 pixels", K1, P);
-  return AXVS_OK;
-}
+TileSplit crit_plan(int nprob, long long P) { return split_tiles((P + kCritTP - 1) / kCritTP, nprob, 512, 65536); }
 
 int fill_args(CritArgs& a, const float* const* pred_masks, const float* const* pred_logits, const int* m_per_video, int L, int B, int* total) {
   memset(&a, 0, sizeof(a));
   if (!pred_masks || !pred_logits || !m_per_video) return fail(AXVS_ERR_ARG, "null pointer");
-  int off = 0;
-  for (int b = 0; b < B; ++b) {
-    if (m_per_video[b] < 0 || m_per_video[b] > kCritMaxM) return fail(AXVS_ERR_ARG, "m_per_video[%d]=%d is outside 0..%d", b, m_per_video[b], kCritMaxM);
-    a.m[b] = m_per_video[b];
-    a.off[b] = off;
-    off += m_per_video[b];
-  }
-  for (int l = 0; l < L; ++l) {
-    if (!pred_masks[l] || !pred_logits[l]) return fail(AXVS_ERR_ARG, "null pointer (layer %d)", l);
-    a.masks[l] = pred_masks[l];
-    a.logits[l] = pred_logits[l];
-  }
-  *total = off;
-  return AXVS_OK;
+  VideoFill v;
+  if (int rc = fill_videos(m_per_video, B, kMaxObjects, "", a.m, a.off, &v)) return rc;
+  if (int rc = fill_layers(pred_masks, L, a.masks)) return rc;
+  *total = v.total;
+  return fill_layers(pred_logits, L, a.logits);
 }
 
 }  // namespace
 
 size_t axvs_set_criterion_saved_bytes(int L, int B, int N) {
-  if (L <= 0 || L > kCritMaxLayers || B <= 0 || B > kCritMaxVideos || N <= 0 || N > kCritMaxN) {
-    fail(AXVS_ERR_ARG, "L=%d must be in 1..%d, B=%d in 1..%d and N=%d in 1..%d", L, kCritMaxLayers, B, kCritMaxVideos, N, kCritMaxN);
-    return 0;
-  }
+  if (check_shape("L", L, B, "N", N)) return 0;
   return align_up((size_t)crit_saved_words(L, B, N) * 4);
 }
 
 size_t axvs_set_criterion_workspace_bytes(int L, int B, int N, int K1, long long P) {
-  if (crit_check_shape(L, B, N, K1, P)) return 0;
-  const CritPlan pl = crit_plan(L * B, P);
+  if (check_shape("L", L, B, "N", N, K1, P)) return 0;
+  const TileSplit pl = crit_plan(L * B, P);
   return align_up((size_t)L * B * pl.npb * crit_part_stride(N) * sizeof(float));
 }
 
@@ -72,8 +43,8 @@ int axvs_set_criterion_fwd(const float* const* pred_masks, const float* const* p
                            const float* matched_dice, const float* matched_cls, int kmax, int L, int B, int N, int K1, long long P,
                            int masking_void_pixel, int share_final_matching, float* losses, void* saved, void* workspace,
                            long long workspace_bytes, void* stream) {
-  if (int rc = crit_check_shape(L, B, N, K1, P)) return rc;
-  if (target_dtype != AXVS_F32 && target_dtype != AXVS_U8) return fail(AXVS_ERR_ARG, "target dtype %d is not AXVS_F32 / AXVS_U8", target_dtype);
+  if (int rc = check_shape("L", L, B, "N", N, K1, P)) return rc;
+  if (int rc = check_target_dtype(target_dtype)) return rc;
   CritArgs a;
   int total = 0;
   if (int rc = fill_args(a, pred_masks, pred_logits, m_per_video, L, B, &total)) return rc;
@@ -84,21 +55,15 @@ int axvs_set_criterion_fwd(const float* const* pred_masks, const float* const* p
   if (int rc = check_ws(workspace_bytes, need)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nprob = L * B, share = share_final_matching != 0, masking = masking_void_pixel != 0;
-  const CritPlan pl = crit_plan(nprob, P);
+  const TileSplit pl = crit_plan(nprob, P);
   const CritSaved s = crit_saved_views(saved, L, B, N);
   float* part = static_cast<float*>(workspace);
   hipLaunchKernelGGL(criterion_index_kernel, dim3((share ? 1 : L) * B), dim3(256), 0, st, a, rows, cols, matched_dice, matched_cls, labels, B, N, K1, kmax, s);
   const dim3 grid(pl.npb, nprob);
-#define AXVS_CRIT_FWD(KERNEL)                                                                                                              \
-  do {                                                                                                                                     \
-    if (target_dtype == AXVS_U8) hipLaunchKernelGGL(KERNEL<kCritU8>, grid, dim3(256), 0, st, a, targets, (const int*)s.inv, B, N, P,    \
-                                                    pl.tiles_per_wg, masking, share, part);                                                \
-    else hipLaunchKernelGGL(KERNEL<kCritF32>, grid, dim3(256), 0, st, a, targets, (const int*)s.inv, B, N, P, pl.tiles_per_wg, masking, \
-                            share, part);                                                                                                  \
-  } while (0)
-  if (N <= 4 * kCritNPW) AXVS_CRIT_FWD(criterion_fwd_kernel);
-  else AXVS_CRIT_FWD(criterion_fwd_any_kernel);
-#undef AXVS_CRIT_FWD
+  by_target_dtype(target_dtype, [&](auto td) {
+    hipLaunchKernelGGL(N <= 4 * kCritNPW ? criterion_fwd_kernel<td()> : criterion_fwd_any_kernel<td()>, grid, dim3(256), 0, st, a, targets, (const int*)s.inv,
+                       B, N, P, pl.tiles_per_wg, masking, share, part);
+  });
   hipLaunchKernelGGL(criterion_finish_kernel, dim3(L), dim3(256), 0, st, a, (const float*)part, pl.npb, B, N, K1, masking, share, s, losses);
   return last_launch_status();
 }
@@ -106,8 +71,8 @@ int axvs_set_criterion_fwd(const float* const* pred_masks, const float* const* p
 int axvs_set_criterion_bwd(const float* grad_losses, const float* const* pred_masks, const float* const* pred_logits, const void* targets,
                            int target_dtype, const int* m_per_video, int L, int B, int N, int K1, long long P, int masking_void_pixel,
                            int share_final_matching, const void* saved, float* const* d_pred_masks, float* const* d_pred_logits, void* stream) {
-  if (int rc = crit_check_shape(L, B, N, K1, P)) return rc;
-  if (target_dtype != AXVS_F32 && target_dtype != AXVS_U8) return fail(AXVS_ERR_ARG, "target dtype %d is not AXVS_F32 / AXVS_U8", target_dtype);
+  if (int rc = check_shape("L", L, B, "N", N, K1, P)) return rc;
+  if (int rc = check_target_dtype(target_dtype)) return rc;
   CritArgs a;
   int total = 0;
   if (int rc = fill_args(a, pred_masks, pred_logits, m_per_video, L, B, &total)) return rc;
@@ -122,20 +87,14 @@ int axvs_set_criterion_bwd(const float* grad_losses, const float* const* pred_ma
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nprob = L * B, share = share_final_matching != 0, masking = masking_void_pixel != 0;
-  const CritPlan pl = crit_plan(nprob, P);
+  const TileSplit pl = crit_plan(nprob, P);
   const CritSaved s = crit_saved_views(const_cast<void*>(saved), L, B, N);
   const dim3 grid(pl.npb, nprob);
-#define AXVS_CRIT_BWD(KERNEL)                                                                                                              \
-  do {                                                                                                                                     \
-    if (target_dtype == AXVS_U8) hipLaunchKernelGGL(KERNEL<kCritU8>, grid, dim3(256), 0, st, a, targets, grad_losses, B, N, P,          \
-                                                    pl.tiles_per_wg, masking, share, s);                                                   \
-    else hipLaunchKernelGGL(KERNEL<kCritF32>, grid, dim3(256), 0, st, a, targets, grad_losses, B, N, P, pl.tiles_per_wg, masking, share, s); \
-  } while (0)
-  if (any_masks) {
-    if (N <= 4 * kCritNPW) AXVS_CRIT_BWD(criterion_bwd_kernel);
-    else AXVS_CRIT_BWD(criterion_bwd_any_kernel);
-  }
-#undef AXVS_CRIT_BWD
+  if (any_masks)
+    by_target_dtype(target_dtype, [&](auto td) {
+      hipLaunchKernelGGL(N <= 4 * kCritNPW ? criterion_bwd_kernel<td()> : criterion_bwd_any_kernel<td()>, grid, dim3(256), 0, st, a, targets, grad_losses, B,
+                         N, P, pl.tiles_per_wg, masking, share, s);
+    });
   const int nrows = nprob * N;
   if (any_logits) hipLaunchKernelGGL(criterion_logits_bwd_kernel, dim3((nrows + 3) / 4), dim3(256), 0, st, a, grad_losses, B, N, K1, s, nrows);
   return last_launch_status();

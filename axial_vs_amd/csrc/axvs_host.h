@@ -32,6 +32,19 @@ inline int g_spatial_wgs = 512;
 // the split-precision 16-bit MFMA one (three bf16 pieces per operand, a frame's score tiles in registers; axis length <= 128)
 inline int g_train_attn_split = 1;
 
+// optional per-stage event recording (bench.py / tuning): events[i] is recorded on the stream after stage i; the entry point that
+// records stages sets g_prof_next = 0 first (the axvs_profile_* entry points of axvs_api.hip read the state)
+inline thread_local hipEvent_t* g_prof_events = nullptr;
+inline thread_local int g_prof_cap = 0;
+inline thread_local int g_prof_next = 0;
+constexpr int kMaxStages = 32;
+inline thread_local const char* g_stage_names[kMaxStages] = {};
+inline void mark(hipStream_t st, const char* name) {
+  if (g_prof_next < kMaxStages) g_stage_names[g_prof_next] = name;
+  if (g_prof_events && g_prof_next < g_prof_cap) (void)hipEventRecord(g_prof_events[g_prof_next], st);
+  ++g_prof_next;
+}
+
 inline int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);

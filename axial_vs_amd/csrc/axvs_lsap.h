@@ -154,7 +154,6 @@ __device__ __forceinline__ int lsap_wave_min_i32(int k) {
 // `chain` > 1: problems k = 0 .. chain-1 of a batch entry are solved one after the other and problem k's ROWS are taken in the order
 // of problem k-1's result (row t of problem k is row out[k-1][t] of its stored matrix): the clip loop of maxtron_cc_model.py:280-301
 // (`prev = cur[idx]` before the next match) on raw pair-wise cost matrices, in one launch per batch of videos.
-constexpr int kLsapMax = 512;
 template <int CPL, bool LDS_COST>
 __global__ __launch_bounds__(64) void lsap_kernel(const float* __restrict__ cost_all, long long* __restrict__ out_all, int n, int chain) {
   extern __shared__ float scost[];

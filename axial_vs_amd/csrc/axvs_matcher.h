@@ -20,36 +20,27 @@
 // per tile, one tile in flight per workgroup, and the MFMA phase does not overlap it).  A 16-bit MFMA form could save at most those
 // 70 us; the softmax half is what limits the kernel.
 #pragma once
-#include "axvs_common.h"
+#include "axvs_targets.h"
 #include "axvs_lsap.h"
 
 namespace axvs {
 
-constexpr int kMatcherMaxVideos = 64, kMatcherMaxLayers = 16;
 constexpr int kMatcherTP = 64;                 // pixels per tile: one per lane, so a query's row of a tile is one coalesced wave read
 constexpr int kMatcherLDP = kMatcherTP + 1;    // LDS row stride (odd: the MFMA operand reads walk 32 rows at one pixel)
 constexpr int kMatcherMaxRows = 576;            // ceil32(Q) + ceil32(M_max) rows of LDS tiles (150 KB of the 160)
 constexpr int kMatcherBlocksPerChunk = 16;     // 32 x 32 output blocks per workgroup: 4 waves x 4 accumulator tiles
-constexpr int kMatcherF16 = 0, kMatcherBF16 = 1, kMatcherF32 = 2, kMatcherU8 = 3;     // AXVS_F16 / AXVS_BF16 / AXVS_F32 / AXVS_U8
 
 struct MatcherArgs {
-  const void* masks[kMatcherMaxLayers];      // per layer: pred_masks [B][Q][P]
-  const float* logits[kMatcherMaxLayers];    // per layer: pred_logits fp32 [B][Q][K1]
-  int m[kMatcherMaxVideos];                  // objects of video b
-  int off[kMatcherMaxVideos];                // first row of video b in the concatenated targets / labels
+  const void* masks[kMaxLayers];      // per layer: pred_masks [B][Q][P]
+  const float* logits[kMaxLayers];    // per layer: pred_logits fp32 [B][Q][K1]
+  int m[kMaxVideos];                  // objects of video b
+  int off[kMaxVideos];                // first row of video b in the concatenated targets / labels
 };
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // floats of one workgroup's partial sums: inter [Q][Mmax], in_sum [Q], t_sum [Mmax]
 __host__ __device__ inline long long matcher_part_stride(int Q, int Mmax) { return (long long)Q * Mmax + Q + Mmax; }
-
-template <int DT>
-__device__ __forceinline__ float matcher_load(const void* p, long long i) {
-  if constexpr (DT == kMatcherF32) return static_cast<const float*>(p)[i];
-  else if constexpr (DT == kMatcherU8) return (float)static_cast<const unsigned char*>(p)[i];
-  else return H16<DT == kMatcherBF16>::to_f32(static_cast<const u16*>(p)[i]);
-}
 
 // grid (npb, chunks, L * B), 256 threads.  Dynamic LDS: sp [Qp][LDP] (logits -> exp -> masked probabilities) and st [Mp][LDP] (targets),
 // Qp / Mp = Q / Mmax rounded up to 32.
@@ -93,14 +84,14 @@ __global__ __launch_bounds__(256) void matcher_sim_kernel(MatcherArgs a, const v
     // targets of the tile; column sums for the non-void flag, row sums for the denominator
     float cs = 0.f;
     for (int m = g; m < Mp; m += 4) {
-      const float t = (m < M && ok) ? matcher_load<TDT>(targets, tbase + (long long)m * P + pix) : 0.f;
+      const float t = (m < M && ok) ? load_f32<TDT>(targets, tbase + (long long)m * P + pix) : 0.f;
       st[m * kMatcherLDP + lane] = t;
       cs += t;
     }
     // softmax over the queries of every pixel: wave g holds queries g, g + 4, ...
     float mx = -__builtin_huge_valf();
     for (int q = g; q < Q; q += 4) {
-      const float x = ok ? matcher_load<DT>(mask, mbase + (long long)q * P + pix) : 0.f;
+      const float x = ok ? load_f32<DT>(mask, mbase + (long long)q * P + pix) : 0.f;
       sp[q * kMatcherLDP + lane] = x;
       mx = fmaxf(mx, x);
     }

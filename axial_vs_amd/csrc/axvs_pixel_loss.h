@@ -21,15 +21,13 @@
 //
 // Every sum has a fixed order (no floating-point atomics), so two runs give the same bits.
 #pragma once
-#include "axvs_common.h"
+#include "axvs_targets.h"
 
 namespace axvs {
 
-constexpr int kPxMaxLayers = 16, kPxMaxVideos = 64, kPxMaxN = 512, kPxMaxM = 512;
-constexpr int kPxMaxRows = kPxMaxLayers + 1;      // noise rows of a step: one per layer ('pixels') and one for 'aux_semantic'
+constexpr int kPxMaxRows = kMaxLayers + 1;      // noise rows of a step: one per layer ('pixels') and one for 'aux_semantic'
 constexpr int kPxMaxK = 8192, kPxMaxC = 256;
 constexpr long long kPxMaxP = 1ll << 20;
-constexpr int kPxU8 = 3, kPxF32 = 2;              // AXVS_U8 / AXVS_F32
 constexpr int kPxSelThreads = 1024;
 constexpr int kPxTJ = 16;                         // columns of a workgroup of the streamed kernels; its 4 waves share the rows of k
 constexpr float kPxInvTau = 1.0f / 0.3f;          // instance_discrimination_temperature (wc_criterion.py:282)
@@ -38,8 +36,8 @@ constexpr float kPxVoidLogit = -99999.0f;         // _SOFTMAX_MASKING_CONSTANT
 typedef float px_f32x4 __attribute__((ext_vector_type(4)));
 
 struct PxVideos {
-  int m[kPxMaxVideos];                            // objects of video b
-  int off[kPxMaxVideos];                          // first row of video b in the concatenated targets
+  int m[kMaxVideos];                            // objects of video b
+  int off[kMaxVideos];                          // first row of video b in the concatenated targets
 };
 
 struct PxRows {
@@ -51,15 +49,9 @@ struct PxRows {
 };
 
 struct PxLayers {
-  const float* feat[kPxMaxLayers];                // per layer: pixel_feature [B][C][P]
-  float* dfeat[kPxMaxLayers];
+  const float* feat[kMaxLayers];                // per layer: pixel_feature [B][C][P]
+  float* dfeat[kMaxLayers];
 };
-
-template <int TD>
-__device__ __forceinline__ float px_target(const void* t, long long i) {
-  if constexpr (TD == kPxU8) return (float)static_cast<const unsigned char*>(t)[i];
-  else return static_cast<const float*>(t)[i];
-}
 
 // a product / sum rounded once, whatever the compiler's contraction mode: the result never fuses into a neighbouring operation
 __device__ __forceinline__ float px_mul(float a, float b) {
@@ -101,7 +93,7 @@ __global__ __launch_bounds__(256) void px_area_kernel(PxVideos v, const void* __
   float acc = 0.f;
   if (i < px_pairs(v, b, N)) {                    // uniform over the workgroup
     const long long base = (long long)(v.off[b] + px_col(cols, (long long)z * kmax + i, v.m[b])) * P;
-    for (int p = threadIdx.x; p < P; p += 256) acc += px_target<TD>(targets, base + p);
+    for (int p = threadIdx.x; p < P; p += 256) acc += load_f32<TD>(targets, base + p);
   }
   const float s = px_block_sum256(acc, red);
   if (threadIdx.x == 0) area[(long long)z * kmax + i] = s;
@@ -110,8 +102,8 @@ __global__ __launch_bounds__(256) void px_area_kernel(PxVideos v, const void* __
 template <int TD>
 __global__ __launch_bounds__(256) void px_key_kernel(PxVideos v, PxRows rw, const void* __restrict__ targets, const long long* __restrict__ cols,
                                                      const float* __restrict__ area, int kmax, int B, int N, int P, float* __restrict__ keys) {
-  __shared__ float s_area[kPxMaxM];
-  __shared__ int s_row[kPxMaxM];
+  __shared__ float s_area[kMaxObjects];
+  __shared__ int s_row[kMaxObjects];
   const int z = blockIdx.y, b = z % B, lm = z / B, kb = px_pairs(v, b, N);
   for (int i = threadIdx.x; i < kb; i += 256) {
     s_area[i] = area[(long long)z * kmax + i];
@@ -122,7 +114,7 @@ __global__ __launch_bounds__(256) void px_key_kernel(PxVideos v, PxRows rw, cons
   if (p >= P) return;
   float st = 0.f, pa = 0.f;
   for (int i = 0; i < kb; ++i) {
-    const float t = px_target<TD>(targets, (long long)s_row[i] * P + p);
+    const float t = load_f32<TD>(targets, (long long)s_row[i] * P + p);
     st += t;
     pa += t * s_area[i];
   }
@@ -234,7 +226,7 @@ __global__ __launch_bounds__(256) void px_gather_tgt_kernel(PxVideos v, const vo
   float* dst = G + ((long long)lb * Kp + j) * Mp;
   for (int i = threadIdx.x >> 6; i < Mp; i += 4) {
     float t = 0.f;
-    if (p >= 0 && i < kb) t = px_target<TD>(targets, (long long)(v.off[b] + px_col(cols, (long long)z * kmax + i, v.m[b])) * P + p);
+    if (p >= 0 && i < kb) t = load_f32<TD>(targets, (long long)(v.off[b] + px_col(cols, (long long)z * kmax + i, v.m[b])) * P + p);
     dst[i] = t;
   }
 }

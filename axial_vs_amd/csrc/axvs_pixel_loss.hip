@@ -4,7 +4,6 @@
 #include <algorithm>
 #include <cstring>
 
-#include "axvs_host.h"
 #include "axvs_pixel_loss.h"
 
 using namespace axvs;
@@ -13,19 +12,11 @@ namespace {
 
 int ceil16(int x) { return (x + 15) / 16 * 16; }
 
-int px_check_videos(PxVideos& v, const int* m_per_video, int B, int N, int* total) {
+int px_fill_videos(PxVideos& v, const int* m_per_video, int B, int* total) {
   memset(&v, 0, sizeof(v));
-  if (B <= 0 || B > kPxMaxVideos) return fail(AXVS_ERR_ARG, "B=%d videos must be in 1..%d", B, kPxMaxVideos);
-  if (N <= 0 || N > kPxMaxN) return fail(AXVS_ERR_ARG, "N=%d queries must be in 1..%d", N, kPxMaxN);
-  if (!m_per_video) return fail(AXVS_ERR_ARG, "null pointer");
-  int off = 0;
-  for (int b = 0; b < B; ++b) {
-    if (m_per_video[b] < 0 || m_per_video[b] > kPxMaxM) return fail(AXVS_ERR_ARG, "m_per_video[%d]=%d is outside 0..%d", b, m_per_video[b], kPxMaxM);
-    v.m[b] = m_per_video[b];
-    v.off[b] = off;
-    off += m_per_video[b];
-  }
-  *total = off;
+  VideoFill f;
+  if (int rc = fill_videos(m_per_video, B, kMaxObjects, "", v.m, v.off, &f)) return rc;
+  *total = f.total;
   return AXVS_OK;
 }
 
@@ -37,16 +28,10 @@ int px_check_samples(int k, int kstride, long long P) {
   return AXVS_OK;
 }
 
-int px_check_dtype(int target_dtype) {
-  if (target_dtype != AXVS_F32 && target_dtype != AXVS_U8) return fail(AXVS_ERR_ARG, "target dtype %d is not AXVS_F32 / AXVS_U8", target_dtype);
-  return AXVS_OK;
-}
-
 int px_check_insdis(int L, int B, int C, int kmax, int N) {
-  if (L <= 0 || L > kPxMaxLayers) return fail(AXVS_ERR_ARG, "L=%d layers must be in 1..%d", L, kPxMaxLayers);
-  if (B <= 0 || B > kPxMaxVideos) return fail(AXVS_ERR_ARG, "B=%d videos must be in 1..%d", B, kPxMaxVideos);
+  if (int rc = check_shape("L", L, B, "N", N)) return rc;
   if (C <= 0 || C > kPxMaxC || C % 4) return fail(AXVS_ERR_ARG, "C=%d feature channels must be a multiple of 4 in 4..%d", C, kPxMaxC);
-  if (kmax < 0 || kmax > N || kmax > kPxMaxM) return fail(AXVS_ERR_ARG, "kmax=%d pairs per problem must be in 0..min(N, %d)", kmax, kPxMaxM);
+  if (kmax < 0 || kmax > N || kmax > kMaxObjects) return fail(AXVS_ERR_ARG, "kmax=%d pairs per problem must be in 0..min(N, %d)", kmax, kMaxObjects);
   return AXVS_OK;
 }
 
@@ -86,12 +71,10 @@ int insdis_gather(const InsdisCall& c, const void* targets, int target_dtype, co
                   int B, int N, int C, int P, int k, int kstride, const InsdisWs& w, hipStream_t st) {
   const dim3 grid((c.Kp + 63) / 64, L * B);
   hipLaunchKernelGGL(px_gather_feat_kernel, grid, dim3(256), 0, st, c.ly, idx, B, C, P, k, kstride, c.Kp, c.Cp, w.F);
-  if (c.Mp > 0) {
-    if (target_dtype == AXVS_U8)
-      hipLaunchKernelGGL(px_gather_tgt_kernel<kPxU8>, grid, dim3(256), 0, st, c.v, targets, cols, idx, kmax, share, B, N, P, k, kstride, c.Kp, c.Mp, w.G);
-    else
-      hipLaunchKernelGGL(px_gather_tgt_kernel<kPxF32>, grid, dim3(256), 0, st, c.v, targets, cols, idx, kmax, share, B, N, P, k, kstride, c.Kp, c.Mp, w.G);
-  }
+  if (c.Mp > 0)
+    by_target_dtype(target_dtype, [&](auto td) {
+      hipLaunchKernelGGL(px_gather_tgt_kernel<td()>, grid, dim3(256), 0, st, c.v, targets, cols, idx, kmax, share, B, N, P, k, kstride, c.Kp, c.Mp, w.G);
+    });
   return AXVS_OK;
 }
 
@@ -102,10 +85,10 @@ int axvs_pixel_sample(const void* targets, int target_dtype, const int* m_per_vi
                       float* area, float* keys, int* idx, int kstride, void* stream) {
   PxVideos v;
   int total = 0;
-  if (int rc = px_check_videos(v, m_per_video, B, N, &total)) return rc;
-  if (int rc = px_check_dtype(target_dtype)) return rc;
+  if (int rc = check_shape("LM", LM, B, "N", N)) return rc;
+  if (int rc = px_fill_videos(v, m_per_video, B, &total)) return rc;
+  if (int rc = check_target_dtype(target_dtype)) return rc;
   if (R <= 0 || R > kPxMaxRows) return fail(AXVS_ERR_ARG, "R=%d noise rows must be in 1..%d", R, kPxMaxRows);
-  if (LM <= 0 || LM > kPxMaxLayers) return fail(AXVS_ERR_ARG, "LM=%d matchings must be in 1..%d", LM, kPxMaxLayers);
   if (kmax < 0 || kmax > N) return fail(AXVS_ERR_ARG, "kmax=%d pairs per problem must be in 0..N=%d", kmax, N);
   if (!noise || !row_matching || !row_temperature || !row_k || !keys || !idx) return fail(AXVS_ERR_ARG, "null pointer");
   if (kmax > 0 && (!targets || !cols || !area)) return fail(AXVS_ERR_ARG, "null pointer");
@@ -125,20 +108,17 @@ int axvs_pixel_sample(const void* targets, int target_dtype, const int* m_per_vi
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int Pi = (int)P;
   const dim3 kgrid((Pi + 255) / 256, LM * B);
-  if (target_dtype == AXVS_U8) {
-    if (kmax > 0) hipLaunchKernelGGL(px_area_kernel<kPxU8>, dim3(kmax, LM * B), dim3(256), 0, st, v, targets, cols, kmax, B, N, Pi, area);
-    hipLaunchKernelGGL(px_key_kernel<kPxU8>, kgrid, dim3(256), 0, st, v, rw, targets, cols, (const float*)area, kmax, B, N, Pi, keys);
-  } else {
-    if (kmax > 0) hipLaunchKernelGGL(px_area_kernel<kPxF32>, dim3(kmax, LM * B), dim3(256), 0, st, v, targets, cols, kmax, B, N, Pi, area);
-    hipLaunchKernelGGL(px_key_kernel<kPxF32>, kgrid, dim3(256), 0, st, v, rw, targets, cols, (const float*)area, kmax, B, N, Pi, keys);
-  }
+  by_target_dtype(target_dtype, [&](auto td) {
+    if (kmax > 0) hipLaunchKernelGGL(px_area_kernel<td()>, dim3(kmax, LM * B), dim3(256), 0, st, v, targets, cols, kmax, B, N, Pi, area);
+    hipLaunchKernelGGL(px_key_kernel<td()>, kgrid, dim3(256), 0, st, v, rw, targets, cols, (const float*)area, kmax, B, N, Pi, keys);
+  });
   hipLaunchKernelGGL(px_select_kernel, dim3(R * B), dim3(kPxSelThreads), 0, st, rw, (const float*)keys, B, Pi, kstride, idx);
   return last_launch_status();
 }
 
 size_t axvs_pixel_insdis_saved_bytes(int L, int B, int k) {
-  if (L <= 0 || L > kPxMaxLayers || B <= 0 || B > kPxMaxVideos || k < 0 || k > kPxMaxK) {
-    fail(AXVS_ERR_ARG, "L=%d must be in 1..%d, B=%d in 1..%d and k=%d in 0..%d", L, kPxMaxLayers, B, kPxMaxVideos, k, kPxMaxK);
+  if (L <= 0 || L > kMaxLayers || B <= 0 || B > kMaxVideos || k < 0 || k > kPxMaxK) {
+    fail(AXVS_ERR_ARG, "L=%d must be in 1..%d, B=%d in 1..%d and k=%d in 0..%d", L, kMaxLayers, B, kMaxVideos, k, kPxMaxK);
     return 0;
   }
   size_t bytes = 0;
@@ -147,7 +127,7 @@ size_t axvs_pixel_insdis_saved_bytes(int L, int B, int k) {
 }
 
 size_t axvs_pixel_insdis_workspace_bytes(int L, int B, int C, int kmax, int k) {
-  if (px_check_insdis(L, B, C, kmax, kPxMaxN)) return 0;
+  if (px_check_insdis(L, B, C, kmax, kMaxQueries)) return 0;
   if (k < 0 || k > kPxMaxK) {
     fail(AXVS_ERR_ARG, "k=%d samples must be in 0..%d", k, kPxMaxK);
     return 0;
@@ -160,17 +140,14 @@ int axvs_pixel_insdis_fwd(const float* const* pixel_feature, const void* targets
                           float* losses, void* saved, void* workspace, long long workspace_bytes, void* stream) {
   InsdisCall c;
   int total = 0;
-  if (int rc = px_check_videos(c.v, m_per_video, B, N, &total)) return rc;
   if (int rc = px_check_insdis(L, B, C, kmax, N)) return rc;
-  if (int rc = px_check_dtype(target_dtype)) return rc;
+  if (int rc = px_fill_videos(c.v, m_per_video, B, &total)) return rc;
+  if (int rc = check_target_dtype(target_dtype)) return rc;
   if (int rc = px_check_samples(k, kstride, P)) return rc;
   if (!pixel_feature || !losses || !saved || !workspace || (k > 0 && !idx)) return fail(AXVS_ERR_ARG, "null pointer");
   if (kmax > 0 && (!targets || !cols)) return fail(AXVS_ERR_ARG, "null pointer");
   memset(&c.ly, 0, sizeof(c.ly));
-  for (int l = 0; l < L; ++l) {
-    if (!pixel_feature[l]) return fail(AXVS_ERR_ARG, "null pointer (layer %d)", l);
-    c.ly.feat[l] = pixel_feature[l];
-  }
+  if (int rc = fill_layers(pixel_feature, L, c.ly.feat)) return rc;
   const size_t need = axvs_pixel_insdis_workspace_bytes(L, B, C, kmax, k);
   if (int rc = check_ws(workspace_bytes, need)) return rc;
   c.Kp = ceil16(k), c.Cp = ceil16(C), c.Mp = ceil16(kmax);
@@ -192,18 +169,15 @@ int axvs_pixel_insdis_bwd(const float* grad_losses, const float* const* pixel_fe
                           long long workspace_bytes, void* stream) {
   InsdisCall c;
   int total = 0;
-  if (int rc = px_check_videos(c.v, m_per_video, B, N, &total)) return rc;
   if (int rc = px_check_insdis(L, B, C, kmax, N)) return rc;
-  if (int rc = px_check_dtype(target_dtype)) return rc;
+  if (int rc = px_fill_videos(c.v, m_per_video, B, &total)) return rc;
+  if (int rc = check_target_dtype(target_dtype)) return rc;
   if (int rc = px_check_samples(k, kstride, P)) return rc;
   if (!grad_losses || !pixel_feature || !d_pixel_feature || !saved || !workspace || (k > 0 && !idx)) return fail(AXVS_ERR_ARG, "null pointer");
   if (kmax > 0 && (!targets || !cols)) return fail(AXVS_ERR_ARG, "null pointer");
   memset(&c.ly, 0, sizeof(c.ly));
-  for (int l = 0; l < L; ++l) {
-    if (!pixel_feature[l]) return fail(AXVS_ERR_ARG, "null pointer (layer %d)", l);
-    c.ly.feat[l] = pixel_feature[l];
-    c.ly.dfeat[l] = d_pixel_feature[l];      // NULL: that layer's gradient is skipped
-  }
+  if (int rc = fill_layers(pixel_feature, L, c.ly.feat)) return rc;
+  for (int l = 0; l < L; ++l) c.ly.dfeat[l] = d_pixel_feature[l];      // NULL: that layer's gradient is skipped
   const size_t need = axvs_pixel_insdis_workspace_bytes(L, B, C, kmax, k);
   if (int rc = check_ws(workspace_bytes, need)) return rc;
   if (k == 0) return AXVS_OK;
@@ -224,8 +198,8 @@ int axvs_pixel_insdis_bwd(const float* grad_losses, const float* const* pixel_fe
 }
 
 size_t axvs_pixel_semantic_saved_bytes(int B, int k) {
-  if (B <= 0 || B > kPxMaxVideos || k < 0 || k > kPxMaxK) {
-    fail(AXVS_ERR_ARG, "B=%d must be in 1..%d and k=%d in 0..%d", B, kPxMaxVideos, k, kPxMaxK);
+  if (B <= 0 || B > kMaxVideos || k < 0 || k > kPxMaxK) {
+    fail(AXVS_ERR_ARG, "B=%d must be in 1..%d and k=%d in 0..%d", B, kMaxVideos, k, kPxMaxK);
     return 0;
   }
   return align_up((size_t)B * k * 4) * 2 + align_up((size_t)B * 4);
@@ -242,7 +216,7 @@ SemSaved sem_saved(void* p, int B, int k) {
   return s;
 }
 int sem_check(int B, int Cs, long long P, int k, int kstride, int num_classes) {
-  if (B <= 0 || B > kPxMaxVideos) return fail(AXVS_ERR_ARG, "B=%d videos must be in 1..%d", B, kPxMaxVideos);
+  if (B <= 0 || B > kMaxVideos) return fail(AXVS_ERR_ARG, "B=%d videos must be in 1..%d", B, kMaxVideos);
   if (Cs <= 0 || Cs > kPxMaxC) return fail(AXVS_ERR_ARG, "%d class channels must be in 1..%d", Cs, kPxMaxC);
   if (num_classes < 0) return fail(AXVS_ERR_ARG, "num_classes=%d is negative", num_classes);
   return px_check_samples(k, kstride, P);

@@ -30,28 +30,26 @@
 // long-image row and walks that row's points in increasing point index, so every pixel is written by one thread at a time in a
 // fixed order and two runs give the same bits.
 #pragma once
-#include "axvs_common.h"
+#include "axvs_targets.h"
 
 namespace axvs {
 
-constexpr int kTLMaxLayers = 16, kTLMaxVideos = 64, kTLMaxQ = 512, kTLMaxM = 512;
 constexpr int kTLMaxPoints = 16384, kTLMaxCand = 65536;
 constexpr int kTLMaxRows = 8192;          // T * h rows of the long image: the scatter kernel keeps two counters per row in LDS
 constexpr int kTLTP = 32;                 // points per tile of the cost kernel
 constexpr int kTLLDP = kTLTP + 1;         // LDS row stride (odd: the MFMA operand reads walk 32 rows at one point)
-constexpr int kTLU8 = 3, kTLF32 = 2;      // AXVS_U8 / AXVS_F32
 constexpr int kTLThreads = 1024;          // workgroup of the per-pair kernels
 
 typedef float tl_f32x16 __attribute__((ext_vector_type(16)));
 
 struct TLArgs {
-  const float* cls[kTLMaxLayers];         // per layer: cls_scores [B][Q][K1]
-  const float* masks[kTLMaxLayers];       // per layer: mask_preds [B][T][Q][h][w]
-  float* dcls[kTLMaxLayers];
-  float* dmasks[kTLMaxLayers];
-  int m[kTLMaxVideos];                    // objects of video b
-  int off[kTLMaxVideos];                  // first row of video b in the concatenated targets / labels
-  int goff[kTLMaxVideos + 1];             // first matched pair of video b in a layer's pair list: sum of min(Q, M_b') over b' < b
+  const float* cls[kMaxLayers];         // per layer: cls_scores [B][Q][K1]
+  const float* masks[kMaxLayers];       // per layer: mask_preds [B][T][Q][h][w]
+  float* dcls[kMaxLayers];
+  float* dmasks[kMaxLayers];
+  int m[kMaxVideos];                    // objects of video b
+  int off[kMaxVideos];                  // first row of video b in the concatenated targets / labels
+  int goff[kMaxVideos + 1];             // first matched pair of video b in a layer's pair list: sum of min(Q, M_b') over b' < b
 };
 
 struct TLShape {
@@ -108,11 +106,6 @@ __device__ __forceinline__ float tl_sample_pred(const float* __restrict__ base, 
   }
   return v;
 }
-template <int TDT>
-__device__ __forceinline__ float tl_load_target(const void* __restrict__ p, long long i) {
-  if constexpr (TDT == kTLF32) return static_cast<const float*>(p)[i];
-  else return (float)static_cast<const unsigned char*>(p)[i];
-}
 // target mask: contiguous [T * Hg][Wg] from element `base`
 template <int TDT>
 __device__ __forceinline__ float tl_sample_target(const void* __restrict__ tg, long long base, const Bilin& t, int W, int R) {
@@ -120,13 +113,13 @@ __device__ __forceinline__ float tl_sample_target(const void* __restrict__ tg, l
   const bool xa = t.x0 >= 0, xb = t.x0 + 1 < W;
   if (t.y0 >= 0) {
     const long long row = base + (long long)t.y0 * W;
-    if (xa) v += tl_load_target<TDT>(tg, row + t.x0) * (t.wx0 * t.wy0);
-    if (xb) v += tl_load_target<TDT>(tg, row + t.x0 + 1) * (t.wx1 * t.wy0);
+    if (xa) v += load_f32<TDT>(tg, row + t.x0) * (t.wx0 * t.wy0);
+    if (xb) v += load_f32<TDT>(tg, row + t.x0 + 1) * (t.wx1 * t.wy0);
   }
   if (t.y0 + 1 < R) {
     const long long row = base + (long long)(t.y0 + 1) * W;
-    if (xa) v += tl_load_target<TDT>(tg, row + t.x0) * (t.wx0 * t.wy1);
-    if (xb) v += tl_load_target<TDT>(tg, row + t.x0 + 1) * (t.wx1 * t.wy1);
+    if (xa) v += load_f32<TDT>(tg, row + t.x0) * (t.wx0 * t.wy1);
+    if (xb) v += load_f32<TDT>(tg, row + t.x0 + 1) * (t.wx1 * t.wy1);
   }
   return v;
 }
@@ -142,7 +135,7 @@ template <int TDT>
 __global__ __launch_bounds__(256) void tl_cost_kernel(TLArgs a, const void* __restrict__ targets, const float* __restrict__ match_coords,
                                                       TLShape s, int tiles_per_wg, float* __restrict__ part) {
   extern __shared__ float tsm[];
-  __shared__ float sacc[64 + kTLMaxM];      // running sums of the sigmoid, softplus and target rows, in LDS row order
+  __shared__ float sacc[64 + kMaxObjects];      // running sums of the sigmoid, softplus and target rows, in LDS row order
   const int z = blockIdx.z, l = z / s.B, b = z - l * s.B;
   const int M = a.m[b];
   if (M <= 0) return;
@@ -155,7 +148,7 @@ __global__ __launch_bounds__(256) void tl_cost_kernel(TLArgs a, const void* __re
   const long long fs = (long long)s.Q * s.h * s.w, tsz = (long long)Rg * s.Wg;
   const float* pbase = a.masks[l] + (long long)b * s.T * fs;
   const float* coords = match_coords + (long long)z * s.P * 2;
-  for (int i = tid; i < 64 + kTLMaxM; i += 256) sacc[i] = 0.f;
+  for (int i = tid; i < 64 + kMaxObjects; i += 256) sacc[i] = 0.f;
   tl_f32x16 acc1[4], acc2[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k)

@@ -4,7 +4,6 @@
 #include <algorithm>
 #include <cstring>
 
-#include "axvs_host.h"
 #include "axvs_tl_loss.h"
 
 using namespace axvs;
@@ -12,14 +11,7 @@ using namespace axvs;
 namespace {
 
 // workgroups per (problem, query block) of the cost kernel: about four per CU over everything, at least 4 point tiles each
-struct TLPlan { int npb, tiles_per_wg; };
-TLPlan tl_plan(int nprob, int nqb, int P) {
-  const int ntiles = (P + kTLTP - 1) / kTLTP;
-  int npb = std::min((1024 + nprob * nqb - 1) / (nprob * nqb), (ntiles + 3) / 4);
-  npb = std::max(npb, 1);
-  const int per = (ntiles + npb - 1) / npb;
-  return {(ntiles + per - 1) / per, per};
-}
+TileSplit tl_plan(int nprob, int nqb, int P) { return split_tiles((P + kTLTP - 1) / kTLTP, nprob * nqb, 1024); }
 
 struct TLHost {
   TLArgs a;
@@ -30,10 +22,7 @@ struct TLHost {
 int tl_setup(TLHost& h, const AxvsTLLossCfg* c, const int* m_per_video) {
   memset(&h, 0, sizeof(h));
   if (!c || !m_per_video) return fail(AXVS_ERR_ARG, "null pointer");
-  if (c->L <= 0 || c->L > kTLMaxLayers || c->B <= 0 || c->B > kTLMaxVideos)
-    return fail(AXVS_ERR_ARG, "L=%d must be in 1..%d and B=%d in 1..%d", c->L, kTLMaxLayers, c->B, kTLMaxVideos);
-  if (c->Q <= 0 || c->Q > kTLMaxQ) return fail(AXVS_ERR_ARG, "Q=%d queries must be in 1..%d (the assignment kernel's bound)", c->Q, kTLMaxQ);
-  if (c->K1 < 2) return fail(AXVS_ERR_ARG, "need K + 1 = %d >= 2 class logits", c->K1);
+  if (int rc = check_shape("L", c->L, c->B, "Q", c->Q, c->K1)) return rc;
   if (c->T <= 0 || c->h <= 0 || c->w <= 0 || c->Hg <= 0 || c->Wg <= 0) return fail(AXVS_ERR_ARG, "T, h, w, Hg, Wg must be positive");
   if ((long long)c->T * c->h > kTLMaxRows || (long long)c->T * c->Hg > (1 << 24) || c->w > (1 << 20) || c->Wg > (1 << 20))
     return fail(AXVS_ERR_ARG, "T*h=%lld rows of the long image must be at most %d (T*Hg at most 2^24, w and Wg at most 2^20)", (long long)c->T * c->h, kTLMaxRows);
@@ -42,27 +31,19 @@ int tl_setup(TLHost& h, const AxvsTLLossCfg* c, const int* m_per_video) {
   if (c->num_cand < 0 || c->num_cand > kTLMaxCand) return fail(AXVS_ERR_ARG, "S=%d candidate points must be in 0..%d", c->num_cand, kTLMaxCand);
   if (c->num_kept < 0 || c->num_kept > c->num_points || c->num_kept > c->num_cand)
     return fail(AXVS_ERR_ARG, "k=%d kept points must be in 0..min(num_points=%d, S=%d)", c->num_kept, c->num_points, c->num_cand);
-  if (c->target_dtype != AXVS_F32 && c->target_dtype != AXVS_U8) return fail(AXVS_ERR_ARG, "target dtype %d is not AXVS_F32 / AXVS_U8", c->target_dtype);
+  if (int rc = check_target_dtype(c->target_dtype)) return rc;
   TLShape& s = h.s;
   s.L = c->L; s.B = c->B; s.Q = c->Q; s.K1 = c->K1; s.T = c->T; s.h = c->h; s.w = c->w; s.Hg = c->Hg; s.Wg = c->Wg;
   s.P = c->num_points; s.S = c->num_cand; s.k = c->num_kept;
   s.cost_cls = c->cost_cls; s.cost_mask = c->cost_mask; s.cost_dice = c->cost_dice;
   s.loss_cls = c->loss_cls; s.loss_mask = c->loss_mask; s.loss_dice = c->loss_dice; s.eps = c->dice_eps;
-  int off = 0, G = 0, Mmax = 0;
-  for (int b = 0; b < c->B; ++b) {
-    if (m_per_video[b] < 0 || m_per_video[b] > kTLMaxM) return fail(AXVS_ERR_ARG, "m_per_video[%d]=%d is outside 0..%d", b, m_per_video[b], kTLMaxM);
-    h.a.m[b] = m_per_video[b];
-    h.a.off[b] = off;
-    h.a.goff[b] = G;
-    off += m_per_video[b];
-    G += std::min(c->Q, m_per_video[b]);
-    Mmax = std::max(Mmax, m_per_video[b]);
-  }
-  h.a.goff[c->B] = G;
-  s.G = G;
-  s.Mmax = Mmax;
-  s.kmax = std::min(c->Q, Mmax);
-  h.total = off;
+  VideoFill v;
+  if (int rc = fill_videos(m_per_video, c->B, kMaxObjects, "", h.a.m, h.a.off, &v)) return rc;
+  for (int b = 0; b < c->B; ++b) h.a.goff[b + 1] = h.a.goff[b] + std::min(c->Q, h.a.m[b]);
+  s.G = h.a.goff[c->B];
+  s.Mmax = v.max;
+  s.kmax = std::min(c->Q, v.max);
+  h.total = v.total;
   return AXVS_OK;
 }
 
@@ -84,7 +65,7 @@ TLWork tl_work_views(void* ws, const TLShape& s, size_t* bytes) {
   TLWork v{nullptr, nullptr};
   if (s.G > 0) {
     const int Qp = (s.Q + 31) & ~31, Mpm = (s.Mmax + 31) & ~31, nprob = s.L * s.B;
-    const TLPlan pl = tl_plan(nprob, Qp >> 5, s.P);
+    const TileSplit pl = tl_plan(nprob, Qp >> 5, s.P);
     v.part = cv.f((size_t)nprob * pl.npb * tl_part_stride(Qp, Mpm));
     v.cost = cv.f((size_t)nprob * s.Q * s.Mmax);
   }
@@ -118,11 +99,8 @@ int axvs_tl_loss_fwd(const AxvsTLLossCfg* cfg, const float* const* cls_scores, c
   if (int rc = tl_setup(h, cfg, m_per_video)) return rc;
   const TLShape& s = h.s;
   if (!cls_scores || !mask_preds || !class_weight || !num_total_masks || !losses || !saved || !workspace) return fail(AXVS_ERR_ARG, "null pointer");
-  for (int l = 0; l < s.L; ++l) {
-    if (!cls_scores[l] || !mask_preds[l]) return fail(AXVS_ERR_ARG, "null pointer (layer %d)", l);
-    h.a.cls[l] = cls_scores[l];
-    h.a.masks[l] = mask_preds[l];
-  }
+  if (int rc = fill_layers(cls_scores, s.L, h.a.cls)) return rc;
+  if (int rc = fill_layers(mask_preds, s.L, h.a.masks)) return rc;
   if (s.G > 0 && (!targets || !labels || !match_coords || !rows || !cols)) return fail(AXVS_ERR_ARG, "null pointer");
   if (s.G > 0 && s.k > 0 && !cand_coords) return fail(AXVS_ERR_ARG, "null pointer (cand_coords)");
   if (s.G > 0 && s.P - s.k > 0 && !rand_coords) return fail(AXVS_ERR_ARG, "null pointer (rand_coords)");
@@ -132,30 +110,28 @@ int axvs_tl_loss_fwd(const AxvsTLLossCfg* cfg, const float* const* cls_scores, c
   hipStream_t st = static_cast<hipStream_t>(stream);
   const TLSaved sv = tl_saved_views(saved, s, nullptr);
   const int nprob = s.L * s.B;
-  const bool u8 = cfg->target_dtype == AXVS_U8;
   if (s.G > 0) {
     const int Qp = (s.Q + 31) & ~31, Mpm = (s.Mmax + 31) & ~31;
-    const TLPlan pl = tl_plan(nprob, Qp >> 5, s.P);
+    const TileSplit pl = tl_plan(nprob, Qp >> 5, s.P);
     const size_t lds = (size_t)(96 + Mpm) * kTLLDP * sizeof(float);
     float* cst = cost ? cost : wk.cost;
     const dim3 grid(pl.npb, Qp >> 5, nprob);
-    if (u8) {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&tl_cost_kernel<kTLU8>))) return rc;
-      hipLaunchKernelGGL(tl_cost_kernel<kTLU8>, grid, dim3(256), lds, st, h.a, targets, match_coords, s, pl.tiles_per_wg, wk.part);
-    } else {
-      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&tl_cost_kernel<kTLF32>))) return rc;
-      hipLaunchKernelGGL(tl_cost_kernel<kTLF32>, grid, dim3(256), lds, st, h.a, targets, match_coords, s, pl.tiles_per_wg, wk.part);
-    }
+    const int rc = by_target_dtype(cfg->target_dtype, [&](auto td) {
+      if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&tl_cost_kernel<td()>))) return rc;
+      hipLaunchKernelGGL(tl_cost_kernel<td()>, grid, dim3(256), lds, st, h.a, targets, match_coords, s, pl.tiles_per_wg, wk.part);
+      return (int)AXVS_OK;
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(tl_cost_finish_kernel, dim3((s.Q * s.Mmax + 255) / 256, nprob), dim3(256), 0, st, h.a, (const float*)wk.part, pl.npb, labels, s, cst);
     if (int rc = last_launch_status()) return rc;
-    int nc[kTLMaxLayers * kTLMaxVideos];
+    int nc[kMaxLayers * kMaxVideos];
     for (int z = 0; z < nprob; ++z) nc[z] = h.a.m[z % s.B];
     if (int rc = axvs_linear_sum_assignment_rect(cst, s.Mmax, s.Q, s.Mmax, nc, rows, cols, nprob, stream)) return rc;
     const dim3 pgrid(s.G, s.L);
-    if (u8) hipLaunchKernelGGL(tl_select_loss_kernel<kTLU8>, pgrid, dim3(kTLThreads), 0, st, h.a, targets, (const long long*)rows, (const long long*)cols,
-                               cand_coords, rand_coords, s, sv, sel_idx);
-    else hipLaunchKernelGGL(tl_select_loss_kernel<kTLF32>, pgrid, dim3(kTLThreads), 0, st, h.a, targets, (const long long*)rows, (const long long*)cols,
-                            cand_coords, rand_coords, s, sv, sel_idx);
+    by_target_dtype(cfg->target_dtype, [&](auto td) {
+      hipLaunchKernelGGL(tl_select_loss_kernel<td()>, pgrid, dim3(kTLThreads), 0, st, h.a, targets, (const long long*)rows, (const long long*)cols, cand_coords,
+                         rand_coords, s, sv, sel_idx);
+    });
   }
   hipLaunchKernelGGL(tl_finish_kernel, dim3(s.L), dim3(256), 0, st, h.a, labels, class_weight, num_total_masks, s, sv, losses);
   return last_launch_status();
@@ -170,11 +146,10 @@ int axvs_tl_loss_bwd(const AxvsTLLossCfg* cfg, const float* grad_losses, const f
   if (!grad_losses || !cls_scores || !mask_preds || !class_weight || !num_total_masks || !saved || !d_cls_scores || !d_mask_preds)
     return fail(AXVS_ERR_ARG, "null pointer");
   if (s.G > 0 && !targets) return fail(AXVS_ERR_ARG, "null pointer");
+  if (int rc = fill_layers(cls_scores, s.L, h.a.cls)) return rc;
+  if (int rc = fill_layers(mask_preds, s.L, h.a.masks)) return rc;
   bool any_masks = false, any_cls = false;
   for (int l = 0; l < s.L; ++l) {
-    if (!cls_scores[l] || !mask_preds[l]) return fail(AXVS_ERR_ARG, "null pointer (layer %d)", l);
-    h.a.cls[l] = cls_scores[l];
-    h.a.masks[l] = mask_preds[l];
     h.a.dcls[l] = d_cls_scores[l];
     h.a.dmasks[l] = d_mask_preds[l];
     any_masks |= d_mask_preds[l] != nullptr;
@@ -189,13 +164,12 @@ int axvs_tl_loss_bwd(const AxvsTLLossCfg* cfg, const float* grad_losses, const f
     if (s.G > 0) {
       const size_t lds = (size_t)(2 * (s.T * s.h + 1) + 1) * sizeof(int) + (size_t)2 * s.P * sizeof(unsigned short);
       const dim3 pgrid(s.G, s.L);
-      if (cfg->target_dtype == AXVS_U8) {
-        if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&tl_scatter_kernel<kTLU8>))) return rc;
-        hipLaunchKernelGGL(tl_scatter_kernel<kTLU8>, pgrid, dim3(kTLThreads), lds, st, h.a, targets, grad_losses, num_total_masks, s, sv);
-      } else {
-        if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&tl_scatter_kernel<kTLF32>))) return rc;
-        hipLaunchKernelGGL(tl_scatter_kernel<kTLF32>, pgrid, dim3(kTLThreads), lds, st, h.a, targets, grad_losses, num_total_masks, s, sv);
-      }
+      const int rc = by_target_dtype(cfg->target_dtype, [&](auto td) {
+        if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&tl_scatter_kernel<td()>))) return rc;
+        hipLaunchKernelGGL(tl_scatter_kernel<td()>, pgrid, dim3(kTLThreads), lds, st, h.a, targets, grad_losses, num_total_masks, s, sv);
+        return (int)AXVS_OK;
+      });
+      if (rc) return rc;
     }
   }
   const long long nrows = (long long)s.L * s.B * s.Q;

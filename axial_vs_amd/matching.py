@@ -120,8 +120,7 @@ def _run_matcher(layers: List[Dict[str, Tensor]], targets: List[Dict[str, Tensor
     Lb = _lib.lib()
     st = _stream(dev)
     ws = _workspace(dev, Lb.axvs_video_matcher_workspace_bytes(L, B, Q, M_max, P), st)
-    _lib.check(Lb.axvs_video_matcher((C.c_void_p * L)(*[x.data_ptr() for x in masks]), _mask_dtype(masks[0]),
-                                     (C.c_void_p * L)(*[x.data_ptr() for x in logits]), tcat.data_ptr(),
+    _lib.check(Lb.axvs_video_matcher(_lib.ptrs(masks), _mask_dtype(masks[0]), _lib.ptrs(logits), tcat.data_ptr(),
                                      _lib.AXVS_U8 if tcat.dtype == torch.uint8 else _lib.AXVS_F32, lcat.data_ptr(), (C.c_int * B)(*m),
                                      L, B, Q, K1, P, M_max, int(bool(masking_void_pixel)), sims.data_ptr(), rows.data_ptr(), cols.data_ptr(),
                                      dice.data_ptr(), cls.data_ptr(), ws.data_ptr(), ws.numel(), st), "axvs_video_matcher")

@@ -21,10 +21,6 @@ from . import _lib
 from ._autograd import cast, f32c, nbytes, place, require_gpu
 
 
-def _ptrs(ts) -> C.Array:
-    return (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
-
-
 def sample_counts(num_points: int, oversample_ratio: float, importance_sample_ratio: float) -> Tuple[int, int]:
     """(S, k): candidates per matched mask and how many of them are kept (mmdet/models/utils/point_sample.py:60, :74)."""
     if oversample_ratio < 1 or not 0 <= importance_sample_ratio <= 1:
@@ -86,7 +82,7 @@ class _TubeLinkLoss(torch.autograd.Function):
             sel = torch.empty(L, G, k, dtype=torch.int32, device=dev) if debug else None
             saved, saved_ptr, scratch = place(dev, nbytes("axvs_tl_loss_saved_bytes", c, mv), nbytes("axvs_tl_loss_workspace_bytes", c, mv))
             ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-            _lib.check(lib.axvs_tl_loss_fwd(c, _ptrs(cls), _ptrs(masks), ptr(tcat), ptr(lcat), mv, cw.data_ptr(), ptr(match), ptr(cand), ptr(rand),
+            _lib.check(lib.axvs_tl_loss_fwd(c, _lib.ptrs(cls), _lib.ptrs(masks), ptr(tcat), ptr(lcat), mv, cw.data_ptr(), ptr(match), ptr(cand), ptr(rand),
                                             ntm.data_ptr(), losses.data_ptr(), ptr(rows), ptr(cols), ptr(cost), ptr(sel), saved_ptr,
                                             scratch.data_ptr(), scratch.numel(), _stream(dev)), "axvs_tl_loss_fwd")
         ctx.save_for_backward(saved, *cls, *masks)
@@ -112,8 +108,8 @@ class _TubeLinkLoss(torch.autograd.Function):
             need = ctx.needs_input_grad[7:]
             dc = [torch.empty_like(x) if need[i] else None for i, x in enumerate(cls)]
             dm = [torch.empty_like(x) if need[L + i] else None for i, x in enumerate(masks)]
-            _lib.check(_lib.lib().axvs_tl_loss_bwd(c, g.data_ptr(), _ptrs(cls), _ptrs(masks), None if tcat is None else tcat.data_ptr(),
-                                                   (C.c_int * len(m))(*m), cw.data_ptr(), ntm.data_ptr(), saved.data_ptr(), _ptrs(dc), _ptrs(dm),
+            _lib.check(_lib.lib().axvs_tl_loss_bwd(c, g.data_ptr(), _lib.ptrs(cls), _lib.ptrs(masks), None if tcat is None else tcat.data_ptr(),
+                                                   (C.c_int * len(m))(*m), cw.data_ptr(), ntm.data_ptr(), saved.data_ptr(), _lib.ptrs(dc), _lib.ptrs(dm),
                                                    _stream(dev)), "axvs_tl_loss_bwd")
         grads = [None if d is None else d.reshape(s) for d, s in zip(dc + dm, ctx.in_shapes)]
         return (None,) * 7 + tuple(cast(grads, ctx.in_dtypes))

@@ -834,3 +834,60 @@ def test_every_signed_workspace_size_refuses_a_negative_one():
         err = L.axvs_last_error().decode()
         assert rc == -2, (name, rc, err)
         assert "workspace too small" in err and "-1" in err, (name, err)
+
+
+def _target_unit_calls():
+    """unit -> (its name for the query count, call(L, B, Q, m, tdt, layers, M_max)): one forward entry point of each training-target unit
+    at L layers x B videos with Q queries, K + 1 = 3 logits and 130 pixels (TL: T = 2, h = w = 8, 32 points).  `layers` are the per-layer
+    prediction pointers (None: NULL); every other pointer is made up as in _short_workspace_calls."""
+    from axial_vs_amd import _lib
+    lib = _lib.lib()
+    p = [ctypes.c_void_p(0x10000 * (i + 1)) for i in range(12)]
+    arr = lambda layers: (ctypes.c_void_p * len(layers))(*layers)
+    ints = lambda m: (ctypes.c_int * len(m))(*m)
+    big = 1 << 40
+
+    def matcher(L, B, Q, m, tdt, layers, M_max):
+        return lib.axvs_video_matcher(arr(layers), _lib.AXVS_F32, arr(layers), p[0], tdt, p[1], ints(m), L, B, Q, 3, 130, M_max, 1, p[2], p[3], p[4], p[5],
+                                      p[6], p[7], big, None)
+
+    def criterion(L, B, Q, m, tdt, layers, M_max):
+        return lib.axvs_set_criterion_fwd(arr(layers), arr(layers), p[0], tdt, p[1], ints(m), p[2], p[3], p[4], p[5], 1, L, B, Q, 3, 130, 1, 0, p[6], p[7],
+                                          p[8], big, None)
+
+    def insdis(L, B, Q, m, tdt, layers, M_max):
+        return lib.axvs_pixel_insdis_fwd(arr(layers), p[0], tdt, ints(m), p[1], 1, 0, L, B, Q, 4, 130, p[2], 16, 16, p[3], p[4], p[5], big, None)
+
+    def tl(L, B, Q, m, tdt, layers, M_max):
+        cfg = _lib.AxvsTLLossCfg(L=L, B=B, Q=Q, K1=3, T=2, h=8, w=8, Hg=8, Wg=8, num_points=32, num_cand=0, num_kept=0, target_dtype=tdt,
+                                 cost_cls=2, cost_mask=5, cost_dice=5, loss_cls=2, loss_mask=5, loss_dice=5, dice_eps=1)
+        return lib.axvs_tl_loss_fwd(ctypes.byref(cfg), arr(layers), arr(layers), p[0], p[1], ints(m), p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], None,
+                                    None, p[10], p[11], big, None)
+
+    return {"matcher": ("Q", matcher), "criterion": ("N", criterion), "pixel": ("N", insdis), "tl": ("Q", tl)}
+
+
+@pytest.mark.parametrize("unit", ["matcher", "criterion", "pixel", "tl"])
+def test_target_units_refuse_each_out_of_bounds_argument_by_name(unit):
+    """The matcher, the set criterion, the sampled pixel losses and Tube-Link's loss take the same kind of input (L layers x B videos,
+    per-layer pointers, m_per_video, u8 / fp32 targets) and share its checks: with ONE argument out of bounds the forward returns
+    AXVS_ERR_ARG before any device work, and the text names the offending value and its bound."""
+    from axial_vs_amd import _lib
+    lib = _lib.lib()
+    q, call = _target_unit_calls()[unit]
+    mb = lambda bound: f"0..M_max={bound}" if unit == "matcher" else "0..512"      # the matcher's bound on an entry is the caller's M_max
+    cases = [(dict(L=0), ["L=0", "1..16"]), (dict(L=17), ["L=17", "1..16"]), (dict(B=65), ["B=65", "1..64"]), (dict(Q=513), [f"{q}=513", "1..512"]),
+             (dict(m=[-1, 3]), ["m_per_video[0]=-1", mb(3)]), (dict(m=[3, 513], M_max=512), ["m_per_video[1]=513", mb(512)]),
+             (dict(tdt=_lib.AXVS_F16), ["target dtype 0", "AXVS_F32 / AXVS_U8"]), (dict(null_layer=1), ["null pointer (layer 1)"])]
+    if unit == "matcher":
+        cases.append((dict(M_max=4), ["M_max=4", "largest entry of m_per_video (3)"]))
+    for kw, words in cases:
+        L, B = kw.get("L", 2), kw.get("B", 2)
+        m = kw.get("m", [3] + [0] * (B - 1))
+        layers = [0x100000 * (i + 1) for i in range(max(L, 1))]
+        if "null_layer" in kw:
+            layers[kw["null_layer"]] = None
+        rc = call(L, B, kw.get("Q", 8), m, kw.get("tdt", _lib.AXVS_U8), layers, kw.get("M_max", max(m)))
+        err = lib.axvs_last_error().decode()
+        assert rc == -1, (unit, kw, rc, err)
+        assert all(w in err for w in words), (unit, kw, err)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / spill summary of the kernels of any translation unit of the library whose mangled name matches a pattern:
-#   tools/kernel_resources_unit.sh axvs_api.hip 'matcher|lsap_rect' [extra hipcc flags]
+#   tools/kernel_resources_unit.sh axvs_matching.hip 'matcher|lsap_rect' [extra hipcc flags]
 # prints one line per kernel: name, VGPRs, AGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, occupancy, static LDS bytes.
 R=$(cd "$(dirname "$0")/.." && pwd)
 UNIT=${1:?translation unit under axial_vs_amd/csrc}; PAT=${2:-.}; shift 2
