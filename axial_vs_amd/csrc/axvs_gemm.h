@@ -439,8 +439,9 @@ inline void launch_gemm_batched(const GemmBatch<ALoad, Epi, NB>& b, int M, int N
   hipLaunchKernelGGL((gemm64_batched_kernel<BF, ALoad, Epi, NB>), grid, dim3(256), 0, st, b, M, Nout, K);
 }
 
+// (not `inline`: an `extern template` declaration -- axvs_infer.h has one -- keeps a unit from instantiating the launcher and its kernels again)
 template <bool BF, class ALoad, class Epi>
-inline void launch_gemm(const ALoad& al, const u16* Wp, const Epi& epi, int M, int Nout, int K, hipStream_t st, int max_ks = 4 /* k-waves of the direct kernels: up to 7 */) {
+void launch_gemm(const ALoad& al, const u16* Wp, const Epi& epi, int M, int Nout, int K, hipStream_t st, int max_ks = 4 /* k-waves of the direct kernels: up to 7 */) {
   if (gemm_is_small(M, Nout, 1, K)) {
     const int kw = gemm_direct_waves(K, max_ks);
     const bool wide_n = (long long)((M + 15) / 16) * ((Nout + 63) / 64) >= 256;

@@ -1,6 +1,6 @@
 // C[M,N] = epilogue(A[M,K] B[N,K]^T) on fp32 operands in split precision ("bf16x3" / three-piece): the GEMM of the training tier's
 // Linear layers (axvs_train_gemm.h has the story), which the inference path uses too for projections whose fp32 inputs and outputs
-// make a 128 x 128 tile pay (the deformable attention's projections and the 1x1 convolutions of axvs_api.hip, the query decoders of
+// make a 128 x 128 tile pay (the deformable attention's projections and the 1x1 convolutions of axvs_pixdec.hip, the query decoders of
 // axvs_m2f.hip and axvs_kmax.hip).  This header is what its callers see: the argument structs and gemm_nt(), the one launcher.  The
 // kernel itself, tr_gemm_nt_kernel, is instantiated and launched in axvs_gemm_nt.hip alone: one code object carries each
 // instantiation, and every caller gets the same argument checks.

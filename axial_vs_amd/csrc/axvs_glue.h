@@ -272,10 +272,10 @@ __global__ void pos2d_kernel(float* __restrict__ pos, const float* __restrict__ 
   for (int b = 0; b < N; ++b) pos[((long long)b * S + row0 + r) * C + c] = v;
 }
 
-// x[i] += v[i % C]  (level embedding added to a channels-last position embedding, WC/msdeformattn.py:117-118)
-__global__ void add_channel_vector_kernel(float* __restrict__ x, const float* __restrict__ v, size_t n, int C) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) x[i] += v[i % C];
+__global__ void scaled_residual_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                       const float* __restrict__ gamma, float* __restrict__ out, size_t n, int C) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = a[i] + gamma[i % C] * b[i];
 }
 
 }  // namespace axvs

@@ -32,8 +32,17 @@ inline int g_spatial_wgs = 512;
 // the split-precision 16-bit MFMA one (three bf16 pieces per operand, a frame's score tiles in registers; axis length <= 128)
 inline int g_train_attn_split = 1;
 
+// axvs_set_option("cc_aspp_affine", 1): the ASPP projection's norm is a per-channel affine (norm_fn 'syncbn' in eval mode, folded by the caller into
+// aspp_norm_w / aspp_norm_b = scale / shift; 'none' = ones / zeros) instead of the channels-first LayerNorm of the shipped configs
+inline thread_local int g_cc_aspp_affine = 0;
+// axvs_set_option("cc_last_heads_only", 1): axvs_cc_module_fwd computes the predictor heads (class logits, mask einsum) of the LAST layer
+// only; pred_logits / pred_masks then hold ONE layer.  The reference computes every layer's predictions in eval too (CC/...:283-318) and
+// its inference path drops all but the last (maxtron_cc_model.py:301-: aux_outputs are read under self.training only): an inference
+// pipeline that does not want them saves 3/4 of the mask einsum's HBM writes
+inline thread_local int g_cc_last_only = 0;
+
 // optional per-stage event recording (bench.py / tuning): events[i] is recorded on the stream after stage i; the entry point that
-// records stages sets g_prof_next = 0 first (the axvs_profile_* entry points of axvs_api.hip read the state)
+// records stages sets g_prof_next = 0 first (the axvs_profile_* entry points of the axial unit, axvs_api.hip, read the state)
 inline thread_local hipEvent_t* g_prof_events = nullptr;
 inline thread_local int g_prof_cap = 0;
 inline thread_local int g_prof_next = 0;
@@ -73,6 +82,14 @@ struct Carver {  // bump allocator over a caller-owned buffer (nullptr: size onl
   }
   float* f(size_t n) { return take<float>(n); }
 };
+
+// bytes a carve step takes: the size query of a layout that its carver states -- carved([&](Carver& c) { carve_x(c, ...); })
+template <class F>
+size_t carved(F&& step) {
+  Carver c(nullptr);
+  step(c);
+  return c.off;
+}
 
 inline int check_ws(size_t have, size_t need) {
   if (have < need) return fail(AXVS_ERR_WORKSPACE, "workspace too small: %zu < %zu", have, need);

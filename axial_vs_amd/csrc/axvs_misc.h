@@ -1,33 +1,9 @@
 // Small kernels around the GEMMs: weight packing, LayerNorm, the temporal attention (v1, unfused),
-// positional embedding, scaled residual.
+// positional embedding (and the level embedding added to it).
 #pragma once
 #include "axvs_common.h"
 
 namespace axvs {
-
-// ---------------- weight packing: fp32 nn.Linear [Nout, K] -> blocked 16-bit weight layout (wblk_off, axvs_common.h) ----------------
-// Either dimension may be "head structured": `parts` consecutive groups of (heads x d) channels, each head padded
-// from d to 32 (zero rows / columns), so that kernels always see 32-wide head blocks.
-// Stored position p (0..31) of a permuted head block holds channel perm32(p): the order in which an MFMA D tile pair
-// (two 16-row tiles, rows 4g+r) leaves 8 consecutive values per lane, so attention/QKV epilogues store 16 B per lane.
-__device__ __host__ inline int perm32(int p) { return ((p >> 2) & 1) * 16 + (p >> 3) * 4 + (p & 3); }
-
-struct PackDim {
-  int orig;    // original size
-  int padded;  // padded size
-  int heads;   // 0: plain (identity up to `orig`, zero beyond); >0: head structured
-  int d;       // head dim (when heads > 0)
-  int perm;    // head structured only: positions within a 32-block are stored in perm32 order
-  __device__ __host__ int to_orig(int i) const {
-    if (heads == 0) return i < orig ? i : -1;
-    int per = heads * 32;
-    int part = i / per, w = i - part * per;
-    int h = w >> 5, dd = perm ? perm32(w & 31) : (w & 31);
-    if (dd >= d) return -1;
-    int o = part * heads * d + h * d + dd;
-    return o < orig ? o : -1;
-  }
-};
 
 // n_off / n_total: the rows written are rows [n_off, n_off + nd.padded) of a wider blocked matrix with n_total rows
 // (several nn.Linear weights stacked along the output dimension).
@@ -317,10 +293,10 @@ __global__ void pos3d_masked_kernel(float* __restrict__ pos, const unsigned char
   pos[idx] = v;
 }
 
-__global__ void scaled_residual_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                       const float* __restrict__ gamma, float* __restrict__ out, size_t n, int C) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = a[i] + gamma[i % C] * b[i];
+// x[i] += v[i % C]  (level embedding added to a channels-last position embedding, WC/msdeformattn.py:117-118)
+__global__ void add_channel_vector_kernel(float* __restrict__ x, const float* __restrict__ v, size_t n, int C) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] += v[i % C];
 }
 
 }  // namespace axvs

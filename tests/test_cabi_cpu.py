@@ -891,3 +891,66 @@ def test_target_units_refuse_each_out_of_bounds_argument_by_name(unit):
         err = lib.axvs_last_error().decode()
         assert rc == -1, (unit, kw, rc, err)
         assert all(w in err for w in words), (unit, kw, err)
+
+
+def _inference_unit_calls():
+    """family -> [(what is wrong, call(dtype), words of the message)]: entry points of the three inference units (axial, cross-clip, pixel
+    decoder), each called with ONE wrong argument.  Pointers are made up as in _short_workspace_calls; what the host reads before the
+    failing check (spatial_shapes, rates, the parameter struct's address) is real."""
+    from axial_vs_amd import _lib
+    L = _lib.lib()
+    p = [ctypes.c_void_p(0x10000 * (i + 1)) for i in range(8)]
+    B, T, H, W, C, h, F = 1, 2, 16, 12, 256, 8, 1024
+    Q, Tc, K1, fpc = 16, 3, 25, 2
+    N, S, Lq, P = 2, 80, 80, 4
+    rates = (ctypes.c_int * 3)(1, 2, 3)
+    shapes = (ctypes.c_int * 4)(8, 8, 4, 4)          # two levels, S = 80
+    tlp = ctypes.byref(_lib.AxvsTLHeadParams())
+    big = 1 << 40
+
+    def axial_pass(dtype, pass_=1, src=p[0]):
+        return L.axvs_axial_pass_fwd(src, p[1], p[2], p[3], pass_, B, T, H, W, C, h, F, dtype, p[4], big, None)
+
+    def cc_layer(dtype, ws=big, out=p[1]):
+        return L.axvs_cc_layer_fwd(p[0], out, p[2], B, Q, Tc, rates, dtype, p[3], ws, None)
+
+    def msda(dtype, ref_dim=2):
+        return L.axvs_msda_fwd(p[0], p[1], ref_dim, p[2], None, shapes, p[3], p[4], N, Lq, S, C, h, 2, P, dtype, p[5], big, None)
+
+    def fpn(dtype, groups=32):
+        return L.axvs_fpn_level_fwd(p[0], p[1], 5 * 7 * 256, 256, 5, 7, p[2], None, p[3], N, 10, 14, 512, 256, 0, groups, 1e-5, dtype, p[4], big, None)
+
+    cc_need = L.axvs_cc_layer_workspace_bytes(B, Q, Tc)
+    return {
+        "axial": (axial_pass, [
+            ("pass = 2", lambda dt: axial_pass(dt, pass_=2), -1, ["pass must be 0 (height) or 1 (width + FFN)"]),
+            ("null src", lambda dt: axial_pass(dt, src=None), -1, ["null pointer"])]),
+        "cross-clip": (cc_layer, [
+            ("Cm = 64", lambda dt: L.axvs_tl_heads_pack(tlp, p[0], K1, 64, dt, None), -1, ["mask feature channels must be 128 or 256 (got 64)"]),
+            ("null out", lambda dt: cc_layer(dt, out=None), -1, ["null pointer"]),
+            ("workspace one byte short", lambda dt: cc_layer(dt, ws=cc_need - 1), -2, ["workspace too small", f"{cc_need - 1} < {cc_need}"])]),
+        "pixel decoder": (msda, [
+            ("ref_dim = 3", lambda dt: msda(dt, ref_dim=3), -1, ["Last dim of reference_points must be 2 or 4, but get 3 instead."]),
+            ("groups = 7", lambda dt: fpn(dt, groups=7), -1, ["groups=7 must divide C=256"])]),
+    }
+
+
+@pytest.mark.parametrize("family", ["axial", "cross-clip", "pixel decoder"])
+def test_inference_units_refuse_each_wrong_argument_by_name(family):
+    """The axial, cross-clip and pixel-decoder entry points live in three translation units that share their argument checks (dtype,
+    configuration, workspace): a call with one wrong argument returns its error code before any device work and axvs_last_error() names
+    what was wrong -- and a library built without the bf16 operand tier refuses AXVS_BF16 in every one of the three."""
+    from axial_vs_amd import _lib
+    L = _lib.lib()
+    entry, cases = _inference_unit_calls()[family]
+    for what, call, code, words in cases:
+        rc = call(_lib.AXVS_F16)
+        err = L.axvs_last_error().decode()
+        assert rc == code, (family, what, rc, err)
+        assert all(w in err for w in words), (family, what, err)
+    if not L.axvs_has_bf16():
+        rc = entry(_lib.AXVS_BF16)
+        err = L.axvs_last_error().decode()
+        assert rc == -1 and "the bf16 operand tier is not built into this library" in err, (family, rc, err)
+    rc = entry(7)
+    assert rc == -1 and "unknown dtype 7" in L.axvs_last_error().decode(), (family, rc)

@@ -2,7 +2,7 @@
 before an `s_waitcnt lgkmcnt(..)`.  lgkmcnt is a 4-bit counter: 16 outstanding operations wrap it (see lds_fence() in
 axvs_common.h).  Linear scan per kernel (branch targets do not reset the count: conservative).
 
-    python tools/check_lgkm.py [file.s ...]     # with no argument: compiles axvs_api.hip to ISA first
+    python tools/check_lgkm.py [file.s ...]     # with no argument: compiles the three inference units to ISA first
 """
 import os, re, subprocess, sys, tempfile
 
@@ -40,10 +40,11 @@ def main():
     files = sys.argv[1:]
     if not files:
         tmp = tempfile.mkdtemp()
-        out = os.path.join(tmp, "axvs.s")
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out,
-                               os.path.join(ROOT, "axial_vs_amd", "csrc", "axvs_api.hip")], stderr=subprocess.DEVNULL)
-        files = [out]
+        for unit in ("axvs_api", "axvs_cross_clip", "axvs_pixdec"):
+            out = os.path.join(tmp, unit + ".s")
+            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out,
+                                   os.path.join(ROOT, "axial_vs_amd", "csrc", unit + ".hip")], stderr=subprocess.DEVNULL)
+            files.append(out)
     bad = 0
     for f in files:
         for k, (peak, where) in sorted(scan(f).items(), key=lambda kv: -kv[1][0]):
