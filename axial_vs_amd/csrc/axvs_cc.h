@@ -118,26 +118,22 @@ __device__ __forceinline__ void class_logits_256(const float* __restrict__ wcT, 
   }
 }
 
-// Class head of MaXTronCCPredictor (CC/...:48-52): per query q, softmax over ALL (b, clip) entries of a 256->1 activation
-// head, weighted sum of the class embeddings, 256->K1 class head, void bias on the last class.
-// emb: fp32 [(b q t)][ld] (class embedding = columns 0..255); out: fp32 [Q][K1].  One workgroup (256 threads) per q.
-__global__ __launch_bounds__(256) void cc_class_head_kernel(const float* __restrict__ emb, int ld, const float* __restrict__ wa,
-                                                            const float* __restrict__ ba, const float* __restrict__ wc /* transposed: [256][K1] */,
-                                                            const float* __restrict__ bc, float* __restrict__ out, int Bv, int Q,
-                                                            int Tc, int K1, float void_bias) {
+// The body the two class heads share, one workgroup of 256 threads (= channels) per output row: activation logits
+// a_e = w_a . row_e + b_a of the E entries, softmax over e, pooled = sum_e softmax_e row_e, out = W_c pooled + b_c (+ last_extra on the
+// last class).  row(e): this thread's element of entry e's 256-channel row.
+template <class Row>
+__device__ __forceinline__ void class_head_256(Row row, int E, const float* __restrict__ wa, const float* __restrict__ ba,
+                                               const float* __restrict__ wc /* transposed: [256][K1] */, const float* __restrict__ bc,
+                                               float* __restrict__ out, int K1, float last_extra) {
   constexpr int C = 256, MAXE = 1024;
   __shared__ float logit[MAXE], pooled[C], red[16];
-  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  emb += (long long)blockIdx.y * Bv * Q * Tc * ld;    // blockIdx.y: layer (the module loop runs the heads of all layers in one launch)
-  out += (long long)blockIdx.y * Q * K1;
-  const int E = Bv * Tc;                              // entries the softmax runs over (dim 0 of the reference tensor)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float wac = wa[tid];
-  auto row = [&](int e) { const int b = e / Tc, t = e - b * Tc; return emb + (((long long)b * Q + q) * Tc + t) * ld + tid; };
   // entries in groups of 4: their loads are independent (one L2 round trip per group instead of one per entry), one barrier pair per group
   for (int e0 = 0; e0 < E; e0 += 4) {
     float v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = *row(min(e0 + j, E - 1)) * wac;
+    for (int j = 0; j < 4; ++j) v[j] = row(min(e0 + j, E - 1)) * wac;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float sj = wave_sum(v[j]);
@@ -155,14 +151,29 @@ __global__ __launch_bounds__(256) void cc_class_head_kernel(const float* __restr
   for (int e0 = 0; e0 < E; e0 += 4) {
     float v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = *row(min(e0 + j, E - 1));
+    for (int j = 0; j < 4; ++j) v[j] = row(min(e0 + j, E - 1));
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (e0 + j < E) p += __expf(logit[e0 + j] - mx) / sum * v[j];
   }
   pooled[tid] = p;
   __syncthreads();
-  class_logits_256(wc, bc, pooled, logit /* free now (>= 256 floats) */, out + (long long)q * K1, K1, void_bias, tid);
+  class_logits_256(wc, bc, pooled, logit /* free now (>= 256 floats) */, out, K1, last_extra, tid);
+}
+
+// Class head of MaXTronCCPredictor (CC/...:48-52): per query q, softmax over ALL (b, clip) entries of a 256->1 activation
+// head, weighted sum of the class embeddings, 256->K1 class head, void bias on the last class.
+// emb: fp32 [(b q t)][ld] (class embedding = columns 0..255); out: fp32 [Q][K1].  One workgroup (256 threads) per q.
+__global__ __launch_bounds__(256) void cc_class_head_kernel(const float* __restrict__ emb, int ld, const float* __restrict__ wa,
+                                                            const float* __restrict__ ba, const float* __restrict__ wc /* transposed: [256][K1] */,
+                                                            const float* __restrict__ bc, float* __restrict__ out, int Bv, int Q,
+                                                            int Tc, int K1, float void_bias) {
+  const int q = blockIdx.x, tid = threadIdx.x;
+  emb += (long long)blockIdx.y * Bv * Q * Tc * ld;    // blockIdx.y: layer (the module loop runs the heads of all layers in one launch)
+  out += (long long)blockIdx.y * Q * K1;
+  // the softmax runs over the E = Bv * Tc entries (b, t): dim 0 of the reference tensor
+  auto row = [&](int e) { const int b = e / Tc, t = e - b * Tc; return emb[(((long long)b * Q + q) * Tc + t) * ld + tid]; };
+  class_head_256(row, Bv * Tc, wa, ba, wc, bc, out + (long long)q * K1, K1, void_bias);
 }
 
 // Mask logits as a strided batched contraction over channels, shared by the two heads:
@@ -266,41 +277,11 @@ constexpr size_t einsum_lds_bytes() { return (size_t)(CK / 32) * kEinsumPx * 32 
 __global__ __launch_bounds__(256) void tl_class_head_kernel(const float* __restrict__ x, const float* __restrict__ wa,
                                                             const float* __restrict__ ba, const float* __restrict__ wc,
                                                             const float* __restrict__ bc, float* __restrict__ out, int Tc, int K1) {
-  constexpr int C = 256, MAXT = 1024;
-  __shared__ float logit[MAXT], pooled[C], red[16];
-  const int bq = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int C = 256;
+  const int bq = blockIdx.x, tid = threadIdx.x;
   const float* xr = x + ((long long)blockIdx.y * gridDim.x + bq) * Tc * C;   // blockIdx.y: layer
   out += (long long)blockIdx.y * gridDim.x * K1;
-  const float wac = wa[tid];
-  for (int t0 = 0; t0 < Tc; t0 += 4) {      // clips in groups of 4 (independent loads, one barrier pair per group)
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = xr[min(t0 + j, Tc - 1) * C + tid] * wac;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float sj = wave_sum(v[j]);
-      if (lane == 0) red[j * 4 + wave] = sj;
-    }
-    __syncthreads();
-    if (tid < 4 && t0 + tid < Tc) logit[t0 + tid] = red[tid * 4] + red[tid * 4 + 1] + red[tid * 4 + 2] + red[tid * 4 + 3] + ba[0];
-    __syncthreads();
-  }
-  float mx = -INFINITY;
-  for (int t = 0; t < Tc; ++t) mx = fmaxf(mx, logit[t]);
-  float sum = 0.f;
-  for (int t = 0; t < Tc; ++t) sum += __expf(logit[t] - mx);
-  float p = 0.f;
-  for (int t0 = 0; t0 < Tc; t0 += 4) {
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = xr[min(t0 + j, Tc - 1) * C + tid];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (t0 + j < Tc) p += __expf(logit[t0 + j] - mx) / sum * v[j];
-  }
-  pooled[tid] = p;
-  __syncthreads();
-  class_logits_256(wc, bc, pooled, logit /* free now (>= 256 floats) */, out + (long long)bq * K1, K1, 0.f, tid);
+  class_head_256([&](int t) { return xr[t * C + tid]; }, Tc, wa, ba, wc, bc, out + (long long)bq * K1, K1, 0.f);
 }
 
 }  // namespace axvs

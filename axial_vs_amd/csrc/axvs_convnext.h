@@ -15,7 +15,7 @@
 //   cnx_grn_gx_kernel       GRN: chunk sums in chunk order -> Gx
 //   cnx_grn_scale_kernel    GRN: Gx -> s = 1 + gamma Gx / (mean_c Gx + 1e-6) per frame
 //   cnx_scale_w_kernel      W2 diag(s_n): pwconv2's weight of one frame
-// and rows [N*h*w][C] -> [N, C, h, w] for the outputs: rows_to_nchw_kernel (axvs_eval_host.h).
+// and rows [N*h*w][C] -> [N, C, h, w] for the outputs: rows_to_nchw() (axvs_layout.h).
 // No kernel waits for another workgroup and none adds floating-point numbers atomically: equal inputs give equal bits, and a frame's
 // bits do not depend on the frames stacked beside it.
 #pragma once

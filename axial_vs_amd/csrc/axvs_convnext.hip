@@ -10,6 +10,7 @@
 
 #include "axvs_convnext.h"
 #include "axvs_eval_host.h"
+#include "axvs_layout.h"
 
 using namespace axvs;
 

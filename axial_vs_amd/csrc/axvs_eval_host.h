@@ -1,7 +1,6 @@
 // Host scaffold shared by the eval-forward units (axvs_m2f.hip, axvs_kmax.hip, axvs_kmax_pix.hip, axvs_convnext.hip): the Linear layer
 // on the split-precision GEMM, the slot lists of a packed blob (a parameter struct read as an array of pointers, axial_vs_amd/_params.py
-// states the same order), a flat block index -> (stage, block of the stage), and the one layout kernel two of them share.
-//   rows_to_nchw_kernel     rows [N*h*w][C] -> [N, C, h, w]
+// states the same order), and a flat block index -> (stage, block of the stage).  The device pieces they share: axvs_layout.h.
 #pragma once
 #include "axvs_gemm_nt.h"
 #include "axvs_host.h"
@@ -52,38 +51,6 @@ inline int locate(const int (&counts)[4], int index, const char* whose, int* sta
     index -= counts[i];
   }
   return fail(AXVS_ERR_ARG, "block index outside the %s blocks", whose);
-}
-
-// ---- rows [N*hw][C] -> [N, C, hw]: a 32 (pixels) x 64 (channels) tile through LDS.  grid (ceil(hw/32) * ceil(C/64), N), 256 threads ----
-// (static: each unit that launches it carries its own copy in its code object, the others none)
-static __global__ __launch_bounds__(256) void rows_to_nchw_kernel(const float* __restrict__ rows, float* __restrict__ out, int C, int hw) {
-  __shared__ float tile[32][65];
-  const int tid = threadIdx.x;
-  const int cchunks = (C + 63) / 64;
-  const int p0 = (int)(blockIdx.x / cchunks) * 32, c0 = (int)(blockIdx.x % cchunks) * 64;
-  const size_t n = blockIdx.y;
-  {
-    const int c = tid & 63, pr = tid >> 6;
-    if (c0 + c < C) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int p = p0 + pr + 4 * j;
-        if (p < hw) tile[pr + 4 * j][c] = rows[(n * hw + p) * C + c0 + c];
-      }
-    }
-  }
-  __syncthreads();
-  const int tx = tid & 31, cy = tid >> 5, p = p0 + tx;
-  if (p >= hw) return;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = c0 + cy + 8 * j;
-    if (c < C) out[(n * C + c) * (size_t)hw + p] = tile[tx][cy + 8 * j];
-  }
-}
-
-static inline void rows_to_nchw(const float* rows, float* out, int N, int C, int hw, hipStream_t st) {
-  hipLaunchKernelGGL(rows_to_nchw_kernel, dim3((unsigned)((hw + 31) / 32 * ((C + 63) / 64)), (unsigned)N), dim3(256), 0, st, rows, out, C, hw);
 }
 
 }  // namespace axvs

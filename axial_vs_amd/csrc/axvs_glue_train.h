@@ -2,7 +2,7 @@
 // (WC/msdeformattn.py:349-375, used at :412 and :434) forward AND backward, so that the within-clip module's train() mode runs no torch kernel between the
 // backbone maps and its output maps.  fp32 tensors, the GEMMs on the training tier's split-precision kernels (axvs_train_gemm.h: three bf16 pieces
 // forward -- fp32 accuracy --, two backward), GroupNorm statistics and their gradients in fp32 with fixed summation orders (no atomics).
-//   forward   y = x W^T + b            [M = N HW rows, Cout]                   (token rows; an NCHW input is transposed once)
+//   forward   y = x W^T + b            [M = N HW rows, Cout]                   (token rows; an NCHW input is transposed once: axvs_layout.h)
 //             mean, rstd per (sample n, group g) over HW x Cout/G values, centred at every level (block, channel, group): no E[y^2] - mean^2
 //             out = (y - mean) rstd gamma + beta
 //   backward  xhat = (y - mean) rstd;   A[n,c] = sum_p d_out,  B[n,c] = sum_p d_out xhat
@@ -12,54 +12,10 @@
 // Part of axvs_train.hip's translation unit only: the kernels have internal linkage.
 #pragma once
 #include "axvs_common.h"
+#include "axvs_layout.h"
 
 namespace axvs {
 namespace {
-
-// t [N][HW][C] token rows -> x [N][C][HW] (the inverse of nchw_to_tokens_kernel); 64 x 64 tiles through LDS, any HW, C a multiple of 4
-__global__ __launch_bounds__(256) void gt_tokens_to_nchw_kernel(const float* __restrict__ t, float* __restrict__ x, int C, int HW, long long t_batch_stride, long long t_ld) {
-  __shared__ float tile[64][65];
-  const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, n = blockIdx.z;
-  const int rc = (threadIdx.x & 15) * 4, rp = threadIdx.x >> 4;      // read: 16 threads x float4 cover 64 channels of a pixel row
-  const float* src = t + (long long)n * t_batch_stride + (long long)p0 * t_ld + c0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = rp + 16 * i;
-    float4 v = {0.f, 0.f, 0.f, 0.f};
-    if (p0 + p < HW && c0 + rc < C) v = *reinterpret_cast<const float4*>(src + (long long)p * t_ld + rc);
-    tile[p][rc] = v.x; tile[p][rc + 1] = v.y; tile[p][rc + 2] = v.z; tile[p][rc + 3] = v.w;
-  }
-  __syncthreads();
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;            // write: tx = pixel, 4 channel rows at a time
-  float* dst = x + ((long long)n * C + c0) * HW + p0;
-#pragma unroll 4
-  for (int i = 0; i < 16; ++i) {
-    const int c = ty + 4 * i;
-    if (c0 + c < C && p0 + tx < HW) dst[(long long)c * HW + tx] = tile[tx][c];
-  }
-}
-
-// x [N][C][HW] -> token rows t [N][HW][C] (contiguous)
-__global__ __launch_bounds__(256) void gt_nchw_to_tokens_kernel(const float* __restrict__ x, float* __restrict__ t, int C, int HW) {
-  __shared__ float tile[64][65];
-  const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, n = blockIdx.z;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const float* src = x + ((long long)n * C + c0) * HW + p0;
-#pragma unroll 4
-  for (int i = 0; i < 16; ++i) {
-    const int c = ty + 4 * i;
-    tile[c][tx] = (c0 + c < C && p0 + tx < HW) ? src[(long long)c * HW + tx] : 0.f;
-  }
-  __syncthreads();
-  const int wc = (threadIdx.x & 15) * 4, wp = threadIdx.x >> 4;
-  float* dst = t + ((long long)n * HW + p0) * C + c0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = wp + 16 * i;
-    if (p0 + p < HW && c0 + wc < C)
-      *reinterpret_cast<float4*>(dst + (long long)p * C + wc) = float4{tile[wc][p], tile[wc + 1][p], tile[wc + 2][p], tile[wc + 3][p]};
-  }
-}
 
 // token rows that are a slice of a wider buffer -> contiguous [N][HW][C]
 __global__ __launch_bounds__(256) void gt_gather_tokens_kernel(const float* __restrict__ src, float* __restrict__ dst, int HW, int C, long long batch_stride, long long ld,

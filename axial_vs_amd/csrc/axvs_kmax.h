@@ -4,7 +4,9 @@
 // FMAs: the cluster assignment is a hard decision.  Pixels travel channels-last, rows in the order (clip, frame, y, x): the reference's
 // stacked `b c (t h) w` map.
 //
-//   kmax_to_cl_kernel       [(B T), C, h, w] -> rows [B*T*h*w][C], optionally through gelu (a layer's input activation, once per level)
+//   (axvs_layout.h)         [(B T), C, h, w] -> rows [B*T*h*w][C], optionally through gelu (a layer's input activation, once per level):
+//                           nchw_to_rows<GELU>(); the cluster centres' broadcast over the clips and the class logits: broadcast_rows(),
+//                           class_logits_rows()
 //   kmax_dw5_kernel         depthwise 5 x 5 (+ folded BN + gelu) over the stacked T*h x w map through an LDS halo tile: the window crosses
 //                           frame boundaries, as the reference's does
 //   kmax_assign_kernel      a tile of pixels: L2-normalise the 128-channel rows, contract with the [L,128] mask kernels (held in LDS in
@@ -21,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "axvs_common.h"
+#include "axvs_layout.h"
 
 namespace axvs {
 
@@ -32,58 +35,6 @@ constexpr int kKmaxLLd = kKmaxD + 4;  // LDS row stride of a mask kernel
 constexpr int kKmaxSumMinChunk = 256; // pixels per cluster-sum chunk, at least
 constexpr int kKmaxSumMaxChunks = 64; // chunks per clip, at most: the slabs do not grow with the map
 constexpr int kKmaxAug = kKmaxC + 4;  // a cluster-sum row: 256 sums, the pixel count, three zeros
-
-// ---- [(B T), C, h, w] -> channels-last rows: a 32 (x) x 64 (channels) tile through LDS ----------------------------------------------
-// grid (ceil(w/32) * ceil(C/64), h, B*T), 256 threads
-template <bool GELU>
-__global__ __launch_bounds__(256) void kmax_to_cl_kernel(const float* __restrict__ src, float* __restrict__ out, int C, int h, int w) {
-  __shared__ float tile[32][65];
-  const int tid = threadIdx.x;
-  const int cchunks = (C + 63) / 64;
-  const int x0 = (int)(blockIdx.x / cchunks) * 32, c0 = (int)(blockIdx.x % cchunks) * 64, y = blockIdx.y;
-  const size_t bt = blockIdx.z;
-  {
-    const int tx = tid & 31, cy = tid >> 5, x = x0 + tx;
-    if (x < w) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int c = c0 + cy + 8 * j;
-        if (c < C) {
-          const float v = src[((bt * C + c) * h + y) * w + x];
-          tile[tx][cy + 8 * j] = GELU ? gelu_exact(v) : v;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  const int c = tid & 63, xr = tid >> 6;
-  if (c0 + c >= C) return;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int x = x0 + xr + 4 * j;
-    if (x >= w) continue;
-    out[((bt * h + y) * w + x) * C + c0 + c] = tile[xr + 4 * j][c];
-  }
-}
-
-// x[b*L + l] = centers[l]
-__global__ __launch_bounds__(256) void kmax_init_kernel(const float* __restrict__ centers, float* __restrict__ x, int L, int rows) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows * kKmaxC) return;
-  x[i] = centers[(i / kKmaxC % L) * kKmaxC + i % kKmaxC];
-}
-
-// cls[row][k] = y[row] . w[k] + b[k]   (K + 1 classes: any count, so not a tile of the GEMM; b holds the bias towards void)
-__global__ __launch_bounds__(256) void kmax_cls_kernel(const float* __restrict__ y, const float* __restrict__ w, const float* __restrict__ b,
-                                                       float* __restrict__ cls, int rows, int K1) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows * K1) return;
-  const float* const yr = y + (i / K1) * kKmaxC;
-  const float* const wr = w + (i % K1) * kKmaxC;
-  float acc = 0.f;
-  for (int c = 0; c < kKmaxC; ++c) acc = fmaf(yr[c], wr[c], acc);
-  cls[i] = acc + b[i % K1];
-}
 
 // ---- depthwise 5 x 5, padding 2, over the stacked map [B][TH][w][256]: out = gelu(sum_k wt[k][c] in[y + ky - 2][x + kx - 2][c] + bias[c]) -----
 // A workgroup: 4 rows x 8 columns of outputs x 64 channels; the 8 x 12 halo tile in LDS (zeros outside the stacked map -- and only

@@ -130,8 +130,7 @@ KmaxWs kmax_carve(void* ws, const AxvsKmaxCfg* c, int what, int arg) {
 // ---- launches -------------------------------------------------------------------------------------------------------------------------------
 template <bool GELU>
 void to_cl(const float* src, float* out, int BT, int Cin, int h, int w, hipStream_t st) {
-  const dim3 grid((unsigned)((w + 31) / 32 * ((Cin + 63) / 64)), (unsigned)h, (unsigned)BT);
-  hipLaunchKernelGGL((kmax_to_cl_kernel<GELU>), grid, dim3(256), 0, st, src, out, Cin, h, w);
+  nchw_to_rows<GELU>(src, out, BT, Cin, h * w, st);
 }
 
 // the predictor's pixel branch on rows `in` [B*TH*w][256] (which it does not change): dw 5x5 -> pb, 1x1 -> `mid`, 1x1 + bias -> pf [.][128]
@@ -181,9 +180,7 @@ int update(const AxvsKmaxCfg* c, int i, const KmaxW& p, const KmaxWs& w, const f
 }
 
 void class_logits(const AxvsKmaxCfg* c, float* const* pr, const float* emb, float* out, hipStream_t st) {
-  const int R = c->B * c->L;
-  hipLaunchKernelGGL(kmax_cls_kernel, dim3((unsigned)(((size_t)R * c->K1 + 255) / 256)), dim3(256), 0, st, emb, (const float*)pr[PR_CLS_W],
-                     (const float*)pr[PR_CLS_B], out, R, c->K1);
+  class_logits_rows(emb, pr[PR_CLS_W], pr[PR_CLS_B], out, c->B * c->L, c->K1, st);
 }
 
 }  // namespace
@@ -230,7 +227,7 @@ int axvs_kmax_decoder_fwd(const AxvsKmaxCfg* cfg, const void* packed, const floa
       if (!features[l]) return fail(AXVS_ERR_ARG, "null pointer (level %d features)", l);
       to_cl<true>(features[l], w.gx[l], BT, cfg->in_channels[l], cfg->h[l], cfg->w[l], st);      // the input gelu, once per level
     }
-  hipLaunchKernelGGL(kmax_init_kernel, dim3((unsigned)(((size_t)R * C + 255) / 256)), dim3(256), 0, st, (const float*)p.head[HD_CENTERS], w.x, cfg->L, R);
+  broadcast_rows(p.head[HD_CENTERS], w.x, cfg->L, R, st);
   int* dbg = debug_idx;
   for (int i = 0; i < nl; ++i) {
     const int l = cfg->layer_level[i];

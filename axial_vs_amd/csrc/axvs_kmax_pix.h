@@ -13,13 +13,14 @@
 //                           never exist
 //   kpix_conv3_kernel       3 x 3, stride 1, zero padding 1, folded BN, gelu: implicit GEMM over a halo tile in LDS
 //   kpix_resize_add_kernel  out = high + bilinear(low), either align_corners value (axvs_resize.h's coordinate rule)
-//   kpix_to_rows_kernel     [N, C, h, w] -> rows [N*h*w][C]; the other way: rows_to_nchw_kernel (axvs_eval_host.h)
+// [N, C, h, w] <-> rows [N*h*w][C] without a norm: nchw_to_rows() / rows_to_nchw() (axvs_layout.h).
 // No kernel waits for another workgroup and none adds floating-point numbers atomically: equal inputs give equal bits, and a frame's
 // bits do not depend on the frames stacked beside it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "axvs_common.h"
+#include "axvs_layout.h"
 #include "axvs_resize.h"
 
 namespace axvs {
@@ -90,33 +91,6 @@ __global__ __launch_bounds__(256) void kpix_gelu_kernel(const float* __restrict_
   if (i >= n4) return;
   const float4 v = reinterpret_cast<const float4*>(x)[i];
   reinterpret_cast<float4*>(y)[i] = float4{gelu_exact(v.x), gelu_exact(v.y), gelu_exact(v.z), gelu_exact(v.w)};
-}
-
-// [N, C, h*w] -> rows [N*hw][C] (the stage entries' inputs): rows_to_nchw_kernel's tile (axvs_eval_host.h) the other way.  grid (ceil(hw/32) * ceil(C/64), N), 256 threads
-__global__ __launch_bounds__(256) void kpix_to_rows_kernel(const float* __restrict__ src, float* __restrict__ out, int C, int hw) {
-  __shared__ float tile[32][65];
-  const int tid = threadIdx.x;
-  const int cchunks = (C + 63) / 64;
-  const int p0 = (int)(blockIdx.x / cchunks) * 32, c0 = (int)(blockIdx.x % cchunks) * 64;
-  const size_t n = blockIdx.y;
-  {
-    const int tx = tid & 31, cy = tid >> 5, p = p0 + tx;
-    if (p < hw) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int c = c0 + cy + 8 * j;
-        if (c < C) tile[tx][cy + 8 * j] = src[(n * C + c) * (size_t)hw + p];
-      }
-    }
-  }
-  __syncthreads();
-  const int c = tid & 63, pr = tid >> 6;
-  if (c0 + c >= C) return;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int p = p0 + pr + 4 * j;
-    if (p < hw) out[(n * hw + p) * C + c0 + c] = tile[pr + 4 * j][c];
-  }
 }
 
 // ---- one axis pass of the axial attention ---------------------------------------------------------------------------------------------------

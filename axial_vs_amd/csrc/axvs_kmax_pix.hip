@@ -140,10 +140,7 @@ void innorm(const float* src, const float* g, const float* b, float* out, int N,
   else hipLaunchKernelGGL((kpix_innorm_kernel<false>), grid, dim3(256), 0, st, src, g, b, out, C, hw);
 }
 
-void to_rows(const float* src, float* out, int N, int C, int h, int w, hipStream_t st) {
-  const int hw = h * w;
-  hipLaunchKernelGGL(kpix_to_rows_kernel, dim3((unsigned)((hw + 31) / 32 * ((C + 63) / 64)), (unsigned)N), dim3(256), 0, st, src, out, C, hw);
-}
+void to_rows(const float* src, float* out, int N, int C, int h, int w, hipStream_t st) { nchw_to_rows(src, out, N, C, h * w, st); }
 
 template <int DK, int DV>
 int attn_launch(const float* qkv, KpixSeq sq, int L, long long nseq, float* const* ax, float* out, int act, hipStream_t st) {

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "axvs_common.h"
+#include "axvs_layout.h"
 #include "axvs_resize.h"
 
 namespace axvs {
@@ -97,16 +98,8 @@ __global__ __launch_bounds__(256) void m2f_to_cl_kernel(const float* __restrict_
 }
 
 // ---- rows ---------------------------------------------------------------------------------------------------------------------------------
-// x[n*Q + q] = query_feat[q], qpos[n*Q + q] = query_embed[q]
-__global__ __launch_bounds__(256) void m2f_init_kernel(const float* __restrict__ query_feat, const float* __restrict__ query_embed,
-                                                       float* __restrict__ x, float* __restrict__ qpos, int Q, int rows) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows * kM2fC) return;
-  const size_t src = (i / kM2fC % Q) * kM2fC + i % kM2fC;
-  x[i] = query_feat[src];
-  qpos[i] = query_embed[src];
-}
-
+// (x[n*Q + q] = query_feat[q], qpos[n*Q + q] = query_embed[q]: one broadcast_rows() launch with two pairs; the class logits:
+//  class_logits_rows(), both axvs_layout.h)
 __device__ __forceinline__ float4 m2f_ln_row(float4 v, const float* __restrict__ g, const float* __restrict__ b, int lane) {
   float s = v.x + v.y + v.z + v.w;
 #pragma unroll
@@ -150,18 +143,6 @@ __global__ __launch_bounds__(256) void m2f_ln_kernel(const float* __restrict__ i
   }
   if (g2) *reinterpret_cast<float4*>(out2 + off) = m2f_ln_row(v, g2, b2, lane);
   if (flags && lane == 0) flags[row] = 0;
-}
-
-// cls[row][k] = y[row] . w[k] + b[k]   (K + 1 classes: any count, so not a tile of the GEMM)
-__global__ __launch_bounds__(256) void m2f_cls_kernel(const float* __restrict__ y, const float* __restrict__ w, const float* __restrict__ b,
-                                                      float* __restrict__ cls, int rows, int K1) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows * K1) return;
-  const float* const yr = y + (i / K1) * kM2fC;
-  const float* const wr = w + (i % K1) * kM2fC;
-  float acc = 0.f;
-  for (int c = 0; c < kM2fC; ++c) acc = fmaf(yr[c], wr[c], acc);
-  cls[i] = acc + b[i % K1];
 }
 
 // ---- mask_embed . features ------------------------------------------------------------------------------------------------------------------

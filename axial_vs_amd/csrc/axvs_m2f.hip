@@ -288,8 +288,7 @@ int axvs_m2f_decoder_fwd(const AxvsM2fCfg* cfg, const void* packed, const float*
   // the sequential chain
   unsigned* bits = debug_bits ? debug_bits : w.bits;
   int* flags = debug_flags ? debug_flags : w.flags;
-  hipLaunchKernelGGL(m2f_init_kernel, dim3((unsigned)(((size_t)R * C + 255) / 256)), dim3(256), 0, st, (const float*)p.query_feat, (const float*)p.query_embed, w.x,
-                     w.qpos, cfg->Q, R);
+  broadcast_rows(p.query_feat, w.x, cfg->Q, R, st, p.query_embed, w.qpos);
   layer_norm(w.x, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, p.post_norm_w, p.post_norm_b, w.y, flags, R, st);
   for (int i = 0; i < nl; ++i) {
     const int l = i % 3, j = i / 3;
@@ -305,8 +304,7 @@ int axvs_m2f_decoder_fwd(const AxvsM2fCfg* cfg, const void* packed, const float*
     bits = nbits, flags = nflags;
   }
   if (cfg->return_predictions) {      // the one full-resolution mask einsum
-    hipLaunchKernelGGL(m2f_cls_kernel, dim3((unsigned)(((size_t)R * cfg->K1 + 255) / 256)), dim3(256), 0, st, (const float*)w.y, (const float*)p.cls_w,
-                       (const float*)p.cls_b, cls_pred, R, cfg->K1);
+    class_logits_rows(w.y, p.cls_w, p.cls_b, cls_pred, R, cfg->K1, st);
     if (int rc = mask_embed(cfg, p, w, w.y, st)) return rc;
     dim3 grid;
     int per_y;
@@ -353,8 +351,7 @@ int axvs_m2f_layer_fwd(const AxvsM2fCfg* cfg, const void* packed, int layer_inde
   hipStream_t st = static_cast<hipStream_t>(stream);
   const M2fW p = m2f_weights(const_cast<void*>(packed), cfg);
   const int R = cfg->N * cfg->Q, l = layer_index % 3, j = layer_index / 3;
-  hipLaunchKernelGGL(m2f_init_kernel, dim3((unsigned)(((size_t)R * C + 255) / 256)), dim3(256), 0, st, (const float*)p.query_feat, (const float*)p.query_embed, w.x,
-                     w.qpos, cfg->Q, R);      // (w.x: scratch here; the layer's input is the caller's x)
+  broadcast_rows(p.query_feat, w.x, cfg->Q, R, st, p.query_embed, w.qpos);      // (w.x: scratch here; the layer's input is the caller's x)
   if (int rc = project_level(cfg, l, memory, p, w, p.wk[l] + (size_t)j * C * C, p.bk[l] + j * C, p.wv[l] + (size_t)j * C * C, p.bv[l] + j * C, 1, st)) return rc;
   if (int rc = layer(cfg, layer_index, p, w, x, w.K[l], w.V[l], C, bits, flags, out, nullptr, nullptr, st)) return rc;
   return last_launch_status();

@@ -139,7 +139,7 @@ int launch_nt128(const float* X, const float* X2, const float* W, float* Y, long
 // NCHW x [N][K][HW] -> token rows `tok` (64 x 64 tiles through LDS), then Y = epilogue(tok . W^T) on the same kernel in ONE launch over all frames
 int nchw_nt128(const float* x, float* tok, const float* W, float* Y, int N, int HW, int K, int Nout, const tr::GemmEpi& e, hipStream_t st,
                int use = kNt128Plain, int zsplit = 1) {
-  hipLaunchKernelGGL(nchw_to_tokens_kernel, dim3((unsigned)((HW + 63) / 64), (unsigned)((K + 63) / 64), N), dim3(256), 0, st, x, tok, K, HW);
+  nchw_to_rows(x, tok, N, K, HW, st);
   return launch_nt128(tok, nullptr, W, Y, (long long)N * HW, Nout, K, e, st, use, 0, zsplit);
 }
 // per-(frame, 64-row block) partial GroupNorm sums of fp32 rows y [N HW][C]: a thread owns 4 channels, 256 / (C / 4) row groups share a block

@@ -668,7 +668,7 @@ int axvs_conv1x1_gn_train_fwd(const float* x, int in_layout, long long in_batch_
   const int nblk = (HW + 63) / 64;
   const float* xt = x;
   if (in_layout == 0) {
-    hipLaunchKernelGGL(gt_nchw_to_tokens_kernel, dim3((unsigned)nblk, (unsigned)((Cin + 63) / 64), (unsigned)N), dim3(256), 0, st, x, b.xt, Cin, HW);
+    nchw_to_rows(x, b.xt, N, Cin, HW, st);
     xt = b.xt;
   } else if (copy_x) {
     const long long t4 = M * Cin / 4;
@@ -689,8 +689,7 @@ int axvs_conv1x1_gn_train_fwd(const float* x, int in_layout, long long in_batch_
   } else {
     hipLaunchKernelGGL(gt_gn_apply_kernel, dim3(blocks((size_t)t4)), dim3(256), 0, st, (const float*)b.y, (const float*)b.stats, p->gn_w, p->gn_b, b.otok, HW, Cout, groups,
                        (long long)HW * Cout, (long long)Cout, t4);
-    hipLaunchKernelGGL(gt_tokens_to_nchw_kernel, dim3((unsigned)nblk, (unsigned)((Cout + 63) / 64), (unsigned)N), dim3(256), 0, st, (const float*)b.otok, out, Cout, HW,
-                       (long long)HW * Cout, (long long)Cout);
+    rows_to_nchw(b.otok, out, N, Cout, HW, st);
   }
   return last_launch_status();
 }
@@ -715,7 +714,7 @@ int axvs_conv1x1_gn_train_bwd(const float* d_out, int out_layout, long long out_
   const float* xt = copy_x ? b.xt : x;
   // d_out -> contiguous token rows (they are overwritten with d_y below)
   if (out_layout == 0) {
-    hipLaunchKernelGGL(gt_nchw_to_tokens_kernel, dim3((unsigned)nblk, (unsigned)((Cout + 63) / 64), (unsigned)N), dim3(256), 0, st, d_out, b.dy, Cout, HW);
+    nchw_to_rows(d_out, b.dy, N, Cout, HW, st);
   } else {
     const long long t4 = M * Cout / 4;
     hipLaunchKernelGGL(gt_gather_tokens_kernel, dim3(blocks((size_t)t4)), dim3(256), 0, st, d_out, b.dy, HW, Cout, out_batch_stride, out_ld, t4);
@@ -736,8 +735,7 @@ int axvs_conv1x1_gn_train_bwd(const float* d_out, int out_layout, long long out_
     // backward of the projection in front of it, whose bias gradient is a sum that cancels analytically (the second GroupNorm removes a constant shift)
     if (int rc = c.dgrad(b.dy, p->conv_w, dxt, M, Cout, Cin, 0.f, 0, true)) return rc;
     if (in_layout == 0) {
-      hipLaunchKernelGGL(gt_tokens_to_nchw_kernel, dim3((unsigned)nblk, (unsigned)((Cin + 63) / 64), (unsigned)N), dim3(256), 0, st, (const float*)dxt, d_x, Cin, HW,
-                         (long long)HW * Cin, (long long)Cin);
+      rows_to_nchw(dxt, d_x, N, Cin, HW, st);
     } else if (copy_x) {      // strided token rows: scatter back through the apply kernel's addressing (identity statistics)
       return fail(AXVS_ERR_ARG, "conv1x1 + GroupNorm backward: an input gradient in strided token rows is not built (pass contiguous rows or NCHW)");
     }
