@@ -76,6 +76,8 @@ CASES = {
     "ffn_wide_does_not": _c("ffn", 1, 1, 256, 16384, 1),
     # frames of 272 keys: the long spatial kernel
     "full_272_keys": _c("full", 1, 2, 256, 17, 16),
+    # frames of 576 keys: three key chunks of the long spatial kernel (256 + 256 + 64)
+    "full_576_keys": _c("full", 1, 2, 256, 24, 24),
     # strided frames: a 16 x 16 level inside a 336-row token buffer
     "in_place_level": _c("axial", 1, 2, 256, 16, 16, sine=True, in_place=336),
     # sine positions materialised (C != 256) / generated in the kernel
@@ -115,6 +117,7 @@ STAGES = {
     "ffn_wide_pays": ['norm1+ffn+norm2'],
     "ffn_wide_does_not": ['norm1+ffn+norm2'],
     "full_272_keys": ['begin', 'qkv_proj', 'spatial_attn', 'temporal_fused', 'norm1+ffn+norm2'],
+    "full_576_keys": ['begin', 'qkv_proj', 'spatial_attn', 'temporal_fused', 'norm1+ffn+norm2'],
     "in_place_level": ['begin', 'h.qkv+traj', 'w.qkv+traj', 'norm1+ffn+norm2'],
     "sine_materialised": ['begin', 'pos3d', 'h.qkv_proj', 'h.spatial_attn', 'h.proj_q', 'h.proj_kv', 'h.temporal_attn', 'h.proj', 'w.qkv_proj', 'w.spatial_attn', 'w.proj_q', 'w.proj_kv', 'w.temporal_attn', 'w.proj', 'norm1', 'ffn.linear1', 'ffn.linear2', 'norm2'],
     "sine_in_kernel": ['begin', 'h.qkv+traj', 'w.qkv+traj', 'norm1+ffn+norm2'],
@@ -135,13 +138,13 @@ STAGES = {
 CC_LAYERS, CC_CLASSES, CC_PIXELS = 1, 11, (1, 5, 7)      # the cross-clip module around the layer: (V, H, W) of the pixel features
 
 
-def _weights(c):
+def _weights(c, seed=SEED):
     if c.kind == "cc":
-        return orc.random_weights(orc.cc_module_param_shapes(CC_LAYERS, CC_CLASSES), SEED)
+        return orc.random_weights(orc.cc_module_param_shapes(CC_LAYERS, CC_CLASSES), seed)
     shapes = orc.axial_layer_param_shapes(c.C, c.F)
     if c.kind == "full":
         shapes = {k.replace("height_attn", "temporal_attn"): v for k, v in shapes.items() if "width_attn" not in k}
-    return orc.random_weights(shapes, SEED)
+    return orc.random_weights(shapes, seed)
 
 
 def _inputs(c):
@@ -174,12 +177,13 @@ def _stage_names():
 _modules = {}
 
 
-def _module(c):
-    """the case's module on the device, built once per (kind, sizes, activation)"""
+def _module(c, weights=None):
+    """the case's module on the device, built once per (kind, sizes, activation); weights: a module of its own with these parameters
+    in place of _weights(c), not kept"""
     import axial_vs_amd as ax
     key = (c.kind, c.C, c.F, c.extras.get("activation", "relu"))
-    if key not in _modules:
-        w = _weights(c)
+    if weights is not None or key not in _modules:
+        w = _weights(c) if weights is None else dict(weights)
         if c.kind == "cc":
             V = CC_PIXELS[0]
             mod = ax.CrossClipTrackingModule(num_layers=CC_LAYERS, num_classes=CC_CLASSES, attn_drop=0.0, aspp_drop=0.0, kernel_sizes=[3, 3, 3],
@@ -192,17 +196,20 @@ def _module(c):
         else:
             mod = ax.TemporalAxialTrajectoryAttentionLayer(c.C, c.F, n_heads=8, activation=key[3])
         mod.load_state_dict(w, strict=True)
+        if weights is not None:
+            return mod.eval().cuda()
         _modules[key] = mod.eval().cuda()
     return _modules[key]
 
 
-def run(name):
-    """One eval forward of the case on the device -> ({label: tensor}, stage names).  "out" is what `reference` answers for."""
+def run(name, weights=None):
+    """One eval forward of the case on the device -> ({label: tensor}, stage names).  "out" is what `reference` answers for.
+    weights: the parameters to load in place of _weights(c) (tests/infer_regime_cases.py)."""
     import axial_vs_amd as ax
     from axial_vs_amd import _lib
     c = CASES[name]
     L = _lib.lib()
-    mod = _module(c)
+    mod = _module(c, weights)
     ins = [x.cuda() for x in _inputs(c)]
     for k, v in c.options:
         _lib.check(L.axvs_set_option(k.encode(), v), "axvs_set_option")
