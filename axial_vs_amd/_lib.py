@@ -252,6 +252,7 @@ SIGNATURES = {
     "axvs_profile_stage_count": (C.c_int, []),
     "axvs_profile_stage_name": (C.c_char_p, [C.c_int]),
     "axvs_set_option": (C.c_int, [C.c_char_p, C.c_int]),
+    "axvs_plan_regular_tiles": (C.c_int, []),
     "axvs_traj_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "axvs_traj_pack": (C.c_int, [C.POINTER(AxvsTrajParams), _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "axvs_axial_layer_packed_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

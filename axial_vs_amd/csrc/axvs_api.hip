@@ -33,6 +33,7 @@ thread_local int g_ffn_split_pairs = 1;  // option "plan_force" bit 8 clears it:
 thread_local int g_spatial_only = 0;     // option "spatial_only": 1 = the fused trajectory kernels return after QK^T / softmax / AV (timing only; outputs unwritten);
                                          // 2 = the merged q/k/v + trajectory kernels return after their q/k/v part (the two-launch kernels treat it as 1)
 thread_local int g_no_ffn_fusion = 0;    // option "no_ffn_fusion": keep the FFN in its own kernel
+thread_local int g_no_reg_tiles = 0;     // option "plan_force" bit 128: never the regular-tile instantiation of the merged trajectory kernels (TrajPlan::reg)
 thread_local int g_no_reassoc = 0;       // option "plan_force" bit 64: generic tier computes k2, v2 = proj_kv(x) for every frame slot (the reference's form)
 thread_local int g_ffn_gelu = 0;         // option "ffn_gelu": the layer's FFN activation is exact GELU (F.gelu) instead of ReLU -- set by the
                                          // host module around its calls for activation="gelu" (WC/temporal_attention.py:9-17): the FFN then runs on the
@@ -211,6 +212,9 @@ TrajPlan plan_traj(int S, int T, int L, int C, int heads, bool want_attn, bool s
   const bool merge = p.tier == TrajPlan::kFused && may_merge && !g_no_merge_qkv && g_sync != nullptr && (size_t)S <= g_sync_words &&
                      (T <= 4 || p.rows == 32) && p.nks <= (p.rows == 16 ? 4 : 3) && 2 * (long long)heads * 32 * Mp * 2 < (1ll << 32) && fits();
   p.mq = !merge ? 0 : own_frame ? 2 : 1;
+  // Regular tiles: the frames are not padded (L is a multiple of 16, so the RowMap's Lv stays 0), every sequence is T whole 64-row tiles (mq = 2),
+  // the row-addressed tensors stay below 4 GiB (the write-through rows' 32-bit byte offsets) and the rows leave as fp32.
+  p.reg = p.mq == 2 && p.L == L && !g_no_reg_tiles && (g_row_span ? g_row_span : Mp) * 256 * 4 < (1ll << 32) && !(p.with_ffn && g_out_dtype);
   return p;
 }
 namespace {
@@ -331,7 +335,7 @@ int launch_temporal(const TrajPlan& pl, int nks, const TrajWs& w, const TrajPack
                     int T, float scale, hipStream_t st, const FfnArgs* fa = nullptr, const OwnQkv* oq = nullptr) {
   // output rows are addressed through the RowMap: the largest byte offset is that of the natural [rows, 256] fp32 tensor
   const int wt = ((g_row_span ? g_row_span : Mp) * 256 * 4 < (1ll << 32) ? 1 : 0) | (g_spatial_only && nks > 0 ? (oq ? g_spatial_only : 1) << 1 : 0) |
-                 (fa != nullptr && g_out_dtype ? (g_out_dtype == 1 ? kOutF16 : kOutBf16) : 0);
+                 (fa != nullptr && g_out_dtype ? (g_out_dtype == 1 ? kOutF16 : kOutBf16) : 0) | (pl.reg && oq ? kTrajReg : 0);
   if (oq && !(nks > 0 && T <= 8)) return fail(AXVS_ERR_ARG, "internal: own q,k,v need the in-kernel spatial half and T <= 8");
   return by_int<12>(T, [&](auto t) {
     constexpr int kT = decltype(t)::value;
@@ -375,6 +379,8 @@ int run_traj(const TrajPlan& pl, const float* qsrc, const float* ksrc, const flo
   const FfnArgs* const fa = pl.with_ffn ? ffn : nullptr;
   float* const dst = pl.with_ffn ? ffn_out : out;
   const PosGen pg = posgen ? *posgen : PosGen{};
+  // (a height pass or a stand-alone trajectory attention starts the record afresh; a width pass adds its bit)
+  g_reg_passes = pass == 2 ? (g_reg_passes & 1) | (pl.mq && pl.reg ? 2 : 0) : (pl.mq && pl.reg ? 1 : 0);
   if (pl.mq) {      // one launch per pass: the trajectory kernel computes q, k, v of its own rows
     const OwnQkv oq{qsrc, qk_add, pg, p.wq, p.wk, p.wv, p.bq, p.bk, p.bv, qscale, g_sync, g_status, g_sync_spin_limit};
     if (int rc = launch_temporal<BF>(pl, pl.nks, w, p, res, dst, rm, Mp, N, T, scale, st, fa, &oq)) return rc;
@@ -514,10 +520,14 @@ int run_ffn(const FfnPlan& pl, float* X, float* out, const LayerPacked& p, long 
     }
     case FfnPlan::kFused: {
       const int rc = by_gelu(pl.gelu, [&](auto g) {
-        const auto kern = &ffn_fused_kernel<BF, decltype(g)::value>;
-        if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), ffn_lds_bytes(F), st, X, p.w1, p.b1, p.w2, p.b2, p.g1, p.be1, p.g2, p.be2, out, M, F, rs, pl.oflags);
-        return (int)AXVS_OK;
+        const auto launch = [&](auto of) {      // the output form is a template argument: the plan's, nothing decided here
+          const auto kern = &ffn_fused_kernel<BF, decltype(g)::value, decltype(of)::value>;
+          if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
+          hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), ffn_lds_bytes(F), st, X, p.w1, p.b1, p.w2, p.b2, p.g1, p.be1, p.g2, p.be2, out, M, F, rs);
+          return (int)AXVS_OK;
+        };
+        return pl.oflags == kOutF16 ? launch(std::integral_constant<int, kOutF16>{})
+               : pl.oflags == kOutBf16 ? launch(std::integral_constant<int, kOutBf16>{}) : launch(std::integral_constant<int, 0>{});
       });
       if (rc != AXVS_OK) return rc;
       break;
@@ -720,6 +730,7 @@ int axvs_profile_stages(void** events, int capacity) {
   g_prof_cap = events ? capacity : 0;
   return kMaxStages;
 }
+int axvs_plan_regular_tiles(void) { return g_reg_passes; }
 int axvs_profile_stage_count(void) { return g_prof_next < kMaxStages ? g_prof_next : kMaxStages; }
 const char* axvs_profile_stage_name(int i) { return (i >= 0 && i < kMaxStages && g_stage_names[i]) ? g_stage_names[i] : ""; }
 
@@ -734,7 +745,7 @@ int axvs_debug_read_stamps(unsigned long long* host, int n) {
 // merge_qkv_any, spatial_only, train_valu, train_exact.  Test hooks: sync_spin_limit, and plan_force -- ONE diagnostic bit mask that forces the planner's
 // size-dependent choices for the bit-identity tests (forms that are bit-identical by construction, so the row count may decide):
 //   1 never the 16-row trajectory tiles | 2 / 4 the 128-row FFN tiles always / never | 8 no two-chunk FFN workgroups | 16 / 32 merged launch on 16-row tiles
-//   never / at any size | 64 generic tier without the reassociated temporal half.
+//   never / at any size | 64 generic tier without the reassociated temporal half | 128 never the regular-tile instantiation of the merged kernels.
 // (Rounds 2 - 5 exposed 37 keys, most of them thresholds and forms measured slower; those are constants / gone since round 6: DESIGN.md.)
 int axvs_set_option(const char* key, int value) {
   if (!key) return fail(AXVS_ERR_ARG, "null option key");
@@ -766,6 +777,7 @@ int axvs_set_option(const char* key, int value) {
     g_ffn_split_pairs = (value & 8) ? 0 : 1;
     g_merge_small = (value & 16) ? 0 : (value & 32) ? 1 : kMergeSmall;
     g_no_reassoc = (value & 64) ? 1 : 0;
+    g_no_reg_tiles = (value & 128) ? 1 : 0;
     return AXVS_OK;
   }
   return fail(AXVS_ERR_ARG, "unknown option");

@@ -222,14 +222,21 @@ struct PosGenLane {
     }
   }
   // v_sin_f32 / v_cos_f32 take revolutions and need a bounded argument: reduce with v_fract_f32 first
-  __device__ __forceinline__ float4 eval(const PosGen& pg, int packed) const {
-    const float z = (float)((packed & 255) + 1) * pg.zs;
+  // the frame (z) term of frame t: the same for every token of that frame, so a loader whose rows share a frame evaluates it once
+  struct ZTerm { float s0, c0, s1, c1; };
+  __device__ __forceinline__ ZTerm zterm(const PosGen& pg, int t) const {
+    const float z = (float)(t + 1) * pg.zs;
+    const float b0 = __builtin_amdgcn_fractf(z * g0), b1 = __builtin_amdgcn_fractf(z * g1);
+    return ZTerm{__builtin_amdgcn_sinf(b0), __builtin_amdgcn_cosf(b0), __builtin_amdgcn_sinf(b1), __builtin_amdgcn_cosf(b1)};
+  }
+  // the y / x term of a token plus a given frame term plus the level embedding, added in that order
+  __device__ __forceinline__ float4 eval_yx(const PosGen& pg, int packed, const ZTerm& zt) const {
     const float u = xside ? (float)(((packed >> 20) & 4095) + 1) * pg.xs : (float)(((packed >> 8) & 4095) + 1) * pg.ys;
     const float a0 = __builtin_amdgcn_fractf(u * f0), a1 = __builtin_amdgcn_fractf(u * f1);
-    const float b0 = __builtin_amdgcn_fractf(z * g0), b1 = __builtin_amdgcn_fractf(z * g1);
-    return float4{__builtin_amdgcn_sinf(a0) + __builtin_amdgcn_sinf(b0) + lv[0], __builtin_amdgcn_cosf(a0) + __builtin_amdgcn_cosf(b0) + lv[1],
-                  __builtin_amdgcn_sinf(a1) + __builtin_amdgcn_sinf(b1) + lv[2], __builtin_amdgcn_cosf(a1) + __builtin_amdgcn_cosf(b1) + lv[3]};
+    return float4{__builtin_amdgcn_sinf(a0) + zt.s0 + lv[0], __builtin_amdgcn_cosf(a0) + zt.c0 + lv[1],
+                  __builtin_amdgcn_sinf(a1) + zt.s1 + lv[2], __builtin_amdgcn_cosf(a1) + zt.c1 + lv[3]};
   }
+  __device__ __forceinline__ float4 eval(const PosGen& pg, int packed) const { return eval_yx(pg, packed, zterm(pg, packed & 255)); }
 };
 
 // Blocked 16-bit matrix [K/32][R][32]: element (row r, col k).

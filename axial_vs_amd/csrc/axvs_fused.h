@@ -150,6 +150,90 @@ __device__ __forceinline__ void load_wfrags(u16x8 (&wf)[NT][KB], const u16* __re
 // flag bits of the `wt` argument of ffn_body / the kernels that carry it: bit 0 = write-through (sc1) output rows; bits 4, 5 = the
 // output rows are 16-bit (f16 / bf16) instead of fp32 (`out` then points at a [rows][256] 16-bit map)
 constexpr int kOutF16 = 16, kOutBf16 = 32, kOut16Mask = kOutF16 | kOutBf16;
+// host side only (launch_temporal_n's `flags`): bit 3 = the plan's regular-tile instantiation (TrajPlan::reg; temporal_fused_kernel<..., REG>)
+constexpr int kTrajReg = 8;
+
+// ---- row tails: the output form as a compile-time constant, the wave's rows as independent instruction streams ----
+// OF = the form bits of `wt` (bit 0 | kOutF16 | kOutBf16) as a template argument.  A kernel whose form is known when it is launched
+// carries it as a template parameter; the shape-generic instantiations (kFormRt) pick it ONCE per tail from the runtime word
+// (by_out_form), never per row: the rows of a tail are straight-line code either way.
+constexpr int kFormBits = 1 | kOut16Mask;
+constexpr int kFormRt = -1;                      // "decided at run time, once per tail"
+template <int OF>
+__device__ __forceinline__ void store_row(float* __restrict__ out, long long off /* elements, this lane's 4 channels */, float4 y) {
+  static_assert(OF >= 0 && (OF & ~kFormBits) == 0, "a compile-time output form");
+  if constexpr ((OF & kOut16Mask) != 0) {        // the layer's output map in 16 bits (option "layer_out_dtype"): rows of 512 B, written here instead of by a cast pass
+    const u16x4 h = cvt4<(OF & kOutBf16) != 0>(f32x4{y.x, y.y, y.z, y.w});
+    u16* o16 = reinterpret_cast<u16*>(out);
+    if constexpr ((OF & 1) != 0) WtBuf(o16).store8((unsigned)(off * 2), h);
+    else *reinterpret_cast<u16x4*>(o16 + off) = h;
+  } else if constexpr ((OF & 1) != 0) {
+    WtBuf(out).store16((unsigned)(off * 4), y);  // the next kernel reads these rows from other XCDs
+  } else {
+    *reinterpret_cast<float4*>(out + off) = y;
+  }
+}
+// f(std::integral_constant<int, form>{}) for the form bits of a runtime `wt`; OF >= 0: that form, no test at all
+template <int OF, class F>
+__device__ __forceinline__ void by_out_form(int wt, F&& f) {
+  if constexpr (OF >= 0) {
+    f(std::integral_constant<int, OF>{});
+  } else {
+    switch (wt & kFormBits) {
+      case 0: f(std::integral_constant<int, 0>{}); break;
+      case 1: f(std::integral_constant<int, 1>{}); break;
+      case kOutF16: f(std::integral_constant<int, kOutF16>{}); break;
+      case kOutF16 | 1: f(std::integral_constant<int, kOutF16 | 1>{}); break;
+      default:                                   // (bf16 wins where both 16-bit bits are set, as the per-row test had it)
+        if (wt & 1) f(std::integral_constant<int, kOutBf16 | 1>{});
+        else f(std::integral_constant<int, kOutBf16>{});
+    }
+  }
+}
+// wave_sum of R rows, stepped together: every row runs wave_sum's butterfly in wave_sum's order (same bits), and the R dependency
+// chains overlap instead of following each other
+template <int R>
+__device__ __forceinline__ void wave_sum_rows(float (&s)[R]) {
+#pragma unroll
+  for (int i = 0; i < R; ++i) s[i] += lane_xor1(s[i]);
+#pragma unroll
+  for (int i = 0; i < R; ++i) s[i] += lane_xor2(s[i]);
+#pragma unroll
+  for (int i = 0; i < R; ++i) s[i] += lane_hmirror(s[i]);
+#pragma unroll
+  for (int i = 0; i < R; ++i) s[i] += lane_mirror(s[i]);
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(s[i]), __float_as_uint(s[i]), false, false);
+    s[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  }
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(s[i]), __float_as_uint(s[i]), false, false);
+    s[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  }
+}
+// LayerNorm statistics (eps 1e-5) of R whole rows of 256 channels, float4 column `lane` of each in v: v <- v - mean, rstd <- 1 / std.
+// Per row exactly the operations of the one-row form: wave_sum(x + y + z + w) / 256, then wave_sum of the squared differences.
+template <int R>
+__device__ __forceinline__ void ln_stats_rows(float4 (&v)[R], float (&rstd)[R]) {
+  float s[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) s[i] = v[i].x + v[i].y + v[i].z + v[i].w;
+  wave_sum_rows<R>(s);
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const float mu = s[i] * (1.f / 256);
+    v[i] = float4{v[i].x - mu, v[i].y - mu, v[i].z - mu, v[i].w - mu};
+    s[i] = v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
+  }
+  wave_sum_rows<R>(s);
+#pragma unroll
+  for (int i = 0; i < R; ++i) rstd[i] = rsqrtf(s[i] * (1.f / 256) + 1e-5f);
+}
+__device__ __forceinline__ float4 ln_apply(float4 d, float rstd, float4 g, float4 b) {
+  return float4{d.x * rstd * g.x + b.x, d.y * rstd * g.y + b.y, d.z * rstd * g.z + b.z, d.w * rstd * g.w + b.w};
+}
 
 struct FfnLds {
   float* xtile;   // [64][kEpiLd] fp32
@@ -189,8 +273,10 @@ __device__ __forceinline__ void ffn_stage_params(const FfnLds& l, const float* _
 // PRE / `pre`: the wave's 8 input rows (row 8 wave + rr, float4 column `lane`) handed over in registers -- the caller then
 // has NOT written them to xtile, and norm1 below skips reading them back (the fused width-pass kernel: its residual epilogue and
 // this norm1 walk the same rows; one LDS round trip per row less).
+// OF: the output form (store_row) as a constant, or kFormRt: picked once, ahead of the output rows, from the form bits of `wt`.
+// ALL: every row of the tile exists (`row_off(r) >= 0` for all r) -- no test per row.
 struct NoRows { float4 v[8]; };
-template <bool BF, class RowOff, bool GELU = false, bool PRE = false>
+template <bool BF, class RowOff, bool GELU = false, bool PRE = false, int OF = kFormRt, bool ALL = false>
 __device__ __forceinline__ void ffn_body(const FfnLds& l, u16x8 (&w1f)[2][8], const u16* __restrict__ W1, const u16* __restrict__ W2,
                                          float* __restrict__ out, RowOff row_off, int F, int rot, int crot, int tid, int wt = 0,
                                          const NoRows& pre = NoRows{}) {
@@ -207,19 +293,22 @@ __device__ __forceinline__ void ffn_body(const FfnLds& l, u16x8 (&w1f)[2][8], co
   // ---- norm1, row-wise: y (fp32) back into xtile, y (16-bit) into ytile ----
   {
     const float4 gg = *reinterpret_cast<const float4*>(sg1 + lane * 4), bb = *reinterpret_cast<const float4*>(sbe1 + lane * 4);
+    // the wave's 8 rows as independent streams: all reads, the two reductions of all rows stepped together, then the stores
+    float4 v[8];
+    float rstd[8];
+#pragma unroll
+    for (int rr = 0; rr < 8; ++rr) {
+      if constexpr (PRE) v[rr] = pre.v[rr];
+      else v[rr] = *reinterpret_cast<const float4*>(l.xtile + (wave * 8 + rr) * kEpiLd + lane * 4);
+    }
+    ln_stats_rows<8>(v, rstd);
 #pragma unroll
     for (int rr = 0; rr < 8; ++rr) {
       const int r = wave * 8 + rr;
-      float4 v;
-      if constexpr (PRE) v = pre.v[rr];
-      else v = *reinterpret_cast<const float4*>(l.xtile + r * kEpiLd + lane * 4);
-      const float mu = wave_sum(v.x + v.y + v.z + v.w) * (1.f / C);
-      const float a = v.x - mu, b = v.y - mu, c = v.z - mu, d = v.w - mu;
-      const float rstd = rsqrtf(wave_sum(a * a + b * b + c * c + d * d) * (1.f / C) + 1e-5f);
-      const f32x4 y = {a * rstd * gg.x + bb.x, b * rstd * gg.y + bb.y, c * rstd * gg.z + bb.z, d * rstd * gg.w + bb.w};
-      *reinterpret_cast<float4*>(l.xtile + r * kEpiLd + lane * 4) = float4{y[0], y[1], y[2], y[3]};
-      act_store4<BF>(l.ytile, lane * 4, r, y);
-      if (rr == 3) lds_fence();
+      const float4 y = ln_apply(v[rr], rstd[rr], gg, bb);
+      *reinterpret_cast<float4*>(l.xtile + r * kEpiLd + lane * 4) = y;
+      act_store4<BF>(l.ytile, lane * 4, r, f32x4{y.x, y.y, y.z, y.w});
+      if (rr == 3) lds_fence();      // 8 LDS writes in flight at the most
     }
   }
   FSTAMP(1);
@@ -334,27 +423,19 @@ __device__ __forceinline__ void ffn_body(const FfnLds& l, u16x8 (&w1f)[2][8], co
   FSTAMP(11);
   {
     const float4 g2v = *reinterpret_cast<const float4*>(sg2 + lane * 4), be2v = *reinterpret_cast<const float4*>(sbe2 + lane * 4);
+    // the wave's 8 rows as independent streams: all LDS reads, the two reductions of all rows stepped together, the stores last
+    float4 v[8];
+    float rstd[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int r = wave * 8 + i;
-      const float4 v = *reinterpret_cast<const float4*>(l.xtile + r * kEpiLd + lane * 4);
-      const float mu = wave_sum(v.x + v.y + v.z + v.w) * (1.f / C);
-      const float d0 = v.x - mu, d1 = v.y - mu, d2 = v.z - mu, d3 = v.w - mu;
-      const float rstd = rsqrtf(wave_sum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.f / C) + 1e-5f);
-      const long long off = row_off(r);
-      if (off >= 0) {
-        const float4 y = float4{d0 * rstd * g2v.x + be2v.x, d1 * rstd * g2v.y + be2v.y, d2 * rstd * g2v.z + be2v.z, d3 * rstd * g2v.w + be2v.w};
-        if (wt & kOut16Mask) {      // the layer's output map in 16 bits (option "layer_out_dtype"): rows of 512 B, written here instead of by a cast pass
-          const f32x4 yv = {y.x, y.y, y.z, y.w};
-          const u16x4 h = (wt & kOutBf16) ? cvt4<true>(yv) : cvt4<false>(yv);
-          u16* o16 = reinterpret_cast<u16*>(out);
-          if (wt & 1) WtBuf(o16).store8((unsigned)((off + lane * 4) * 2), h);
-          else *reinterpret_cast<u16x4*>(o16 + off + lane * 4) = h;
-        } else if (wt & 1) WtBuf(out).store16((unsigned)((off + lane * 4) * 4), y);       // the next kernel reads these rows from other XCDs
-        else *reinterpret_cast<float4*>(out + off + lane * 4) = y;
+    for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const float4*>(l.xtile + (wave * 8 + i) * kEpiLd + lane * 4);
+    ln_stats_rows<8>(v, rstd);
+    by_out_form<OF>(wt, [&](auto form) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const long long off = row_off(wave * 8 + i);
+        if (ALL || off >= 0) store_row<decltype(form)::value>(out, off + lane * 4, ln_apply(v[i], rstd[i], g2v, be2v));
       }
-      if (i == 3) lds_fence();
-    }
+    });
   }
   FSTAMP(12);
   FSTAMP_FLUSH(16);
@@ -374,14 +455,15 @@ __device__ __forceinline__ void ffn_body(const FfnLds& l, u16x8 (&w1f)[2][8], co
 #endif
 }
 
-// stand-alone kernel: X fp32 [M][256] rows in, out rows out
-template <bool BF, bool GELU = false>
+// stand-alone kernel: X fp32 [M][256] rows in, out rows out.  OF: the output form (0 / kOutF16 / kOutBf16; plain stores), picked by the
+// host from FfnPlan::oflags
+template <bool BF, bool GELU = false, int OF = 0>
 __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict__ X, const u16* __restrict__ W1,
                                                         const float* __restrict__ b1, const u16* __restrict__ W2,
                                                         const float* __restrict__ b2, const float* __restrict__ g1,
                                                         const float* __restrict__ be1, const float* __restrict__ g2,
                                                         const float* __restrict__ be2, float* __restrict__ out,
-                                                        long long M, int F, RowStride rs, int oflags = 0 /* kOutF16 / kOutBf16 */) {
+                                                        long long M, int F, RowStride rs) {
   constexpr int C = 256, KB = 8;
   extern __shared__ __attribute__((aligned(16))) char smem_c[];
   FfnLds l;
@@ -414,7 +496,7 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
   }
   __syncthreads();                       // parameters staged
   auto row_off = [=](int r) { return m0 + r < M ? rs.row(m0 + r) * C : -1ll; };
-  ffn_body<BF, decltype(row_off), GELU>(l, w1f, W1, W2, out, row_off, F, rot, crot, tid, oflags);
+  ffn_body<BF, decltype(row_off), GELU, false, OF>(l, w1f, W1, W2, out, row_off, F, rot, crot, tid);
 }
 
 constexpr size_t kFfnTiles = (size_t)kRows * kEpiLd * sizeof(float) + 2 * 8 * kTileElems * sizeof(u16);   // x | y | h
@@ -521,7 +603,12 @@ __device__ __forceinline__ void sweep8(f32x4 (&acc)[2][MT], u16x8 (&wf)[2][8], c
 //     independent, so the result does not depend on the order).
 // (Rounds 3 - 5 also carried a row-form-V variant, a variant that emitted the next pass's q/k/v from the epilogue, and a persistent team grid for
 //  merged launches beyond two rounds of the chip: all three bit-identical and measured slower -- DESIGN.md, profiles/r5_persistent_merged.txt -- removed in round 6.)
-template <bool BF, int T, int MT, int NKS = 0, bool FFN = false, int MQ = 0>
+// REG ("regular tiles", MQ == 2 only; the planner's TrajPlan::reg): every sequence is T whole, unpadded 64-key frames (N = 64 T, Lv = 0) and
+//     every row offset fits 32 bits, so a tile is frame `tile % T` of sequence `tile / T` and all of its rows exist: the nvalid / Lr
+//     clamps, the row_exists mask, the ragged key mask and the three divisions per row of the RowMap are compiled out (a row's offset
+//     is the tile's plus l * sL, in scalar registers), output rows are fp32 write-through without a test, and the frame term of a
+//     generated sine position is evaluated once per wave.  Same operations per output element as the generic instantiation.
+template <bool BF, int T, int MT, int NKS = 0, bool FFN = false, int MQ = 0, bool REG = false>
 __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restrict__ X16 /* [8][T][Mp][32] */,
                                                              const u16* __restrict__ Wpq_a, const float* __restrict__ bpq,
                                                              const u16* __restrict__ Wpkv_a, const float* __restrict__ bpkv,
@@ -539,6 +626,7 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
   static_assert(!FFN || MT == 4, "the FFN half works on 64-row tiles");
   static_assert(MQ == 0 || ((MT == 4 || MT == 2 || MT == 1) && NKS > 0), "own q/k/v: 64-, 32- or 16-row tiles");
   static_assert(MQ != 2 || (MT == 4 && NKS == 2 && T >= 2), "own frame first: a 64-row tile is one 64-key frame");
+  static_assert(!REG || MQ == 2, "regular tiles: a 64-row tile is one whole frame");
   constexpr int C = 256, ROWS = MT * 16;
   extern __shared__ __attribute__((aligned(16))) u16 smem[];
   u16* xt = smem;                                              // [T][8][ROWS][32]; later re-used as the o tile [8][ROWS][32]
@@ -559,7 +647,7 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
   // clamped copies that are computed and never stored.  Without it (x staged from HBM) tiles are plain ROWS-row slices.
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fi = lane & 15, fg = lane >> 4;
-  const int N = N_a, L = L_a;
+  const int N = REG ? T * 64 : N_a, L = REG ? 64 : L_a;      // (REG: constants -- every division by them below is a shift / a multiply)
   const u16* const Wpq = Wpq_a;
   const u16* const Wpkv = Wpkv_a;
   const u16* const Wp = Wp_a;
@@ -569,6 +657,8 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
   long long tile = blockIdx.x;
   long long m0;                                                 // first sequence-order row of the tile
   int nvalid;                                                   // rows of the tile that exist
+  [[maybe_unused]] int rg_f = 0, rg_o = 0;                      // REG: my frame, the off-axis coordinate of my sequence ...
+  [[maybe_unused]] long long rg_row0 = 0;                       // ... and the natural row of my tile's row 0 (wave-uniform: scalar registers)
   if constexpr (NKS > 0) {
     const int tps = (N + ROWS - 1) / ROWS;                      // tiles per sequence
     if (gridDim.x % (8 * tps) == 0) {
@@ -578,14 +668,20 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
     const long long sq = tile / tps;
     const int n0 = (int)(tile - sq * tps) * ROWS;
     m0 = sq * N + n0;
-    nvalid = min(ROWS, N - n0);
+    nvalid = REG ? ROWS : min(ROWS, N - n0);
+    if constexpr (REG) {
+      const int s = (int)sq, b = s / rm.Loff;
+      rg_f = n0 / ROWS;
+      rg_o = s - b * rm.Loff;
+      rg_row0 = b * rm.sB + rg_f * rm.sT + rg_o * rm.sO;
+    }
   } else {
     m0 = tile * ROWS;
     nvalid = (int)min((long long)ROWS, Mp - m0);
   }
 
   // padded frames (RowMap): L is the frame length of the row space (a multiple of 16), Lr the number of keys / rows that exist
-  [[maybe_unused]] const int Lr = rm.Lv ? rm.Lv : L;
+  [[maybe_unused]] const int Lr = REG ? L : rm.Lv ? rm.Lv : L;
   AXVS_STAMP_DECL;
   AXVS_WG_BEGIN;
   AXVS_STAMP(0);
@@ -670,16 +766,32 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
         // wave + 8k; rows past the sequence's end are clamped copies), v_readlane broadcasts
         constexpr int RPWq = ROWS / 8;               // rows per wave: 8 (64-row tiles) or 2 (16-row tiles)
         constexpr int GRPq = RPWq >= 4 ? 4 : RPWq;   // rows of a wave in flight together
-        int off_lo, off_hi, coords = 0;
-        {
+        [[maybe_unused]] int off_lo = 0, off_hi = 0, coords = 0;
+        if constexpr (!REG) {
           const int myrow = wave + 8 * (lane & (RPWq - 1));
           const int mym = (int)m0 + min(myrow, nvalid - 1);
           const long long myoff = (oq.pg.mode ? nat_row_coords(rm, mym, oq.pg.l_is_h, &coords) : nat_row(rm, mym)) * C;
           off_lo = (int)(myoff & 0xffffffffll);
           off_hi = (int)(myoff >> 32);
         }
+        // k-th row of this wave (row wave + 8 k): element offset of its lane's 4 channels, packed grid coordinates
+        [[maybe_unused]] const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+        auto row_src = [&](int k, long long& off, int& co) {
+          if constexpr (REG) {
+            const int l = wave_u + 8 * k;
+            off = (rg_row0 + l * rm.sL) * C + lane * 4;
+            co = rg_f | ((oq.pg.l_is_h ? l : rg_o) << 8) | ((oq.pg.l_is_h ? rg_o : l) << 20);
+          } else {
+            off = (((long long)__builtin_amdgcn_readlane(off_hi, k) << 32) | (unsigned)__builtin_amdgcn_readlane(off_lo, k)) + lane * 4;
+            co = __builtin_amdgcn_readlane(coords, k);
+          }
+        };
         PosGenLane pl;
-        if (oq.pg.mode) pl.init(oq.pg, lane * 4);
+        [[maybe_unused]] PosGenLane::ZTerm zt{};
+        if (oq.pg.mode) {
+          pl.init(oq.pg, lane * 4);
+          if constexpr (REG) zt = pl.zterm(oq.pg, rg_f);      // a tile lies in one frame: the frame term of all 8 rows, once
+        }
         float amax = 0.f;
 #pragma unroll
         for (int half = 0; half < RPWq / GRPq; ++half) {
@@ -687,9 +799,11 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
 #pragma unroll
           for (int i = 0; i < GRPq; ++i) {
             const int k = half * GRPq + i;
-            const long long off = (((long long)__builtin_amdgcn_readlane(off_hi, k) << 32) | (unsigned)__builtin_amdgcn_readlane(off_lo, k)) + lane * 4;
+            long long off;
+            int co;
+            row_src(k, off, co);
             a[i] = *reinterpret_cast<const float4*>(oq.src + off);
-            if (oq.pg.mode) p[i] = pl.eval(oq.pg, __builtin_amdgcn_readlane(coords, k));      // sine embedding generated, not read
+            if (oq.pg.mode) p[i] = REG ? pl.eval_yx(oq.pg, co, zt) : pl.eval(oq.pg, co);      // sine embedding generated, not read
             else p[i] = oq.pos ? *reinterpret_cast<const float4*>(oq.pos + off) : float4{0.f, 0.f, 0.f, 0.f};
           }
           if (half == 0) request_params();   // behind the first group of row requests (-0.45 us on the width-pass kernel, A/B)
@@ -851,7 +965,7 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
 #pragma unroll
     for (int qt = 0; qt < MT; ++qt) qf[qt] = *reinterpret_cast<const u16x8*>(Qh + (m0 + min(qt * 16 + fi, nvalid - 1)) * 32 + fg * 8);
     }
-    const bool ragged = Lr != NKS * 32;
+    const bool ragged = !REG && Lr != NKS * 32;
     u16x8 ones;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = H16<BF>::from_f32(1.f);
@@ -1076,7 +1190,7 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       const int row = mt * 16 + fi;
-      const int fown = __builtin_amdgcn_ds_bpermute(row * 4, fown_l);
+      const int fown = REG ? rg_f : __builtin_amdgcn_ds_bpermute(row * 4, fown_l);      // (REG: the tile's one frame)
       bown[mt] = xt_off<MT>(fown, 0, row, fg);
       bfr[mt] = xt_off<MT>(0, 0, row, fg);
     }
@@ -1267,7 +1381,15 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
   // v_readlane -- instead of RPW unrolled copies of the same ~75-instruction sequence
   [[maybe_unused]] int roff_lo = 0, roff_hi = 0;    // element offset of row (lane % RPW) of this wave, as two words (re-read with v_readlane)
   unsigned rok;                                     // bit i: row i of this wave exists (inside its sequence, not a padding row of its frame) -> stored
-  {
+  if constexpr (REG) {                              // every row exists; row l of the tile is l * sL rows behind the tile's first
+    rok = (1u << RPW) - 1u;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+      roff[i] = (rg_row0 + (wave_u * RPW + i) * rm.sL) * C + lane * 4;
+      rres[i] = *reinterpret_cast<const float4*>(res + roff[i]);
+    }
+  } else {
     const int myrow = wave * RPW + (lane % RPW);
     const int mym = (int)m0 + min(myrow, nvalid - 1);
     rok = (unsigned)__builtin_amdgcn_ballot_w64(myrow < nvalid && row_exists(rm, mym)) & ((1u << RPW) - 1u);
@@ -1299,31 +1421,41 @@ __global__ __launch_bounds__(512) void temporal_fused_kernel(const u16* __restri
   }
   __syncthreads();
   [[maybe_unused]] NoRows yrows;                   // FFN: the wave's rows after the residual
+  // the wave's rows as independent streams: all LDS reads first; the post-norm (where the layer has one) and the output form are
+  // picked once, ahead of the rows, and the stores come last
+  constexpr int TOF = REG ? 1 : kFormRt;           // REG: fp32 rows, write-through (what the planner admits it for)
+  {
+    float4 y[RPW];
 #pragma unroll
-  for (int i = 0; i < RPW; ++i) {
-    const int row = wave * RPW + i;
-    const float4 v = *reinterpret_cast<const float4*>(etile + row * kEpiLd + lane * 4);
-    float4 y = float4{v.x + rres[i].x, v.y + rres[i].y, v.z + rres[i].z, v.w + rres[i].w};
-    if constexpr (!FFN) {
-      if (ln_g) {      // post-norm layer (cross-clip TrajectoryAttentionLayer.forward_post, CC/...:156-161): LayerNorm(x + attn(x)), eps 1e-5
-        const float mu = wave_sum(y.x + y.y + y.z + y.w) * (1.f / C);
-        const float d0 = y.x - mu, d1 = y.y - mu, d2 = y.z - mu, d3 = y.w - mu;
-        const float rstd = rsqrtf(wave_sum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.f / C) + 1e-5f);
-        const float4 g = *reinterpret_cast<const float4*>(ln_g + lane * 4), b = *reinterpret_cast<const float4*>(ln_b + lane * 4);
-        y = float4{d0 * rstd * g.x + b.x, d1 * rstd * g.y + b.y, d2 * rstd * g.z + b.z, d3 * rstd * g.w + b.w};
-      }
+    for (int i = 0; i < RPW; ++i) {
+      const float4 v = *reinterpret_cast<const float4*>(etile + (wave * RPW + i) * kEpiLd + lane * 4);
+      y[i] = float4{v.x + rres[i].x, v.y + rres[i].y, v.z + rres[i].z, v.w + rres[i].w};
     }
-    if constexpr (FFN) yrows.v[i] = y;             // stays on the CU: input row of the FFN half, handed to its norm1 in registers
-    else if ((rok >> i) & 1u) {
-      if (wt & 1) WtBuf(out).store16((unsigned)(roff[i] * 4), y);
-      else *reinterpret_cast<float4*>(out + roff[i]) = y;
+    if constexpr (FFN) {
+#pragma unroll
+      for (int i = 0; i < RPW; ++i) yrows.v[i] = y[i];      // stay on the CU: input rows of the FFN half, handed to its norm1 in registers
+    } else {
+      if (ln_g) {      // post-norm layer (cross-clip TrajectoryAttentionLayer.forward_post, CC/...:156-161): LayerNorm(x + attn(x)), eps 1e-5
+        const float4 g = *reinterpret_cast<const float4*>(ln_g + lane * 4), b = *reinterpret_cast<const float4*>(ln_b + lane * 4);
+        float rstd[RPW];
+        ln_stats_rows<RPW>(y, rstd);
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) y[i] = ln_apply(y[i], rstd[i], g, b);
+      }
+      const auto store_rows = [&](auto form) {      // fp32 rows (16-bit maps: the FFN-carrying kernel only)
+#pragma unroll
+        for (int i = 0; i < RPW; ++i)
+          if (REG || ((rok >> i) & 1u)) store_row<decltype(form)::value>(out, roff[i], y[i]);
+      };
+      if (REG || (wt & 1)) store_rows(std::integral_constant<int, 1>{});
+      else store_rows(std::integral_constant<int, 0>{});
     }
   }
   AXVS_STAMP(8);
   if constexpr (FFN) {
     static_assert(RPW == 8, "the FFN half walks 8 rows per wave");
     auto row_off_ = [=](int row) { return ((rok >> (row % RPW)) & 1u) ? roff[row % RPW] - lane * 4 : -1ll; };       // rows of this wave
-    ffn_body<BF, decltype(row_off_), false, true>(fl, wf, fa.W1, fa.W2, out, row_off_, fa.F, 0, crot, tid, wt, yrows);
+    ffn_body<BF, decltype(row_off_), false, true, TOF, REG>(fl, wf, fa.W1, fa.W2, out, row_off_, fa.F, 0, crot, tid, wt, yrows);
   }
   AXVS_STAMP(10);
   AXVS_WG_END(FFN ? 0 : 1);

@@ -46,6 +46,7 @@ inline thread_local int g_cc_last_only = 0;
 inline thread_local hipEvent_t* g_prof_events = nullptr;
 inline thread_local int g_prof_cap = 0;
 inline thread_local int g_prof_next = 0;
+inline thread_local int g_reg_passes = 0;      // bit 0 / 1: the last height (or only) / width trajectory pass ran the regular-tile instantiation (axvs_plan_regular_tiles)
 constexpr int kMaxStages = 32;
 inline thread_local const char* g_stage_names[kMaxStages] = {};
 inline void mark(hipStream_t st, const char* name) {
@@ -143,7 +144,7 @@ struct OwnQkv;    // axvs_fused.h
 // layer's FFN rides along (needs nks > 0 and 64-row tiles).
 template <bool BF, int T, int MT>
 int launch_temporal_n(int nks, const TrajWs& w, const TrajPacked& p, const float* res, float* out, RowMap rm, long long Mp, int N,
-                      int L, float scale, hipStream_t st, const FfnArgs* fa, int flags /* bit 0: write-through output rows, bits 1-2: stop after the spatial half / the q,k,v part, bits 4-5: 16-bit output map of the FFN-carrying kernel (kOutF16 / kOutBf16) */,
+                      int L, float scale, hipStream_t st, const FfnArgs* fa, int flags /* bit 0: write-through output rows, bits 1-2: stop after the spatial half / the q,k,v part, bit 3: the regular-tile instantiation (kTrajReg; merged launches on 64-key frames), bits 4-5: 16-bit output map of the FFN-carrying kernel (kOutF16 / kOutBf16) */,
                       const OwnQkv* oq /* non-null: the kernel computes q, k, v of its own rows first (merged launch) */);
 
 }  // namespace axvs

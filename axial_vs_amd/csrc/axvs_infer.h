@@ -167,6 +167,8 @@ struct TrajPlan {
   int rows;         // rows per tile of the trajectory kernel: 64, 32 or 16 (0: kGeneric)
   int mq;           // merged q/k/v + trajectory launch: 0 = two launches, 1 = merged, 2 = merged and a row tile IS a frame (own K / V^T from registers)
   bool with_ffn;    // the layer's FFN rides in this pass's kernel
+  bool reg;         // mq == 2 on regular tiles: whole unpadded 64-key frames, row offsets that fit 32 bits, fp32 output rows -- the kernel's REG
+                    // instantiation (clamps, row masks and per-row RowMap divisions compiled out; bit-identical to the generic one)
   bool reassoc;     // kGeneric: the reassociated temporal half
   bool may_merge;   // (input) the caller's sequences may use the registered sync words: one trajectory call at a time per buffer
 };

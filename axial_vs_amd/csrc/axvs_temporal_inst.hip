@@ -13,10 +13,10 @@
 
 namespace axvs {
 
-template <bool BF, int T, int MT, int NKS, bool FFN, int MQ = 0>
+template <bool BF, int T, int MT, int NKS, bool FFN, int MQ = 0, bool REG = false>
 static int launch_one(unsigned grid, const TrajWs& w, const TrajPacked& p, const float* res, float* out, RowMap rm, long long Mp, int N, int L,
                       float scale, hipStream_t st, const FfnArgs* fa, int wt, const OwnQkv* oq = nullptr) {
-  auto kern = &temporal_fused_kernel<BF, T, MT, NKS, FFN, MQ>;
+  auto kern = &temporal_fused_kernel<BF, T, MT, NKS, FFN, MQ, REG>;
   if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
   const size_t lds = temporal_lds_bytes<T, MT, FFN, MQ>(FFN ? fa->F : 0);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, w.x16, p.wpq, p.bpq, p.wpkv, p.bpkv, p.wp, p.bp, res, out, rm, Mp, N, L, scale,
@@ -34,6 +34,10 @@ static int launch_temporal_t(const TrajWs& w, const TrajPacked& p, const float* 
     if (oq) {                           // merged q/k/v + trajectory launch
       if constexpr (NKS == 2 && T >= 2) {
         if (L == 64) {                  // a 64-row tile is one frame: own frame first, from registers
+          if (wt & kTrajReg) {          // the plan's regular-tile instantiation: whole unpadded frames, 32-bit offsets, fp32 write-through rows
+            if (fa) return launch_one<BF, T, MT, NKS, true, 2, true>(grid, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
+            return launch_one<BF, T, MT, NKS, false, 2, true>(grid, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
+          }
           if (fa) return launch_one<BF, T, MT, NKS, true, 2>(grid, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
           return launch_one<BF, T, MT, NKS, false, 2>(grid, w, p, res, out, rm, Mp, N, L, scale, st, fa, wt, oq);
         }

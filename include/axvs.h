@@ -130,8 +130,14 @@ const char* axvs_profile_stage_name(int i);
  *        "sync_spin_limit"     polls before a hand-off wait gives up and sets AXVS_STATUS_SYNC_TIMEOUT (default 2^22, about one second; 0 restores it)
  *        "plan_force"          ONE bit mask that forces the planner's size-dependent choices between forms that are bit-identical by construction (the bit-identity tests):
  *                              1 never the 16-row trajectory tiles | 2 / 4 the 128-row FFN tiles always / never | 8 no two-chunk FFN workgroups |
- *                              16 / 32 merged launch on 16-row tiles never / at any size | 64 generic tier without the reassociated temporal half; 0 = the planner's own choice */
+ *                              16 / 32 merged launch on 16-row tiles never / at any size | 64 generic tier without the reassociated temporal half |
+ *                              128 never the regular-tile instantiation of the merged trajectory kernels (the shape-generic one serves every shape); 0 = the planner's own choice */
 int axvs_set_option(const char* key, int value);
+
+/* ---- which instantiation the last trajectory passes of this thread ran: bit 0 = the height pass of a layer (or a stand-alone trajectory attention),
+ *      bit 1 = the width pass, set when the pass ran the regular-tile instantiation of the merged kernel (whole unpadded 64-key frames; bit-identical
+ *      to the shape-generic one, which "plan_force" 128 forces) */
+int axvs_plan_regular_tiles(void);
 
 /* ---- weight packing (once per load_state_dict; result is opaque, device-resident: 16-bit operands in MFMA-fragment order,
  *      16 rows x 32 k-values per KiB, so that a wave's fragment load reads consecutive addresses in lane order) ---- */
