@@ -22,9 +22,10 @@ from .clip_decoder import TubeLinkClipDecoder, tube_link_clip_queries
 from .kmax_decoder import KMaXTransformerDecoder, filter_training_keys, kmax_decoder_forward
 from .kmax_pixel_decoder import KMaXPixelDecoder, MaXTronDeepLabHead, kmax_pixel_decoder_forward
 from .convnext import ConvNeXtBackbone, ConvNeXtV2Backbone, convnext_forward
+from .resnet import ResNetBackbone, resnet_forward
 from .msda import MSDeformAttn, MSDeformAttnFunction, MSDeformAttnTransformerEncoderLayer, ms_deform_attn_backward, ms_deform_attn_forward
 
-__all__ = ["video_panoptic_inference", "VideoPanopticPostProcessor", "video_instance_inference", "VideoInstancePostProcessor", "unpack_bits", "MultiScaleDeformableAxialTrajectoryAttention", "TubeLinkPixelDecoder", "TubeLinkClipDecoder", "tube_link_clip_queries", "KMaXTransformerDecoder", "kmax_decoder_forward", "filter_training_keys", "KMaXPixelDecoder", "kmax_pixel_decoder_forward", "MaXTronDeepLabHead", "ConvNeXtBackbone", "ConvNeXtV2Backbone", "convnext_forward", "linear_sum_assignment", "match_from_embds", "match_clips", "VideoHungarianMatcher", "match_layers", "matcher_costs", "MaXTronCCSetCriterion", "MaXTronWCSetCriterion", "set_criterion_losses", "draw_sampling_noise", "sampled_pixel_losses", "TubeLinkSetCriterion", "draw_point_coords", "tube_link_losses", "WithinClipTrackingModule", "MSDeformAttnPixelDecoder", "MSDeformAttnTransformerEncoder", "MSDeformAttnTransformerEncoderOnly",
+__all__ = ["video_panoptic_inference", "VideoPanopticPostProcessor", "video_instance_inference", "VideoInstancePostProcessor", "unpack_bits", "MultiScaleDeformableAxialTrajectoryAttention", "TubeLinkPixelDecoder", "TubeLinkClipDecoder", "tube_link_clip_queries", "KMaXTransformerDecoder", "kmax_decoder_forward", "filter_training_keys", "KMaXPixelDecoder", "kmax_pixel_decoder_forward", "MaXTronDeepLabHead", "ConvNeXtBackbone", "ConvNeXtV2Backbone", "convnext_forward", "ResNetBackbone", "resnet_forward", "linear_sum_assignment", "match_from_embds", "match_clips", "VideoHungarianMatcher", "match_layers", "matcher_costs", "MaXTronCCSetCriterion", "MaXTronWCSetCriterion", "set_criterion_losses", "draw_sampling_noise", "sampled_pixel_losses", "TubeLinkSetCriterion", "draw_point_coords", "tube_link_losses", "WithinClipTrackingModule", "MSDeformAttnPixelDecoder", "MSDeformAttnTransformerEncoder", "MSDeformAttnTransformerEncoderOnly",
            "PositionEmbeddingSine", "CrossClipTrackingModule", "TubeLinkCrossClipHead", "MSDeformAttn", "MSDeformAttnTransformerEncoderLayer", "ms_deform_attn_forward", "ms_deform_attn_backward", "MSDeformAttnFunction", "TrajectoryAttention", "TemporalAxialTrajectoryAttentionLayer", "TemporalTrajectoryAttentionLayer",
            "TemporalEncoder", "TubeLinkTemporalEncoder", "PositionEmbeddingSine3D", "AxialTrajectoryAttention5D",
            "set_default_dtype", "GraphedForward", "invalidate_pack", "enable_range_check", "range_check_report", "disable_range_check", "check_status", "set_handoff_policy"]

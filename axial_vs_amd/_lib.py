@@ -177,6 +177,23 @@ class AxvsCnxCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("N", "H", "W")] + [(n, C.c_int * 4) for n in ("dims", "depths", "h", "w")] + [("v2", C.c_int)]
 
 
+RN_STEM_FIELDS = ("w", "b")
+RN_BLOCK_FIELDS = ("w1", "b1", "w2", "b2", "w3", "b3", "ws", "bs")
+
+
+class AxvsRnStemParams(C.Structure):
+    _fields_ = [(n, _fp) for n in RN_STEM_FIELDS]
+
+
+class AxvsRnBlockParams(C.Structure):
+    _fields_ = [(n, _fp) for n in RN_BLOCK_FIELDS]
+
+
+class AxvsRnCfg(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("N", "H", "W", "in_channels", "stem_channels")]
+                + [(n, C.c_int * 4) for n in ("width", "out_channels", "blocks", "stride", "dilation", "h", "w")] + [("stride_in_1x1", C.c_int)])
+
+
 class AxvsMsdaParams(C.Structure):
     _fields_ = [(n, _fp) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
                                    "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
@@ -390,6 +407,13 @@ SIGNATURES = {
     "axvs_cnx_down_fwd": (C.c_int, [C.POINTER(AxvsCnxCfg), _fp, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
     "axvs_cnx_dwln_fwd": (C.c_int, [C.POINTER(AxvsCnxCfg), _fp, C.c_int, _fp, _fp, _fp]),
     "axvs_cnx_block_fwd": (C.c_int, [C.POINTER(AxvsCnxCfg), _fp, C.c_int, _fp, _fp, _fp, C.c_longlong, _fp]),
+    "axvs_rn_packed_bytes": (C.c_size_t, [C.POINTER(AxvsRnCfg)]),
+    "axvs_rn_pack": (C.c_int, [C.POINTER(AxvsRnStemParams), C.POINTER(AxvsRnBlockParams), C.POINTER(AxvsRnCfg), _fp, _fp]),
+    "axvs_rn_workspace_bytes": (C.c_size_t, [C.POINTER(AxvsRnCfg)]),
+    "axvs_rn_fwd": (C.c_int, [C.POINTER(AxvsRnCfg), _fp, _fp, C.POINTER(_fp), _fp, _fp, C.c_longlong]),      # (the workspace goes last)
+    "axvs_rn_stem_fwd": (C.c_int, [C.POINTER(AxvsRnCfg), _fp, _fp, _fp, _fp]),
+    "axvs_rn_conv3_fwd": (C.c_int, [C.POINTER(AxvsRnCfg), _fp, C.c_int, _fp, _fp, _fp]),
+    "axvs_rn_block_fwd": (C.c_int, [C.POINTER(AxvsRnCfg), _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_longlong]),
     "axvs_add_channel_vector": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int, _fp]),
     "axvs_pos2d": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.c_longlong, C.c_longlong, C.c_float, C.c_int, C.c_float, _fp]),
     "axvs_msda_packed_bytes": (C.c_size_t, [C.c_int] * 4),

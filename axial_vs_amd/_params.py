@@ -329,3 +329,38 @@ def convnext_block_folded(sd, p: str) -> List[Optional[Tensor]]:
     dw = sd[p + "dwconv.weight"].double()
     return [dw.view(dw.shape[0], 49).t().contiguous(), sd[p + "dwconv.bias"].double(), sd[p + "norm.weight"].double(), sd[p + "norm.bias"].double(),
             sd[p + "pwconv1.weight"].double(), sd[p + "pwconv1.bias"].double(), w2.contiguous(), b2, grn]
+
+
+# ---- ResNet bottleneck backbone -----------------------------------------------------------------------------------------------------------
+# AxvsRnStemParams / AxvsRnBlockParams hold float64 tensors with every BatchNorm FOLDED, in the kernels' layouts; the names are the
+# reference ResNet's own state-dict names (`<conv>.weight`, `<conv>.norm.{weight,bias,running_mean,running_var}`).
+def resnet_block_shapes(cin: int, width: int, cout: int, shortcut: bool) -> List[tuple]:
+    """(slot, shape or None) of AxvsRnBlockParams, in order (_lib.RN_BLOCK_FIELDS)"""
+    return [("w1", (width, cin)), ("b1", (width,)), ("w2", (width, 9, width)), ("b2", (width,)), ("w3", (cout, width)), ("b3", (cout,)),
+            ("ws", (cout, cin) if shortcut else None), ("bs", (cout,) if shortcut else None)]
+
+
+def _resnet_conv_bn(sd, p: str, eps: float):
+    """conv `p` behind its eval BatchNorm `p.norm` -> (weight scaled per output channel, bias), float64"""
+    n = p + "norm."
+    scale = sd[n + "weight"].double() / torch.sqrt(sd[n + "running_var"].double() + eps)
+    return sd[p + "weight"].double() * scale[:, None, None, None], sd[n + "bias"].double() - sd[n + "running_mean"].double() * scale
+
+
+def resnet_stem_folded(sd, eps: float) -> List[Tensor]:
+    """AxvsRnStemParams of `stem.conv1`: w [147][C] ((colour, ky, kx) major, output channel fastest), b"""
+    w, b = _resnet_conv_bn(sd, "stem.conv1.", eps)
+    return [w.flatten(1).t().contiguous(), b]
+
+
+def resnet_block_folded(sd, p: str, eps: float) -> List[Optional[Tensor]]:
+    """AxvsRnBlockParams of the bottleneck block `p`: the 1x1 weights as matrices, the 3x3 weight as (output channel, tap, input channel);
+    the block without `shortcut` has None in the last two slots"""
+    w1, b1 = _resnet_conv_bn(sd, p + "conv1.", eps)
+    w2, b2 = _resnet_conv_bn(sd, p + "conv2.", eps)
+    w3, b3 = _resnet_conv_bn(sd, p + "conv3.", eps)
+    ws, bs = (None, None)
+    if p + "shortcut.weight" in sd:
+        ws, bs = _resnet_conv_bn(sd, p + "shortcut.", eps)
+        ws = ws.flatten(1).contiguous()
+    return [w1.flatten(1).contiguous(), b1, w2.permute(0, 2, 3, 1).flatten(1, 2).contiguous(), b2, w3.flatten(1).contiguous(), b3, ws, bs]

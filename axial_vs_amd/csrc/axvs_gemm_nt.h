@@ -73,7 +73,7 @@ inline bool gemm_nt_general(const GemmLd& ld, int K) { return !(ld.al_a == 4 && 
 struct GemmEpi {
   const float* bias;   // nullable [N]: added first
   float mul;           // then multiplied
-  int relu;            // then max(., 0); with GemmNtForm::gelu also 2 / 3, see there
+  int relu;            // then max(., 0); with GemmNtForm::gelu also 2 / 3 / 4, see there
   Drop dr;             // then dropout, element index row * N + col (thr = 0: none)
   float beta;          // 0: overwrite C, 1: add to it
   const float* res = nullptr;   // optional residual [M][ldc], added last (out = ... + res)
@@ -110,8 +110,9 @@ __device__ __forceinline__ void split_n(const float4& a, const float4& b, u16x8 
 struct GemmNtForm {
   int pieces;          // 16-bit pieces per operand: 3 (fp32 accuracy, six MFMAs per product), 2 (1.5e-5, three), 1 (autocast's products)
   bool f16 = false;    // pieces == 1: an fp16 piece instead of a bf16 one
-  bool gelu = false;   // GemmEpi::relu also takes 2 (exact GELU in the ReLU's place) and 3 (exact GELU after the residuals: out =
-                       // gelu(... + res)): an instantiation of its own, three pieces on the 16-byte loader without addend
+  bool gelu = false;   // GemmEpi::relu also takes 2 (exact GELU in the ReLU's place), 3 (exact GELU after the residuals: out =
+                       // gelu(... + res)) and 4 (ReLU after the residuals: out = relu(... + res)): an instantiation of its own, three
+                       // pieces on the 16-byte loader without addend
 };
 
 // The refusals of gemm_nt() alone, no device work (AXVS_ERR_ARG with a message): N and the row strides against the stated alignment,

@@ -24,8 +24,9 @@ namespace tr {
 // kernel of the common case carries none of that code (these kernels are sensitive to their size: +3 us per launch with both
 // loaders in one body)
 // ADD (with !GEN): the x + pos addend ld.a2 on the 16-byte path (the general loader takes it at run time).
-// ACT: ep.relu also takes 2 (exact GELU in the ReLU's place) and 3 (exact GELU after the residuals: out = gelu(... + res)) -- the
-// Video-kMaX query decoder's ConvBN + gelu chains (axvs_kmax.hip); its own flag, so that no other instantiation carries the erf.
+// ACT: ep.relu also takes 2 (exact GELU in the ReLU's place), 3 (exact GELU after the residuals: out = gelu(... + res)) -- the
+// Video-kMaX query decoder's ConvBN + gelu chains (axvs_kmax.hip) -- and 4 (ReLU after the residuals: out = relu(... + res), the last
+// 1x1 convolution of a ResNet bottleneck, axvs_resnet.hip); its own flag, so that no other instantiation carries the erf.
 template <int NS, bool GEN = false, bool ADD = false, bool F16 = false, bool AFF = false, bool ACT = false>
 __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                                          float* __restrict__ C, long long M, int N, int K, GemmLd ld, GemmEpi ep) {
@@ -288,6 +289,10 @@ __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const 
 #pragma unroll
             for (int e = 0; e < 4; ++e) t[e] = gelu_exact(t[e]);
           }
+          if (ep.relu == 4) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = fmaxf(t[e], 0.f);
+          }
         }
         if (ok[i]) *reinterpret_cast<float4*>(C + off[i]) = make_float4(t[0], t[1], t[2], t[3]);
       }
@@ -385,6 +390,7 @@ int gemm_nt_check(int N, int K, const GemmLd& ld, const GemmEpi& ep, GemmNtForm 
   if (N % 4 || ld.c % 4 || (ld.al_a == 4 && ld.a % 4) || (ld.al_b == 4 && ld.b % 4))
     return fail(AXVS_ERR_ARG, "split-precision GEMM: N=%d and the row strides must be multiples of 4 (K=%d)", N, K);
   if (ld.aff && !ld.a2) return fail(AXVS_ERR_ARG, "split-precision GEMM: the affine loader needs its second operand");
+  if (ep.relu < 0 || ep.relu > 4) return fail(AXVS_ERR_ARG, "split-precision GEMM: epilogue %d is not one of 0..4", ep.relu);
   if (ep.relu > 1 && !f.gelu) return fail(AXVS_ERR_ARG, "split-precision GEMM: epilogue %d needs the GELU instantiation", ep.relu);
   if (ep.relu > 1 && ep.out16) return fail(AXVS_ERR_ARG, "split-precision GEMM: the GELU epilogues write fp32 rows only");
   const bool gen = gemm_nt_general(ld, K), aff = ld.aff != nullptr, add = !gen && !aff && ld.a2 != nullptr;

@@ -1082,6 +1082,53 @@ int axvs_cnx_dwln_fwd(const AxvsCnxCfg* cfg, const void* packed, int block_index
 int axvs_cnx_block_fwd(const AxvsCnxCfg* cfg, const void* packed, int block_index, const float* x, float* out, void* workspace, long long workspace_bytes,
                        void* stream);
 
+/* ---- ResNet bottleneck backbone (eval forward; csrc/axvs_resnet.hip) ------------------------------------------------------------------------
+ * All tensors fp32; forward only.  N frames, each on its own.  image [N, 3, H, W] -> the stem (7x7 / stride 2 / padding 3 convolution,
+ * BatchNorm, ReLU, 3x3 / stride 2 / padding 1 max pool: stem_channels at ceil(ceil(H / 2) / 2)) -> four stages of bottleneck blocks (1x1
+ * -> 3x3 -> 1x1, each with its BatchNorm, ReLU behind the first two and behind the sum with the shortcut).  Stage i: blocks[i] blocks of
+ * bottleneck width width[i] and out_channels[i] outputs; its first block has stride[i] (in the 1x1 with stride_in_1x1, else in the 3x3)
+ * and a projection shortcut where its input channels differ from out_channels[i]; every 3x3 of the stage has dilation[i] = its padding.
+ * h[i] x w[i] is the map stage i READS; it leaves ceil(h[i] / stride[i]) x ceil(w[i] / stride[i]).  Activations are rows [N][h][w][C]
+ * (channels-last) between the entries; only axvs_rn_fwd writes NCHW.  Equal inputs give equal bits, and a frame's bits do not depend on
+ * the frames beside it.
+ * Bounds (AXVS_ERR_ARG outside them): in_channels 3; stem_channels a multiple of 16 in 16..128; 1..64 blocks per stage; width a multiple
+ * of 32 in 32..512; out_channels multiples of 16 in 16..2048; stride and dilation 1 or 2, stride 2 only where the channels change and not together with dilation 2; N in
+ * 1..4096; h, w in 1..16383 and N*h*w < 2^24 per stage.  axvs_rn_fwd also wants h / w to be the sizes H / W give; the step entries read
+ * h[stage], w[stage] alone (and axvs_rn_stem_fwd H, W, h[0], w[0]).
+ * Parameters arrive with every BatchNorm FOLDED by the caller (float64): w = conv weight * bn_w / sqrt(running_var + eps) per output channel,
+ * b = bn_b - running_mean * that scale.  Stem: w [147][stem_channels] ((colour, ky, kx) major, output channel fastest), b.  A block: w1
+ * [width][in], w2 [width][9][width] (output channel, tap ky*3 + kx, input channel), w3 [out][width], ws [out][in] the projection (NULL
+ * with bs where the block has none), each with its b.  The workspace size goes LAST in these entries. */
+typedef struct AxvsRnStemParams {
+  const float *w, *b;
+} AxvsRnStemParams;
+typedef struct AxvsRnBlockParams {
+  const float *w1, *b1, *w2, *b2, *w3, *b3, *ws, *bs;
+} AxvsRnBlockParams;
+typedef struct AxvsRnCfg {
+  int N, H, W;
+  int in_channels, stem_channels;
+  int width[4], out_channels[4], blocks[4], stride[4], dilation[4], h[4], w[4];
+  int stride_in_1x1;
+} AxvsRnCfg;
+size_t axvs_rn_packed_bytes(const AxvsRnCfg* cfg);      /* depends on the channels, blocks and strides only; 0: cfg refused */
+/* blocks: sum(cfg->blocks) structs, stage after stage.  Copies and splits on `stream`; the parameter tensors must stay alive until they
+ * have run. */
+int axvs_rn_pack(const AxvsRnStemParams* stem, const AxvsRnBlockParams* blocks, const AxvsRnCfg* cfg, void* packed, void* stream);
+size_t axvs_rn_workspace_bytes(const AxvsRnCfg* cfg);   /* enough for the network and for every step entry below */
+/* outputs: a host array of five device pointers -- stem, res2 .. res5 as [N, C, h, w]; NULL: that map is not written */
+int axvs_rn_fwd(const AxvsRnCfg* cfg, const void* packed, const float* image, float* const* outputs, void* stream, void* workspace,
+                long long workspace_bytes);
+/* Step entries, rows in and out.  image [N, 3, H, W] -> out [N, h[0], w[0], stem_channels] */
+int axvs_rn_stem_fwd(const AxvsRnCfg* cfg, const void* packed, const float* image, float* out, void* stream);
+/* block_index counts the blocks of all stages.  The block's 3x3 convolution + BatchNorm + ReLU on conv1's map: x [N, hm, wm, width] ->
+ * out [N, ceil(hm / s), ceil(wm / s), width], s the stride the block puts into its 3x3 (out != x) */
+int axvs_rn_conv3_fwd(const AxvsRnCfg* cfg, const void* packed, int block_index, const float* x, float* out, void* stream);
+/* one whole block: x [N, hin, win, in] -> out [N, ho, wo, out_channels] (out != x); a stage's first block reads h[stage] x w[stage], the
+ * others the map the stage leaves */
+int axvs_rn_block_fwd(const AxvsRnCfg* cfg, const void* packed, int block_index, const float* x, float* out, void* stream, void* workspace,
+                      long long workspace_bytes);
+
 /* ---- test hooks, not part of the drop-in surface ----------------------------------------------------------------------------------
  * One call of the training tier's split-precision GEMM dispatch (tr_gemm_nt_kernel / tr_gemm_tn_kernel behind the host code every
  * training entry point above uses), with every operand, stride and epilogue field explicit: what tests/test_hip_train_gemm.py holds
