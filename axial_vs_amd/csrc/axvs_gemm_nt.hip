@@ -10,8 +10,8 @@ namespace tr {
 
 // ---- C[M,N] = epilogue(A[M,K] . B[N,K]^T): both operands row-major with the contraction index contiguous -----------------------------
 // NS = 2: the bf16x3 product above.  NS = 3: operands split into THREE bf16 pieces (24 mantissa bits = all of fp32) and six MFMAs per
-// product (hh, hm, mh, mm, hl, lh; the dropped terms are 2^-24 of the product): as accurate as an fp32 GEMM at twice the matrix
-// time of NS = 2.  The FORWARD GEMMs run this way (option `train_exact`, default 1).  Why: the layer has one discontinuity, the ReLU.
+// product (hh, hm, mh, mm, hl, lh; the dropped terms are 2^-24 of the product): an fp32 GEMM's products at twice the matrix
+// time of NS = 2 (the sum's error against float64: 1.8 .. 5.2 x an fp32 GEMM's up to K = 2048, see SUM below for deeper ones).  The FORWARD GEMMs run this way (option `train_exact`, default 1).  Why: the layer has one discontinuity, the ReLU.
 // With 1.5e-5 relative error on the pre-activations about one hidden unit in 1e5 lands on the other side of zero than in an fp32
 // forward, and every such flip moves the input gradient of its token by ~1e-2 of the gradient's scale (measured at [1,4,256,32,32],
 // d_ffn 1024, two-piece forward: d_src 7e-3 .. 2e-2 in max-norm, relative L2 3e-4, output 5e-6).  The three-piece forward costs
@@ -27,7 +27,13 @@ namespace tr {
 // ACT: ep.relu also takes 2 (exact GELU in the ReLU's place), 3 (exact GELU after the residuals: out = gelu(... + res)) -- the
 // Video-kMaX query decoder's ConvBN + gelu chains (axvs_kmax.hip) -- and 4 (ReLU after the residuals: out = relu(... + res), the last
 // 1x1 convolution of a ResNet bottleneck, axvs_resnet.hip); its own flag, so that no other instantiation carries the erf.
-template <int NS, bool GEN = false, bool ADD = false, bool F16 = false, bool AFF = false, bool ACT = false>
+// SUM (NS = 3 only; gemm_nt_check takes it where an accumulator contracts over more than kNtSumSteps k-steps): a k-step sums its six
+// products from zero and adds that sum to the running accumulator ONCE, as the 3x3 kernel of axvs_resnet.h does.  A rounding of the
+// accumulator is as large as the accumulator whatever is added, and five of six additions are spent on the small cross terms: with all
+// products added one by one the max-norm error against float64 grows to 5.4 .. 11.7 x that of an fp32 GEMM at K = 6144 (1152 additions)
+// and ConvNeXt-L's 3072-deep downsample layer sat at 10.1 x, outside this project's bound of 8 x (profiles/deep_contraction_parity.txt).
+// Up to kNtSumSteps steps every call keeps the one-by-one order and with it its bits.
+template <int NS, bool GEN = false, bool ADD = false, bool F16 = false, bool AFF = false, bool ACT = false, bool SUM = false>
 __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                                          float* __restrict__ C, long long M, int N, int K, GemmLd ld, GemmEpi ep) {
   extern __shared__ __attribute__((aligned(16))) char gsmem[];
@@ -152,15 +158,34 @@ __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const 
       for (int m2 = 0; m2 < 2; ++m2)
 #pragma unroll
         for (int s = 0; s < NS; ++s) af[m2][s] = *reinterpret_cast<const u16x8*>(base + s * kGTileElems + aoff[2 * mp + m2]);
-#pragma unroll
-      for (int p = 0; p < kProducts; ++p)
+      if constexpr (SUM) {                                      // the step's products from zero, one addition into the accumulator
+        static_assert(!SUM || (NS == 3 && !F16), "step sums exist for three bf16 pieces");
+        f32x4 part[2][2];
 #pragma unroll
         for (int m2 = 0; m2 < 2; ++m2)
 #pragma unroll
-          for (int nt = 0; nt < 2; ++nt) {                      // D[n = 4 fg + r][m = fi]
-            if (p == 0) acc[2 * mp + m2][nt] = H16<!F16>::mfma(bf[nt][0], af[m2][0], acc[2 * mp + m2][nt]);
-            else acc[2 * mp + m2][nt] = H16<true>::mfma(bf[nt][kPieceB[p]], af[m2][kPieceA[p]], acc[2 * mp + m2][nt]);
-          }
+          for (int nt = 0; nt < 2; ++nt) part[m2][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int p = 0; p < kProducts; ++p)
+#pragma unroll
+          for (int m2 = 0; m2 < 2; ++m2)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) part[m2][nt] = H16<true>::mfma(bf[nt][kPieceB[p]], af[m2][kPieceA[p]], part[m2][nt]);
+#pragma unroll
+        for (int m2 = 0; m2 < 2; ++m2)
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt) acc[2 * mp + m2][nt] += part[m2][nt];
+      } else {
+#pragma unroll
+        for (int p = 0; p < kProducts; ++p)
+#pragma unroll
+          for (int m2 = 0; m2 < 2; ++m2)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {                    // D[n = 4 fg + r][m = fi]
+              if (p == 0) acc[2 * mp + m2][nt] = H16<!F16>::mfma(bf[nt][0], af[m2][0], acc[2 * mp + m2][nt]);
+              else acc[2 * mp + m2][nt] = H16<true>::mfma(bf[nt][kPieceB[p]], af[m2][kPieceA[p]], acc[2 * mp + m2][nt]);
+            }
+      }
     }
     // the next step's operands into the other stage (every wave left its reads of it behind the previous barrier) -- unconditionally:
     // after the last step the registers hold an old tile and the stage is not read again.  (Forcing the split's VALU instructions
@@ -363,9 +388,13 @@ __global__ __launch_bounds__(512, NS <= 2 ? 4 : 2) void tr_gemm_nt_kernel(const 
 namespace {
 
 using NtKernel = decltype(&tr_gemm_nt_kernel<3>);
-constexpr int nt_id(int ns, bool gen = false, bool add = false, bool f16 = false, bool aff = false, bool act = false) {
-  return 0x100 | ns | gen << 2 | add << 3 | f16 << 4 | aff << 5 | act << 6;      // AxvsTestGemm::variant (include/axvs.h)
+constexpr int nt_id(int ns, bool gen = false, bool add = false, bool f16 = false, bool aff = false, bool act = false, bool sum = false) {
+  return 0x100 | ns | gen << 2 | add << 3 | f16 << 4 | aff << 5 | act << 6 | sum << 7;      // AxvsTestGemm::variant (include/axvs.h)
 }
+// Three pieces: the k-steps one accumulator may take with its products added one by one.  64 steps (K = 2048 unsplit) is the deepest
+// contraction the suite held to 8 x an fp32 GEMM's error before the step sums existed (measured there: 3.7 .. 5.2 x); at 96 steps the
+// ConvNeXt-L downsample layer missed it (10.1 x).  Every call up to here keeps its bits.
+constexpr int kNtSumSteps = 64;
 // The instantiations that exist: the ones some caller reaches today.
 NtKernel nt_kernel(int id) {
 #define AXVS_NT_CASE(...) case nt_id(__VA_ARGS__): return tr_gemm_nt_kernel<__VA_ARGS__>
@@ -377,6 +406,9 @@ NtKernel nt_kernel(int id) {
     AXVS_NT_CASE(1, false, false, true); AXVS_NT_CASE(1, true, false, true); AXVS_NT_CASE(1, false, true, true);      // one fp16 piece (2)
     AXVS_NT_CASE(2, false, false, false, true); AXVS_NT_CASE(2, true, false, false, true);      // the affine loader
     AXVS_NT_CASE(3, false, false, false, false, true);      // the GELU epilogues
+    // three pieces over more than kNtSumSteps k-steps: the same four with step sums
+    AXVS_NT_CASE(3, false, false, false, false, false, true); AXVS_NT_CASE(3, true, false, false, false, false, true);
+    AXVS_NT_CASE(3, false, true, false, false, false, true); AXVS_NT_CASE(3, false, false, false, false, true, true);
   }
 #undef AXVS_NT_CASE
   return nullptr;
@@ -385,7 +417,7 @@ NtKernel nt_kernel(int id) {
 }  // namespace
 
 // The refusals, and the instantiation a call takes: GEN from gemm_nt_general(), AFF from ld.aff, ADD from ld.a2 where neither holds (the
-// general and the affine loader take the second operand themselves).
+// general and the affine loader take the second operand themselves), SUM from the k-steps of one accumulator (of one split with split-K).
 int gemm_nt_check(int N, int K, const GemmLd& ld, const GemmEpi& ep, GemmNtForm f, int* variant) {
   if (N % 4 || ld.c % 4 || (ld.al_a == 4 && ld.a % 4) || (ld.al_b == 4 && ld.b % 4))
     return fail(AXVS_ERR_ARG, "split-precision GEMM: N=%d and the row strides must be multiples of 4 (K=%d)", N, K);
@@ -398,7 +430,8 @@ int gemm_nt_check(int N, int K, const GemmLd& ld, const GemmEpi& ep, GemmNtForm 
   if (f.gelu && (gen || add || aff || f.pieces != 3))
     return fail(AXVS_ERR_ARG, "split-precision GEMM: the GELU epilogues exist for three pieces on 16-byte rows with K %% 4 == 0 and no second operand (K=%d)", K);
   if (aff && f.pieces != 2) return fail(AXVS_ERR_ARG, "split-precision GEMM: the affine loader exists for two pieces, not %d", f.pieces);
-  const int id = nt_id(f.pieces, gen, add, f.f16, aff, f.gelu);
+  const int nk_all = (K + kGK - 1) / kGK, nk = ld.ksteps > 0 && ld.ksteps < nk_all ? ld.ksteps : nk_all;
+  const int id = nt_id(f.pieces, gen, add, f.f16, aff, f.gelu, f.pieces == 3 && nk > kNtSumSteps);
   if (!nt_kernel(id)) return fail(AXVS_ERR_ARG, "split-precision GEMM: no kernel for %d piece(s)%s", f.pieces, f.f16 ? " of fp16" : "");
   if (variant) *variant = id;
   return AXVS_OK;
@@ -416,10 +449,10 @@ int gemm_nt(const float* A, const float* B, float* C, long long M, int N, int K,
   // The kernel takes more dynamic LDS than the default limit.  Per thread and instantiation: 1 + the device the limit was last raised
   // on, so a repeat launch costs a compare (a thread that alternates between devices falls through to ensure_max_lds, which remembers
   // every (device, kernel) pair).
-  static thread_local int lds_dev[128];
-  if (lds_dev[id & 127] != dev + 1) {
+  static thread_local int lds_dev[256];
+  if (lds_dev[id & 255] != dev + 1) {
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern))) return rc;
-    lds_dev[id & 127] = dev + 1;
+    lds_dev[id & 255] = dev + 1;
   }
   if (variant) *variant = id;
   const dim3 grid((unsigned)((M + kGT - 1) / kGT), (unsigned)((N + kGT - 1) / kGT), (unsigned)zsplits);

@@ -1148,8 +1148,9 @@ int axvs_rn_block_fwd(const AxvsRnCfg* cfg, const void* packed, int block_index,
  *   instead, rows with zero_rows[row] != 0 written as zeros.  relu = 2: exact GELU in the ReLU's place, relu = 3: exact GELU after the sums (out =
  *   gelu(... + res + res2)) -- the ACT instantiation the query decoders' Linear layers run: three pieces (`exact`, no train_amp), 16-byte rows, K % 4 == 0,
  *   no a2, fp32 rows out; anything else is refused.
- *   variant (out): the instantiation launched last, 0x100 | NS | GEN << 2 | ADD << 3 | F16 << 4 | AFF << 5 | ACT << 6 for
- *   tr_gemm_nt_kernel<NS, GEN, ADD, F16, AFF, ACT> (every caller in the library launches these same instantiations: axvs_gemm_nt.hip holds them all),
+ *   variant (out): the instantiation launched last, 0x100 | NS | GEN << 2 | ADD << 3 | F16 << 4 | AFF << 5 | ACT << 6 | SUM << 7 for
+ *   tr_gemm_nt_kernel<NS, GEN, ADD, F16, AFF, ACT, SUM> (SUM: the step sums three pieces take where an accumulator contracts over more than 64
+ *   k-steps, K > 2048 unsplit; every caller in the library launches these same instantiations: axvs_gemm_nt.hip holds them all),
  *   0x200 | GEN | AMP << 1 | STATS << 3 | GRP << 4 for tr_gemm_tn_kernel<GEN, AMP, STATS, GRP>; 0 when nothing was launched.
  *   scratch: axvs_test_train_gemm_scratch_bytes(t) bytes (0 for NT, FWD and TN_DIRECT).  Refusals before any device work return AXVS_ERR_ARG. */
 #define AXVS_TEST_GEMM_NT 0

@@ -12,7 +12,9 @@ No hard decision is taken anywhere in these networks, so no case is screened.
 `wrong=` makes the restatement wrong on purpose in one of the three ways a kernel of this path can be (tests/test_convnext_cpu.py checks
 that each moves the float64 result by far more than the bound, i.e. that the cases can tell): "pad_zero" -- a padded pixel of a
 downsample layer as zeros BEHIND the LayerNorm instead of its bias; "halo" -- the depthwise convolution's border replicated instead of
-zero; "grn_shared" -- GRN statistics over all frames at once.
+zero; "grn_shared" -- GRN statistics over all frames at once.  A fourth is what an off-by-one in a GEMM's step count does: "k_short" --
+the contraction of `pwconv2` and of the downsample convolutions without its last 32 inputs (one k-step of the device's GEMM, in the order
+the device contracts in: the hidden units as they stand, the 2 x 2 patch as (ky, kx, c)).
 """
 from collections import OrderedDict, namedtuple
 
@@ -25,11 +27,14 @@ _DEEP = dict(dims=(16, 32, 48, 64), depths=(3, 3, 27, 3))
 NETS = [Net(f"{n}_{'v2' if v2 else 'v1'}", seed + v2, size, N, **kw, v2=bool(v2), gamma=True)
         for n, seed, size, N, kw in (("A", 2701, (65, 97), 2, _SMALL), ("B", 2703, (64, 96), 1, _SMALL), ("C", 2705, (33, 161), 3, _SMALL),
                                      ("deep", 2707, (65, 97), 1, _DEEP)) for v2 in (0, 1)]
-BY_NAME = {c.name: c for c in NETS}
+LARGE = dict(dims=(192, 384, 768, 1536), depths=(3, 3, 27, 3))
+# ConvNeXt-L's widths on a small image (maps 9 x 13, 5 x 7, 3 x 4, 2 x 2): four blocks that contract over 3072 and two over 6144, back to
+# back.  Not in NETS: the tests that walk NETS (bit equality, repacking) need no 0.25 GB of parameters
+LARGE_NETS = [Net(f"L_{'v2' if v2 else 'v1'}", 2715 + v2, (33, 49), 2, LARGE["dims"], (1, 1, 4, 2), v2=bool(v2), gamma=True) for v2 in (0, 1)]
+BY_NAME = {c.name: c for c in NETS + LARGE_NETS}
 SHALLOW = [c.name for c in NETS if not c.name.startswith("deep")]
 # fixtures of the reference's own classes (tools/gen_golden_convnext.py)
 FIXTURES = [Net("g27_cnx_v1", 2711, (65, 97), 1, **_SMALL, v2=False, gamma=True), Net("g27_cnx_v2", 2712, (65, 97), 1, **_SMALL, v2=True, gamma=True)]
-LARGE = dict(dims=(192, 384, 768, 1536), depths=(3, 3, 27, 3))
 OUTPUTS = ("stem", "res2", "res3", "res4", "res5")
 
 # the depthwise kernel's tiles (csrc/axvs_convnext.h): TH x 16 output pixels, 64 channels per pass; the tallest TH of 8, 4, 2 that gives
@@ -43,9 +48,14 @@ DWLN_CASES = [(1, 1, 16, 2), (3, 5, 32, 1), (6, 7, 48, 1), (7, 7, 192, 1), (9, 1
 # image sizes of the stem: all four residues of (H + 3) mod 4
 STEM_CASES = [(1, 1), (2, 3), (5, 9), (32, 48), (33, 49), (34, 50), (35, 51)]
 # (h, w, C) of one downsample layer (C -> 2 C): odd sizes have the padded row / column
-DOWN_CASES = [(h, w, C) for (h, w) in ((1, 1), (2, 2), (3, 4), (9, 13)) for C in (16, 192)]
+# the last one is ConvNeXt-L's deepest downsample layer: a contraction over 4 C = 3072 into 1536 outputs
+DOWN_CASES = [(h, w, C) for (h, w) in ((1, 1), (2, 2), (3, 4), (9, 13)) for C in (16, 192)] + [(9, 13, 768)]
 # (h, w, N, kind) of one whole block at C = 48: v1, v2, and v1 without gamma
 BLOCK_CASES = [(h, w, N, kind) for (h, w, N) in ((1, 1, 1), (5, 7, 2), (17, 25, 3)) for kind in ("v1", "v2")] + [(5, 7, 2, "v1_nogamma")]
+# (h, w, N, kind, C) of whole blocks at the widths of ConvNeXt-L's last two stages: `pwconv2` contracts over 4 C = 3072 and 6144, the
+# deepest contractions of the library.  Without gamma nothing scales the pwconv2 error down in front of the residual; v2 runs pwconv2 once
+# per frame on GRN-scaled weights
+DEEP_BLOCK_CASES = [(9, 13, N, kind, C) for C in (768, 1536) for N, kind in ((1, "v1_nogamma"), (2, "v2"))]
 
 
 def map_sizes(H, W):
@@ -140,7 +150,11 @@ class Restatement:
             x = F.pad(self.ln_first(x, p + "0."), (0, 1, 0, 1, 0, 0, 0, 0), "constant", 0)
         else:
             x = self.ln_first(F.pad(x, (0, 1, 0, 1, 0, 0, 0, 0), "constant", 0), p + "0.")
-        return F.conv2d(x, self.p[p + "1.weight"], self.p[p + "1.bias"], stride=2)
+        w = self.p[p + "1.weight"]
+        if self.wrong == "k_short":
+            w = w.clone()
+            w[:, -32:, 1, 1] = 0
+        return F.conv2d(x, w, self.p[p + "1.bias"], stride=2)
 
     def dwln(self, x, p):
         """-> channels-last [N, h, w, C]"""
@@ -164,7 +178,10 @@ class Restatement:
         x = F.gelu(x)
         if self.v2:
             x = self.grn(x, p + "grn.")
-        x = F.linear(x, self.p[p + "pwconv2.weight"], self.p[p + "pwconv2.bias"])
+        if self.wrong == "k_short":
+            x = F.linear(x[..., :-32], self.p[p + "pwconv2.weight"][:, :-32], self.p[p + "pwconv2.bias"])
+        else:
+            x = F.linear(x, self.p[p + "pwconv2.weight"], self.p[p + "pwconv2.bias"])
         if p + "gamma" in self.p:
             x = self.p[p + "gamma"] * x
         return inp + x.permute(0, 3, 1, 2)
@@ -297,16 +314,16 @@ def down_study(spec, wrong=None):
     return _once(("down", spec, wrong), make)
 
 
-def block_study(spec, wrong=None):
-    """x [N, h, w, 48] float32 (channels-last; frame n scaled by 1 + n, so that the frames' GRN statistics differ) -> out float64 alike"""
+def block_study(spec, wrong=None, C=48):
+    """x [N, h, w, C] float32 (channels-last; frame n scaled by 1 + n, so that the frames' GRN statistics differ) -> out float64 alike"""
     h, w, N, kind = spec
 
     def make():
-        dims = (48, 16, 16, 16)
+        dims = (C, 16, 16, 16)
         params = _stage_params(dims, kind == "v2", kind != "v1_nogamma", 2750 + h + N)
-        x = torch.randn(N, 48, h, w, generator=torch.Generator().manual_seed(2751 + w), dtype=torch.float64)
+        x = torch.randn(N, C, h, w, generator=torch.Generator().manual_seed(2751 + w), dtype=torch.float64)
         x = x * (1 + torch.arange(N, dtype=torch.float64))[:, None, None, None]
         fn = lambda r, t: r.block(t, "stages.0.0.")
         x32, want, e = _teacher(Restatement(params, torch.float64, wrong), Restatement(params, torch.float32), fn, x)
         return dict(params=params, dims=dims, v2=kind == "v2", gamma=kind != "v1_nogamma", x=rows(x32), out=rows(want), tol=8 * e)
-    return _once(("block", spec, wrong), make)
+    return _once(("block", spec, wrong, C), make)

@@ -13,7 +13,8 @@ Parameters are drawn so that every part matters: convolutions N(0, 1/fan_in); Ba
 `wrong=` makes the restatement wrong on purpose in one of the ways a kernel of this path can be (tests/test_resnet_cpu.py checks that each
 moves the float64 result by far more than the bound): "stride_phase" -- a stride-2 3x3 centred on pixel 2y + 1 instead of 2y;
 "shortcut_phase" -- the same for a strided 1x1; "dilation_pad" -- a dilated 3x3 whose taps start one pixel, not `dilation` pixels, in front
-of the output pixel; "relu_before_add" -- the block's last ReLU in front of the sum with the shortcut.
+of the output pixel; "relu_before_add" -- the block's last ReLU in front of the sum with the shortcut; "k_short" -- a block's first 1x1
+(its deepest contraction) without its last 32 input channels, one k-step of the device's GEMM, what an off-by-one in a step count does.
 """
 from collections import OrderedDict, namedtuple
 import ctypes
@@ -73,6 +74,13 @@ BLOCK_CASES = [(h, w, N, kind) for (h, w, N) in ((1, 1, 1), (5, 7, 2), (17, 25, 
 # the network the step studies cut their blocks from: (stage, block) of each kind
 _STEP = dict(stem=32, widths=(32, 32, 64, 32), outs=(64, 96, 128, 160), blocks=(2, 1, 1, 1))
 _KIND_AT = {"identity": (0, 1, False, 1), "proj_s1": (0, 0, False, 1), "proj_s2": (1, 0, False, 1), "s2_in_1x1": (2, 0, True, 1), "dil2": (3, 0, False, 2)}
+# R-50's own widths, two blocks in res5: the 1x1 convolutions' contractions at their real depths.  res5.0: the projection shortcut
+# 1024 -> 2048, conv1 over 1024, conv3 over 512 with the ReLU behind the residual; res5.1: the identity shortcut, conv1 over 2048;
+# res4.0: 512 -> 256 -> 1024.  Both forms: "a" strides in the 3x3, "b" strides in the first 1x1 and dilates res5 instead of striding it
+R50_WIDTHS = dict(stem=64, widths=(64, 128, 256, 512), outs=(256, 512, 1024, 2048), blocks=(1, 1, 1, 2))
+_KIND_AT.update({f"res{i + 2}.{j}_{f}": (i, j, s1, d5) for i, j in ((3, 0), (3, 1), (2, 0)) for f, s1, d5 in _FORMS})
+# (h, w, N, kind) of one whole block of R50_WIDTHS: 5 x 7, and 6 x 8 where the block strides
+WIDE_BLOCK_CASES = [((6, 8) if j == 0 and not (i == 3 and d5 == 2) else (5, 7)) + (2, f"res{i + 2}.{j}_{f}") for i, j in ((3, 0), (3, 1), (2, 0)) for f, _, d5 in _FORMS]
 
 
 def strides_of(case):
@@ -162,7 +170,10 @@ class Restatement:
         if stride == 2 and self.wrong == "shortcut_phase":
             x = F.pad(x, (0, 1, 0, 1))[:, :, 1::2, 1::2]
             stride = 1
-        return self.bn(F.conv2d(x, self.p[p + "weight"], None, stride=stride), p + "norm.")
+        w = self.p[p + "weight"]
+        if self.wrong == "k_short" and p.endswith("conv1."):
+            x, w = x[:, :-32], w[:, :-32]
+        return self.bn(F.conv2d(x, w, None, stride=stride), p + "norm.")
 
     def conv3x3(self, x, p, stride, d):
         """conv2 + BatchNorm + ReLU"""
@@ -319,13 +330,14 @@ def stem_study(size):
     return _once(("stem", size), make)
 
 
-def block_study(spec, wrong=None):
-    """-> the network (`case`) and the (`stage`, `index`) of a block of the kind, x [N, h, w, in] float32 (channels-last), out float64"""
+def block_study(spec, wrong=None, net=_STEP):
+    """-> the network (`case`, of the widths `net`) and the (`stage`, `index`) of a block of the kind, x [N, h, w, in] float32
+    (channels-last), out float64"""
     h, w, N, kind = spec
 
     def make():
         stage, index, s1, d5 = _KIND_AT[kind]
-        case = Net(f"blk_{kind}", 2840 + h + N, None, N, **_STEP, stride_in_1x1=s1, res5_dilation=d5)
+        case = Net(f"blk_{kind}", 2840 + h + N, None, N, **net, stride_in_1x1=s1, res5_dilation=d5)
         params = net_params(case)
         cin = case.outs[stage] if index else (case.stem if stage == 0 else case.outs[stage - 1])
         x = torch.randn(N, cin, h, w, generator=torch.Generator().manual_seed(2841 + w), dtype=torch.float64)
@@ -333,7 +345,7 @@ def block_study(spec, wrong=None):
         fn = lambda r, t: r.block(t, f"res{stage + 2}.{index}.", *r.geometry(stage, index))
         x32, want, e = _teacher(r64, restatement(case, params, torch.float32), fn, x)
         return dict(case=case, stage=stage, index=index, params=params, x=rows(x32), out=rows(want), tol=8 * e)
-    return _once(("block", spec, wrong), make)
+    return _once(("block", spec, wrong, net["widths"], net["outs"]), make)
 
 
 # ---- what both test modules share: fixtures, modules, a C configuration ----------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """CPU: the restatement of the ConvNeXt / ConvNeXtV2 backbone (tests/convnext_cases.py) against fixtures of the reference's own classes,
 the modules' state-dict names and shapes, their refusals, the new C-ABI symbols (axvs_cnx_*) and their argument errors, which are
-reported before any device work -- and that the cases can tell a wrong halo, a wrong pad rule and shared GRN statistics apart."""
+reported before any device work -- and that the cases can tell a wrong halo, a wrong pad rule, shared GRN statistics and (the cases at
+ConvNeXt-L's widths) a contraction one k-step short apart."""
 import ctypes
 import json
 import os
@@ -261,6 +262,38 @@ def test_cases_tell_padded_pixels_as_zeros():
     bad = cc.Restatement(st["params"], torch.float64, "pad_zero").forward(st["x"], cc.BY_NAME["A_v1"].depths)
     for k in ("res3", "res4", "res5"):
         assert cc.err(bad[k], st["want"][k]) > 1000 * st["tol"][k], k
+
+
+def test_deep_cases_tell_a_dropped_k_step():
+    """The cases at ConvNeXt-L's contraction depths (K = 3072, 6144) against a GEMM that stops one 32-wide k-step early: the float64 result
+    moves by more than 100 x the case's bound -- in the whole blocks, in the deepest downsample layer, and in every step of the L
+    networks' last two stages on the float64 chain."""
+    for spec in cc.DEEP_BLOCK_CASES:
+        right, bad = cc.block_study(spec[:4], C=spec[4]), cc.block_study(spec[:4], "k_short", C=spec[4])
+        d = cc.err(bad["out"], right["out"])
+        print(f"block {spec}: one k-step of {4 * spec[4] // 32} dropped moves float64 by {d:.3e} = {d / right['tol']:.0f} x the bound {right['tol']:.3e}")
+        assert d > 100 * right["tol"], spec
+    spec = cc.DOWN_CASES[-1]
+    assert spec == (9, 13, 768)
+    right, bad = cc.down_study(spec), cc.down_study(spec, "k_short")
+    d = cc.err(bad["out"], right["out"])
+    print(f"downsample {spec}: one k-step of {4 * spec[2] // 32} dropped moves float64 by {d:.3e} = {d / right['tol']:.0f} x the bound {right['tol']:.3e}")
+    assert d > 100 * right["tol"], spec
+    for case in cc.LARGE_NETS:
+        st = cc.study(case)
+        bad = cc.Restatement(st["params"], torch.float64, "k_short")
+        seen = 0
+        with torch.no_grad():
+            for y in st["steps"]:
+                stage = y["index"] if y["kind"] == "down" else y["index"][0]
+                if stage < 2:
+                    continue
+                got = bad.down(y["x"].double(), stage) if y["kind"] == "down" else bad.block(y["x"].double(), f"stages.{stage}.{y['index'][1]}.")
+                d = cc.err(got, y["out"])
+                print(f"{case.name} {y['kind']} {y['index']}: one k-step dropped moves float64 by {d / y['tol']:.0f} x the bound {y['tol']:.3e}")
+                assert d > 100 * y["tol"], (case.name, y["kind"], y["index"])
+                seen += 1
+        assert seen == 8          # two downsample layers (K = 1536, 3072), four blocks at K = 3072, two at K = 6144
 
 
 def test_cases_tell_shared_grn_statistics():

@@ -3,7 +3,10 @@ restatement of tests/convnext_cases.py.  Every bound is 8 x the float32 restatem
 tensor (9 x against fixtures of the reference, whose fp32 run carries 1 x itself).  The restatements of a case run once
 (convnext_cases.study / *_study) and are shared.
 
-Measured on an MI355X (profiles/convnext_parity.txt): every compared tensor sits inside its bound."""
+Measured on an MI355X (profiles/convnext_parity.txt): every compared tensor sits inside its bound.  The cases at ConvNeXt-L's widths
+(DEEP_BLOCK_CASES, the 9 x 13 x 768 downsample layer, L_v1 / L_v2) hold the GEMM's contractions over 3072 and 6144 inputs to the same
+bound (profiles/deep_contraction_parity.txt: the downsample layer sat at 10.1 x before the GEMM's step sums, every one at 1.2 .. 6.0 x
+since)."""
 import pytest
 import torch
 
@@ -33,8 +36,9 @@ _DEVICE = {}
 
 @pytest.fixture(scope="module", autouse=True)
 def release_device_state():
-    """this module's shared device state and the scratch buffer its largest case grew (the hidden rows of the 25 x 43 x 1536 map) are
-    dropped when its tests are done, so that tests which measure peak device memory see what they saw before"""
+    """this module's shared device state (the L cases' networks among it: 0.25 GB of parameters each, and as much again packed) and the
+    scratch buffer its largest case grew (the hidden rows of the 25 x 43 x 1536 map) are dropped when its tests are done, so that tests
+    which measure peak device memory see what they saw before"""
     yield
     import gc
     _DEVICE.clear()
@@ -103,9 +107,19 @@ def test_block_teacher_forced(spec):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", [c.name for c in cc.NETS])
+@pytest.mark.parametrize("spec", cc.DEEP_BLOCK_CASES, ids=lambda s: "x".join(map(str, s)))
+def test_deep_block_teacher_forced(spec):
+    """Whole blocks at the widths of ConvNeXt-L's last two stages: `pwconv2` contracts over 3072 and 6144 inputs, 96 and 192 k-steps of
+    the three-piece GEMM in one accumulator (test_convnext_cpu: one k-step less misses the bound by more than 100 x)."""
+    st = cc.block_study(spec[:4], C=spec[4])
+    check(stage_net(st, st["v2"], st["gamma"]).block(st["x"].cuda(), 0, 0), st["out"], st["tol"], f"block {spec}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [c.name for c in cc.NETS + cc.LARGE_NETS])
 def test_network_free_running(name):
-    """The whole network against float64; the deep cases (36 blocks) show the error growth."""
+    """The whole network against float64; the deep cases (36 blocks) show the error growth, the L cases the growth over four blocks that
+    contract over 3072 and two over 6144."""
     st, net, x = on_device(cc.BY_NAME[name])
     outs = net(x)
     assert list(outs) == list(cc.OUTPUTS)
@@ -114,7 +128,7 @@ def test_network_free_running(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["A_v1", "A_v2"])
+@pytest.mark.parametrize("name", ["A_v1", "A_v2", "L_v1", "L_v2"])
 def test_steps_teacher_forced(name):
     """Every downsample layer and every block of the network on the float64 chain's inputs."""
     st, net, _ = on_device(cc.BY_NAME[name])

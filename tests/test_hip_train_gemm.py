@@ -59,8 +59,17 @@ def lib():
 
 
 # ---- instantiation ids (AxvsTestGemm::variant) and the dispatch rules of Gemm (axvs_train.hip) --------------------------------------
-def nt_var(ns, gen=False, add=False, f16=False, aff=False, act=False):
-    return 0x100 | ns | gen << 2 | add << 3 | f16 << 4 | aff << 5 | act << 6
+def nt_var(ns, gen=False, add=False, f16=False, aff=False, act=False, sum_=False):
+    return 0x100 | ns | gen << 2 | add << 3 | f16 << 4 | aff << 5 | act << 6 | sum_ << 7
+
+
+SUM_STEPS = 64      # three pieces: more 32-wide k-steps than this in one accumulator take the step sums (kNtSumSteps, csrc/axvs_gemm_nt.hip)
+
+
+def deep(K, ksteps=0):
+    """an accumulator's k-steps (of one split-K partial) are past SUM_STEPS"""
+    nk = (K + 31) // 32
+    return (min(ksteps, nk) if ksteps else nk) > SUM_STEPS
 
 
 def tn_var(gen, amp=0, stats=False, grp=False):
@@ -69,7 +78,7 @@ def tn_var(gen, amp=0, stats=False, grp=False):
 
 def vname(v):
     if v >> 8 == 1:
-        flags = [n for n, b in (("GEN", 4), ("ADD", 8), ("F16", 16), ("AFF", 32), ("ACT", 64)) if v & b]
+        flags = [n for n, b in (("GEN", 4), ("ADD", 8), ("F16", 16), ("AFF", 32), ("ACT", 64), ("SUM", 128)) if v & b]
         return f"nt<{v & 3}{''.join(',' + f for f in flags)}>"
     if v >> 8 == 2:
         flags = [n for n, b in (("GEN", 1), ("STATS", 8), ("GRP", 16)) if v & b]
@@ -96,6 +105,7 @@ def registered():
         out |= {nt_var(1, gen, add, f16) for f16 in (False, True)}       # train_amp 1 (bf16) / 2 (fp16): one piece
     out |= {nt_var(2, gen, aff=True) for gen in (False, True)}           # the affine loader: two pieces, no addend
     out |= {nt_var(3, act=True)}                                         # the GELU epilogues: three pieces, 16-byte loader, no addend
+    out |= {nt_var(3, gen, add, sum_=True) for gen, add in ((False, False), (True, False), (False, True))} | {nt_var(3, act=True, sum_=True)}      # past SUM_STEPS
     out |= {tn_var(False, amp) for amp in (0, 1, 2)}                     # weight gradient: 16-byte loader, follows train_amp
     for gen in (False, True):                                            # einsum: plain, with statistics, or grouped output rows
         out |= {tn_var(gen), tn_var(gen, stats=True), tn_var(gen, grp=True)}
@@ -107,19 +117,20 @@ def amp_mode():
     return _lib.current_amp()
 
 
-def expect_nt(K, exact, al_a=4, al_b=4, a2=False, aff=False, gelu=0):
+def expect_nt(K, exact, al_a=4, al_b=4, a2=False, aff=False, gelu=0, ksteps=0):
     """K % 4 != 0 or a row alignment below 16 bytes: the general loader; the addend without it: ADD; the affine loader: two pieces
     whatever `exact` and train_amp; train_amp: one 16-bit piece whatever `exact`; else three pieces iff exact.  relu = 2 / 3 (the
-    GELU epilogues): the one ACT instantiation -- any other combination with them is refused (test_train_gemm_cpu.py)."""
+    GELU epilogues): the one ACT instantiation -- any other combination with them is refused (test_train_gemm_cpu.py).  Three pieces over
+    more than SUM_STEPS k-steps per accumulator: the same instantiation with step sums."""
     gen = al_a != 4 or al_b != 4 or K % 4 != 0
     if gelu:
-        return nt_var(3, act=True)
+        return nt_var(3, act=True, sum_=deep(K, ksteps))
     if aff:
         return nt_var(2, gen, aff=True)
     amp = amp_mode()
     if amp:
         return nt_var(1, gen, a2 and not gen, amp == 2)
-    return nt_var(3 if exact else 2, gen, a2 and not gen)
+    return nt_var(3 if exact else 2, gen, a2 and not gen, sum_=bool(exact) and deep(K, ksteps))
 
 
 def amp(mode):
@@ -312,7 +323,7 @@ def nt_case(M, N, K, exact=1, seed=0, op="nt", al_a=4, al_b=4, ldc_pad=0, stride
             zr_d = zr.cuda()
             keep.append(zr_d)
             kw["zero_rows"] = zr_d.data_ptr()
-    expect = expect_nt(K, exact, al_a if op == "nt" else 4, al_b if op == "nt" else 4, a2 and not aff_rows, aff_rows > 0, gelu)
+    expect = expect_nt(K, exact, al_a if op == "nt" else 4, al_b if op == "nt" else 4, a2 and not aff_rows, aff_rows > 0, gelu, ksteps)
     v = call(op, M, N, K, A, B, Cm, expect, what, **kw)
     cls = vclass(v)
     if kind16:
@@ -386,7 +397,7 @@ def test_nt_affine_loader_with_groups_not_dividing_the_tile(K):
     nt_case(257, 128, K, 0, seed=6, aff_rows=100, al_a=1, beta=1.0)
 
 
-@pytest.mark.parametrize("K,ksteps,splits", [(1000, 11, 3), (999, 8, 4), (65, 1, 3)])
+@pytest.mark.parametrize("K,ksteps,splits", [(1000, 11, 3), (999, 8, 4), (65, 1, 3), (4200, 70, 2)])      # (the last: partials past SUM_STEPS)
 def test_nt_split_k_partials(K, ksteps, splits):
     nt_case(129, 132, K, 1, seed=K, ksteps=ksteps, zsplits=splits, ldc_pad=8)
     nt_case(300, 128, K, 0, seed=K + 1, ksteps=ksteps, zsplits=splits, aff_rows=100)
@@ -586,6 +597,72 @@ def test_tn_direct_tile_statistics(K, al):
     tn_case(128, 384, K, al, seed=5 + al, stats=True)
 
 
+# ---- how the three-piece GEMM's error grows with the depth of the contraction ------------------------------------------------------------
+# The element-wise bound above is per product: it scales with sum |a| |b| and says nothing about how the error of one accumulator grows
+# with the number of fp32 additions into it (six MFMAs per 32-wide k-step, so 1152 at K = 6144, ConvNeXt-L's last pwconv2).  The
+# backbones' tests hold every tensor to 8 x the error of a float32 restatement against float64 in max-norm; this is that bound on the
+# GEMM alone, at the backbones' depths and epilogues.
+DEEP_KS = (512, 2048, 3072, 4608, 6144)
+DEEP_EPILOGUES = {"bias": 0, "gelu": 2, "relu_after_res": 4}      # name -> AxvsTestGemm::relu; every one carries a bias
+DEEP_M, DEEP_N = 130, 160      # a part tile in both directions; 20800 elements
+FLOOR = 2.0 ** -24             # one float32 rounding relative to the tensor's largest value (attention_edge_cases.bound)
+
+
+def deep_case(K, epi, operand):
+    """C = epilogue(A B^T + bias) through the forward dispatch with three pieces.  A ~ N(0, 1) ("normal") or gelu(1.5 N(0, 1)) ("hidden":
+    the one-sided mean of a hidden activation), B ~ N(0, 1 / K).  -> (max |C - C64|, the bound, the float32 operation's own error)"""
+    relu = DEEP_EPILOGUES[epi]
+    g = torch.Generator().manual_seed(5000 + K + 7 * relu + (operand == "hidden"))
+    M, N = DEEP_M, DEEP_N
+    a = rnd(g, M, K)
+    if operand == "hidden":
+        a = torch.nn.functional.gelu(1.5 * a)
+    b, bv = rnd(g, N, K, scale=K ** -0.5), rnd(g, N, scale=0.1)
+    r = rnd(g, M, N) if relu == 4 else None
+    what = f"deep fwd M={M} N={N} K={K} epilogue={epi} A={operand}"
+
+    def op(a_, b_, bv_, r_):      # the same operation in the operands' type
+        y = torch.nn.functional.linear(a_, b_, bv_)
+        if relu == 2:
+            return torch.nn.functional.gelu(y)
+        return torch.relu(y + r_) if relu == 4 else y
+    ref = op(a.double(), b.double(), bv.double(), r.double() if relu == 4 else None)
+    own = op(a, b, bv, r).double()
+    mag = a.double().abs() @ b.double().abs().T + bv.double().abs()
+    if relu == 2:
+        mag = GELU_SLOPE * mag
+    A, B, Bv, Cm = Mat(a), Mat(b), Mat(bv.reshape(1, N)), Mat(nan(M, N))
+    kw = dict(exact=1, relu=relu, bias=Bv.ptr)
+    if relu == 4:
+        R = Mat(r)
+        kw["res"] = R.ptr
+        mag = mag + r.double().abs()      # (a ReLU does not enlarge an error)
+    v = call("fwd", M, N, K, A, B, Cm, nt_var(3, act=relu > 1, sum_=deep(K)), what, **kw)
+    Cm.assert_guards()
+    for m in (A, B, Bv):
+        m.assert_guards(written=False)
+    out = Cm.get()
+    check(out, ref, mag, vclass(v), what)
+    e, e32, top = float((out - ref).abs().max()), float((own - ref).abs().max()), float(ref.abs().max())
+    floor = e32 < FLOOR * top
+    bound = 8 * (FLOOR * top if floor else e32)
+    print(f"[deep-gemm] K={K} {epi} A={operand}: max |device - float64| {e:.3e}, float32 on the CPU {e32:.3e}{' (below one rounding: floor)' if floor else ''}, "
+          f"bound {bound:.3e}, ratio to the float32 error {8 * e / bound:.2f}")
+    return e, bound, e32
+
+
+@pytest.mark.parametrize("epi", list(DEEP_EPILOGUES))
+@pytest.mark.parametrize("K", DEEP_KS)
+def test_deep_contraction_error_growth(K, epi):
+    """The three-piece forward GEMM at the backbones' contraction depths (ConvNeXt-L's pwconv2: 3072 and 6144; its downsample layers: up to
+    3072; R-50's 1x1 convolutions: up to 2048) and with their three epilogues, so on both three-piece 16-byte instantiations: besides the
+    element-wise bound, max |C - C64| <= 8 x the max-norm error of the same operation in float32 on the CPU (8 x 2^-24 max |C64| where
+    that error is below one rounding).  The printed ratios per K are the growth curve (profiles/deep_contraction_parity.txt)."""
+    got = {operand: deep_case(K, epi, operand) for operand in ("normal", "hidden")}      # (every figure is printed before any is held to its bound)
+    for operand, (e, bound, _) in got.items():
+        assert e <= bound, f"K={K} {epi} A={operand}: {e:.3e} > {bound:.3e}"
+
+
 # ---- the bounds discriminate ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("K", [1, 4])
 def test_bounds_reject_the_next_coarser_arithmetic(K):
@@ -615,7 +692,7 @@ def test_bounds_reject_the_next_coarser_arithmetic(K):
 def test_zz_every_registered_instantiation_was_launched_by_its_rule():
     """Last in the file: every instantiation Gemm::init registers was launched, and every call of the file launched the one the
     dispatch rules document (K % 4 != 0 or unaligned rows -> GEN; an addend without GEN -> ADD; AMP -> one piece whatever `exact`, F16
-    iff fp16; the affine loader -> two pieces; relu = 2 / 3 -> ACT; wgrad -> the 16-byte tn loader; tn_direct -> GEN unless 16-byte rows and K % 4 == 0).
+    iff fp16; the affine loader -> two pieces; relu = 2 / 3 -> ACT; three pieces past 64 k-steps -> SUM; wgrad -> the 16-byte tn loader; tn_direct -> GEN unless 16-byte rows and K % 4 == 0).
     Small calls of each rule run here too, so the test stands alone when the file is run in part."""
     nt_case(1, 4, 4, 1, seed=90)
     nt_case(1, 4, 4, 0, seed=89)
@@ -626,6 +703,10 @@ def test_zz_every_registered_instantiation_was_launched_by_its_rule():
     nt_case(1, 4, 4, 0, seed=95, aff_rows=1)
     nt_case(1, 4, 5, 1, seed=96, aff_rows=1)
     nt_case(1, 4, 4, 1, seed=107, gelu=2)
+    nt_case(1, 4, 2080, 1, seed=108)                 # 65 k-steps: the step sums, on each loader and with the GELU epilogue
+    nt_case(1, 4, 2049, 1, seed=109)
+    nt_case(1, 4, 2080, 1, seed=110, a2=True)
+    nt_case(1, 4, 2080, 1, seed=111, gelu=3, res=True)
     for mode in (1, 2):
         with amp(mode):
             nt_case(1, 4, 4, 1, seed=97)
@@ -642,7 +723,7 @@ def test_zz_every_registered_instantiation_was_launched_by_its_rule():
     assert not wrong, wrong[:5]
     reached = {v for v, _, _ in SEEN}
     want = registered()
-    assert len(want) == 23, sorted(map(vname, want))
+    assert len(want) == 27, sorted(map(vname, want))
     missing = sorted(map(vname, want - reached))
     assert not missing, f"registered but never launched: {missing}"
     assert reached <= want, f"launched but not registered: {sorted(map(vname, reached - want))}"

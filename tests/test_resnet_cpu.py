@@ -1,6 +1,7 @@
 """CPU: the restatement of the ResNet bottleneck backbone (tests/resnet_cases.py) against fixtures of the reference's own classes, the
 module's state-dict names and shapes, its refusals, the new C-ABI symbols (axvs_rn_*) and their argument errors, which are reported
-before any device work -- and that the cases can tell a wrong stride phase, a wrong dilation padding and a misplaced ReLU apart."""
+before any device work -- and that the cases can tell a wrong stride phase, a wrong dilation padding, a misplaced ReLU and (the blocks at
+R-50's widths) a contraction one k-step short apart."""
 import ctypes
 import os
 
@@ -222,6 +223,18 @@ def test_cases_tell_wrong_blocks():
             assert rc.err(rc.block_study(spec, "stride_phase")["out"], right["out"]) > 1000 * right["tol"], spec
         if kind == "dil2":
             assert rc.err(rc.block_study(spec, "dilation_pad")["out"], right["out"]) > 1000 * right["tol"], spec
+
+
+def test_wide_cases_tell_a_dropped_k_step():
+    """The blocks at R-50's own widths against a first 1x1 that stops one 32-wide k-step early (of 16, 32 and 64): the float64 result moves
+    by more than 100 x the case's bound."""
+    for spec in rc.WIDE_BLOCK_CASES:
+        right, bad = rc.block_study(spec, net=rc.R50_WIDTHS), rc.block_study(spec, "k_short", net=rc.R50_WIDTHS)
+        d = rc.err(bad["out"], right["out"])
+        cin = right["x"].shape[-1]
+        print(f"block {spec}: one k-step of {cin // 32} dropped moves float64 by {d:.3e} = {d / right['tol']:.0f} x the bound {right['tol']:.3e}")
+        assert d > 100 * right["tol"], spec
+    assert sorted({rc.block_study(s, net=rc.R50_WIDTHS)["x"].shape[-1] for s in rc.WIDE_BLOCK_CASES}) == [512, 1024, 2048]
 
 
 def test_cases_tell_wrong_networks():
